@@ -2,8 +2,13 @@
 """Headline benchmark: PWCLO-Net forward frame-pairs/s on 2x8192-point KITTI-shaped pairs,
 batch 32 per GPU, fp32, eval mode (BASELINE.json metric, configs[2]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does only what the headline line needs: set-up, W warm-up steps, exactly K timed steps, the outputs of the
+last step under DIR (`--dump-outputs`), the JSON line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step`, ...).  `--full` adds everything else described below: the repeated timed region, `roofline` / `kernels`,
+`variants`, `cpu_baseline` and the other configurations (`configs`); `--no-*` switch single parts of it off again.
 
 One process per GPU.  Started WITHOUT torchrun and with --gpus N > 1, the process only supervises: before
 making any GPU call it starts N fresh rank processes of itself (dist_util.spawn_ranks) and exits with their
@@ -13,13 +18,17 @@ are replicas ("weak" scaling); the only collectives are the barrier around the t
 the MAX-reduce of its duration.  Rank 0 prints ONE JSON line.
 
 Timed region: W warm-up steps, then exactly K steps between two fences (device sync + barrier +
-device sync), MAX over ranks.  The region is repeated `--repeats` R times back to back (each repeat again
-exactly K steps between fences); `value` / `ms_per_step` are the MEDIAN repeat, `repeats` lists min / median /
-max (the GPU is busy for R*K steps, so an outside sampler sees the work).  By default a step is one hipGraph
+device sync), MAX over ranks.  With `--full` (or an explicit `--repeats R`) the region is repeated R times back to back
+(each repeat again exactly K steps between fences); `value` / `ms_per_step` are the MEDIAN repeat, `repeats` lists
+min / median / max (the GPU is busy for R*K steps, so an outside sampler sees the work).  By default a step is one hipGraph
 replay and four batches are kept in flight (`--inflight 4`, each a forward over its own batch of 32; DESIGN.md
 "Launch structure").
 
-`roofline`: after the timed region the same step runs three more times eagerly with HIP events
+`--dump-outputs DIR`: after the timed steps, what the timed path returned in its last step (the poses, (B, 4, 7); with
+`--config 5` also the survivor counts) as DIR/<name>.npy in float32 / float64.  Inputs and weights are seeded, so two
+builds run with the same arguments can be compared output for output.
+
+`roofline` (`--full`): after the timed region the same step runs three more times eagerly with HIP events
 around every launch of the library (events recorded on the launch stream); the object reports the
 dominant MFMA kernel by time (one template instantiation, named as rocprofv3 names it) as
 algorithmic FLOP / measured time against the fp32 MFMA peak, `traffic` from the committed PMC
@@ -64,6 +73,25 @@ def make_batch(batch, npoints, seed, device):
                             for r in range(reps)], axis=0)[:batch].astype(np.float32)
         out.append(torch.from_numpy(np.ascontiguousarray(x)).permute(0, 2, 1).contiguous().to(device))
     return out[0], out[1]
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: `arrays` (name -> tensor the timed path returned in its last step) as out_dir/<name>.npy, float32
+    tensors as float32, everything else (indices, counts) as float64 -- exact for every integer below 2**53.  The outputs
+    of this benchmark are a few KB; a set over the 64 MB cap is an error, not silently cut."""
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        host[name] = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte cap" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 class LaunchProfiler:
@@ -277,8 +305,8 @@ def other_configs(args, budget_s=90.0):
     so the GPU is the child's), bounded in time, and a failure is recorded, not raised: the headline line is printed
     either way."""
     import subprocess
-    runs = {"1": ["--batch", "1", "--no-cpu-baseline", "--no-variants", "--no-configs", "--timed-seconds", "1.0"],
-            "4": ["--config", "5", "--no-configs", "--repeats", "3", "--cpu-threads", str(args.cpu_threads)]}
+    runs = {"1": ["--full", "--batch", "1", "--no-cpu-baseline", "--no-variants", "--no-configs", "--timed-seconds", "1.0"],
+            "4": ["--full", "--config", "5", "--no-configs", "--repeats", "3", "--cpu-threads", str(args.cpu_threads)]}
     out, t_all = {}, time.perf_counter()
     for key, extra in runs.items():
         left = budget_s - (time.perf_counter() - t_all)
@@ -459,7 +487,7 @@ def run_config5(args):
 
     run_steps(max(1, args.warmup))
     times = []
-    for _ in range(max(3, args.repeats)):
+    for _ in range(max(3, args.repeats) if args.full else args.repeats):
         dist_util.fence(dev)
         t0 = time.perf_counter()
         pose, counts = run_steps(args.steps)
@@ -470,6 +498,27 @@ def run_config5(args):
     ordered = sorted(times)
     dt = ordered[len(ordered) // 2]
     if rank != 0:
+        dist_util.finish()
+        return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"pose": pose, "counts": counts})
+    out = {
+        "metric": "PWCLO-Net forward frame-pairs/sec, raw ~120k-pt KITTI-360 frames -> 8192-pt FPS -> pyramid, batch 8",
+        "value": world * B * args.steps / dt, "unit": "frame-pairs/s", "n_gpus": world, "steps": args.steps,
+        "warmup": max(1, args.warmup), "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+        "repeats": {"n": len(times), "reported": "median", "ms_per_step_all": [1e3 * t / args.steps for t in times]},
+        "config": {"workload": "BASELINE.json configs[4]: %d pairs x 2 x %d raw rows (x,y,z,i) per GPU, KITTI-360 filter, "
+                               "exact furthest point sampling to %d, full 4-level pyramid; stack layers in %s (fp32 "
+                               "accumulate), coordinates / distances / indices fp32" % (B, rows, npts, args.dtype),
+                   "global_batch": world * B, "npoints": npts, "parallelism": "replicas x%d" % world,
+                   "launch": "eager; large-cloud sampler: %s" % ("plain launch, two batches in flight on two streams"
+                                                                  if depth > 1 else "cooperative launch, one batch in flight"),
+                   "batches_in_flight": depth, "pyramids_on_their_own_stream": bool(pyr is not None),
+                   "spatial_order": order + (" (torch argsort front end: see profiles/r03/README.md)" if order == "torch"
+                                             else " (csrc/sampling.hip fps_spatial_order kernels)")}}
+    if not args.full:
+        print(json.dumps(out), flush=True)
         dist_util.finish()
         return
     # per-stage times (HIP events on the launch stream) and the per-launch profile of one more step
@@ -492,22 +541,11 @@ def run_config5(args):
     t_pyr = sum(d["ms"] for d in fam.values())
     n_surv = int(cnts.max())
     fps_bytes = 2 * B * (12.0 * n_surv + 16.0 * npts)
-    out = {
-        "metric": "PWCLO-Net forward frame-pairs/sec, raw ~120k-pt KITTI-360 frames -> 8192-pt FPS -> pyramid, batch 8",
-        "value": world * B * args.steps / dt, "unit": "frame-pairs/s", "n_gpus": world, "steps": args.steps,
-        "warmup": max(1, args.warmup), "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-        "repeats": {"n": len(times), "reported": "median", "ms_per_step_all": [1e3 * t / args.steps for t in times]},
-        "config": {"workload": "BASELINE.json configs[4]: %d pairs x 2 x %d raw rows (x,y,z,i) per GPU, KITTI-360 filter "
-                               "(survivors up to %d per frame), exact furthest point sampling to %d, full 4-level pyramid; "
-                               "stack layers in %s (fp32 accumulate), coordinates / distances / indices fp32"
-                               % (B, rows, n_surv, npts, args.dtype),
-                   "global_batch": world * B, "npoints": npts, "parallelism": "replicas x%d" % world,
-                   "launch": "eager; large-cloud sampler: %s" % ("plain launch, two batches in flight on two streams"
-                                                                  if depth > 1 else "cooperative launch, one batch in flight"),
-                   "batches_in_flight": depth, "pyramids_on_their_own_stream": bool(pyr is not None),
-                   "spatial_order": order + (" (torch argsort front end: see profiles/r03/README.md)" if order == "torch"
-                                             else " (csrc/sampling.hip fps_spatial_order kernels)")},
+    out["config"]["workload"] = ("BASELINE.json configs[4]: %d pairs x 2 x %d raw rows (x,y,z,i) per GPU, KITTI-360 filter "
+                                 "(survivors up to %d per frame), exact furthest point sampling to %d, full 4-level pyramid; "
+                                 "stack layers in %s (fp32 accumulate), coordinates / distances / indices fp32"
+                                 % (B, rows, n_surv, npts, args.dtype))
+    out.update({
         "stages_ms": {"kitti360_filter": t_filter, "compaction": t_compact, "fps_%d_to_%d" % (n_surv, npts): t_fps,
                       "pyramid_kernels_%s" % args.dtype: t_pyr},
         "roofline": {"kernel": "fps_coop_kernel<16>", "bound": "hbm",
@@ -526,7 +564,7 @@ def run_config5(args):
                                     "algorithmic_gflop_per_step": mlp["flops"] / 1e9,
                                     "achieved_tflops": mlp["flops"] / 1e9 / mlp["ms"] if mlp["ms"] else 0.0,
                                     "peak_tflops": BF16_MFMA_PEAK_TFLOPS if args.dtype == "bf16" else MFMA_F32_PEAK_TFLOPS,
-                                    "note": "batch 8: every stack launch is launch / fill bound (<= 16 clouds)"}}}
+                                    "note": "batch 8: every stack launch is launch / fill bound (<= 16 clouds)"}}})
     if not args.no_cpu_baseline and world == 1:
         sd = {k: v.detach().cpu() for k, v in net.state_dict().items()}
         out["cpu_baseline"] = config5_cpu_baseline(sd, f1[:2].cpu(), f2[:2].cpu(), npts, near, args.cpu_threads)
@@ -558,10 +596,17 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None, help="default 40 (--config 5: 5)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and report everything beyond the headline line: repeated timed region, roofline / "
+                         "per-kernel figures, bf16 variants, CPU baseline, the other configurations (each part can be "
+                         "switched off again with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy")
     ap.add_argument("--repeats", type=int, default=0,
-                    help="how many times the K-step timed region is run back to back (median reported); 0 = as many "
-                         "as fit in about --timed-seconds (at least 5, at most 200), decided from the first repeat")
-    ap.add_argument("--timed-seconds", type=float, default=3.0)
+                    help="how many times the K-step timed region is run back to back (median reported); 0 = once, or with "
+                         "--full as many as fit in about --timed-seconds (at least 5, at most 200; --config 5: 3), "
+                         "decided from the first repeat")
+    ap.add_argument("--timed-seconds", type=float, default=3.0, help="--full: see --repeats")
     ap.add_argument("--batch", type=int, default=None, help="frame pairs per GPU per step: default 32 (--config 5: 8)")
     ap.add_argument("--npoints", type=int, default=8192)
     ap.add_argument("--log-mode", default="host", choices=["host", "device", "none"],
@@ -593,7 +638,7 @@ def main():
                     help="host threads of the CPU baseline (0 = the cgroup CPU quota / affinity of this process)")
     ap.add_argument("--no-configs", action="store_true",
                     help="skip the extra measurement of BASELINE configs[1] (--batch 1) and configs[4] (--config 5) that the "
-                         "default single-GPU run appends under \"configs\"")
+                         "single-GPU --full run appends under \"configs\"")
     ap.add_argument("--no-variants", action="store_true",
                     help="skip the extra (untimed-region) measurement of the opt-in bf16x3 split path")
     ap.add_argument("--config", type=int, default=3, choices=[3, 5],
@@ -631,7 +676,7 @@ def main():
     if args.config == 5:
         args.dtype = args.dtype or "bf16"
         if args.repeats <= 0:
-            args.repeats = 3
+            args.repeats = 3 if args.full else 1
         return run_config5(args)
     dev = torch.device("cuda", local_rank)
     torch.cuda.set_device(dev)
@@ -672,7 +717,7 @@ def main():
     for _ in range(args.warmup):
         step()
 
-    times, repeats = [], (args.repeats if args.repeats > 0 else 5)
+    times, repeats = [], (args.repeats if args.repeats > 0 else (5 if args.full else 1))
     while len(times) < repeats:
         dist_util.fence(dev)
         t0 = time.perf_counter()
@@ -680,13 +725,15 @@ def main():
             pose = step()
         dist_util.fence(dev)
         times.append(dist_util.max_over_ranks(time.perf_counter() - t0, dev))
-        if args.repeats <= 0 and len(times) == 1:     # same decision on every rank: times[0] is the MAX over ranks
+        if args.full and args.repeats <= 0 and len(times) == 1:  # same decision on every rank: times[0] is the MAX
             repeats = int(min(200, max(5, round(args.timed_seconds / max(times[0], 1e-6)))))
     assert torch.isfinite(pose).all()
     _lib.synchronize(dev)             # raises if any kernel reported a device-side failure
     ordered = sorted(times)
     dt = ordered[len(ordered) // 2]   # median repeat
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"pose": pose})
     if rank == 0:
         out = {
             "metric": "PWCLO-Net forward frame-pairs/sec, 2x%d-pt KITTI pair, batch %d" % (args.npoints, args.batch),
@@ -711,23 +758,23 @@ def main():
                        else "fused gather+MFMA-MLP kernels (BN folded)",
                        "log_dict": args.log_mode + " (lazy)"},
         }
-        if not args.no_roofline and not args.unfused:
+        if args.full and not args.no_roofline and not args.unfused:
             fam = instrumented_pass(net, x1, x2)
             roof, kernels = roofline_objects(fam)
             roof["step"] = step_roofline(fam, out["ms_per_step"])
             out["roofline"] = roof
             out["kernels"] = kernels
-        if not args.no_variants and world == 1 and pipe is not None and not args.unfused \
+        if args.full and not args.no_variants and world == 1 and pipe is not None and not args.unfused \
                 and args.pipeline == "whole" and (args.dtype or "f32") == "f32" \
                 and os.environ.get("PWCLO_BF16X3", "0") == "0":
             ref_pose = pose.clone()
             out["variants"] = {"bf16x3": bf16x3_variant(args, dev, x1, x2, ref_pose, pipe.streams, "bf16x3"),
                                "bf16": bf16x3_variant(args, dev, x1, x2, ref_pose, pipe.streams, "bf16")}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(net, args.npoints, args.cpu_forwards, args.cpu_threads, args.cpu_seconds)
         default_workload = (args.batch == 32 and args.npoints == 8192 and not args.unfused and args.launch == "graph"
                             and (args.dtype or "f32") == "f32")
-        if not args.no_configs and world == 1 and default_workload:
+        if args.full and not args.no_configs and world == 1 and default_workload:
             torch.cuda.synchronize(dev)
             out["configs"] = other_configs(args)
         print(json.dumps(out), flush=True)

@@ -270,6 +270,21 @@ def test_bench_refuses_more_gpus_than_visible():
     assert out.returncode == 2 and "GPU(s) visible" in out.stderr, (out.returncode, out.stderr)
 
 
+def test_bench_dump_outputs_writes_float_arrays(tmp_path):
+    """bench.py --dump-outputs: one .npy per returned tensor, float32 kept, integer outputs as exact float64, and a set
+    over the 64 MB cap refused rather than cut."""
+    import bench
+    pose = torch.randn(2, 4, 7)
+    counts = torch.tensor([95811, 2 ** 40], dtype=torch.int64)
+    bench.dump_outputs(str(tmp_path / "d"), {"pose": pose, "counts": counts})
+    p, c = np.load(str(tmp_path / "d" / "pose.npy")), np.load(str(tmp_path / "d" / "counts.npy"))
+    assert p.dtype == np.float32 and np.array_equal(p, pose.numpy())
+    assert c.dtype == np.float64 and c.tolist() == [95811.0, float(2 ** 40)]
+    with pytest.raises(RuntimeError, match="cap"):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": torch.zeros(17 << 20)})
+    assert not (tmp_path / "big").exists()
+
+
 DDP_WORKER = r"""
 import os, sys
 sys.path.insert(0, %r)

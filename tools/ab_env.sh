@@ -2,7 +2,7 @@
 # Developer tool: alternating A/B of environment switches in the pipelined bench (one line per setting: runs and mean).
 #   bash tools/ab_env.sh "PWCLO_COARSE_W4=0" "PWCLO_FL_ROUNDS=2" ...   (the empty setting = defaults is always included)
 O=gpurun_out/ab_env; mkdir -p $O
-B="--no-cpu-baseline --no-configs --no-variants --no-roofline"
+B="--full --no-cpu-baseline --no-configs --no-variants --no-roofline"
 settings=("" "$@")
 for r in 1 2 3; do
   for i in "${!settings[@]}"; do

@@ -19,21 +19,21 @@ rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_ACTIVE_INST_VALU -
 python tools/pmc_mfma.py "$(find $out/sq -name '*counter_collection.csv' | head -1)" -o $out/pmc_mfma_busy.json > $out/pmc_mfma_busy.txt
 cp $out/pmc_traffic.json $out/pmc_mfma_busy.json profiles/
 find $out -name "*counter_collection.csv" -delete
-python bench.py > $out/${tag}_default_bench.json
-python bench.py --config 5 --no-configs > $out/${tag}_config5_bench.json
-python bench.py --config 5 --config5-inflight 1 --no-cpu-baseline --no-configs > $out/${tag}_config5_one_in_flight_bench.json
-python bench.py --batch 1 --no-cpu-baseline --no-variants --no-configs > $out/${tag}_config2_batch1_bench.json
+python bench.py --full > $out/${tag}_default_bench.json
+python bench.py --full --config 5 --no-configs > $out/${tag}_config5_bench.json
+python bench.py --full --config 5 --config5-inflight 1 --no-cpu-baseline --no-configs > $out/${tag}_config5_one_in_flight_bench.json
+python bench.py --full --batch 1 --no-cpu-baseline --no-variants --no-configs > $out/${tag}_config2_batch1_bench.json
 python tools/launch_table.py > $out/${tag}_launch_table.txt 2>&1
 python tools/wgtrace.py > $out/${tag}_wgtrace_inflight4.txt 2>&1
 python tools/wgtrace.py --ablate knn > $out/${tag}_wgtrace_noknn.txt 2>&1
 python tools/wgtrace.py --ablate fps,knn > $out/${tag}_wgtrace_mlp_only.txt 2>&1
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/default -o default -- python bench.py --no-cpu-baseline --no-variants --no-configs --repeats 3 > $out/${tag}_default_bench_under_rocprof.json 2> $out/rocprof_default.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/eager -o eager -- python bench.py --launch eager --inflight 1 --no-cpu-baseline --no-variants --no-configs --repeats 3 > $out/${tag}_eager_inflight1_under_rocprof.json 2> $out/rocprof_eager.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/default -o default -- python bench.py --full --no-cpu-baseline --no-variants --no-configs --repeats 3 > $out/${tag}_default_bench_under_rocprof.json 2> $out/rocprof_default.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/eager -o eager -- python bench.py --full --launch eager --inflight 1 --no-cpu-baseline --no-variants --no-configs --repeats 3 > $out/${tag}_eager_inflight1_under_rocprof.json 2> $out/rocprof_eager.err
 # config 5 under the profiler, COOPERATIVE launch of the large-cloud sampler (one batch in flight).  rocprofv3 writes its
 # outputs and finalises, THEN the process faults inside its exit handlers (profiles/r03/README.md: the only code of
 # libpwclo_hip.so that runs at exit() is the compiler-generated __hip_module_dtor -> __hipUnregisterFatBinary, after the
 # tool has already torn the runtime down): the exit status is ignored, the kernel statistics are what is kept.
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/c5 -o c5 -- python bench.py --config 5 --config5-inflight 1 --no-cpu-baseline --no-configs > $out/${tag}_config5_coop_under_rocprof.json 2> $out/rocprof_c5.err || echo "config-5 rocprof pass: exit status $? (see rocprof_c5.err; the statistics file is checked below)"
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/c5 -o c5 -- python bench.py --full --config 5 --config5-inflight 1 --no-cpu-baseline --no-configs > $out/${tag}_config5_coop_under_rocprof.json 2> $out/rocprof_c5.err || echo "config-5 rocprof pass: exit status $? (see rocprof_c5.err; the statistics file is checked below)"
 find $out -name "*kernel_stats.csv" | sort
 cp "$(find $out/default -name '*kernel_stats.csv' | head -1)" $out/${tag}_default_bench_kernel_stats.csv
 cp "$(find $out/eager -name '*kernel_stats.csv' | head -1)" $out/${tag}_eager_inflight1_kernel_stats.csv

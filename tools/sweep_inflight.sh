@@ -4,7 +4,7 @@
 # r03_v4_hw_queue_sweep.txt were made with it).
 O=${1:-gpurun_out/sweep_inflight}
 mkdir -p $O
-B="--no-cpu-baseline --no-configs --no-variants --no-roofline --timed-seconds 1.5"
+B="--full --no-cpu-baseline --no-configs --no-variants --no-roofline --timed-seconds 1.5"
 for q in 8 16 24; do for d in 4 6 8 12; do
   GPU_MAX_HW_QUEUES=$q python bench.py --batch 1 --inflight $d $B > $O/b1_q${q}_d$d.json 2> $O/b1_q${q}_d$d.err || echo "b1 q$q d$d failed"
 done; done
