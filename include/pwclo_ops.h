@@ -234,6 +234,10 @@ void ingest_pairs_kernel_wrapper(int b, int n, const float *xyz_f1, const float 
 void ingest_frames_kernel_wrapper(int b, int n, int n_total, int c, const float *frame1,
                                   const float *frame2, float *out);
 
+/* Sequence form of ingest_frames (FusedPWCLONet.sample_sequence): frames (t, n_total, c) point-major, c >= 3;
+ * the first n points and first 3 channels of each frame -> out (t, n, 3), frame order kept. */
+void ingest_sequence_kernel_wrapper(int t, int n, int n_total, int c, const float *frames, float *out);
+
 /* Hamilton product of quaternion rows (PW/PWCLO_utils.py:83-95 mul_q_point, :117-129 mul_point_q -- the same
  * component expressions): out (b,4,n) = a (b,4,na) (x) q (b,4,nb), na and nb each 1 (broadcast) or n; conj_a / conj_b
  * != 0 use that operand's conjugate.  Products rounded before the left-to-right sums: the torch expression bit for

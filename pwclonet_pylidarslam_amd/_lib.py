@@ -55,6 +55,7 @@ SIGNATURES = {
     "quat_warp_pm_kernel_wrapper": ([_i, _i, _F, _F, _F, _F], None),
     "ingest_pairs_kernel_wrapper": ([_i, _i, _F, _F, _F], None),
     "ingest_frames_kernel_wrapper": ([_i, _i, _i, _i, _F, _F, _F], None),
+    "ingest_sequence_kernel_wrapper": ([_i, _i, _i, _i, _F, _F], None),
     "kitti_transform_filter_kernel_wrapper": ([_i, _F, _F, _F, _F], None),
     "kitti360_filter_kernel_wrapper": ([_i, ctypes.c_float, ctypes.c_float, _F, _F, _F], None),
     "compact_frames_kernel_wrapper": ([_i, _i, _i, _F, _F, _F, _F, _F], None),

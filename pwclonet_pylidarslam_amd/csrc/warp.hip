@@ -68,6 +68,16 @@ __global__ __launch_bounds__(256) void ingest_pairs_kernel(int bsz, int n, const
 // c >= 3 floats per point, of which the first n points and the first 3 channels are used
 // (`pcd[:, :num_points, :3]`) -> the same (2B,n,3) batch.  Replaces slice + permute + contiguous in
 // the reference's adapter and the permute back in the fused forward.
+// Point j of output cloud b: the first 3 of the c floats of `frame`'s row j.
+__device__ __forceinline__ void ingest_point(int b, int j, int n, int c, const float *__restrict__ frame,
+                                             float *__restrict__ out) {
+  const float *src = frame + (size_t)j * c;
+  float *dst = out + ((size_t)b * n + j) * 3;
+  dst[0] = src[0];
+  dst[1] = src[1];
+  dst[2] = src[2];
+}
+
 __global__ __launch_bounds__(256) void ingest_frames_kernel(int bsz, int n, int n_total, int c,
                                                             const float *__restrict__ f1,
                                                             const float *__restrict__ f2,
@@ -75,11 +85,17 @@ __global__ __launch_bounds__(256) void ingest_frames_kernel(int bsz, int n, int 
   const int b = blockIdx.y;               // 0 .. 2*bsz-1
   const int j = blockIdx.x * 256 + threadIdx.x;
   if (j >= n) return;
-  const float *src = (b < bsz ? f1 + (size_t)b * n_total * c : f2 + (size_t)(b - bsz) * n_total * c) + (size_t)j * c;
-  float *dst = out + ((size_t)b * n + j) * 3;
-  dst[0] = src[0];
-  dst[1] = src[1];
-  dst[2] = src[2];
+  ingest_point(b, j, n, c, b < bsz ? f1 + (size_t)b * n_total * c : f2 + (size_t)(b - bsz) * n_total * c, out);
+}
+
+// Sequence form (FusedPWCLONet.sample_sequence): one window of t frames (t, n_total, c) -> (t, n, 3), frame order kept;
+// every frame is ingested once and serves as frame 2 of one pair and frame 1 of the next.
+__global__ __launch_bounds__(256) void ingest_sequence_kernel(int n, int n_total, int c, const float *__restrict__ frames,
+                                                              float *__restrict__ out) {
+  const int b = blockIdx.y;               // 0 .. t-1
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  ingest_point(b, j, n, c, frames + (size_t)b * n_total * c, out);
 }
 
 // Raw KITTI velodyne frame -> camera-frame cloud + keep mask (kitti_odometry_dataset.py:375-397 and
@@ -231,6 +247,16 @@ extern "C" void ingest_frames_kernel_wrapper(int b, int n, int n_total, int c, c
   hipLaunchKernelGGL(ingest_frames_kernel, dim3(ceil_div(n, 256), 2 * b), dim3(256), 0, current_stream(), b, n,
                      n_total, c, frame1, frame2, out);
   check_launch("ingest_frames");
+}
+
+extern "C" void ingest_sequence_kernel_wrapper(int t, int n, int n_total, int c, const float *frames, float *out) {
+  if (t <= 0 || n <= 0) return;
+  PWCLO_REQUIRE(t <= 65535, "ingest_sequence: t=%d exceeds the grid limit", t);
+  PWCLO_REQUIRE(c >= 3 && n_total >= n, "ingest_sequence: need c >= 3 and n_total >= n (c=%d n_total=%d n=%d)", c,
+                n_total, n);
+  hipLaunchKernelGGL(ingest_sequence_kernel, dim3(ceil_div(n, 256), t), dim3(256), 0, current_stream(), n, n_total, c,
+                     frames, out);
+  check_launch("ingest_sequence");
 }
 
 extern "C" void ingest_pairs_kernel_wrapper(int b, int n, const float *xyz_f1, const float *xyz_f2,

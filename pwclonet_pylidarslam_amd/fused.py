@@ -870,7 +870,12 @@ class FusedPWCLONet:
     packed once; call again after loading a new ``state_dict``.  The siamese pyramid runs both
     frames as one batch, the level-4 FPS of ``flow_feature_encoding`` reuses ``psa_4``'s (same
     cloud, same result: SURVEY.md appendix B) and the two set-upconvs of a level share one
-    neighbour search (identical inputs)."""
+    neighbour search (identical inputs).
+
+    Cloud addressing: the pyramid runs C clouds, the pair stage P pairs whose frame-1 clouds are [0, P) and whose
+    frame-2 clouds are [o, o + P).  Pair mode (``__call__``): C = 2B, P = B, o = B.  Sequence mode
+    (``forward_sequence``): C = T frames, P = T - 1, o = 1 -- every frame's pyramid runs once and serves as frame 2 of
+    one pair and frame 1 of the next."""
 
     def __init__(self, net):
         from .pwclonet import PWCLO_utils as pw
@@ -905,16 +910,15 @@ class FusedPWCLONet:
 
     def _refine(self, br, d, row, pose, x1, f1, x2, f2, x1_prev, emb_prev, mask_prev, q_prev, t_prev,
                 taps=None, tap="", warped=None, warp_next=None, st_up=None, st_q=None, cvj=None, pres=None, nxt=None,
-                carry=None):
+                carry=None, o=None):
         """``warped``: quat_warp_pm(x1, q_prev, t_prev) when the previous level's pose head already produced it;
         ``warp_next``: the next (finer) level's cloud, warped by this level's head with the pose it composes (returned as a
-        fifth value).  ``st_up`` / ``st_q``: search structures (``knn_keep``) the pyramid built for the 2B clouds that
-        x1_prev (frame 1: clouds [0, B)) and x2 (frame 2: clouds [B, 2B)) belong to, or None.
+        fifth value).  ``st_up`` / ``st_q``: search structures (``knn_keep``) the pyramid built for the C clouds that
+        x1_prev (frame 1: clouds [0, P)) and x2 (frame 2: clouds [o, o + P)) belong to, or None; ``o`` = that offset.
         Hoisted partial products that something earlier already produced: ``cvj`` = (u, v, u2) of this level's cost volume
         (they need the pyramid features only: ``rest`` computes them beside the set abstractions' seeds), ``pres`` = (pre_f,
         pre_m), the set-upconv seeds (written by the previous level's flow predictors as a linear tail).  ``nxt`` = the next
         (finer) level's modules: when given, this level's predictors write that level's seeds into ``carry["pres"]``."""
-        B = x1.shape[0]
         idx_up = br.hold(knn_on(st_up, 0, 8, x1) if st_up is not None and x1.shape[1] >= 256 else knn(8, x1_prev, x1))
         if taps is not None:
             taps[tap + ".up.idx"] = idx_up
@@ -940,7 +944,7 @@ class FusedPWCLONet:
             taps[tap + ".warped"] = warped
         idx_q = None
         if self.hoist and st_q is not None and warped.shape[1] >= 256:
-            idx_q = br.hold(knn_on(st_q, B, d["cv"].nsample_q, warped))
+            idx_q = br.hold(knn_on(st_q, o, d["cv"].nsample_q, warped))
         resid = br.hold(d["cv"](warped, x2, u, v, u2, idx_q=idx_q, taps=taps, tap=tap + ".cv") if self.hoist else
                         d["cv"](warped, f1, x2, f2, taps=taps, tap=tap + ".cv"))
         br.join(1)
@@ -970,7 +974,7 @@ class FusedPWCLONet:
         x = torch.empty((2 * B, N0, 3), dtype=torch.float32, device=xyz_f1.device)  # both frames, point-major
         _lib.call("ingest_pairs_kernel_wrapper", x.device, B, N0, _p(xyz_f1.contiguous()),
                   _p(xyz_f2.contiguous()), _p(x))
-        return self._sample_chain(B, x, br)
+        return self._sample_chain(x, br, B, B)
 
     @torch.no_grad()
     def sample_frames(self, frame1, frame2, num_points, br=None):
@@ -981,9 +985,26 @@ class FusedPWCLONet:
         x = torch.empty((2 * B, num_points, 3), dtype=torch.float32, device=frame1.device)
         _lib.call("ingest_frames_kernel_wrapper", x.device, B, num_points, n_total, c, _p(frame1.contiguous()),
                   _p(frame2.contiguous()), _p(x))
-        return self._sample_chain(B, x, br)
+        return self._sample_chain(x, br, B, B)
 
-    def _sample_chain(self, B, x, br):
+    @torch.no_grad()
+    def sample_sequence(self, frames, num_points, br=None):
+        """Stage 1 of a sequence window: frames (T, n_total, c>=3) point-major, of which ``[:, :num_points, :3]`` is
+        used.  Every frame goes through the pyramid once; the pair stage then runs the T - 1 consecutive pairs
+        (frame i, frame i + 1).  A contiguous fp32 (T, num_points, 3) batch (``preprocess.frames_to_clouds``) is used
+        as it is, anything else goes through one ingest launch."""
+        T, n_total, c = frames.shape
+        assert T >= 2 and c >= 3 and n_total >= num_points and frames.dtype == torch.float32
+        if c == 3 and n_total == num_points and frames.is_contiguous():
+            x = frames
+        else:
+            x = torch.empty((T, num_points, 3), dtype=torch.float32, device=frames.device)
+            _lib.call("ingest_sequence_kernel_wrapper", x.device, T, num_points, n_total, c, _p(frames.contiguous()), _p(x))
+        return self._sample_chain(x, br, T - 1, 1)
+
+    def _sample_chain(self, x, br, P, o):
+        """``P`` pairs over the clouds of ``x``: frame 1 of pair i is cloud i, frame 2 cloud o + i."""
+        assert 0 < P and o + P <= x.shape[0]
         if br is None:
             br = _Branches(x.device, False)
         # The sampling chain of all four levels depends only on the input cloud: it runs ahead on its
@@ -1012,16 +1033,16 @@ class FusedPWCLONet:
                 ready.append(br.mark(0))
             if flag is not None:
                 br.hold(flag)
-        return dict(B=B, x=x, samples=samples, ready=ready, br=br, ws0=ws0)
+        return dict(B=P, P=P, o=o, x=x, samples=samples, ready=ready, br=br, ws0=ws0)
 
     @torch.no_grad()
     def rest(self, state, return_intermediates=False):
         """Stage 2 -- neighbour search, feature pyramid, cost volumes, pose refinement."""
-        B, x, samples, ready, br = state["B"], state["x"], state["samples"], state["ready"], state["br"]
+        P, o, x, samples, ready, br = state["P"], state["o"], state["x"], state["samples"], state["ready"], state["br"]
         f = None
         lv = []
         reuse = os.environ.get("PWCLO_KNN_REUSE", "1") != "0"
-        built = {}                       # pyramid level -> search structure of its 2B clouds (knn_keep)
+        built = {}                       # pyramid level -> search structure of its C clouds (knn_keep)
         # neighbour lists of every knn call (tests compare them with the oracle's); only when asked for
         taps = {} if return_intermediates else None
         early_users, cvj = {}, {}
@@ -1054,7 +1075,7 @@ class FusedPWCLONet:
                     # from them depend on nothing else -- same launch as this level's set-abstraction seeds
                     users = early_users.get(lvl, [])
                     for cv in users:
-                        jobs = jobs + cv.jobs(f[:B], f[B:])
+                        jobs = jobs + cv.jobs(f[:P], f[o:o + P])
                     outs = run_linear_jobs(jobs)
                     br.hold(*outs, None)
                     pre = outs[0]
@@ -1065,13 +1086,13 @@ class FusedPWCLONet:
                 f = br.hold(fsa(x, new_x, f, idx))
             x = new_x
             lv.append((x, f))
-        (x11, f11), (x12, f12), (x13, f13), (x14, f14) = [(a[:B], b[:B]) for a, b in lv]
-        (x21, f21), (x22, f22), (x23, f23), _ = [(a[B:], b[B:]) for a, b in lv]
+        (x11, f11), (x12, f12), (x13, f13), (x14, f14) = [(a[:P], b[:P]) for a, b in lv]
+        (x21, f21), (x22, f22), (x23, f23), _ = [(a[o:o + P], b[o:o + P]) for a, b in lv]
 
         # flow_feature_encoding samples the same cloud as psa_4(frame 1): reuse x14
         if self.ffe_cfg == self.sa_cfg[3] and os.environ.get("PWCLO_FFE_REUSE", "1") != "0":
             # same search as psa_4's on frame 1 (queries x14 among x13, same nsample; clouds are searched independently)
-            idx_ffe = idx_last[:B]
+            idx_ffe = idx_last[:P]
         else:
             idx_ffe = knn(self.ffe_cfg[1], x13, x14)
         if self.hoist:
@@ -1083,29 +1104,29 @@ class FusedPWCLONet:
         if taps is not None:
             taps["ffe.knn_idx"] = idx_ffe
         mask4 = self.l4_pred(f14, emb4)
-        pose = torch.empty((B, 4, 7), dtype=torch.float32, device=x.device)   # rows = levels 1..4
+        pose = torch.empty((P, 4, 7), dtype=torch.float32, device=x.device)   # rows = levels 1..4
         if os.environ.get("PWCLO_HEAD_WARP", "1") != "0":
             # every pose head also warps the next finer cloud with the pose it has just composed (one launch fewer per level)
             q4, t4, w3 = br.hold(*self.l4_head(emb4, mask4, pose, 3, warp_next=x13))
             c3, c2 = {}, {}
             q3, t3, emb3, mask3, w2 = self._refine(br, self.pwr[0], 2, pose, x13, f13, x23, f23, x14, emb4, mask4, q4, t4,
-                                                   taps, "pwr3", warped=w3, warp_next=x12, st_up=built.get(4), st_q=built.get(3),
+                                                   taps, "pwr3", o=o, warped=w3, warp_next=x12, st_up=built.get(4), st_q=built.get(3),
                                                    cvj=cvj.get(id(self.pwr[0]["cv"])), nxt=self.pwr[1] if tails else None, carry=c3)
             q2, t2, emb2, mask2, w1 = self._refine(br, self.pwr[1], 1, pose, x12, f12, x22, f22, x13, emb3, mask3, q3, t3,
-                                                   taps, "pwr2", warped=w2, warp_next=x11, st_up=built.get(3), st_q=built.get(2),
+                                                   taps, "pwr2", o=o, warped=w2, warp_next=x11, st_up=built.get(3), st_q=built.get(2),
                                                    cvj=cvj.get(id(self.pwr[1]["cv"])), pres=c3.get("pres"),
                                                    nxt=self.pwr[2] if tails else None, carry=c2)
             q1, t1, emb1, mask1 = self._refine(br, self.pwr[2], 0, pose, x11, f11, x21, f21, x12, emb2, mask2, q2, t2,
-                                               taps, "pwr1", warped=w1, st_up=built.get(2), st_q=built.get(1),
+                                               taps, "pwr1", o=o, warped=w1, st_up=built.get(2), st_q=built.get(1),
                                                cvj=cvj.get(id(self.pwr[2]["cv"])), pres=c2.get("pres"))
         else:
             q4, t4 = self.l4_head(emb4, mask4, pose, 3)
             q3, t3, emb3, mask3 = self._refine(br, self.pwr[0], 2, pose, x13, f13, x23, f23, x14, emb4, mask4, q4, t4,
-                                               taps, "pwr3", st_up=built.get(4), st_q=built.get(3), cvj=cvj.get(id(self.pwr[0]["cv"])))
+                                               taps, "pwr3", o=o, st_up=built.get(4), st_q=built.get(3), cvj=cvj.get(id(self.pwr[0]["cv"])))
             q2, t2, emb2, mask2 = self._refine(br, self.pwr[1], 1, pose, x12, f12, x22, f22, x13, emb3, mask3, q3, t3,
-                                               taps, "pwr2", st_up=built.get(3), st_q=built.get(2), cvj=cvj.get(id(self.pwr[1]["cv"])))
+                                               taps, "pwr2", o=o, st_up=built.get(3), st_q=built.get(2), cvj=cvj.get(id(self.pwr[1]["cv"])))
             q1, t1, emb1, mask1 = self._refine(br, self.pwr[2], 0, pose, x11, f11, x21, f21, x12, emb2, mask2, q2, t2,
-                                               taps, "pwr1", st_up=built.get(2), st_q=built.get(1), cvj=cvj.get(id(self.pwr[2]["cv"])))
+                                               taps, "pwr1", o=o, st_up=built.get(2), st_q=built.get(1), cvj=cvj.get(id(self.pwr[2]["cv"])))
         if return_intermediates:
             return pose, dict(x11=x11, f11=f11, f13=f13, flow=flow, emb4=emb4, mask4=mask4, emb3=emb3,
                               mask3=mask3, emb2=emb2, mask2=mask2, emb1=emb1, mask1=mask1, q=(q1, q2, q3, q4),
@@ -1123,3 +1144,9 @@ class FusedPWCLONet:
         """The forward from two (B, n_total, c>=3) point-major frames (see ``sample_frames``)."""
         br = _Branches(frame1.device, self.branch and torch.cuda.is_current_stream_capturing())
         return self.rest(self.sample_frames(frame1, frame2, num_points, br), return_intermediates)
+
+    @torch.no_grad()
+    def forward_sequence(self, frames, num_points, return_intermediates=False):
+        """frames (T, n_total, c>=3) point-major -> pose_params (T-1, 4, 7): row i = pair (frame i, frame i + 1)."""
+        br = _Branches(frames.device, self.branch and torch.cuda.is_current_stream_capturing())
+        return self.rest(self.sample_sequence(frames, num_points, br), return_intermediates)

@@ -21,20 +21,25 @@ class GraphedForward:
         self._graphs = {}
         self._saved_log_mode = None
 
-    def _capture(self, xyz_f1, xyz_f2):
+    def _run(self, s1, s2):
+        """The captured call on the static input buffers."""
+        return self.net(s1, None, s2, None)
+
+    def _capture(self, *inputs):
         net = self.net
         log_mode = net.log_mode
         if log_mode == "host":          # a D2H copy cannot be captured; keep the values on device
             net.log_mode = "device"
         try:
-            s1, s2 = xyz_f1.clone(), xyz_f2.clone()
-            side = torch.cuda.Stream(device=s1.device)
-            side.wait_stream(torch.cuda.current_stream(s1.device))
+            static = [t.clone() for t in inputs]
+            dev = static[0].device
+            side = torch.cuda.Stream(device=dev)
+            side.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.stream(side), torch.no_grad():
                 for _ in range(self.warmup):   # allocator warm-up + one-time kernel attributes
-                    net(s1, None, s2, None)
-            torch.cuda.current_stream(s1.device).wait_stream(side)
-            torch.cuda.synchronize(s1.device)
+                    self._run(*static)
+            torch.cuda.current_stream(dev).wait_stream(side)
+            torch.cuda.synchronize(dev)
             fused = getattr(net, "_fused", None)
             saved_branch = fused.branch if fused is not None else None
             if fused is not None:
@@ -42,24 +47,28 @@ class GraphedForward:
             graph = torch.cuda.CUDAGraph()
             try:
                 with torch.cuda.graph(graph), torch.no_grad():
-                    pose, log = net(s1, None, s2, None)
+                    pose, log = self._run(*static)
             finally:
                 if fused is not None:
                     fused.branch = saved_branch
         finally:
             net.log_mode = log_mode
-        return graph, s1, s2, pose, log
+        return graph, static, pose, log
+
+    def _replay(self, *inputs):
+        """Copy the inputs into the static buffers of the graph captured for their shapes (captured now if new), replay."""
+        key = (tuple(tuple(t.shape) for t in inputs), inputs[0].device)
+        if key not in self._graphs:
+            self._graphs[key] = self._capture(*inputs)
+        graph, static, pose, log = self._graphs[key]
+        for dst, src in zip(static, inputs):
+            dst.copy_(src)
+        graph.replay()
+        self.last_log_dict = self._replay_log(log, inputs[0].device)
+        return pose
 
     def __call__(self, xyz_f1, xyz_f2):
-        key = (tuple(xyz_f1.shape), xyz_f1.device)
-        if key not in self._graphs:
-            self._graphs[key] = self._capture(xyz_f1, xyz_f2)
-        graph, s1, s2, pose, log = self._graphs[key]
-        s1.copy_(xyz_f1)
-        s2.copy_(xyz_f2)
-        graph.replay()
-        self.last_log_dict = self._replay_log(log, xyz_f1.device)
-        return pose
+        return self._replay(xyz_f1, xyz_f2)
 
     def _replay_log(self, log, device):
         """log_dict of THIS replay: a fresh lazy view of the graph's static buffers (nothing cached from an
@@ -70,6 +79,21 @@ class GraphedForward:
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(device))
         return log.fresh(to_host=self.net.log_mode == "host", ready=ev.synchronize)
+
+
+class GraphedSequence(GraphedForward):
+    """``GraphedSequence(net, num_points=None)(frames) -> pose_params (T-1, 4, 7)``: ``net.forward_sequence`` on one
+    window of T frames (T, n_total, c) replayed from a graph, one per window shape; static output as above."""
+
+    def __init__(self, net, num_points=None, warmup=2, branch=True):
+        super().__init__(net, warmup=warmup, branch=branch)
+        self.num_points = num_points
+
+    def _run(self, frames):
+        return self.net.forward_sequence(frames, self.num_points)
+
+    def __call__(self, frames):
+        return self._replay(frames)
 
 
 class PipelinedForward:
@@ -86,7 +110,7 @@ class PipelinedForward:
         # (measured: 5.35 ms/step with branches vs 4.0 ms without, 2 in flight)
         import os
         branch = os.environ.get("PWCLO_PIPE_BRANCH", "0") != "0"
-        self.slots = [GraphedForward(net, branch=branch) for _ in range(depth)]
+        self.slots = [self._make_slot(net, branch) for _ in range(depth)]
         # `streams`: reuse another pipeline's streams -- the runtime binds every new stream to the next
         # hardware queue round-robin, so a second set of streams in one process can collide with itself
         self.streams = list(streams) if streams is not None else None
@@ -94,19 +118,29 @@ class PipelinedForward:
         self.events = [None] * depth
         self._next = 0
 
-    def __call__(self, xyz_f1, xyz_f2):
+    def _make_slot(self, net, branch):
+        return GraphedForward(net, branch=branch)
+
+    def _submit(self, *inputs, after=None):
+        """Replay the next slot on its stream; ``after(out)``, if given, is queued on that stream behind the replay."""
+        dev = inputs[0].device
         if self.streams is None:
-            self.streams = [torch.cuda.Stream(device=xyz_f1.device) for _ in self.slots]
+            self.streams = [torch.cuda.Stream(device=dev) for _ in self.slots]
         i = self._next
         self._next = (i + 1) % len(self.slots)
         st = self.streams[i]
-        st.wait_stream(torch.cuda.current_stream(xyz_f1.device))   # inputs produced on the caller's stream
+        st.wait_stream(torch.cuda.current_stream(dev))   # inputs produced on the caller's stream
         with torch.cuda.stream(st):
-            out = self.slots[i](xyz_f1, xyz_f2)
+            out = self.slots[i](*inputs)
+            if after is not None:
+                after(out)
             ev = torch.cuda.Event()
             ev.record(st)
         self.events[i] = ev
         return out, i
+
+    def __call__(self, xyz_f1, xyz_f2):
+        return self._submit(xyz_f1, xyz_f2)
 
     def prepare(self, xyz_f1, xyz_f2):
         """Capture every slot's graph now (otherwise a slot is captured on its first use)."""
@@ -121,6 +155,68 @@ class PipelinedForward:
     def wait_all(self):
         for s in self.streams or []:
             s.synchronize()
+
+
+def sequence_windows(n, window):
+    """How ``PipelinedSequence`` covers an n-frame sequence with windows of ``window`` frames: [(start, length, first)].
+    Consecutive windows share their boundary frame; the last one is moved back to end at frame n - 1 and keeps the full
+    length (it then overlaps its predecessor by more than one frame), and ``first`` is the first of its pair rows that
+    no earlier window produced (0 for all others).  So every pair (i, i + 1) is taken from exactly one window, and every
+    window runs P = window - 1 pairs: the pair stage's kernel variants are chosen by the launch size (DESIGN.md section
+    10), so a short tail would not give the rows a full window gives.  A sequence shorter than a window is one window."""
+    if window < 2:
+        raise ValueError("sequence window must hold at least 2 frames (got %d)" % window)
+    if n < 2:
+        raise ValueError("a sequence needs at least 2 frames (got %d)" % n)
+    if n <= window:
+        return [(0, n, 0)]
+    step = window - 1
+    wins = [(s, window, 0) for s in range(0, n - window + 1, step)]
+    end = wins[-1][0] + window
+    if end < n:
+        wins.append((n - window, window, end - 1 - (n - window)))
+    return wins
+
+
+class PipelinedSequence(PipelinedForward):
+    """Poses of a long device sequence: ``PipelinedSequence(net, window=33, depth=4)(frames) -> rows (n-1, 4, 7)``,
+    frames (n, n_total, c) point-major on the net's device, row i = pair (frame i, frame i + 1) as
+    ``net.forward_sequence`` computes it.
+
+    The sequence is cut into windows of ``window`` frames that overlap by one frame (``sequence_windows``; the tail window
+    is moved back so that it is full-length too); each window is one replay of a captured ``forward_sequence``
+    (``GraphedSequence``), slots used round-robin on their own streams as in ``PipelinedForward``.  Windows share no
+    state (the overlap frame's pyramid runs in both), so slots pipeline freely.  Rows are bit-identical to
+    ``net.forward_sequence`` on each window; on the whole sequence wherever the pair stage picks the same kernel
+    variants for window - 1 and n - 1 pairs.  Each window's new rows are copied into the returned
+    tensor on the slot's stream behind the replay; the caller's stream waits for them, so the result is ready in stream
+    order and no host sync is made.  A sequence shorter than a window is captured once per length by its slot.  The
+    net's ``log_mode`` does not matter here (rows only)."""
+
+    def __init__(self, net, window=33, depth=4, num_points=None, streams=None):
+        if window < 2:
+            raise ValueError("sequence window must hold at least 2 frames (got %d)" % window)
+        self.window, self.num_points = int(window), num_points
+        super().__init__(net, depth=depth, streams=streams)
+
+    def _make_slot(self, net, branch):
+        return GraphedSequence(net, num_points=self.num_points, branch=branch)
+
+    def __call__(self, frames):
+        if not frames.is_cuda:
+            raise RuntimeError("CPU not supported")
+        n = frames.shape[0]
+        wins = sequence_windows(n, self.window)
+        rows = torch.empty((n - 1, 4, 7), dtype=torch.float32, device=frames.device)
+        used = set()
+        for start, length, first in wins:
+            dst = rows[start + first:start + length - 1]
+            copy = (lambda out, dst=dst, first=first: dst.copy_(out[first:]))
+            used.add(self._submit(frames[start:start + length], after=copy)[1])
+        main = torch.cuda.current_stream(frames.device)
+        for i in used:
+            main.wait_event(self.events[i])
+        return rows
 
 
 class StagedPipeline:

@@ -69,3 +69,9 @@ class PWCLONetPredictionModule(nn.Module):
         pts2 = f2[:, :n, 3:] if f2.size(-1) > 3 else None
         cf = lambda t: t.permute(0, 2, 1).contiguous() if t is not None else None            # :157-160
         return net(cf(xyz1), cf(pts1), cf(xyz2), cf(pts2), bn_decay=bn_decay)
+
+    def forward_sequence(self, frames):
+        """Poses of the consecutive pairs of a sequence window: frames (T, n_total, c>=3) point-major on the GPU ->
+        (pose_params (T-1, 4, 7), log_dict); row i = pair (frame i, frame i + 1) as ``forward`` computes it, with
+        ``num_points`` from the config (``PWCLONet.forward_sequence``)."""
+        return self.pwclonet.forward_sequence(frames, self.num_points)

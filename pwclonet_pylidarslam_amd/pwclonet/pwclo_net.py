@@ -196,19 +196,61 @@ class PWCLONet(nn.Module):
                 b.append(pointnet2_utils.sample_and_gather(b[-1], sa.npoint))
         return a, b
 
+    def _use_fused(self, x):
+        """Whether an eval-mode no-grad call on input ``x`` runs the fused kernels: packs the weights on the first such
+        call (``fused="auto"``) and re-packs after an in-place parameter / buffer edit (not while a graph is captured)."""
+        if self._fused is None and self.fuse_mode == "auto" and not self.training and not torch.is_grad_enabled() \
+                and x.is_cuda and not torch.cuda.is_current_stream_capturing():
+            self.prepare_fused()        # inference call of a drop-in user: same results within 1e-5, five times the speed
+        if self._fused is None or self.training or torch.is_grad_enabled():
+            return False
+        if not torch.cuda.is_current_stream_capturing() and self._state_versions() != self._fused_versions:
+            self.prepare_fused()            # a parameter / buffer was edited in place since packing
+        return True
+
+    def forward_sequence(self, frames, num_points=None):
+        """Poses of a frame sequence: frames (T, n_total, c>=3) point-major fp32 on the GPU, of which
+        ``[:, :num_points, :3]`` is used (``num_points`` defaults to n_total) -> (pose_params (T-1, 4, 7), log_dict).
+        Row i is the pose of the pair (frame i, frame i + 1), in ``forward``'s row format and bit for bit what the fused
+        ``forward`` gives for that pair; ``log_dict`` is ``forward``'s, over the T - 1 pairs.  Every frame's feature
+        pyramid runs once (``forward`` on the pairs runs every interior frame's twice).  Eval mode, no grad, fused path
+        only; packs / re-packs the weights exactly as ``forward`` does.
+
+        The reference's evaluation rows (frame 0 paired with itself, then (0, 1), (1, 2), ...; ``frame_ids`` = the second
+        frame's index) are ``forward_sequence(torch.cat((frames[:1], frames)))``.  One difference to the reference's data
+        path: its ``filter_pcd`` draws a fresh random subset every time a frame is loaded, so a frame gets two different
+        clouds in its two pairs; here every frame has one cloud (with deterministic preprocessing such as
+        ``preprocess.frames_to_clouds`` that is exactly the pair path's input)."""
+        if not frames.is_cuda:
+            raise RuntimeError("CPU not supported")
+        if frames.dim() != 3 or frames.dtype != torch.float32:
+            raise ValueError("forward_sequence: frames must be float32 (T, n_total, c), got %s %s"
+                             % (frames.dtype, tuple(frames.shape)))
+        T, n_total, c = frames.shape
+        num_points = n_total if num_points is None else int(num_points)
+        if T < 2:
+            raise ValueError("forward_sequence: need at least 2 frames (got T=%d)" % T)
+        if c < 3:
+            raise ValueError("forward_sequence: frames need at least 3 channels (got c=%d)" % c)
+        if num_points <= 0 or n_total < num_points:
+            raise ValueError("forward_sequence: frames hold %d points, num_points=%d" % (n_total, num_points))
+        if self.training:
+            raise RuntimeError("forward_sequence is eval-mode only: call .eval() first")
+        if torch.is_grad_enabled():
+            raise RuntimeError("forward_sequence runs without autograd: call it under torch.no_grad()")
+        if self.fuse_mode == "off":
+            raise RuntimeError('forward_sequence runs on the fused kernels, which config["fused"] = "off" disables')
+        if not self._use_fused(frames):
+            raise RuntimeError("forward_sequence: the fused weights are not packed (call prepare_fused() outside capture)")
+        pose, inter = self._fused.forward_sequence(frames, num_points, return_intermediates=True)
+        return pose, self._fused_log_dict(inter)
+
     def forward(self, xyz_f1, points_f1, xyz_f2, points_f2, bn_decay=None, samples=None):
         """``samples`` (not in the reference's signature): ``sample_pyramid(xyz_f1, xyz_f2)`` when the caller has
         already drawn it -- module path only."""
         if samples is not None and not (self.training and xyz_f1.is_cuda):
             return self._forward_modules(xyz_f1, points_f1, xyz_f2, points_f2, samples)
-        if self._fused is None and self.fuse_mode == "auto" and not self.training and not torch.is_grad_enabled() \
-                and points_f1 is None and points_f2 is None and xyz_f1.is_cuda \
-                and not torch.cuda.is_current_stream_capturing():
-            self.prepare_fused()        # inference call of a drop-in user: same results within 1e-5, five times the speed
-        if self._fused is not None and not self.training and not torch.is_grad_enabled() \
-                and points_f1 is None and points_f2 is None:
-            if not torch.cuda.is_current_stream_capturing() and self._state_versions() != self._fused_versions:
-                self.prepare_fused()            # a parameter / buffer was edited in place since packing
+        if points_f1 is None and points_f2 is None and self._use_fused(xyz_f1):
             pose, inter = self._fused(xyz_f1, xyz_f2, return_intermediates=True)
             return pose, self._fused_log_dict(inter)
         if self.training and xyz_f1.is_cuda:

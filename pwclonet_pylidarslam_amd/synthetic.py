@@ -109,3 +109,34 @@ def kitti_like_pair(seed, npoints=8192, batch=1):
         qs.append(np.array([np.cos(yaw / 2), 0.0, -np.sin(yaw / 2), 0.0], dtype=np.float32))
         ts.append(np.array([0.0, 0.0, fwd], dtype=np.float32))
     return np.stack(pcs1), np.stack(pcs2), np.stack(qs), np.stack(ts)
+
+
+def kitti_like_sequence(seed, npoints=8192, frames=9):
+    """Sequence generator: one sensor moving through one ray-cast scene, every step drawn by ``kitti_like_pair``'s
+    motion law (yaw ~ U(-2,2) deg, 0.5-1.5 m forward along the current heading).  Walls are drawn around points of the
+    path, so that every frame sees some.  Returns (pcs, q_gt, t_gt): float32 (frames, npoints, 4), (frames-1, 4)
+    scalar-first and (frames-1, 3): step i takes frame i to frame i + 1, in ``kitti_like_pair``'s convention (the
+    pair (pcs[i], pcs[i+1]) has ground truth (q_gt[i], t_gt[i])).  Raises if a frame has fewer than ``npoints``
+    usable points.  Own RNG stream: the pair generators' streams are untouched."""
+    if frames < 2:
+        raise ValueError("a sequence needs at least 2 frames (got %d)" % frames)
+    r = np.random.default_rng([seed, 0x5E9, frames])
+    yaws = np.deg2rad(r.uniform(-2.0, 2.0, frames - 1))
+    fwds = r.uniform(0.5, 1.5, frames - 1)
+    pos, head = [np.zeros(3)], [0.0]
+    for yaw, fwd in zip(yaws, fwds):
+        h = head[-1]
+        pos.append(pos[-1] + fwd * np.array([np.cos(h), np.sin(h), 0.0]))
+        head.append(h + yaw)
+    walls = []
+    for a in pos[::6]:                          # a _scene-like cluster of walls around every sixth sensor position
+        for wl in _scene(r):
+            walls.append(dict(wl, r=wl["r"] + a @ wl["n"], u0=wl["u0"] + a @ wl["m"]))
+    pcs = np.empty((frames, npoints, 4), dtype=np.float32)
+    for k in range(frames):
+        pcs[k, :, :3] = _to_camera_and_filter(r, _cast(r, walls, pos[k], head[k]), npoints)
+        pcs[k, :, 3] = r.uniform(0, 1, npoints)
+    # camera frame: yaw about velodyne z = rotation about camera -y; forward = camera z
+    q = np.stack([np.cos(yaws / 2), np.zeros_like(yaws), -np.sin(yaws / 2), np.zeros_like(yaws)], axis=1)
+    t = np.stack([np.zeros_like(fwds), np.zeros_like(fwds), fwds], axis=1)
+    return pcs, q.astype(np.float32), t.astype(np.float32)

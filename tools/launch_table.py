@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Developer tool: per-launch table of one eager fused forward (HIP events on the launch stream):
-kernel, time, algorithmic GFLOP / MB, achieved rate.  `--reps R` averages over R passes."""
+kernel, time, algorithmic GFLOP / MB, achieved rate.  `--reps R` averages over R passes.  `--sequence T`: one eager
+sequence window of T frames (PWCLONet.forward_sequence, synthetic.kitti_like_sequence, 4 channels per point: the
+ingest launch included) instead of the pair batch."""
 import argparse, os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -19,6 +21,7 @@ def main():
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--npoints", type=int, default=8192)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--sequence", type=int, default=0, help="T > 1: one T-frame sequence window instead of --batch pairs")
     ap.add_argument("--fake-knn", action="store_true", help="sequential neighbour lists (gather-cost probe)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -32,14 +35,20 @@ def main():
     torch.manual_seed(0)
     net = PWCLONet(dict(num_input_channels=3, sequence_len=2, device="cuda:0", scalar_last=False,
                         log_mode="none")).to(dev).eval().prepare_fused()
-    x1, x2 = bench.make_batch(a.batch, a.npoints, 1000, dev)
+    if a.sequence > 1:
+        from pwclonet_pylidarslam_amd import synthetic
+        frames = torch.from_numpy(synthetic.kitti_like_sequence(1000, a.npoints, a.sequence)[0]).to(dev)
+        fwd = lambda: net.forward_sequence(frames)
+    else:
+        x1, x2 = bench.make_batch(a.batch, a.npoints, 1000, dev)
+        fwd = lambda: net(x1, None, x2, None)
     with torch.no_grad():
-        for _ in range(3): net(x1, None, x2, None)
+        for _ in range(3): fwd()
         torch.cuda.synchronize()
         acc = None
         for _ in range(a.reps):
             rec = Rec(); _lib.profiler = rec
-            net(x1, None, x2, None)
+            fwd()
             _lib.profiler = None
             torch.cuda.synchronize()
             us = [s.elapsed_time(e) * 1e3 for _, _, s, e in rec.rows]
