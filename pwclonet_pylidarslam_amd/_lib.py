@@ -114,6 +114,7 @@ SIGNATURES = {
     "odom_rows_to_transforms_kernel_wrapper": ([_i, _i, _F, _F, _i], None),
     "odom_accumulate_kernel_wrapper": ([_i, _F, _F, _F], None),
     "odom_cumulative_distance_kernel_wrapper": ([_i, _F, _F, _F], None),
+    "odom_stream_append_kernel_wrapper": ([_i, _i, _i, _F, _i, _F, _F, _F, _F], None),
     "odom_sequence_errors_kernel_wrapper": ([_i, _i] + [_F] * 5 + [_i, _i] + [_F] * 3, None),
 }
 

@@ -863,6 +863,54 @@ class _Branches:
         self.wait(self.mark(k))
 
 
+class FrameState:
+    """What the pair stage reads from the pyramid of C clouds -- the state a streamed frame carries from one call to
+    the next.  ``x[l]`` / ``f[l]``: coordinates (C, N_l, 3) and features (C, N_l, c_l) of
+    pyramid level l + 1; ``built``: the kept neighbour-search structures (``knn_keep``) by pyramid cloud; ``idx4``:
+    psa_4's neighbour lists (flow_feature_encoding reuses them); ``cv``: the early cost-volume partial products by cost
+    volume as (u, v, u2) -- u / u2 computed from the frame-1 clouds, v from the frame-2 clouds (pair and sequence mode:
+    [0, P) and [o, o + P); a streamed frame: all of its clouds for all three)."""
+
+    # search structures the pair stage reads: as frame 1, the set-upconv lists of refinement levels 3, 2, 1 search
+    # pyramid clouds 4 (never kept: nothing searches psa_4's samples in the pyramid), 3, 2; as frame 2 the cost-volume
+    # lists search clouds 3, 2, 1
+    FRAME1_BUILT = (4, 3, 2)
+    FRAME2_BUILT = (3, 2, 1)
+
+    def __init__(self, x, f, built, idx4, cv):
+        self.x, self.f, self.built, self.idx4, self.cv = list(x), list(f), dict(built), idx4, dict(cv)
+
+    def frame1_tensors(self):
+        """Every tensor the pair stage reads from this state as frame 1, in a fixed order."""
+        out = self.x + self.f + [self.idx4]
+        out += [self.built[lvl][0] for lvl in self.FRAME1_BUILT if lvl in self.built]
+        for name in sorted(self.cv):
+            u, _, u2 = self.cv[name]
+            out += [u, u2]
+        return out
+
+    def frame1_buffers(self):
+        """A state of fresh buffers for what frame 1 reads (the frame-2-only parts left out): the persistent previous
+        frame of a captured stream step, filled by ``copy_frame1_``."""
+        e = torch.empty_like
+        built = {lvl: (e(self.built[lvl][0]),) + tuple(self.built[lvl][1:]) for lvl in self.FRAME1_BUILT
+                 if lvl in self.built}
+        cv = {name: (e(u), None, e(u2)) for name, (u, _, u2) in self.cv.items()}
+        return FrameState([e(t) for t in self.x], [e(t) for t in self.f], built, e(self.idx4), cv)
+
+    def frame1_bytes(self):
+        return sum(t.numel() * t.element_size() for t in self.frame1_tensors())
+
+    def copy_frame1_(self, src):
+        """Copy what frame 1 reads from ``src`` (a state of the same shapes) into this state's buffers, one ``copy_``
+        per tensor on the current stream."""
+        dst, srcs = self.frame1_tensors(), src.frame1_tensors()
+        assert len(dst) == len(srcs)
+        for d, s_ in zip(dst, srcs):
+            d.copy_(s_)
+        return self
+
+
 class FusedPWCLONet:
     """Eval-mode forward of a ``PWCLONet`` on the fused kernels (point-major activations).
 
@@ -993,14 +1041,20 @@ class FusedPWCLONet:
         used.  Every frame goes through the pyramid once; the pair stage then runs the T - 1 consecutive pairs
         (frame i, frame i + 1).  A contiguous fp32 (T, num_points, 3) batch (``preprocess.frames_to_clouds``) is used
         as it is, anything else goes through one ingest launch."""
+        assert frames.shape[0] >= 2
+        return self._sample_chain(self._ingest(frames, num_points), br, frames.shape[0] - 1, 1)
+
+    @staticmethod
+    def _ingest(frames, num_points):
+        """(T, n_total, c>=3) point-major frames -> the (T, num_points, 3) clouds: a contiguous fp32 (T, num_points, 3)
+        batch as it is, anything else through one ingest launch."""
         T, n_total, c = frames.shape
-        assert T >= 2 and c >= 3 and n_total >= num_points and frames.dtype == torch.float32
+        assert c >= 3 and n_total >= num_points and frames.dtype == torch.float32
         if c == 3 and n_total == num_points and frames.is_contiguous():
-            x = frames
-        else:
-            x = torch.empty((T, num_points, 3), dtype=torch.float32, device=frames.device)
-            _lib.call("ingest_sequence_kernel_wrapper", x.device, T, num_points, n_total, c, _p(frames.contiguous()), _p(x))
-        return self._sample_chain(x, br, T - 1, 1)
+            return frames
+        x = torch.empty((T, num_points, 3), dtype=torch.float32, device=frames.device)
+        _lib.call("ingest_sequence_kernel_wrapper", x.device, T, num_points, n_total, c, _p(frames.contiguous()), _p(x))
+        return x
 
     def _sample_chain(self, x, br, P, o):
         """``P`` pairs over the clouds of ``x``: frame 1 of pair i is cloud i, frame 2 cloud o + i."""
@@ -1035,20 +1089,24 @@ class FusedPWCLONet:
                 br.hold(flag)
         return dict(B=P, P=P, o=o, x=x, samples=samples, ready=ready, br=br, ws0=ws0)
 
+    # Early cost-volume products (hoisted): pyramid level whose features feed which cost volumes' u, v, u2
+    CV_EARLY = {1: ("pwr1",), 2: ("pwr2",), 3: ("cv3", "pwr3")}
+
+    def _cv(self, name):
+        return self.cv3 if name == "cv3" else self.pwr[{"pwr3": 0, "pwr2": 1, "pwr1": 2}[name]]["cv"]
+
     @torch.no_grad()
-    def rest(self, state, return_intermediates=False):
-        """Stage 2 -- neighbour search, feature pyramid, cost volumes, pose refinement."""
+    def pyramid(self, state, taps=None):
+        """Stage 2a -- neighbour search and set abstractions of the C clouds of ``state`` (``_sample_chain``) -> their
+        ``FrameState``.  The early cost-volume products take frame 1 from clouds [0, P) and frame 2 from [o, o + P)."""
         P, o, x, samples, ready, br = state["P"], state["o"], state["x"], state["samples"], state["ready"], state["br"]
         f = None
         lv = []
         reuse = os.environ.get("PWCLO_KNN_REUSE", "1") != "0"
         built = {}                       # pyramid level -> search structure of its C clouds (knn_keep)
-        # neighbour lists of every knn call (tests compare them with the oracle's); only when asked for
-        taps = {} if return_intermediates else None
-        early_users, cvj = {}, {}
+        early, cvj = {}, {}
         if self.hoist and os.environ.get("PWCLO_EARLY_CV", "1") != "0":
-            early_users = {1: [self.pwr[2]["cv"]], 2: [self.pwr[1]["cv"]], 3: [self.cv3, self.pwr[0]["cv"]]}
-        tails = self.hoist and os.environ.get("PWCLO_PW_TAIL", "1") != "0"
+            early = self.CV_EARLY
         for lvl, (fsa, (npoint, nsample)) in enumerate(zip(self.sa, self.sa_cfg)):
             br.wait(ready[lvl])
             new_x = samples[lvl]
@@ -1073,30 +1131,39 @@ class FusedPWCLONet:
                     jobs = fsa.jobs(f)
                     # `f` = the features of pyramid level `lvl` (both frames): the partial products the cost volumes take
                     # from them depend on nothing else -- same launch as this level's set-abstraction seeds
-                    users = early_users.get(lvl, [])
-                    for cv in users:
-                        jobs = jobs + cv.jobs(f[:P], f[o:o + P])
+                    users = early.get(lvl, ())
+                    for name in users:
+                        jobs = jobs + self._cv(name).jobs(f[:P], f[o:o + P])
                     outs = run_linear_jobs(jobs)
                     br.hold(*outs, None)
                     pre = outs[0]
-                    for i, cv in enumerate(users):
-                        cvj[id(cv)] = tuple(outs[1 + 3 * i:4 + 3 * i])
+                    for i, name in enumerate(users):
+                        cvj[name] = tuple(outs[1 + 3 * i:4 + 3 * i])
                 f = br.hold(fsa(x, new_x, pre, idx))
             else:
                 f = br.hold(fsa(x, new_x, f, idx))
             x = new_x
             lv.append((x, f))
-        (x11, f11), (x12, f12), (x13, f13), (x14, f14) = [(a[:P], b[:P]) for a, b in lv]
-        (x21, f21), (x22, f22), (x23, f23), _ = [(a[o:o + P], b[o:o + P]) for a, b in lv]
+        return FrameState([a for a, _ in lv], [b for _, b in lv], built, idx_last, cvj)
+
+    @torch.no_grad()
+    def pair_stage(self, fs1, fs2, P, o, br, taps=None, return_intermediates=False):
+        """Stage 2b -- cost volumes and pose refinement of P pairs: frame 1 = clouds [0, P) of ``fs1``, frame 2 = clouds
+        [o, o + P) of ``fs2`` (``FrameState``s: the same object in pair and sequence mode, the previous and the new
+        frame in a stream step).  Reads u / u2 of the early cost-volume products from ``fs1``, v from ``fs2``."""
+        tails = self.hoist and os.environ.get("PWCLO_PW_TAIL", "1") != "0"
+        (x11, f11), (x12, f12), (x13, f13), (x14, f14) = [(a[:P], b[:P]) for a, b in zip(fs1.x, fs1.f)]
+        (x21, f21), (x22, f22), (x23, f23), _ = [(a[o:o + P], b[o:o + P]) for a, b in zip(fs2.x, fs2.f)]
+        cvj = {name: (u, fs2.cv[name][1], u2) for name, (u, _, u2) in fs1.cv.items() if name in fs2.cv}
 
         # flow_feature_encoding samples the same cloud as psa_4(frame 1): reuse x14
         if self.ffe_cfg == self.sa_cfg[3] and os.environ.get("PWCLO_FFE_REUSE", "1") != "0":
             # same search as psa_4's on frame 1 (queries x14 among x13, same nsample; clouds are searched independently)
-            idx_ffe = idx_last[:P]
+            idx_ffe = fs1.idx4[:P]
         else:
             idx_ffe = knn(self.ffe_cfg[1], x13, x14)
         if self.hoist:
-            flow = self.cv3(x13, x23, *(cvj.get(id(self.cv3)) or run_linear_jobs(self.cv3.jobs(f13, f23))), taps=taps, tap="cv3")
+            flow = self.cv3(x13, x23, *(cvj.get("cv3") or run_linear_jobs(self.cv3.jobs(f13, f23))), taps=taps, tap="cv3")
             emb4 = self.ffe(x13, x14, run_linear_jobs(self.ffe.jobs(flow))[0], idx_ffe)
         else:
             flow = self.cv3(x13, f13, x23, f23, taps=taps, tap="cv3")
@@ -1104,34 +1171,45 @@ class FusedPWCLONet:
         if taps is not None:
             taps["ffe.knn_idx"] = idx_ffe
         mask4 = self.l4_pred(f14, emb4)
-        pose = torch.empty((P, 4, 7), dtype=torch.float32, device=x.device)   # rows = levels 1..4
+        pose = torch.empty((P, 4, 7), dtype=torch.float32, device=x11.device)   # rows = levels 1..4
+        # kept structures of refinement levels 3, 2, 1: set-upconv lists search frame 1, cost-volume lists frame 2
+        up = [fs1.built.get(lvl) for lvl in FrameState.FRAME1_BUILT]
+        qs = [fs2.built.get(lvl) for lvl in FrameState.FRAME2_BUILT]
         if os.environ.get("PWCLO_HEAD_WARP", "1") != "0":
             # every pose head also warps the next finer cloud with the pose it has just composed (one launch fewer per level)
             q4, t4, w3 = br.hold(*self.l4_head(emb4, mask4, pose, 3, warp_next=x13))
             c3, c2 = {}, {}
             q3, t3, emb3, mask3, w2 = self._refine(br, self.pwr[0], 2, pose, x13, f13, x23, f23, x14, emb4, mask4, q4, t4,
-                                                   taps, "pwr3", o=o, warped=w3, warp_next=x12, st_up=built.get(4), st_q=built.get(3),
-                                                   cvj=cvj.get(id(self.pwr[0]["cv"])), nxt=self.pwr[1] if tails else None, carry=c3)
+                                                   taps, "pwr3", o=o, warped=w3, warp_next=x12, st_up=up[0], st_q=qs[0],
+                                                   cvj=cvj.get("pwr3"), nxt=self.pwr[1] if tails else None, carry=c3)
             q2, t2, emb2, mask2, w1 = self._refine(br, self.pwr[1], 1, pose, x12, f12, x22, f22, x13, emb3, mask3, q3, t3,
-                                                   taps, "pwr2", o=o, warped=w2, warp_next=x11, st_up=built.get(3), st_q=built.get(2),
-                                                   cvj=cvj.get(id(self.pwr[1]["cv"])), pres=c3.get("pres"),
+                                                   taps, "pwr2", o=o, warped=w2, warp_next=x11, st_up=up[1], st_q=qs[1],
+                                                   cvj=cvj.get("pwr2"), pres=c3.get("pres"),
                                                    nxt=self.pwr[2] if tails else None, carry=c2)
             q1, t1, emb1, mask1 = self._refine(br, self.pwr[2], 0, pose, x11, f11, x21, f21, x12, emb2, mask2, q2, t2,
-                                               taps, "pwr1", o=o, warped=w1, st_up=built.get(2), st_q=built.get(1),
-                                               cvj=cvj.get(id(self.pwr[2]["cv"])), pres=c2.get("pres"))
+                                               taps, "pwr1", o=o, warped=w1, st_up=up[2], st_q=qs[2],
+                                               cvj=cvj.get("pwr1"), pres=c2.get("pres"))
         else:
             q4, t4 = self.l4_head(emb4, mask4, pose, 3)
             q3, t3, emb3, mask3 = self._refine(br, self.pwr[0], 2, pose, x13, f13, x23, f23, x14, emb4, mask4, q4, t4,
-                                               taps, "pwr3", o=o, st_up=built.get(4), st_q=built.get(3), cvj=cvj.get(id(self.pwr[0]["cv"])))
+                                               taps, "pwr3", o=o, st_up=up[0], st_q=qs[0], cvj=cvj.get("pwr3"))
             q2, t2, emb2, mask2 = self._refine(br, self.pwr[1], 1, pose, x12, f12, x22, f22, x13, emb3, mask3, q3, t3,
-                                               taps, "pwr2", o=o, st_up=built.get(3), st_q=built.get(2), cvj=cvj.get(id(self.pwr[1]["cv"])))
+                                               taps, "pwr2", o=o, st_up=up[1], st_q=qs[1], cvj=cvj.get("pwr2"))
             q1, t1, emb1, mask1 = self._refine(br, self.pwr[2], 0, pose, x11, f11, x21, f21, x12, emb2, mask2, q2, t2,
-                                               taps, "pwr1", o=o, st_up=built.get(2), st_q=built.get(1), cvj=cvj.get(id(self.pwr[2]["cv"])))
+                                               taps, "pwr1", o=o, st_up=up[2], st_q=qs[2], cvj=cvj.get("pwr1"))
         if return_intermediates:
             return pose, dict(x11=x11, f11=f11, f13=f13, flow=flow, emb4=emb4, mask4=mask4, emb3=emb3,
                               mask3=mask3, emb2=emb2, mask2=mask2, emb1=emb1, mask1=mask1, q=(q1, q2, q3, q4),
                               t=(t1, t2, t3, t4), lists=taps)
         return pose
+
+    @torch.no_grad()
+    def rest(self, state, return_intermediates=False):
+        """Stage 2 -- neighbour search and feature pyramid (``pyramid``), then cost volumes and pose refinement
+        (``pair_stage``) of the P pairs ``state`` addresses."""
+        taps = {} if return_intermediates else None     # neighbour lists of every knn call (tests compare them)
+        fs = self.pyramid(state, taps)
+        return self.pair_stage(fs, fs, state["P"], state["o"], state["br"], taps, return_intermediates)
 
     @torch.no_grad()
     def __call__(self, xyz_f1, xyz_f2, return_intermediates=False):
@@ -1150,3 +1228,28 @@ class FusedPWCLONet:
         """frames (T, n_total, c>=3) point-major -> pose_params (T-1, 4, 7): row i = pair (frame i, frame i + 1)."""
         br = _Branches(frames.device, self.branch and torch.cuda.is_current_stream_capturing())
         return self.rest(self.sample_sequence(frames, num_points, br), return_intermediates)
+
+    # ---- streaming: one frame of S streams per call, the previous frame's pyramid kept (DESIGN.md section 11) ----
+
+    @torch.no_grad()
+    def stream_prime(self, frames, num_points):
+        """First frame of S streams: frames (S, n_total, c>=3) point-major, of which ``[:, :num_points, :3]`` is used (as
+        ``sample_sequence``) -> its ``FrameState``.  Pyramid only; every cloud gets all three early cost-volume products
+        (u, u2 for its next pair, v for this one)."""
+        br = _Branches(frames.device, self.branch and torch.cuda.is_current_stream_capturing())
+        return self.pyramid(self._sample_chain(self._ingest(frames, num_points), br, frames.shape[0], 0))
+
+    @torch.no_grad()
+    def stream_step(self, prev_state, frames, num_points, return_intermediates=False):
+        """Pose of the pair (previous frame, this frame) of S streams.  ``prev_state``: the ``FrameState`` of the previous
+        call (``stream_prime`` / ``stream_step``) or a buffer copy of it (``FrameState.copy_frame1_``); frames as
+        ``stream_prime``.  The pyramid runs for the new frames only; the pair stage takes frame 1 from ``prev_state``
+        (clouds [0, S)) and frame 2 from the new state.  Rows are bit for bit the pair forward's at batch S.
+        -> (pose (S,4,7), new_state), or (pose, intermediates, new_state) with ``return_intermediates`` (the pyramid
+        lists ``psa_*`` are the new frames')."""
+        S = frames.shape[0]
+        br = _Branches(frames.device, self.branch and torch.cuda.is_current_stream_capturing())
+        taps = {} if return_intermediates else None
+        new = self.pyramid(self._sample_chain(self._ingest(frames, num_points), br, S, 0), taps)
+        out = self.pair_stage(prev_state, new, S, 0, br, taps, return_intermediates)
+        return (*out, new) if return_intermediates else (out, new)

@@ -1,0 +1,278 @@
+"""Online odometry: one pose per incoming frame, each frame's feature pyramid computed once.
+
+``StreamingOdometry`` runs S independent streams one frame at a time.  Frame k's pyramid (ingest, sampling chain,
+set abstractions, kept neighbour-search structures, the early cost-volume products) is computed when frame k arrives;
+it serves as frame 2 of pair (k-1, k) at once and as frame 1 of pair (k, k+1) on the next call
+(``FusedPWCLONet.stream_step``).  Pair mode (``PWCLONet.forward``) computes every frame's pyramid twice; sequence mode
+(``forward_sequence``) needs the whole window first.  The rows are bit for bit the fused pair forward's at batch S.
+
+Every step appends its level-1 poses to trajectories kept on the device (``odom_stream_append_kernel``, fp64):
+``relative_poses()[k]`` = quat2mat of pair (k-1, k)'s row (``evaluation.rows_to_transforms``, not inverted),
+``trajectory()[k]`` = their product (``evaluation.compute_absolute_poses``), row 0 the identity in both.
+
+``PWCLONetOdometry`` mirrors the reference's ``PoseNetOdometry`` / ``OdometryAlgorithm`` interface for one stream
+(``init``, ``process_next_frame``, ``get_relative_poses``, ...); Hydra / OmegaConf configs stay out of scope.
+"""
+import time
+
+import numpy as np
+import torch
+
+from . import _lib
+
+MAX_STREAMS = 1024          # odom_stream_append_kernel: one workgroup, one thread per stream
+
+
+def _p(t):
+    return t.data_ptr() if t is not None else 0
+
+
+class StreamingOdometry:
+    """``StreamingOdometry(net, streams=S)``; ``step(frames)`` with frames (S, n_total, c>=3) fp32 point-major on the
+    GPU (``[:, :num_points, :3]`` used; ``num_points`` defaults to the first frame's n_total and is fixed from then on)
+    -> pose_params (S, 4, 7) of the pair (previous frame, this frame), ``None`` for the first frame after ``reset()``.
+
+    ``net``: a ``PWCLONet`` in eval mode with its fused weights packed (or packable: ``fused="auto"``); call ``step``
+    under ``torch.no_grad()``.  ``graph=True`` replays one captured prime graph and one captured step graph per input
+    shape; the returned pose is then a static buffer that the next step overwrites (clone to keep it), as with
+    ``graphed.GraphedForward``.  ``max_frames``: capacity of the device trajectories; ``step`` raises once that many
+    frames have been recorded since ``reset()``."""
+
+    def __init__(self, net, streams=1, num_points=None, max_frames=4096, graph=True, warmup=1):
+        if not 1 <= int(streams) <= MAX_STREAMS:
+            raise ValueError("StreamingOdometry: streams=%d outside [1, %d]" % (int(streams), MAX_STREAMS))
+        if int(max_frames) < 1:
+            raise ValueError("StreamingOdometry: max_frames=%d must be >= 1" % int(max_frames))
+        if num_points is not None and int(num_points) <= 0:
+            raise ValueError("StreamingOdometry: num_points=%d must be > 0" % int(num_points))
+        self.net, self.streams, self.max_frames = net, int(streams), int(max_frames)
+        self.num_points = None if num_points is None else int(num_points)
+        self.graph, self.warmup = bool(graph), int(warmup)
+        self.frames_seen = 0
+        self._prev = None           # eager: the previous frame's FrameState
+        self._slot = None           # graph: persistent buffers of the previous frame (outside every graph pool)
+        self._graphs = {}           # input shape -> dict(static, prime, step)
+        self._fused_id = None
+        self._rel = self._abs = self._count = self._overflow = None
+        self.handover_bytes = 0     # bytes the captured step copies into the persistent previous frame
+
+    # ---- checks --------------------------------------------------------------------------------------------------
+
+    def _check(self, frames):
+        """The capacity, then forward_sequence's checks and messages, plus the stream's fixed shape.  -> num_points."""
+        net, what = self.net, "StreamingOdometry"
+        if self.frames_seen >= self.max_frames:           # before any launch: the device trajectories are full
+            raise RuntimeError("%s: max_frames=%d frames recorded since reset(); reset() or raise max_frames"
+                               % (what, self.max_frames))
+        if not frames.is_cuda:
+            raise RuntimeError("CPU not supported")
+        if frames.dim() != 3 or frames.dtype != torch.float32:
+            raise ValueError("%s: frames must be float32 (S, n_total, c), got %s %s" % (what, frames.dtype,
+                                                                                       tuple(frames.shape)))
+        S, n_total, c = frames.shape
+        if S != self.streams:
+            raise ValueError("%s: built for %d streams, got a frame batch of %d" % (what, self.streams, S))
+        if c < 3:
+            raise ValueError("%s: frames need at least 3 channels (got c=%d)" % (what, c))
+        num_points = n_total if self.num_points is None else self.num_points
+        if n_total < num_points:
+            raise ValueError("%s: frames hold %d points, num_points=%d (fixed when the stream was primed)"
+                             % (what, n_total, num_points))
+        if net.training:
+            raise RuntimeError("%s is eval-mode only: call .eval() first" % what)
+        if torch.is_grad_enabled():
+            raise RuntimeError("%s runs without autograd: call it under torch.no_grad()" % what)
+        if net.fuse_mode == "off":
+            raise RuntimeError('%s runs on the fused kernels, which config["fused"] = "off" disables' % what)
+        if not net._use_fused(frames):
+            raise RuntimeError("%s: the fused weights are not packed (call prepare_fused() outside capture)" % what)
+        return num_points
+
+    # ---- public interface ----------------------------------------------------------------------------------------
+
+    def reset(self):
+        """Start new sequences on all S streams: the next ``step`` primes and returns None."""
+        self.frames_seen = 0
+        self._prev = None
+        if self._overflow is not None:
+            self._overflow.zero_()
+
+    def step(self, frames):
+        num_points = self._check(frames)
+        if self.num_points is None:
+            self.num_points = num_points       # fixed from the first frame on: the persistent state has its shapes
+        fused = self.net._fused
+        if id(fused) != self._fused_id:        # re-packed weights (load_state_dict, prepare_fused): capture again
+            self._graphs.clear()
+            self._fused_id = id(fused)
+        if self._rel is None:
+            self._alloc(frames.device)
+        prime = self.frames_seen == 0
+        if self.graph:
+            pose = self._replay(fused, frames, prime)
+        elif prime:
+            self._prev = fused.stream_prime(frames, self.num_points)
+            self._append(None)
+            pose = None
+        else:
+            pose, self._prev = fused.stream_step(self._prev, frames, self.num_points)
+            self._append(pose)
+        self.frames_seen += 1
+        return pose
+
+    def relative_poses(self):
+        """(frames_seen, S, 4, 4) fp64 device view: row 0 the identity, row k the transform of pair (k-1, k)."""
+        return self._view(self._rel)
+
+    def trajectory(self):
+        """(frames_seen, S, 4, 4) fp64 device view: the absolute poses, products of ``relative_poses()``."""
+        return self._view(self._abs)
+
+    def overflowed(self):
+        """Whether the device ever refused an append for lack of capacity (the host check makes this unreachable)."""
+        return self._overflow is not None and bool(self._overflow.item())
+
+    # ---- internals ------------------------------------------------------------------------------------------------
+
+    def _view(self, buf):
+        if buf is None:
+            return torch.empty((0, self.streams, 4, 4), dtype=torch.float64)
+        return buf[:self.frames_seen]
+
+    def _alloc(self, device):
+        shape = (self.max_frames, self.streams, 4, 4)
+        self._rel = torch.zeros(shape, dtype=torch.float64, device=device)
+        self._abs = torch.zeros(shape, dtype=torch.float64, device=device)
+        self._count = torch.zeros((1,), dtype=torch.int32, device=device)
+        self._overflow = torch.zeros((1,), dtype=torch.int32, device=device)
+
+    def _append(self, pose):
+        """One launch: prime (pose None) or append the level-1 rows of pose (S,4,7) to the device trajectories."""
+        rows = pose[:, 0, :] if pose is not None else None
+        _lib.call("odom_stream_append_kernel_wrapper", self._rel.device, self.streams, self.max_frames,
+                  int(pose is None), _p(rows), int(rows.stride(0)) if rows is not None else 0, _p(self._rel),
+                  _p(self._abs), _p(self._count), _p(self._overflow))
+
+    def _warm(self, fn):
+        """Allocator warm-up and one-time kernel attributes on a side stream, as ``GraphedForward`` does."""
+        dev = self._rel.device
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side), torch.no_grad():
+            out = None
+            for _ in range(max(1, self.warmup)):
+                out = fn()
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+        return out
+
+    def _capture(self, fn):
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph), torch.no_grad():
+            out = fn()
+        return graph, out
+
+    def _replay(self, fused, frames, prime):
+        key = (tuple(frames.shape), frames.device)
+        entry = self._graphs.get(key)
+        if entry is None:
+            entry = self._graphs[key] = dict(static=frames.clone(), prime=None, step=None)
+        static, n = entry["static"], self.num_points
+        if prime and entry["prime"] is None:
+            first = self._warm(lambda: fused.stream_prime(static, n))
+            if self._slot is None:
+                # persistent previous frame, allocated outside every graph pool and filled with a real state at once
+                # (a step must never read uninitialised search structures)
+                self._slot = first.frame1_buffers().copy_frame1_(first)
+                self.handover_bytes = self._slot.frame1_bytes()
+
+            def prime_body():
+                self._slot.copy_frame1_(fused.stream_prime(static, n))
+                self._append(None)
+            entry["prime"] = self._capture(prime_body)[0]
+        if not prime and entry["step"] is None:
+            self._warm(lambda: fused.stream_step(self._slot, static, n))
+
+            def step_body():
+                pose, new = fused.stream_step(self._slot, static, n)
+                self._append(pose)
+                # The handover: every branch of the pair stage that reads the previous frame (the set-upconvs on side
+                # streams included) has been joined into this stream by now, so the copy is ordered after them.
+                self._slot.copy_frame1_(new)
+                return pose
+            entry["step"] = self._capture(step_body)
+        static.copy_(frames)
+        if prime:
+            entry["prime"].replay()
+            return None
+        graph, pose = entry["step"]
+        graph.replay()
+        return pose
+
+
+class PWCLONetOdometry:
+    """One-stream odometry with the interface of the reference's ``PoseNetOdometry`` (``slam/odometry``):
+    ``init()`` loads ``torch.load(checkpoint_path)["prediction_module"]`` and starts a new sequence,
+    ``process_next_frame(data_dict)`` reads ``data_dict["numpy_pc"]`` ((n, c) array or tensor) and writes the (4, 4)
+    relative pose of (previous frame, this frame) to ``data_dict["odometry_pose"]`` (the identity for the first frame),
+    ``get_relative_poses()`` -> (n, 4, 4) float32, first row the identity.  Poses follow ``evaluation``'s convention
+    (quat2mat of the level-1 row, not inverted).  Frames need at least ``num_points`` of the prediction config points;
+    the first ``num_points`` are used."""
+
+    def __init__(self, prediction_module_or_config, checkpoint_path=None, device="cuda:0", graph=True,
+                 max_frames=4096):
+        from .prediction import PWCLONetPredictionModule
+        self.device = torch.device(device)
+        mod = prediction_module_or_config
+        if not isinstance(mod, PWCLONetPredictionModule):
+            cfg = dict(mod)
+            cfg.setdefault("device", str(self.device))
+            mod = PWCLONetPredictionModule(cfg)
+        self.prediction_module = mod.to(self.device).eval()
+        self.checkpoint_path = checkpoint_path
+        self.elapsed = []
+        self.stream = StreamingOdometry(mod.pwclonet, streams=1, num_points=mod.num_points, max_frames=max_frames,
+                                        graph=graph)
+
+    def init(self):
+        """Start of a sequence: clears the elapsed times and the trajectory, loads the checkpoint if one is given."""
+        self.elapsed = []
+        if self.checkpoint_path is not None:
+            state_dict = torch.load(self.checkpoint_path, map_location=self.device)
+            self.prediction_module.load_state_dict(state_dict["prediction_module"])
+        self.prediction_module.eval()
+        self.stream.reset()
+
+    def process_next_frame(self, data_dict):
+        beginning = time.time()
+        self.do_process_next_frame(data_dict)
+        self.elapsed.append(time.time() - beginning)
+
+    def do_process_next_frame(self, data_dict):
+        pc = data_dict[self.input_key()]
+        pc = torch.from_numpy(np.ascontiguousarray(pc)) if isinstance(pc, np.ndarray) else pc
+        if pc.dim() != 2:
+            raise ValueError("PWCLONetOdometry: %s must be one (n, c) frame, got shape %s"
+                             % (self.input_key(), tuple(pc.shape)))
+        frame = pc.to(self.device, torch.float32)[None]
+        with torch.no_grad():
+            self.stream.step(frame)
+        data_dict[self.relative_pose_key()] = self.stream.relative_poses()[-1, 0].float().cpu().numpy()
+
+    def get_relative_poses(self):
+        return self.stream.relative_poses()[:, 0].float().cpu().numpy()
+
+    def get_elapsed(self):
+        return sum(self.elapsed)
+
+    @staticmethod
+    def input_key():
+        return "numpy_pc"
+
+    @staticmethod
+    def pointcloud_key():
+        return "odometry_pc"
+
+    @staticmethod
+    def relative_pose_key():
+        return "odometry_pose"
