@@ -384,6 +384,14 @@ void compact_frames_kernel_wrapper(int b, int n, int cap, const int *keep, const
                                    float *out, int *counts);
 /* The same compaction with the scan inside (no `pos` input): one workgroup per frame, ballot / popcount slots, stable. */
 void compact_frames_scan_kernel_wrapper(int b, int n, int cap, const int *keep, const float *xyz, float *out, int *counts);
+/* Filter + compaction of S raw sweeps of different lengths in one launch (one workgroup per stream): sweeps (S,R,4) f32
+ * with row stride R (16-byte aligned), lengths (S) i32 in DEVICE memory (clamped to [0, R]; only rows [0, lengths[s])
+ * are read).  dataset 0: KITTI, tr (S,3,4) f64 per-stream calibration on the device (ground_z / near unused); dataset 1:
+ * KITTI-360 with ground_z / near (tr unused).  Same per-row arithmetic as the two filters above.  packed (S,cap,3) f32:
+ * survivors in frame order, then zero rows up to cap, ALL written by the kernel (no caller zero-fill); counts (S) i32 =
+ * min(kept, cap). */
+void sweep_filter_compact_kernel_wrapper(int S, int R, int cap, const int *lengths, const float *sweeps, int dataset,
+                                         const double *tr, float ground_z, float near, float *packed, int *counts);
 
 /* ---- 3b. module-path layers: training-mode BatchNorm, stack tails, pointwise convolution ---- */
 

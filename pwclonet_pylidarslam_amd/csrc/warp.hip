@@ -101,15 +101,9 @@ __global__ __launch_bounds__(256) void ingest_sequence_kernel(int n, int n_total
 // Raw KITTI velodyne frame -> camera-frame cloud + keep mask (kitti_odometry_dataset.py:375-397 and
 // filter_pcd :149-160): p' = Tr[:3,:4] . (x, y, z, 1) in fp64 like the reference's numpy matmul on the
 // float64-promoted points, keep = not ground (y' <= 1.1) and |x'| < 30 and |z'| < 30 (strict, as
-// the reference's `<` / `>`), coordinates stored as fp32.  One thread per point; HBM-trivial
-// (16 bytes in, 16 bytes out per point).
-__global__ __launch_bounds__(256) void kitti_transform_filter_kernel(int n, const double *__restrict__ tr,
-                                                                     const float *__restrict__ points,
-                                                                     float *__restrict__ xyz,
-                                                                     int *__restrict__ keep) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const float4 p = *reinterpret_cast<const float4 *>(points + (size_t)i * 4);   // (x, y, z, intensity)
+// the reference's `<` / `>`), coordinates stored as fp32.  One row; shared by kitti_transform_filter_kernel and
+// sweep_filter_compact_kernel, so both give the same bits.
+__device__ __forceinline__ bool kitti_row(const float4 p, const double *__restrict__ tr, float o3[3]) {
   const double x = p.x, y = p.y, z = p.z;
   double o[3];
 #pragma unroll
@@ -117,27 +111,52 @@ __global__ __launch_bounds__(256) void kitti_transform_filter_kernel(int n, cons
     o[r] = ((tr[r * 4 + 0] * x + tr[r * 4 + 1] * y) + tr[r * 4 + 2] * z) + tr[r * 4 + 3];
   const bool ground = o[1] > 1.1;
   const bool near = (o[0] < 30.0 && o[0] > -30.0) && (o[2] < 30.0 && o[2] > -30.0);
-  xyz[(size_t)i * 3 + 0] = (float)o[0];
-  xyz[(size_t)i * 3 + 1] = (float)o[1];
-  xyz[(size_t)i * 3 + 2] = (float)o[2];
-  keep[i] = (!ground && near) ? 1 : 0;
+  o3[0] = (float)o[0];
+  o3[1] = (float)o[1];
+  o3[2] = (float)o[2];
+  return !ground && near;
 }
 
 // KITTI-360 front end (slam/dataset/kitti_360_dataset_2.py:113-123): raw velodyne rows stay in the sensor
 // frame; keep = not ground (z >= ground_z) and |x| < near and |y| < near, compared in fp32 as NumPy
-// compares a float32 column with a Python scalar.  xyz = the first three columns.
+// compares a float32 column with a Python scalar.  xyz = the first three columns.  One row, shared as kitti_row.
+__device__ __forceinline__ bool kitti360_row(const float4 p, float ground_z, float near, float o3[3]) {
+  const bool ground = p.z < ground_z;
+  const bool close = (p.x < near && p.x > -near) && (p.y < near && p.y > -near);
+  o3[0] = p.x;
+  o3[1] = p.y;
+  o3[2] = p.z;
+  return !ground && close;
+}
+
+// One thread per point; HBM-trivial (16 bytes in, 16 bytes out per point).
+__global__ __launch_bounds__(256) void kitti_transform_filter_kernel(int n, const double *__restrict__ tr,
+                                                                     const float *__restrict__ points,
+                                                                     float *__restrict__ xyz,
+                                                                     int *__restrict__ keep) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float4 p = *reinterpret_cast<const float4 *>(points + (size_t)i * 4);   // (x, y, z, intensity)
+  float o[3];
+  const bool k = kitti_row(p, tr, o);
+  xyz[(size_t)i * 3 + 0] = o[0];
+  xyz[(size_t)i * 3 + 1] = o[1];
+  xyz[(size_t)i * 3 + 2] = o[2];
+  keep[i] = k ? 1 : 0;
+}
+
 __global__ __launch_bounds__(256) void kitti360_filter_kernel(int n, float ground_z, float near,
                                                               const float *__restrict__ points,
                                                               float *__restrict__ xyz, int *__restrict__ keep) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const float4 p = *reinterpret_cast<const float4 *>(points + (size_t)i * 4);
-  const bool ground = p.z < ground_z;
-  const bool close = (p.x < near && p.x > -near) && (p.y < near && p.y > -near);
-  xyz[(size_t)i * 3 + 0] = p.x;
-  xyz[(size_t)i * 3 + 1] = p.y;
-  xyz[(size_t)i * 3 + 2] = p.z;
-  keep[i] = (!ground && close) ? 1 : 0;
+  float o[3];
+  const bool k = kitti360_row(p, ground_z, near, o);
+  xyz[(size_t)i * 3 + 0] = o[0];
+  xyz[(size_t)i * 3 + 1] = o[1];
+  xyz[(size_t)i * 3 + 2] = o[2];
+  keep[i] = k ? 1 : 0;
 }
 
 // Stable per-frame compaction of the kept rows: pos = inclusive scan of keep along the frame, row i of
@@ -199,6 +218,60 @@ __global__ __launch_bounds__(1024) void compact_frames_scan_kernel(int n, int ca
   if (threadIdx.x == 0) counts[f] = all < cap ? all : cap;
 }
 
+// Raw sweeps of S streams, each of its own length, -> packed survivors in ONE launch (StreamingOdometry.step_sweeps,
+// DESIGN.md section 12): the filters' row bodies above + compact_frames_scan_kernel's layout (one 1024-thread workgroup
+// per stream, ballot / popcount counting pass, LDS scan of the 16 wave totals, writing pass; the row is evaluated again
+// in the writing pass rather than kept: 16 bytes per row, HBM-trivial next to the sampler).  The length is read from
+// device memory and only rows [0, length) of the stream are touched, so one captured graph serves every length up to R.
+// The kernel also zeroes rows [count, cap) of its output: a persistent buffer never shows the previous sweep's survivors.
+template <bool KITTI>
+__global__ __launch_bounds__(1024) void sweep_filter_compact_kernel(int R, int cap, const int *__restrict__ lengths,
+                                                                    const float *__restrict__ sweeps,
+                                                                    const double *__restrict__ tr, float ground_z,
+                                                                    float near, float *__restrict__ packed,
+                                                                    int *__restrict__ counts) {
+  __shared__ int wave_total[16];
+  const int s = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int n = min(max(lengths[s], 0), R);
+  const int per_wave = ((n + 15) / 16 + 63) / 64 * 64;          // multiple of 64: steps never straddle two waves' ranges
+  const int i0 = wave * per_wave, i1 = min(n, i0 + per_wave);
+  const float *sf = sweeps + (size_t)s * R * 4;
+  const double *ts = KITTI ? tr + (size_t)s * 12 : nullptr;
+  auto row = [&](int i, float o[3]) {
+    const float4 p = *reinterpret_cast<const float4 *>(sf + (size_t)i * 4);
+    return KITTI ? kitti_row(p, ts, o) : kitti360_row(p, ground_z, near, o);
+  };
+  int total = 0;
+  for (int i = i0 + lane; i - lane < i1; i += 64) {
+    float o[3];
+    total += __popcll(__ballot(i < i1 && row(i, o)));
+  }
+  if (lane == 0) wave_total[wave] = total;
+  __syncthreads();
+  int base = 0, all = 0;
+  for (int w = 0; w < 16; ++w) {
+    const int t = wave_total[w];
+    if (w < wave) base += t;
+    all += t;
+  }
+  float *of = packed + (size_t)s * cap * 3;
+  for (int i = i0 + lane; i - lane < i1; i += 64) {
+    float o[3];
+    const bool k = i < i1 && row(i, o);
+    const unsigned long long m = __ballot(k);
+    const int p = base + mbcnt64(m);
+    if (k && p < cap) {
+      of[(size_t)p * 3 + 0] = o[0];
+      of[(size_t)p * 3 + 1] = o[1];
+      of[(size_t)p * 3 + 2] = o[2];
+    }
+    base += __popcll(m);
+  }
+  const int count = all < cap ? all : cap;
+  for (size_t j = (size_t)count * 3 + threadIdx.x; j < (size_t)cap * 3; j += 1024) of[j] = 0.0f;   // disjoint from the survivors
+  if (threadIdx.x == 0) counts[s] = count;
+}
+
 }  // namespace pwclo
 
 using namespace pwclo;
@@ -236,6 +309,24 @@ extern "C" void compact_frames_scan_kernel_wrapper(int b, int n, int cap, const 
   PWCLO_REQUIRE(cap > 0 && (long long)n * 3 < (1ll << 31), "compact_frames_scan: n=%d cap=%d out of range", n, cap);
   hipLaunchKernelGGL(compact_frames_scan_kernel, dim3(b), dim3(1024), 0, current_stream(), n, cap, keep, xyz, out, counts);
   check_launch("compact_frames_scan");
+}
+
+extern "C" void sweep_filter_compact_kernel_wrapper(int S, int R, int cap, const int *lengths, const float *sweeps, int dataset,
+                                                    const double *tr, float ground_z, float near, float *packed, int *counts) {
+  if (S <= 0) return;
+  PWCLO_REQUIRE(R > 0 && cap > 0 && (long long)R * 4 < (1ll << 31) && (long long)cap * 3 < (1ll << 31),
+                "sweep_filter_compact: R=%d cap=%d out of range", R, cap);
+  PWCLO_REQUIRE(dataset == 0 || dataset == 1, "sweep_filter_compact: dataset=%d (0 = KITTI, 1 = KITTI-360)", dataset);
+  PWCLO_REQUIRE(lengths != nullptr && sweeps != nullptr && packed != nullptr && counts != nullptr &&
+                (dataset == 1 || tr != nullptr), "sweep_filter_compact: lengths, sweeps, outputs (and tr for KITTI) are required%s", "");
+  PWCLO_REQUIRE((reinterpret_cast<uintptr_t>(sweeps) & 15) == 0, "sweep_filter_compact: sweeps must be 16-byte aligned%s", "");
+  if (dataset == 0)
+    hipLaunchKernelGGL(sweep_filter_compact_kernel<true>, dim3(S), dim3(1024), 0, current_stream(), R, cap, lengths, sweeps,
+                       tr, ground_z, near, packed, counts);
+  else
+    hipLaunchKernelGGL(sweep_filter_compact_kernel<false>, dim3(S), dim3(1024), 0, current_stream(), R, cap, lengths, sweeps,
+                       tr, ground_z, near, packed, counts);
+  check_launch("sweep_filter_compact");
 }
 
 extern "C" void ingest_frames_kernel_wrapper(int b, int n, int n_total, int c, const float *frame1,

@@ -18,9 +18,10 @@ import time
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, preprocess
 
 MAX_STREAMS = 1024          # odom_stream_append_kernel: one workgroup, one thread per stream
+RAW_NUM_POINTS = 8192       # raw mode: points sampled from every sweep's survivors (BASELINE configs[4])
 
 
 def _p(t):
@@ -36,9 +37,16 @@ class StreamingOdometry:
     under ``torch.no_grad()``.  ``graph=True`` replays one captured prime graph and one captured step graph per input
     shape; the returned pose is then a static buffer that the next step overwrites (clone to keep it), as with
     ``graphed.GraphedForward``.  ``max_frames``: capacity of the device trajectories; ``step`` raises once that many
-    frames have been recorded since ``reset()``."""
+    frames have been recorded since ``reset()``.
 
-    def __init__(self, net, streams=1, num_points=None, max_frames=4096, graph=True, warmup=1):
+    Raw mode (``sweeps=dict(dataset="kitti360" | "kitti", capacity=131072, near_threshold=30.0, tr=...)``):
+    ``step_sweeps(sweeps, lengths)`` takes raw LiDAR sweeps (S, R <= capacity, 4) fp32 on the GPU, stream s using rows
+    ``[:lengths[s]]``, and runs filter + compaction + exact sampling to ``num_points`` (default 8192) inside the same
+    prime / step graphs: one capture of each serves every length.  The clouds are bit for bit
+    those of ``preprocess.frames_to_clouds(sweep[None, :length], num_points, dataset, cap=capacity)``;
+    ``survivor_counts()`` tells a caller which streams kept fewer than ``num_points`` points."""
+
+    def __init__(self, net, streams=1, num_points=None, max_frames=4096, graph=True, warmup=1, sweeps=None):
         if not 1 <= int(streams) <= MAX_STREAMS:
             raise ValueError("StreamingOdometry: streams=%d outside [1, %d]" % (int(streams), MAX_STREAMS))
         if int(max_frames) < 1:
@@ -51,19 +59,38 @@ class StreamingOdometry:
         self.frames_seen = 0
         self._prev = None           # eager: the previous frame's FrameState
         self._slot = None           # graph: persistent buffers of the previous frame (outside every graph pool)
-        self._graphs = {}           # input shape -> dict(static, prime, step)
+        self._graphs = {}           # input shape (or "sweeps") -> dict(static, prime, step)
         self._fused_id = None
         self._rel = self._abs = self._count = self._overflow = None
         self.handover_bytes = 0     # bytes the captured step copies into the persistent previous frame
+        self._front = None          # raw mode: preprocess.SweepFrontEnd (persistent sweep, lengths, tr, sampler buffers)
+        if sweeps is not None:
+            if self.num_points is None:
+                self.num_points = RAW_NUM_POINTS
+            self._front = preprocess.SweepFrontEnd(self.streams, self.num_points, **dict(sweeps))
 
     # ---- checks --------------------------------------------------------------------------------------------------
 
-    def _check(self, frames):
-        """The capacity, then forward_sequence's checks and messages, plus the stream's fixed shape.  -> num_points."""
-        net, what = self.net, "StreamingOdometry"
+    def _check_room(self, what):
         if self.frames_seen >= self.max_frames:           # before any launch: the device trajectories are full
             raise RuntimeError("%s: max_frames=%d frames recorded since reset(); reset() or raise max_frames"
                                % (what, self.max_frames))
+
+    def _check_net(self, x, what):
+        net = self.net
+        if net.training:
+            raise RuntimeError("%s is eval-mode only: call .eval() first" % what)
+        if torch.is_grad_enabled():
+            raise RuntimeError("%s runs without autograd: call it under torch.no_grad()" % what)
+        if net.fuse_mode == "off":
+            raise RuntimeError('%s runs on the fused kernels, which config["fused"] = "off" disables' % what)
+        if not net._use_fused(x):
+            raise RuntimeError("%s: the fused weights are not packed (call prepare_fused() outside capture)" % what)
+
+    def _check(self, frames):
+        """The capacity, then forward_sequence's checks and messages, plus the stream's fixed shape.  -> num_points."""
+        what = "StreamingOdometry"
+        self._check_room(what)
         if not frames.is_cuda:
             raise RuntimeError("CPU not supported")
         if frames.dim() != 3 or frames.dtype != torch.float32:
@@ -78,45 +105,76 @@ class StreamingOdometry:
         if n_total < num_points:
             raise ValueError("%s: frames hold %d points, num_points=%d (fixed when the stream was primed)"
                              % (what, n_total, num_points))
-        if net.training:
-            raise RuntimeError("%s is eval-mode only: call .eval() first" % what)
-        if torch.is_grad_enabled():
-            raise RuntimeError("%s runs without autograd: call it under torch.no_grad()" % what)
-        if net.fuse_mode == "off":
-            raise RuntimeError('%s runs on the fused kernels, which config["fused"] = "off" disables' % what)
-        if not net._use_fused(frames):
-            raise RuntimeError("%s: the fused weights are not packed (call prepare_fused() outside capture)" % what)
+        self._check_net(frames, what)
         return num_points
 
     # ---- public interface ----------------------------------------------------------------------------------------
 
-    def reset(self):
-        """Start new sequences on all S streams: the next ``step`` primes and returns None."""
+    def reset(self, tr=None):
+        """Start new sequences on all S streams: the next ``step`` primes and returns None.  ``tr``: raw KITTI mode, the
+        new sequences' calibration (as ``set_calibration``)."""
+        if tr is not None:
+            self.set_calibration(tr)
         self.frames_seen = 0
         self._prev = None
         if self._overflow is not None:
             self._overflow.zero_()
 
+    def set_calibration(self, tr):
+        """Raw KITTI mode: replace the calibration, (3,4) / (4,4) for all streams or (S,3,4) / (S,4,4) per stream.  It lives
+        in a device buffer the captured graphs read, so no new capture follows."""
+        if self._front is None:
+            raise RuntimeError("StreamingOdometry: set_calibration needs raw mode (sweeps=dict(...))")
+        self._front.set_calibration(tr)
+
+    def survivor_counts(self):
+        """Raw mode: (S,) int32 device view of the last sweep's survivor counts (min(kept, capacity)); a stream below
+        ``num_points`` got index-0 repeats past its count.  None before the first sweep."""
+        if self._front is None or self._front.bufs is None:
+            return None
+        return self._front.bufs["counts"]
+
     def step(self, frames):
         num_points = self._check(frames)
         if self.num_points is None:
             self.num_points = num_points       # fixed from the first frame on: the persistent state has its shapes
-        fused = self.net._fused
-        if id(fused) != self._fused_id:        # re-packed weights (load_state_dict, prepare_fused): capture again
-            self._graphs.clear()
-            self._fused_id = id(fused)
-        if self._rel is None:
-            self._alloc(frames.device)
+        fused = self._begin(frames.device)
         prime = self.frames_seen == 0
         if self.graph:
-            pose = self._replay(fused, frames, prime)
-        elif prime:
-            self._prev = fused.stream_prime(frames, self.num_points)
-            self._append(None)
-            pose = None
+            key = (tuple(frames.shape), frames.device)
+            entry = self._graphs.get(key)
+            if entry is None:
+                entry = self._graphs[key] = dict(static=frames.clone(), prime=None, step=None)
+            static = entry["static"]
+            static.copy_(frames)
+            pose = self._replay(fused, entry, lambda: static, prime)
         else:
-            pose, self._prev = fused.stream_step(self._prev, frames, self.num_points)
-            self._append(pose)
+            pose = self._eager(fused, frames, prime)
+        self.frames_seen += 1
+        return pose
+
+    def step_sweeps(self, sweeps, lengths):
+        """Raw mode: sweeps (S, R <= capacity, 4) fp32 on the GPU, lengths (S,) host integers in [1, R] or a device
+        integer tensor (read on the device; clamped to [0, R] there) -> pose as ``step``.  The host copies the rows
+        ``[:R]`` and the lengths into static buffers; filter, compaction and sampling run inside the captured graphs."""
+        what = "StreamingOdometry"
+        front = self._front
+        if front is None:
+            raise RuntimeError("%s: step_sweeps needs raw mode (StreamingOdometry(..., sweeps=dict(dataset=..., "
+                               "capacity=...)))" % what)
+        self._check_room(what)
+        host_lengths = front.check(sweeps, lengths, what)
+        self._check_net(sweeps, what)
+        fused = self._begin(sweeps.device)
+        front.load(sweeps, lengths, host_lengths)
+        prime = self.frames_seen == 0
+        if self.graph:
+            entry = self._graphs.get("sweeps")
+            if entry is None:
+                entry = self._graphs["sweeps"] = dict(static=None, prime=None, step=None)
+            pose = self._replay(fused, entry, front.run, prime)
+        else:
+            pose = self._eager(fused, front.run(), prime)
         self.frames_seen += 1
         return pose
 
@@ -133,6 +191,25 @@ class StreamingOdometry:
         return self._overflow is not None and bool(self._overflow.item())
 
     # ---- internals ------------------------------------------------------------------------------------------------
+
+    def _begin(self, device):
+        """After the checks: the packed weights (a re-pack drops the graphs), the device trajectories."""
+        fused = self.net._fused
+        if id(fused) != self._fused_id:        # re-packed weights (load_state_dict, prepare_fused): capture again
+            self._graphs.clear()
+            self._fused_id = id(fused)
+        if self._rel is None:
+            self._alloc(device)
+        return fused
+
+    def _eager(self, fused, frames, prime):
+        if prime:
+            self._prev = fused.stream_prime(frames, self.num_points)
+            self._append(None)
+            return None
+        pose, self._prev = fused.stream_step(self._prev, frames, self.num_points)
+        self._append(pose)
+        return pose
 
     def _view(self, buf):
         if buf is None:
@@ -172,14 +249,13 @@ class StreamingOdometry:
             out = fn()
         return graph, out
 
-    def _replay(self, fused, frames, prime):
-        key = (tuple(frames.shape), frames.device)
-        entry = self._graphs.get(key)
-        if entry is None:
-            entry = self._graphs[key] = dict(static=frames.clone(), prime=None, step=None)
-        static, n = entry["static"], self.num_points
+    def _replay(self, fused, entry, source, prime):
+        """Replay (capturing first if needed) ``entry``'s prime or step graph.  ``source()`` launches whatever produces
+        the frame batch from the static inputs (the static frames themselves, or the raw front end) and returns it;
+        it is captured into both graphs."""
+        n = self.num_points
         if prime and entry["prime"] is None:
-            first = self._warm(lambda: fused.stream_prime(static, n))
+            first = self._warm(lambda: fused.stream_prime(source(), n))
             if self._slot is None:
                 # persistent previous frame, allocated outside every graph pool and filled with a real state at once
                 # (a step must never read uninitialised search structures)
@@ -187,21 +263,20 @@ class StreamingOdometry:
                 self.handover_bytes = self._slot.frame1_bytes()
 
             def prime_body():
-                self._slot.copy_frame1_(fused.stream_prime(static, n))
+                self._slot.copy_frame1_(fused.stream_prime(source(), n))
                 self._append(None)
             entry["prime"] = self._capture(prime_body)[0]
         if not prime and entry["step"] is None:
-            self._warm(lambda: fused.stream_step(self._slot, static, n))
+            self._warm(lambda: fused.stream_step(self._slot, source(), n))
 
             def step_body():
-                pose, new = fused.stream_step(self._slot, static, n)
+                pose, new = fused.stream_step(self._slot, source(), n)
                 self._append(pose)
                 # The handover: every branch of the pair stage that reads the previous frame (the set-upconvs on side
                 # streams included) has been joined into this stream by now, so the copy is ordered after them.
                 self._slot.copy_frame1_(new)
                 return pose
             entry["step"] = self._capture(step_body)
-        static.copy_(frames)
         if prime:
             entry["prime"].replay()
             return None
@@ -217,10 +292,12 @@ class PWCLONetOdometry:
     relative pose of (previous frame, this frame) to ``data_dict["odometry_pose"]`` (the identity for the first frame),
     ``get_relative_poses()`` -> (n, 4, 4) float32, first row the identity.  Poses follow ``evaluation``'s convention
     (quat2mat of the level-1 row, not inverted).  Frames need at least ``num_points`` of the prediction config points;
-    the first ``num_points`` are used."""
+    the first ``num_points`` are used.  With ``sweeps=dict(dataset=..., capacity=..., ...)`` (``StreamingOdometry``'s raw
+    mode) ``data_dict["numpy_pc"]`` is instead a raw (n, 4) sweep of any n in [1, capacity], filtered and sampled to
+    ``num_points`` on the device."""
 
     def __init__(self, prediction_module_or_config, checkpoint_path=None, device="cuda:0", graph=True,
-                 max_frames=4096):
+                 max_frames=4096, sweeps=None):
         from .prediction import PWCLONetPredictionModule
         self.device = torch.device(device)
         mod = prediction_module_or_config
@@ -232,7 +309,7 @@ class PWCLONetOdometry:
         self.checkpoint_path = checkpoint_path
         self.elapsed = []
         self.stream = StreamingOdometry(mod.pwclonet, streams=1, num_points=mod.num_points, max_frames=max_frames,
-                                        graph=graph)
+                                        graph=graph, sweeps=sweeps)
 
     def init(self):
         """Start of a sequence: clears the elapsed times and the trajectory, loads the checkpoint if one is given."""
@@ -256,7 +333,10 @@ class PWCLONetOdometry:
                              % (self.input_key(), tuple(pc.shape)))
         frame = pc.to(self.device, torch.float32)[None]
         with torch.no_grad():
-            self.stream.step(frame)
+            if self.stream._front is not None:
+                self.stream.step_sweeps(frame, [frame.shape[1]])
+            else:
+                self.stream.step(frame)
         data_dict[self.relative_pose_key()] = self.stream.relative_poses()[-1, 0].float().cpu().numpy()
 
     def get_relative_poses(self):

@@ -15,6 +15,7 @@ a whole batch of equally long frames ``(b, n, 4)``; ``compact`` packs every fram
 of a zero-padded ``(b, cap, 3)`` batch (zero rows are never selected by the sampler, sampling_gpu.cu:100-101)
 and ``frames_to_clouds`` chains filter -> compaction -> one batched furthest-point-sampling call.
 """
+import numpy as np
 import torch
 
 from . import _lib
@@ -89,6 +90,155 @@ def frames_to_clouds(points, npoints, dataset="kitti", tr=None, near_threshold=3
     idx = _ext.furthest_point_sampling(packed, npoints)
     clouds = torch.gather(packed, 1, idx.long().unsqueeze(-1).expand(-1, -1, 3))
     return clouds, counts
+
+
+# ---- raw sweeps of varying length, persistent buffers (StreamingOdometry raw mode) ----------------
+
+_SMALL_CLOUD = 24576            # csrc/sampling.hip: larger clouds go to the cooperative multi-workgroup sampler
+_SORTED_CLOUD = 2 * 1024 * 16   # pointnet2_ops/_ext.py: from this size on in the spatial order
+_COOP_POINTS = 1024 * 16        # points per workgroup of the cooperative sampler
+_COOP_MAX_G = 32                # its workgroups per cloud
+_COOP_PLAIN_WGS = 224           # workgroups one plain (graph-capturable) launch of it keeps co-resident
+SWEEP_CAPACITY_LIMIT = _COOP_POINTS * _COOP_MAX_G + 1    # capacities below it; the index limit 2^23 is above
+
+
+def sampler_max_clouds(n):
+    """Clouds of ``n`` points one plain launch of the large-cloud sampler takes (csrc/sampling.hip ``coop_launch``: 224
+    co-resident workgroups, ceil(n / 16384) per cloud, whole groups of 8 clouds); None: no limit (n <= 24576, the
+    register-resident sampler).  More clouds are split over several launches there; the raw stream refuses them."""
+    if n <= _SMALL_CLOUD:
+        return None
+    per = _COOP_PLAIN_WGS // -(-n // _COOP_POINTS)
+    return per & ~7 if per >= 8 else per
+
+
+def _calibration(tr, streams):
+    """tr (3,4) / (4,4) for all streams or (S,3,4) / (S,4,4) per stream, array-like -> (S,3,4) fp64 host tensor."""
+    t = torch.as_tensor(tr, dtype=torch.float64).cpu()
+    if t.dim() == 2:
+        t = t.unsqueeze(0).expand(streams, -1, -1)
+    if t.dim() != 3 or t.shape[0] != streams or t.shape[1] not in (3, 4) or t.shape[2] != 4:
+        raise ValueError("sweeps: tr must be (3,4) / (4,4) or (%d,3,4) / (%d,4,4), got %s"
+                         % (streams, streams, tuple(t.shape)))
+    return t[:, :3, :].contiguous()
+
+
+class SweepFrontEnd:
+    """Raw sweeps of S streams -> the (S, npoints, 3) clouds ``frames_to_clouds(sweep[None, :length], npoints, dataset,
+    cap=capacity)`` gives for each stream, bit for bit, through a fixed set of launches on persistent buffers: one
+    ``sweep_filter_compact_kernel`` (filter + compaction of every stream's ``[:length]`` rows, zero rows up to
+    ``capacity``, lengths read from the device), then the exact sampler over the (S, capacity, 3) batch writing the
+    sampled coordinates itself (no gather).  A captured graph of ``run()`` therefore serves every length up to
+    ``capacity``; ``load()`` is the only per-frame host work (two copies).  Host-side checks only until ``load``."""
+
+    def __init__(self, streams, npoints, dataset="kitti360", capacity=131072, tr=None, near_threshold=30.0,
+                 ground_z=KITTI360_GROUND_Z):
+        if dataset not in ("kitti", "kitti360"):
+            raise ValueError("sweeps: unknown dataset %r (\"kitti\" or \"kitti360\")" % (dataset,))
+        capacity = int(capacity)
+        if not 1 <= capacity < SWEEP_CAPACITY_LIMIT:
+            raise ValueError("sweeps: capacity=%d outside [1, %d): at or above the sampler's index limit"
+                             % (capacity, SWEEP_CAPACITY_LIMIT))
+        per = sampler_max_clouds(capacity)
+        if per is not None and streams > per:
+            raise ValueError("sweeps: %d streams of capacity %d need %d sampler workgroups each; one plain launch keeps "
+                             "only %d such clouds co-resident (fewer streams or a smaller capacity)"
+                             % (streams, capacity, -(-capacity // _COOP_POINTS), per))
+        if dataset == "kitti" and tr is None:
+            raise ValueError('sweeps: dataset="kitti" needs the calibration tr ((3,4) or (S,3,4))')
+        self.streams, self.npoints, self.dataset, self.capacity = int(streams), int(npoints), dataset, capacity
+        self.near_threshold, self.ground_z = float(near_threshold), float(ground_z)
+        self._tr_host = _calibration(tr, self.streams) if dataset == "kitti" else None
+        self.bufs = None
+
+    def set_calibration(self, tr):
+        """Replace the KITTI calibration (per stream or one for all) in place: a captured graph reads the new one."""
+        if self.dataset != "kitti":
+            raise ValueError("sweeps: the KITTI-360 front end takes no calibration")
+        self._tr_host = _calibration(tr, self.streams)
+        if self.bufs is not None:
+            self.bufs["tr"].copy_(self._tr_host)
+
+    def check(self, sweeps, lengths, what):
+        """Shape, dtype and length checks, then the device -> host lengths as a list, or None for a device tensor
+        (clamped to [0, rows] by the kernel; values are the caller's responsibility there)."""
+        S, cap = self.streams, self.capacity
+        if sweeps.dim() != 3 or sweeps.dtype != torch.float32:
+            raise ValueError("%s: sweeps must be float32 (S, R, 4), got %s %s" % (what, sweeps.dtype, tuple(sweeps.shape)))
+        if sweeps.shape[2] != 4:
+            raise ValueError("%s: sweeps need 4 channels (x, y, z, intensity), got c=%d" % (what, sweeps.shape[2]))
+        if sweeps.shape[0] != S:
+            raise ValueError("%s: built for %d streams, got a sweep batch of %d" % (what, S, sweeps.shape[0]))
+        R = sweeps.shape[1]
+        if R > cap:
+            raise ValueError("%s: sweeps hold %d rows, capacity=%d" % (what, R, cap))
+        host = None
+        if isinstance(lengths, torch.Tensor) and lengths.is_cuda:
+            if lengths.shape != (S,) or lengths.dtype.is_floating_point or lengths.dtype == torch.bool:
+                raise ValueError("%s: lengths must be (%d,) integers, got %s %s" % (what, S, lengths.dtype,
+                                                                                  tuple(lengths.shape)))
+        else:
+            arr = np.asarray(lengths.numpy() if isinstance(lengths, torch.Tensor) else lengths)
+            if arr.shape != (S,) or arr.dtype.kind not in "iu":
+                raise ValueError("%s: lengths must be (%d,) integers, got %s %s" % (what, S, arr.dtype, arr.shape))
+            host = [int(v) for v in arr]
+            bad = [v for v in host if not 1 <= v <= R]
+            if bad:
+                raise ValueError("%s: lengths %s outside [1, %d] (the rows given)" % (what, bad, R))
+        if not sweeps.is_cuda:
+            raise RuntimeError("CPU not supported")
+        return host
+
+    def load(self, sweeps, lengths, host_lengths):
+        """The per-frame host work: rows [:R] into the static sweep buffer, the lengths into the static device lengths."""
+        if self.bufs is None:
+            self._alloc(sweeps.device)
+        b = self.bufs
+        b["sweeps"][:, :sweeps.shape[1]].copy_(sweeps)
+        if host_lengths is None:
+            b["lengths"].copy_(lengths)
+        else:
+            b["lengths"].copy_(torch.tensor(host_lengths, dtype=torch.int32), non_blocking=False)
+
+    def _alloc(self, device):
+        S, cap, m = self.streams, self.capacity, self.npoints
+        e = lambda shape, dt: torch.empty(shape, dtype=dt, device=device)
+        b = dict(sweeps=torch.zeros((S, cap, 4), dtype=torch.float32, device=device), lengths=e((S,), torch.int32),
+                 packed=e((S, cap, 3), torch.float32), counts=torch.zeros((S,), dtype=torch.int32, device=device),
+                 idx=e((S, m), torch.int32), tr=None)
+        if self.dataset == "kitti":
+            b["tr"] = self._tr_host.to(device)
+        if cap > _SMALL_CLOUD:
+            b["tmp"] = e((S, cap), torch.float32)          # the cooperative sampler's exchange workspace
+        if cap >= _SORTED_CLOUD:
+            lib = _lib.load()
+            b["order_ws"] = e((lib.fps_spatial_order_workspace_bytes(S, cap),), torch.uint8)
+            b["sorted"] = e((S, cap, 3), torch.float32)
+            b["perm"] = e((S, cap), torch.int32)
+        self.bufs = b
+
+    def run(self):
+        """Filter + compaction + sampling of the loaded sweeps -> a fresh (S, npoints, 3) contiguous fp32 batch."""
+        b, S, cap, m = self.bufs, self.streams, self.capacity, self.npoints
+        dev = b["packed"].device
+        p = lambda t: t.data_ptr() if t is not None else 0
+        _lib.call("sweep_filter_compact_kernel_wrapper", dev, S, cap, cap, p(b["lengths"]), p(b["sweeps"]),
+                  0 if self.dataset == "kitti" else 1, p(b["tr"]), self.ground_z, self.near_threshold, p(b["packed"]),
+                  p(b["counts"]))
+        clouds = torch.empty((S, m, 3), dtype=torch.float32, device=dev)
+        if cap >= _SORTED_CLOUD:
+            _lib.call("fps_spatial_order_kernel_wrapper", dev, S, cap, p(b["packed"]), p(b["sorted"]), p(b["perm"]),
+                      p(b["order_ws"]))
+            _lib.call("furthest_point_sampling_sorted_kernel_wrapper", dev, S, cap, m, p(b["packed"]), p(b["sorted"]),
+                      p(b["perm"]), p(b["tmp"]), p(b["idx"]), p(clouds))
+        elif cap > _SMALL_CLOUD:
+            b["tmp"].fill_(1e10)                           # the single-workgroup fallback's running distances
+            _lib.call("furthest_point_sampling_xyz_kernel_wrapper", dev, S, cap, m, p(b["packed"]), p(b["tmp"]),
+                      p(b["idx"]), p(clouds))
+        else:
+            _lib.call("furthest_point_sampling_xyz_kernel_wrapper", dev, S, cap, m, p(b["packed"]), 0, p(b["idx"]),
+                      p(clouds))
+        return clouds
 
 
 def kitti_frame_to_cloud(points, tr, npoints, sample="random", generator=None):

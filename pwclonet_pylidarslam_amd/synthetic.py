@@ -46,12 +46,13 @@ def _scene(r):
     return walls
 
 
-def _cast(r, walls, origin, yaw, n_azimuth=2048, noise=0.02, max_range=80.0):
+def _cast(r, walls, origin, yaw, n_azimuth=2048, noise=0.02, max_range=80.0, scan_order=False):
     """Ray-cast a 64-beam spinning lidar at `origin`/`yaw` (world = frame-1 velodyne frame).
-    Returns hit points in the sensor's own velodyne frame, float64 (M,3)."""
+    Returns hit points in the sensor's own velodyne frame, float64 (M,3): beam by beam, or with `scan_order`
+    azimuth step by azimuth step (all 64 beams of one firing, then the next), the order a sensor delivers."""
     elev = np.deg2rad(np.linspace(2.0, -24.8, 64))
     azim = np.linspace(0, 2 * np.pi, n_azimuth, endpoint=False) + r.uniform(0, 2 * np.pi / n_azimuth)
-    e, a = np.meshgrid(elev, azim, indexing="ij")
+    e, a = np.meshgrid(elev, azim, indexing="xy" if scan_order else "ij")
     d = np.stack([np.cos(e) * np.cos(a), np.cos(e) * np.sin(a), np.sin(e)], axis=-1).reshape(-1, 3)
     c, s = np.cos(yaw), np.sin(yaw)
     R = np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])
@@ -121,6 +122,38 @@ def kitti_like_sequence(seed, npoints=8192, frames=9):
     if frames < 2:
         raise ValueError("a sequence needs at least 2 frames (got %d)" % frames)
     r = np.random.default_rng([seed, 0x5E9, frames])
+    yaws, fwds, pos, head, walls = _path_and_scene(r, frames)
+    pcs = np.empty((frames, npoints, 4), dtype=np.float32)
+    for k in range(frames):
+        pcs[k, :, :3] = _to_camera_and_filter(r, _cast(r, walls, pos[k], head[k]), npoints)
+        pcs[k, :, 3] = r.uniform(0, 1, npoints)
+    q, t = _steps_gt(yaws, fwds)
+    return pcs, q, t
+
+
+def raw_sweep_sequence(seed, frames=9, n_azimuth=2048):
+    """Raw sweeps as a sensor delivers them: the 64-beam ray cast of ``kitti_like_sequence``'s motion law and scene,
+    in the velodyne frame (x forward, y left, z up), in scan order, with an intensity column -- not filtered and not
+    sampled, so the row count varies from sweep to sweep (up to 64 * n_azimuth; rays that hit nothing within range
+    return no row).  Returns (sweeps, q_gt, t_gt): a list of ``frames`` float32 (n_i, 4) arrays, then (frames-1, 4)
+    scalar-first and (frames-1, 3) float32 in ``kitti_like_sequence``'s (camera-frame) convention.  Own RNG stream."""
+    if frames < 2:
+        raise ValueError("a sequence needs at least 2 frames (got %d)" % frames)
+    r = np.random.default_rng([seed, 0x5A7, frames])
+    yaws, fwds, pos, head, walls = _path_and_scene(r, frames)
+    sweeps = []
+    for k in range(frames):
+        hits = _cast(r, walls, pos[k], head[k], n_azimuth=n_azimuth, scan_order=True)
+        sweep = np.empty((hits.shape[0], 4), dtype=np.float32)
+        sweep[:, :3] = hits
+        sweep[:, 3] = r.uniform(0, 1, hits.shape[0])
+        sweeps.append(sweep)
+    q, t = _steps_gt(yaws, fwds)
+    return sweeps, q, t
+
+
+def _path_and_scene(r, frames):
+    """kitti_like_sequence's sensor path (yaw ~ U(-2,2) deg, 0.5-1.5 m forward per step) and walls along it."""
     yaws = np.deg2rad(r.uniform(-2.0, 2.0, frames - 1))
     fwds = r.uniform(0.5, 1.5, frames - 1)
     pos, head = [np.zeros(3)], [0.0]
@@ -132,11 +165,11 @@ def kitti_like_sequence(seed, npoints=8192, frames=9):
     for a in pos[::6]:                          # a _scene-like cluster of walls around every sixth sensor position
         for wl in _scene(r):
             walls.append(dict(wl, r=wl["r"] + a @ wl["n"], u0=wl["u0"] + a @ wl["m"]))
-    pcs = np.empty((frames, npoints, 4), dtype=np.float32)
-    for k in range(frames):
-        pcs[k, :, :3] = _to_camera_and_filter(r, _cast(r, walls, pos[k], head[k]), npoints)
-        pcs[k, :, 3] = r.uniform(0, 1, npoints)
+    return yaws, fwds, pos, head, walls
+
+
+def _steps_gt(yaws, fwds):
     # camera frame: yaw about velodyne z = rotation about camera -y; forward = camera z
     q = np.stack([np.cos(yaws / 2), np.zeros_like(yaws), -np.sin(yaws / 2), np.zeros_like(yaws)], axis=1)
     t = np.stack([np.zeros_like(fwds), np.zeros_like(fwds), fwds], axis=1)
-    return pcs, q.astype(np.float32), t.astype(np.float32)
+    return q.astype(np.float32), t.astype(np.float32)

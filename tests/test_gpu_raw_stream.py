@@ -1,0 +1,232 @@
+"""Streaming odometry from raw LiDAR sweeps of varying length (``StreamingOdometry(..., sweeps=...)``).
+The bar: ``sweep_filter_compact_kernel`` is bitwise the existing filter + ``compact(..., cap)`` on each stream's rows, and
+``step_sweeps`` is bitwise ``step`` on the clouds ``frames_to_clouds`` gives, eager and through one captured prime graph and
+one captured step graph for every length."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import params
+from pwclonet_pylidarslam_amd import _lib, preprocess, synthetic
+from pwclonet_pylidarslam_amd.odometry import PWCLONetOdometry, StreamingOdometry
+from pwclonet_pylidarslam_amd.prediction import PWCLONetPredictionModule
+from pwclonet_pylidarslam_amd.pwclonet import PWCLONet
+
+pytestmark = pytest.mark.gpu
+
+CAP = 131072
+NEAR = 30.0
+VELO_TO_CAM = np.array([[0.0, -1.0, 0.0, 0.0], [0.0, 0.0, -1.0, 0.0], [1.0, 0.0, 0.0, 0.0]])
+
+
+def _net(dev, dtype=None):
+    net = PWCLONet(dict(num_input_channels=3, sequence_len=2, device=str(dev), scalar_last=False, log_mode="none"))
+    params.fill_state_dict(net.state_dict())
+    net = net.to(dev).eval()
+    net.prepare_fused(dtype=dtype)
+    return net
+
+
+@functools.lru_cache(maxsize=None)
+def _sweeps(seed, frames):
+    return synthetic.raw_sweep_sequence(seed, frames)[0]
+
+
+def _trs(S):
+    """One calibration per stream: the velodyne -> camera axes, each stream with its own small offset."""
+    tr = np.stack([VELO_TO_CAM] * S)
+    tr[:, :, 3] = np.array([[0.05 * s, -0.08 + 0.01 * s, -0.27 - 0.02 * s] for s in range(S)])
+    return tr
+
+
+def _batch(rows, dev, fill=0.0):
+    """A list of S (n_s, 4) arrays -> (S, max n_s, 4) cuda tensor, rows past each length set to ``fill``, and the lengths."""
+    lengths = [r.shape[0] for r in rows]
+    out = np.full((len(rows), max(lengths), 4), fill, dtype=np.float32)
+    for s, r in enumerate(rows):
+        out[s, :r.shape[0]] = r
+    return torch.from_numpy(out).to(dev), lengths
+
+
+def _reference_packed(batch, lengths, dataset, tr, cap):
+    packed, counts = [], []
+    for s, n in enumerate(lengths):
+        rows = batch[s, :n].contiguous()
+        if dataset == "kitti":
+            xyz, keep = preprocess.transform_filter(rows, tr[s])
+        else:
+            xyz, keep = preprocess.kitti360_filter(rows, NEAR)
+        p, c = preprocess.compact(xyz[None], keep[None], cap)
+        packed.append(p)
+        counts.append(c)
+    return torch.cat(packed), torch.cat(counts)
+
+
+def _kernel(batch, lengths_dev, dataset, tr_dev, cap, packed, counts):
+    S, R, _ = batch.shape
+    _lib.call("sweep_filter_compact_kernel_wrapper", batch.device, S, R, cap, lengths_dev.data_ptr(), batch.data_ptr(),
+              0 if dataset == "kitti" else 1, tr_dev.data_ptr() if tr_dev is not None else 0,
+              float(preprocess.KITTI360_GROUND_Z), NEAR, packed.data_ptr(), counts.data_ptr())
+
+
+@pytest.mark.parametrize("dataset", ["kitti", "kitti360"])
+def test_sweep_kernel_is_bitwise_the_filter_and_compaction(cuda, dataset):
+    sw = _sweeps(11, 3)
+    rows = [sw[0], sw[1][:70000], sw[2][:23456]]                   # three different lengths
+    tr = _trs(3)
+    tr_dev = torch.from_numpy(tr).to(cuda) if dataset == "kitti" else None
+    for cap in (CAP, 5000):                                         # 5000: survivors beyond cap dropped, counts clipped
+        clean, lengths = _batch(rows, cuda, 0.0)
+        dirty, _ = _batch(rows, cuda, float("nan"))                # NaNs past every length: never read
+        want_p, want_c = _reference_packed(clean, lengths, dataset, tr, cap)
+        assert int(want_c.min()) > 0
+        lengths_dev = torch.tensor(lengths, dtype=torch.int32, device=cuda)
+        for batch in (clean, dirty):
+            packed = torch.full((3, cap, 3), 7.0, device=cuda)     # garbage: the kernel itself writes the zero rows
+            counts = torch.full((3,), -1, dtype=torch.int32, device=cuda)
+            _kernel(batch, lengths_dev, dataset, tr_dev, cap, packed, counts)
+            torch.cuda.synchronize()
+            assert torch.equal(counts, want_c), (cap, counts, want_c)
+            assert torch.equal(packed, want_p), cap
+    # a long sweep, then a short one, in the same output buffer: zeros past the new count, no stale survivors
+    long_b, long_l = _batch([sw[0], sw[1], sw[2]], cuda)
+    short_rows = [sw[0][:3000], sw[1][:9000], sw[2][:1]]
+    short_b, short_l = _batch(short_rows, cuda, float("nan"))
+    packed = torch.empty((3, CAP, 3), device=cuda)
+    counts = torch.empty((3,), dtype=torch.int32, device=cuda)
+    _kernel(long_b, torch.tensor(long_l, dtype=torch.int32, device=cuda), dataset, tr_dev, CAP, packed, counts)
+    _kernel(short_b, torch.tensor(short_l, dtype=torch.int32, device=cuda), dataset, tr_dev, CAP, packed, counts)
+    want_p, want_c = _reference_packed(short_b, short_l, dataset, tr, CAP)
+    torch.cuda.synchronize()
+    assert torch.equal(counts, want_c) and torch.equal(packed, want_p)
+    for s in range(3):
+        assert not packed[s, int(want_c[s]):].any()
+    assert _lib.load().pwclo_last_error() == 0
+
+
+def _clouds_ref(batch, lengths, dataset, tr):
+    """frames_to_clouds of every stream's [:length] rows -> (S, 8192, 3), counts."""
+    out, counts = [], []
+    for s, n in enumerate(lengths):
+        c, k = preprocess.frames_to_clouds(batch[s:s + 1, :n].contiguous(), 8192, dataset,
+                                           tr=tr[s] if tr is not None else None, near_threshold=NEAR, cap=CAP)
+        out.append(c)
+        counts.append(k)
+    return torch.cat(out), torch.cat(counts)
+
+
+def _cm(clouds):
+    return clouds.permute(0, 2, 1).contiguous()
+
+
+@pytest.mark.parametrize("graph", [False, True], ids=["eager", "graph"])
+@pytest.mark.parametrize("dtype", [None, "bf16"], ids=["fp32", "bf16"])
+def test_step_sweeps_is_bitwise_step_on_frames_to_clouds(cuda, graph, dtype):
+    S, T = 3, 6
+    seqs = [_sweeps(31 + s, T) for s in range(S)]
+    net = _net(cuda, dtype)
+    fs = net._fused
+    raw = StreamingOdometry(net, streams=S, graph=graph, sweeps=dict(dataset="kitti360", capacity=CAP,
+                                                                     near_threshold=NEAR))
+    ref = StreamingOdometry(net, streams=S, graph=False)
+    prev = None
+    seen = set()
+    with torch.no_grad():
+        for k in range(T):
+            # every step a different set of lengths (and row counts R): whole sweeps and cut ones
+            rows = [seqs[s][k][:seqs[s][k].shape[0] - 1000 * ((k + s) % 3)] for s in range(S)]
+            batch, lengths = _batch(rows, cuda, float("nan"))
+            seen.update(lengths)
+            clouds, counts = _clouds_ref(batch, lengths, "kitti360", None)
+            assert int(counts.min()) > 0                                   # stream 1 (seed 32) keeps < 8192 at times
+            lens = torch.tensor(lengths, dtype=torch.int32, device=cuda) if k % 2 else lengths   # device or host lengths
+            got = raw.step_sweeps(batch, lens)
+            want = ref.step(clouds)
+            assert torch.equal(raw.survivor_counts(), counts), k
+            if k == 0:
+                assert got is None and want is None
+            else:
+                assert torch.equal(got, want), k
+                assert torch.equal(want, fs(_cm(prev), _cm(clouds))), k      # the streaming contract: the pair forward
+            prev = clouds
+    assert len(seen) >= 5
+    assert torch.equal(raw.relative_poses(), ref.relative_poses())
+    assert torch.equal(raw.trajectory(), ref.trajectory())
+    if graph:
+        assert list(raw._graphs) == ["sweeps"]
+        entry = raw._graphs["sweeps"]
+        assert entry["prime"] is not None and entry["step"] is not None     # one of each for all the lengths
+    torch.cuda.synchronize()
+    assert _lib.load().pwclo_last_error() == 0
+
+
+def test_kitti_sweeps_per_stream_calibration_and_replacement(cuda):
+    """KITTI: per-stream tr in a device buffer; a new calibration on reset() is read by the same captured graphs."""
+    S, T = 2, 4
+    seqs = [_sweeps(51 + s, T) for s in range(S)]
+    net = _net(cuda)
+    tr_a, tr_b = _trs(S), _trs(S)[::-1].copy()
+    raw = StreamingOdometry(net, streams=S, graph=True, sweeps=dict(dataset="kitti", capacity=CAP, tr=tr_a))
+    ref = StreamingOdometry(net, streams=S, graph=False)
+    with torch.no_grad():
+        for tr in (tr_a, tr_b):
+            raw.reset(tr=tr)
+            ref.reset()
+            for k in range(T):
+                batch, lengths = _batch([seqs[s][k] for s in range(S)], cuda)
+                clouds, counts = _clouds_ref(batch, lengths, "kitti", tr)
+                got = raw.step_sweeps(batch, lengths)
+                want = ref.step(clouds)
+                assert torch.equal(raw.survivor_counts(), counts)
+                assert (got is None and want is None) or torch.equal(got, want), k
+            assert torch.equal(raw.relative_poses(), ref.relative_poses())
+    assert list(raw._graphs) == ["sweeps"]
+    torch.cuda.synchronize()
+    assert _lib.load().pwclo_last_error() == 0
+
+
+@pytest.mark.parametrize("graph", [False, True], ids=["eager", "graph"])
+def test_too_few_survivors_still_give_a_pose(cuda, graph):
+    sw = _sweeps(71, 2)
+    net = _net(cuda)
+    raw = StreamingOdometry(net, streams=1, graph=graph, sweeps=dict(dataset="kitti360", capacity=CAP))
+    ref = StreamingOdometry(net, streams=1, graph=False)
+    with torch.no_grad():
+        for k, n in enumerate((sw[0].shape[0], 6000)):                         # the second keeps far fewer than 8192
+            batch, lengths = _batch([sw[k][:n]], cuda)
+            clouds, counts = _clouds_ref(batch, lengths, "kitti360", None)
+            got = raw.step_sweeps(batch, lengths)
+            want = ref.step(clouds)
+            assert torch.equal(raw.survivor_counts(), counts)
+    assert 0 < int(counts[0]) < 8192
+    assert got.shape == (1, 4, 7) and torch.isfinite(got).all()
+    assert torch.equal(got, want)
+    torch.cuda.synchronize()
+    assert _lib.load().pwclo_last_error() == 0
+
+
+def test_posenet_odometry_raw_mode(cuda):
+    T = 5
+    sw = _sweeps(91, T)
+    cfg = dict(device=str(cuda), num_input_channels=3, sequence_len=2, num_points=8192,
+               posenet_config=dict(log_mode="none"))
+    mod = PWCLONetPredictionModule(cfg)
+    params.fill_state_dict(mod.pwclonet.state_dict())
+    odo = PWCLONetOdometry(mod, device=cuda, sweeps=dict(dataset="kitti360", capacity=CAP))
+    odo.init()
+    for k in range(T):
+        pc = sw[k][:sw[k].shape[0] - 777 * k]                                  # varying n
+        data = {"numpy_pc": pc if k % 2 else torch.from_numpy(pc)}
+        odo.process_next_frame(data)
+        assert data["odometry_pose"].shape == (4, 4)
+    got = odo.get_relative_poses()
+    so = StreamingOdometry(mod.pwclonet, streams=1, graph=False, sweeps=dict(dataset="kitti360", capacity=CAP))
+    with torch.no_grad():
+        for k in range(T):
+            pc = torch.from_numpy(sw[k][:sw[k].shape[0] - 777 * k]).to(cuda)[None]
+            so.step_sweeps(pc, [pc.shape[1]])
+    want = so.relative_poses()[:, 0].float().cpu().numpy()
+    assert got.shape == (T, 4, 4) and np.array_equal(got, want)
+    assert np.array_equal(got[0], np.eye(4, dtype=np.float32))

@@ -1,0 +1,166 @@
+#!/usr/bin/env python3
+"""Streaming odometry from raw sweeps against pair mode on raw frames, one process, alternated and repeated; one JSON line.
+
+Input: ``synthetic.raw_sweep_sequence`` sweeps (64 x 2048 rays, ~118-127k rows each, every length different), KITTI-360
+front end (near 30 m), capacity 131072, 8192 points.  A long stream plays one generated sequence forwards and backwards.
+(a) S = 1, one frame in flight, HIP events around each call and a sync after it: per-frame time of
+    ``StreamingOdometry(graph=True, sweeps=...).step_sweeps`` (filter + compaction + sampler + pyramid + pair stage in
+    the captured graphs) against pair mode on the raw frames: ``frames_to_clouds`` of the previous and of the new sweep
+    (eager: the row counts differ, so the two cannot share one call) + ``GraphedForward`` at batch 1.
+(b) S = 8 (streams start at different frames): frames/s of ``step_sweeps`` against pair mode (16 ``frames_to_clouds``
+    calls + ``GraphedForward`` at batch 8), one step in flight, HIP events around a region of back-to-back steps.
+(c) ``sweep_filter_compact_kernel`` alone (HIP events around 50 back-to-back launches) at S = 1 and S = 8.
+Modes alternate repeat by repeat; medians over frames per repeat, then median / spread over repeats.
+Check: the streamed rows equal pair mode's bit for bit (the pair forward is the streaming contract's reference).
+
+    python tools/raw_stream_bench.py [--frames F] [--repeats R] [--steps8 K]
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from pwclonet_pylidarslam_amd import _lib, preprocess, synthetic  # noqa: E402
+from pwclonet_pylidarslam_amd.graphed import GraphedForward  # noqa: E402
+from pwclonet_pylidarslam_amd.odometry import StreamingOdometry  # noqa: E402
+from pwclonet_pylidarslam_amd.pwclonet import PWCLONet  # noqa: E402
+
+CAP, NPOINTS, NEAR = 131072, 8192, 30.0
+
+
+def _stats(xs):
+    xs = sorted(xs)
+    med = xs[len(xs) // 2]
+    return {"median": med, "min": xs[0], "max": xs[-1], "spread_pct": 100.0 * (xs[-1] - xs[0]) / med}
+
+
+def _ms(fn):
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    out = fn()
+    e.record()
+    e.synchronize()
+    return s.elapsed_time(e), out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=41, help="frames of the S = 1 stream")
+    ap.add_argument("--base", type=int, default=12, help="sweeps generated; the streams bounce through them")
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--steps8", type=int, default=10, help="steps per timed region at S = 8")
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    base = [torch.from_numpy(s).to(dev) for s in synthetic.raw_sweep_sequence(2024, a.base)[0]]
+    period = 2 * (a.base - 1)
+    order = [min(k % period, period - k % period) for k in range(max(a.frames, a.steps8 + 8 * 3 + 1))]
+    torch.manual_seed(1234)
+    net = PWCLONet(dict(num_input_channels=3, sequence_len=2, device=str(dev), scalar_last=False,
+                        log_mode="none")).to(dev).eval().prepare_fused()
+    torch.set_grad_enabled(False)
+    sweeps_cfg = dict(dataset="kitti360", capacity=CAP, near_threshold=NEAR)
+    res = {"tool": "raw_stream_bench", "capacity": CAP, "npoints": NPOINTS, "frames": a.frames, "repeats": a.repeats,
+           "rows": [int(s.shape[0]) for s in base], "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES")}
+
+    def cloud(k):
+        sw = base[order[k]]
+        return preprocess.frames_to_clouds(sw[None], NPOINTS, "kitti360", near_threshold=NEAR, cap=CAP)[0]
+
+    def cm(c):
+        return c.permute(0, 2, 1).contiguous()
+
+    # ---- (a) S = 1 ----
+    so = StreamingOdometry(net, streams=1, max_frames=a.frames + 1, graph=True, sweeps=sweeps_cfg)
+    pair = GraphedForward(net)
+
+    def stream_frame(k):
+        sw = base[order[k]]
+        return so.step_sweeps(sw[None], [sw.shape[0]])
+
+    def pair_frame(k):
+        return pair(cm(cloud(k - 1)), cm(cloud(k)))
+
+    def stream_pass():
+        so.reset()
+        stream_frame(0)
+        return sorted(_ms(lambda: stream_frame(k))[0] for k in range(1, a.frames))[(a.frames - 1) // 2]
+
+    def pair_pass():
+        return sorted(_ms(lambda: pair_frame(k))[0] for k in range(1, a.frames))[(a.frames - 1) // 2]
+
+    so.reset()
+    stream_frame(0)
+    same = all(torch.equal(stream_frame(k), pair_frame(k)) for k in range(1, min(a.frames, 8)))
+    stream_pass(), pair_pass()                                            # warm-up
+    ts, tp = [], []
+    for _ in range(a.repeats):
+        ts.append(stream_pass())
+        tp.append(pair_pass())
+    res["s1_raw_stream_ms_per_frame"] = _stats(ts)
+    res["s1_raw_pair_ms_per_frame"] = _stats(tp)
+    res["s1_latency_ratio_pair_over_stream"] = _stats(tp)["median"] / _stats(ts)["median"]
+    res["s1_rows_bitwise_equal_pair"] = bool(same)
+
+    # ---- (b) S = 8 ----
+    S = 8
+    idx = [[k + 3 * i for i in range(S)] for k in range(a.steps8 + 1)]    # stream i starts 3 i frames later
+    so8 = StreamingOdometry(net, streams=S, max_frames=a.steps8 + 2, graph=True, sweeps=sweeps_cfg)
+    pair8 = GraphedForward(net)
+
+    def batch(k):
+        rows = [base[order[j]] for j in idx[k]]
+        lengths = [int(r.shape[0]) for r in rows]
+        out = torch.zeros((S, max(lengths), 4), dtype=torch.float32, device=dev)
+        for s, r in enumerate(rows):
+            out[s, :r.shape[0]] = r
+        return out, lengths
+
+    batches = [batch(k) for k in range(a.steps8 + 1)]
+
+    def clouds8(k):
+        return torch.cat([cloud(j) for j in idx[k]])
+
+    def stream8():
+        so8.reset()
+        so8.step_sweeps(*batches[0])
+        return _ms(lambda: [so8.step_sweeps(*batches[k]) for k in range(1, a.steps8 + 1)])[0]
+
+    def pair8_pass():
+        return _ms(lambda: [pair8(cm(clouds8(k - 1)), cm(clouds8(k))) for k in range(1, a.steps8 + 1)])[0]
+
+    so8.reset()
+    so8.step_sweeps(*batches[0])
+    same8 = all(torch.equal(so8.step_sweeps(*batches[k]), pair8(cm(clouds8(k - 1)), cm(clouds8(k)))) for k in (1, 2))
+    stream8(), pair8_pass()
+    r_s, r_p = [], []
+    for _ in range(a.repeats):
+        r_s.append(S * a.steps8 / (stream8() / 1e3))
+        r_p.append(S * a.steps8 / (pair8_pass() / 1e3))
+    res["s8_raw_stream_frames_per_s"] = _stats(r_s)
+    res["s8_raw_pair_pairs_per_s"] = _stats(r_p)
+    res["s8_ratio_stream_over_pair"] = _stats(r_s)["median"] / _stats(r_p)["median"]
+    res["s8_rows_bitwise_equal_pair"] = bool(same8)
+
+    # ---- (c) the filter + compaction kernel alone ----
+    for name, front in (("s1", so._front), ("s8", so8._front)):
+        b = front.bufs
+
+        def launches():
+            for _ in range(50):
+                _lib.call("sweep_filter_compact_kernel_wrapper", dev, front.streams, CAP, CAP, b["lengths"].data_ptr(),
+                          b["sweeps"].data_ptr(), 1, 0, front.ground_z, front.near_threshold, b["packed"].data_ptr(),
+                          b["counts"].data_ptr())
+        launches()
+        res["sweep_filter_compact_ms_" + name] = _stats([_ms(launches)[0] / 50 for _ in range(5)])
+    res["sampler_workgroups_per_pose"] = {"stream": -(-CAP // 16384), "pair": 2 * -(-CAP // 16384)}
+    torch.cuda.synchronize(dev)
+    res["last_error"] = int(_lib.load().pwclo_last_error())
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
