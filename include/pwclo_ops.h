@@ -393,6 +393,30 @@ void compact_frames_scan_kernel_wrapper(int b, int n, int cap, const int *keep, 
 void sweep_filter_compact_kernel_wrapper(int S, int R, int cap, const int *lengths, const float *sweeps, int dataset,
                                          const double *tr, float ground_z, float near, float *packed, int *counts);
 
+/* Training batches from raw LiDAR pairs (batches.TrainBatchBuilder), two launches per batch.
+ * state (3) i64 in DEVICE memory = {seed, next step, step of the batch in flight}; random words are Philox4x32-10 with
+ * key = seed and counter = (index, cloud or pair, step mod 2^32, purpose: 0 selection keys, 1 draws with replacement,
+ * 2 augmentation).
+ * Pose side, one thread per pair: state[2] = state[1], state[1] += 1; mode 0: no augmentation (T_trans = I, T_gt = T_diff,
+ * aug_params zeroed), 1: aug_params (B,6) f32 drawn (six clipped normals, the reference's scales and clips), 2: aug_params
+ * read as the caller left them.  t_diff (B,3,4) f64; t_trans (B,3,4) f64 = [Rx.Ry.Rz(params[:3] * pi / 4) | params[3:]];
+ * t_gt (B,4,4) f64 = T_diff . inv(T_trans) (dataset 0, KITTI) or T_trans . T_diff (dataset 1, KITTI-360); gt (B,7) f32 =
+ * [t_gt translation, quaternion w x y z] (KITTI: through the zyx Euler angles; KITTI-360: the largest-diagonal form). */
+void train_batch_pose_kernel_wrapper(int B, int dataset, int mode, long long *state, const double *t_diff, float *aug_params,
+                                     double *t_trans, double *t_gt, float *gt);
+/* Sample side, one 1024-thread workgroup per cloud c = 2 * pair + frame: sweeps (B,2,R,4) f32 (16-byte aligned), lengths
+ * (B,2) i32 in DEVICE memory (both frames of a pair use rows [0, min of the two), clamped to [0, R]); tr (B,3,4) f64 per
+ * pair (dataset 0) or ground_z / near (dataset 1): the row arithmetic of the filters above.  count >= npoints: the npoints
+ * survivors with the smallest keys (word << 32 | row), in key order; 0 < count < npoints: all survivors in frame order,
+ * then draws (word * count) >> 32 into that list; count == 0: draws (word * n) >> 32 over all rows.  augmented != 0: frame 1
+ * of every pair is moved by t_trans (fp64, rounded once).  xyz_f1 / xyz_f2 (B,3,npoints) f32: KITTI gets (augmented frame 1,
+ * frame 0), KITTI-360 (frame 0, augmented frame 1).  indices (2B,npoints) i32 = the raw row of every output point,
+ * counts (2B) i32 = survivors.  npoints <= 8192; reads state[0] and state[2] as the pose launch left them. */
+void train_batch_sample_kernel_wrapper(int B, int R, int npoints, int dataset, const int *lengths, const float *sweeps,
+                                       const double *tr, float ground_z, float near, const long long *state,
+                                       const double *t_trans, int augmented, float *xyz_f1, float *xyz_f2, int *indices,
+                                       int *counts);
+
 /* ---- 3b. module-path layers: training-mode BatchNorm, stack tails, pointwise convolution ---- */
 
 /* Training-mode BatchNorm over x (b, c, l) f32 (l = product of the trailing dimensions), the statistics pass of

@@ -66,6 +66,9 @@ SIGNATURES = {
     "softmax_wsum_backward_kernel_wrapper": ([ctypes.c_longlong, _i, _F, _F, _F, _F, _F], None),
     "compact_frames_scan_kernel_wrapper": ([_i, _i, _i, _F, _F, _F, _F], None),
     "sweep_filter_compact_kernel_wrapper": ([_i, _i, _i, _F, _F, _i, _F, ctypes.c_float, ctypes.c_float, _F, _F], None),
+    "train_batch_pose_kernel_wrapper": ([_i, _i, _i, _F, _F, _F, _F, _F, _F], None),
+    "train_batch_sample_kernel_wrapper": ([_i, _i, _i, _i, _F, _F, _F, ctypes.c_float, ctypes.c_float, _F, _F, _i, _F, _F, _F,
+                                           _F], None),
     "batchnorm_train_workspace_bytes": ([_i], ctypes.c_longlong),
     "batchnorm_train_forward_kernel_wrapper": ([_i, _i, _i, _F, _F, _F, ctypes.c_float, ctypes.c_float, _F, _F, _F, _F,
                                                 _F, _F, _i], None),

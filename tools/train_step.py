@@ -38,6 +38,9 @@ def main():
     ap.add_argument("--sample-ahead", action="store_true",
                     help="draw the next batch's furthest-point samples on a second stream while this batch's step runs "
                          "(training.TrainStep(sample_ahead=True); the synthetic batch is the same every step)")
+    ap.add_argument("--raw-batches", action="store_true",
+                    help="every step trains on a fresh batch built from raw synthetic sweeps by batches.TrainBatchBuilder "
+                         "(filter, random choice, augmentation, ground truth on the device), written into the step's tensors")
     a = ap.parse_args()
     if a.gpus > 1 and not dist_util.launched_by_torchrun():      # supervise N fresh ranks; no GPU call made here
         sys.exit(dist_util.spawn_ranks(os.path.abspath(__file__), sys.argv[1:], a.gpus))
@@ -65,6 +68,25 @@ def main():
     if a.graph:
         assert world == 1, "--graph is the single-GPU variant (DDP's bucketed all-reduce is not captured here)"
     step = TrainStep(model, opt, x1, x2, gt, graph=a.graph, sample_ahead=a.sample_ahead).step
+    if a.raw_batches:
+        assert not a.sample_ahead, "--raw-batches rewrites the step's tensors every step; not combined with --sample-ahead"
+        from pwclonet_pylidarslam_amd import batches
+        assert a.npoints <= batches.MAX_NPOINTS
+        sweeps, lengths, t_diff = (t.to(dev) for t in batches.synthetic_raw_pairs(a.batch, seed=2000 + rank))
+        builder = batches.TrainBatchBuilder(a.batch, dataset="kitti", npoints=a.npoints, seed=rank, tr=batches.VELO_TO_CAM)
+        feed = lambda: builder.build(sweeps, lengths, t_diff, out=(x1, x2, gt))
+        feed()
+        if a.graph:                                        # one capture serves every step: the counter lives on the device
+            torch.cuda.synchronize(dev)
+            feed_graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(feed_graph):
+                feed()
+            feed = feed_graph.replay
+        train = step
+
+        def step():
+            feed()
+            return train()
 
     losses = [step().item() for _ in range(a.warmup)]
     dist_util.fence(dev)
@@ -79,7 +101,8 @@ def main():
                           "value": world * a.batch * a.steps / dt, "unit": "frame-pairs/s", "n_gpus": world,
                           "ms_per_step": 1e3 * dt / a.steps, "batch_per_gpu": a.batch, "dtype": "f32",
                           "launch": ("one hipGraph per step" if a.graph else "eager (module graph, torch autograd)")
-                          + (", next batch's sampling chain on a second stream" if a.sample_ahead else ""), "loss_first_last": [losses[0], losses[-1]],
+                          + (", next batch's sampling chain on a second stream" if a.sample_ahead else "")
+                          + (", every batch built from raw sweeps on the device" if a.raw_batches else ""), "loss_first_last": [losses[0], losses[-1]],
                           "collective": ("DDP all-reduce of %d fp32 gradient values (network + loss weights), one bucket"
                                          % gradient_bucket_values(unit)) if world > 1 else "none"}), flush=True)
     dist_util.finish()
