@@ -60,13 +60,13 @@ def _compile(src, force, trace=False):
 def source_stamp():
     """sha256 (first 16 hex digits) over everything that decides what the FUSED FORWARD's kernels do and how much memory
     they touch -- the path the PMC artefacts describe: the stack / sampler / neighbour-search / warp sources of csrc/, their
-    shared headers (rows.hpp: the raw-row filters that warp.hip's kernels use) and the host-side packing / launch code
+    shared headers (rows.hpp: the raw-row filters that warp.hip's kernels use; launch.hpp: the stack kernels' launch policy) and the host-side packing / launch code
     (fused.py).  The training-only kernels (conv1x1, batchnorm, train_batch) and the stand-alone ext ops are not part of it.
     Profile artefacts that bench.py reports beside live timings (profiles/pmc_*.json) carry the stamp of the tree they were
     measured on; bench.py marks them stale when it differs from the running tree's."""
     import hashlib
     h = hashlib.sha256()
-    names = ("common.hpp", "rows.hpp", "mlp_core.hpp", "fused_hoisted.hip", "fused_layers.hip", "fused_sa.hip", "knn.hip",
+    names = ("common.hpp", "rows.hpp", "mlp_core.hpp", "launch.hpp", "fused_hoisted.hip", "fused_layers.hip", "fused_sa.hip", "knn.hip",
              "sampling.hip", "warp.hip", "state.hip")
     files = [os.path.join(CSRC, f) for f in names] + [os.path.join(HERE, "fused.py")]   # (the ABI header only declares)
     for f in files:

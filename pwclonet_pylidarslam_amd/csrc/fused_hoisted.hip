@@ -8,19 +8,16 @@
 //   cost volume a1    [geo | feat1[s] | feat2[n]]   -> u[s] = W1_p feat1[s] + b1, v[n] = W1_q feat2[n]
 //   cost volume b     [enc2 | feat1[s] | first[n]]  -> u2[s] = W_p feat1[s] + b,  v2[n] = W_f first[n]
 // MACs per pixel: set-upconv 18 432 -> 10 240, cv_a1 (C=64) 30 208 -> 14 592, cv_b (C=64) 33 408 -> 17 024.
+//
+// Launch policy (tuning variables, stack sizes per weight format, persistent grid, the per-kernel LDS attribute) lives
+// in launch.hpp; the wrappers at the end of this file only choose (kernel, workgroup width, tile count).
 #include <math.h>
-#include <stdlib.h>
 
-#include "mlp_core.hpp"
+#include "launch.hpp"
 
 PWCLO_TRACE_TU(fused_hoisted)
 
 namespace pwclo {
-
-static int fh_tuning(const char *name, int dflt) {
-  const char *e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
 
 // Geometry inputs are laid out "k-step major": logical channel c sits at lane group c % 4, component
 // c / 4, i.e. MFMA k-step c / 4 (a 16x16x4 instruction consumes component r of all four lane
@@ -685,30 +682,6 @@ __global__ __launch_bounds__(W * 64, (W <= 4 ? 2 : 1)) void cv_a_lane6_kernel(CV
   }
 }
 
-// ---- launch helpers ----------------------------------------------------------------------------------------
-template <int W, typename Kern, typename Args>
-static void launch_h(Kern kern, bool &attr_set, int lds_bytes, long long ntiles, const Args &a) {
-  if (lds_bytes > 64 * 1024 && !attr_set) {
-    (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);  // once per kernel: the largest any configuration can ask for
-    attr_set = true;
-  }
-  static const int rounds = fh_tuning("PWCLO_FL_ROUNDS", 1);
-  const int per_cu = (lds_bytes > 80 * 1024 || W > 8) ? 1 : 2;
-  long long grid = (ntiles + W - 1) / W;
-  if (grid > 256LL * per_cu * rounds) grid = 256LL * per_cu * rounds;
-  if (grid < 1) grid = 1;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(W * 64), lds_bytes, current_stream(), a);
-}
-
-static int coarse_tiles_h() {   // fused_layers.hip: coarse_tiles()
-  static const int v = fh_tuning("PWCLO_COARSE_W4_TILES", 2047);
-  return v;
-}
-
-static long long tiles_h(int b, int s, int kp, int p) {
-  return (long long)b * (((long long)s * kp + 16 * p - 1) / (16 * p));
-}
-
 }  // namespace pwclo
 
 using namespace pwclo;
@@ -750,33 +723,22 @@ extern "C" void sa_fused_h_kernel_wrapper(int b, int n, int s, int k, int c1, in
   const bool lvl0 = pre == nullptr;
 #define SAH_CASE(A1, A2, A3, KP, XYZ, PP, WW)                                                         \
   if (c1 == A1 && c2 == A2 && c3 == A3 && kp == KP && lvl0 == XYZ) {                                  \
-    static bool attr = false, attr3 = false;                                                          \
-    constexpr int lds = 4 * (layer_floats(1, A1 / 16) + layer_floats(A1 / 16, A2 / 16) +               \
-                             layer_floats(A2 / 16, A3 / 16));                                          \
-    constexpr int lds3 = 4 * (layer_floats(1, A1 / 16) + layer_floats_any<1>(A1 / 16, A2 / 16) +       \
-                              layer_floats_any<1>(A2 / 16, A3 / 16));                                  \
-    constexpr int lds2 = 4 * (layer_floats(1, A1 / 16) + layer_floats_any<2>(A1 / 16, A2 / 16) +       \
-                              layer_floats_any<2>(A2 / 16, A3 / 16));                                  \
-    static bool attr2 = false;                                                                        \
-    PWCLO_REQUIRE_PACKED("sa_fused_h", wfmt, packed_floats, lds / 4, lds3 / 4, lds2 / 4);              \
-    if (wfmt == PWCLO_WFMT_BF16X3)                                                                    \
-      launch_h<WW>(sa_h_kernel<A1 / 16, A2 / 16, A3 / 16, KP, PP, WW, XYZ, 1>, attr3, lds3,             \
-                   tiles_h(b, s, KP, PP), a);                                                         \
-    else if (wfmt == PWCLO_WFMT_BF16)                                                                 \
-      launch_h<WW>(sa_h_kernel<A1 / 16, A2 / 16, A3 / 16, KP, PP, WW, XYZ, 2>, attr2, lds2,             \
-                   tiles_h(b, s, KP, PP), a);                                                         \
-    else                                                                                              \
-      launch_h<WW>(sa_h_kernel<A1 / 16, A2 / 16, A3 / 16, KP, PP, WW, XYZ>, attr, lds, tiles_h(b, s, KP, PP), a); \
+    using St = Stack<1, A1 / 16, A1 / 16, A2 / 16, A2 / 16, A3 / 16>;                                 \
+    PWCLO_REQUIRE_PACKED("sa_fused_h", wfmt, packed_floats, St);                                      \
+    with_format(wfmt, [&](auto fmt) {                                                                 \
+      constexpr int FMT = decltype(fmt)::value;                                                       \
+      launch_persistent<sa_h_kernel<A1 / 16, A2 / 16, A3 / 16, KP, PP, WW, XYZ, FMT>, WW>(             \
+          St::bytes<FMT>(), stack_tiles(b, s, KP, PP), a);                                            \
+    });                                                                                               \
     check_launch("sa_fused_h");                                                                       \
     return;                                                                                           \
   }
   if (kmajor) {                               // psa_1 with 8-channel layers packed k-step major (fp32 tiles only)
-    static bool attrk = false;
-    constexpr int ldsk = 4 * (layer_floats(1, 1) + layer_floats(1, 1) + layer_floats(1, 1));
+    constexpr int ldsk = Stack<1, 1, 1, 1, 1, 1>::bytes();
     PWCLO_REQUIRE(packed_floats == ldsk / 4, "sa_fused_h: packed weights hold %d floats, the level-0 stack needs %d",
                   packed_floats, ldsk / 4);
     PWCLO_REQUIRE(kp == 32, "sa_fused_h: the level-0 stack is built for nsample in (16, 32] (got %d)", k);
-    launch_h<8>(sa_h_kernel<1, 1, 1, 32, 2, 8, true, 0, true>, attrk, ldsk, tiles_h(b, s, 32, 2), a);
+    launch_persistent<sa_h_kernel<1, 1, 1, 32, 2, 8, true, 0, true>, 8>(ldsk, stack_tiles(b, s, 32, 2), a);
     check_launch("sa_fused_h");
     return;
   }
@@ -784,8 +746,7 @@ extern "C" void sa_fused_h_kernel_wrapper(int b, int n, int s, int k, int c1, in
   SAH_CASE(16, 16, 32, 32, false, 2, 8)     // psa_2
   SAH_CASE(32, 32, 64, 16, false, 1, 16)    // psa_3
   SAH_CASE(64, 64, 128, 16, false, 1, 16)   // psa_4
-  static const int coarse_w4 = fh_tuning("PWCLO_COARSE_W4", 1);
-  if (coarse_w4 && tiles_h(b, s, 16, 1) <= coarse_tiles_h()) { SAH_CASE(128, 64, 64, 16, false, 1, 4) }   // flow_feature_encoding, coarse
+  if (coarse_w4() && stack_tiles(b, s, 16, 1) <= coarse_tiles()) { SAH_CASE(128, 64, 64, 16, false, 1, 4) }   // flow_feature_encoding, coarse
   SAH_CASE(128, 64, 64, 16, false, 1, 16)   // flow_feature_encoding
 #undef SAH_CASE
   set_error(PWCLO_EINVAL, "sa_fused_h: no kernel for mlp=(%d,%d,%d) nsample=%d level0=%d", c1, c2, c3, k, (int)lvl0);
@@ -798,20 +759,36 @@ extern "C" void upconv_fused_h_kernel_wrapper(int b, int n, int s, int k, const 
   PWCLO_REQUIRE(k >= 1 && k <= 8, "upconv_fused_h: nsample=%d outside [1,8]", k);
   PWCLO_REQUIRE(rows_fit_32bit((long long)b * max(n, s * 8)), "upconv_fused_h: batch too large for 32-bit offsets (b=%d)", b);
   UpHArgs a{xyz2, xyz1, pre, idx, packed_w, out, b, n, s, k};
-  static bool attr = false, attr3 = false;
-  constexpr int lds = 4 * (layer_floats(1, 8) + layer_floats(8, 4));
-  constexpr int lds3 = 4 * (layer_floats(1, 8) + layer_floats_bf3(8, 4));
-  static const int lane_up = fh_tuning("PWCLO_LANE_UP", 1);
-  static bool attrl = false;
+  using St = Stack<1, 8, 8, 4>;
+  PWCLO_REQUIRE_PACKED("upconv_fused_h", wfmt, packed_floats, St);
+  static const int lane_up = tuning("PWCLO_LANE_UP", 1);
   const long long t16 = (long long)b * ((s + 15) / 16);
-  constexpr int lds2 = 4 * (layer_floats(1, 8) + layer_floats_bf16(8, 4));
-  static bool attr2 = false;
-  PWCLO_REQUIRE_PACKED("upconv_fused_h", wfmt, packed_floats, lds / 4, lds3 / 4, lds2 / 4);
-  if (wfmt == PWCLO_WFMT_BF16X3) launch_h<16>(upconv_h_kernel<8, 1, 16, 1>, attr3, lds3, tiles_h(b, s, 8, 1), a);
-  else if (wfmt == PWCLO_WFMT_BF16) launch_h<16>(upconv_h_kernel<8, 1, 16, 2>, attr2, lds2, tiles_h(b, s, 8, 1), a);
-  else if (lane_up && t16 > 2048) launch_h<16>(upconv_lane_kernel<16>, attrl, lds, t16, a);   // in-lane max over K
-  else launch_h<16>(upconv_h_kernel<8, 1, 16>, attr, lds, tiles_h(b, s, 8, 1), a);
+  if (wfmt == PWCLO_WFMT_F32 && lane_up && t16 > 2048)   // in-lane max over K (fp32 tiles only)
+    launch_persistent<upconv_lane_kernel<16>, 16>(St::bytes(), t16, a);
+  else
+    with_format(wfmt, [&](auto fmt) {
+      constexpr int FMT = decltype(fmt)::value;
+      launch_persistent<upconv_h_kernel<8, 1, 16, FMT>, 16>(St::bytes<FMT>(), stack_tiles(b, s, 8, 1), a);
+    });
   check_launch("upconv_fused_h");
+}
+
+// 16-wave workgroups when every wave slot of the chip gets a tile, 8-wave ones (twice the workgroups) below that, 4-wave
+// ones at a coarse level (a few hundred tiles: spread them over as many CUs as possible).  The grid is 2-D (blockIdx.y =
+// job) with a cap of its own, shared by the jobs.
+template <int NB2>
+static void launch_upconv_post(const UpPostArgs &a, int njobs) {
+  constexpr int lds = Stack<1, 8, 8, 4, 4 + NB2, 4>::bytes();
+  const long long t16 = (long long)a.B * ((a.S + 15) / 16), tiles = t16 * njobs;
+  auto go = [&](auto waves, long long cap) {
+    constexpr int W = decltype(waves)::value;
+    long long gx = (t16 + W - 1) / W;
+    if (gx > cap / njobs) gx = cap / njobs;
+    launch_grid<upconv_lane_post_kernel<NB2, W>, W>(dim3((unsigned)gx, njobs), lds, a);
+  };
+  if (tiles >= 4096) go(int_c<16>{}, 512);
+  else if (tiles >= 2048) go(int_c<8>{}, 1024);
+  else go(int_c<4>{}, 2048);
 }
 
 extern "C" void upconv_post_fused_h_kernel_wrapper(int njobs, int b, int n, int s, int k, int c2, const float *xyz2,
@@ -825,40 +802,17 @@ extern "C" void upconv_post_fused_h_kernel_wrapper(int njobs, int b, int n, int 
   PWCLO_REQUIRE(c2 == 16 || c2 == 32 || c2 == 64, "upconv_post_fused_h: %d fine feature channels (16, 32 or 64)", c2);
   PWCLO_REQUIRE(rows_fit_32bit((long long)b * max(n, s * 8)), "upconv_post_fused_h: batch too large for 32-bit offsets (b=%d)", b);
   const int nb2 = c2 / 16;
-  PWCLO_REQUIRE(packed_floats == layer_floats(1, 8) + layer_floats(8, 4),
-                "upconv_post_fused_h: packed stack holds %d floats, needs %d (fp32 tiles)", packed_floats,
-                layer_floats(1, 8) + layer_floats(8, 4));
+  constexpr int stack_f = Stack<1, 8, 8, 4>::floats();
+  PWCLO_REQUIRE(packed_floats == stack_f, "upconv_post_fused_h: packed stack holds %d floats, needs %d (fp32 tiles)",
+                packed_floats, stack_f);
   PWCLO_REQUIRE(post_floats == layer_floats(4 + nb2, 4), "upconv_post_fused_h: packed post layer holds %d floats, needs %d",
                 post_floats, layer_floats(4 + nb2, 4));
   UpPostArgs a{xyz2, xyz1, idx, feat2, {pre[0], pre[njobs - 1]}, {packed_w[0], packed_w[njobs - 1]},
                {packed_post[0], packed_post[njobs - 1]}, {out[0], out[njobs - 1]}, b, n, s, k};
-  const long long t16 = (long long)b * ((s + 15) / 16);
-  const int lds = 4 * (layer_floats(1, 8) + layer_floats(8, 4) + layer_floats(4 + nb2, 4));
-  // 16-wave workgroups when every wave slot of the chip gets a tile, 8-wave ones (twice the workgroups) below that, 4-wave
-  // ones at a coarse level (a few hundred tiles: spread them over as many CUs as possible)
-  const long long tiles = t16 * njobs;
-  const int W = tiles >= 4096 ? 16 : tiles >= 2048 ? 8 : 4;
-  long long gx = (t16 + W - 1) / W;
-  const long long cap = (W == 16 ? 512 : W == 8 ? 1024 : 2048) / njobs;
-  if (gx > cap) gx = cap;
-#define UPP_CASE(NB2)                                                                                         \
-  if (nb2 == NB2) {                                                                                           \
-    static bool attr16 = false, attr8 = false, attr4 = false;                                                 \
-    if (W == 4) {                                                                                             \
-      if (!attr4) { (void)hipFuncSetAttribute((const void *)upconv_lane_post_kernel<NB2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr4 = true; } \
-      hipLaunchKernelGGL((upconv_lane_post_kernel<NB2, 4>), dim3((unsigned)gx, njobs), dim3(4 * 64), lds, current_stream(), a); \
-    } else if (W == 16) {                                                                                     \
-      if (!attr16) { (void)hipFuncSetAttribute((const void *)upconv_lane_post_kernel<NB2, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr16 = true; } \
-      hipLaunchKernelGGL((upconv_lane_post_kernel<NB2, 16>), dim3((unsigned)gx, njobs), dim3(16 * 64), lds, current_stream(), a); \
-    } else {                                                                                                  \
-      if (!attr8) { (void)hipFuncSetAttribute((const void *)upconv_lane_post_kernel<NB2, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr8 = true; } \
-      hipLaunchKernelGGL((upconv_lane_post_kernel<NB2, 8>), dim3((unsigned)gx, njobs), dim3(8 * 64), lds, current_stream(), a); \
-    }                                                                                                         \
-    check_launch("upconv_post_fused_h");                                                                      \
-    return;                                                                                                   \
-  }
-  UPP_CASE(1) UPP_CASE(2) UPP_CASE(4)
-#undef UPP_CASE
+  if (nb2 == 1) launch_upconv_post<1>(a, njobs);
+  else if (nb2 == 2) launch_upconv_post<2>(a, njobs);
+  else launch_upconv_post<4>(a, njobs);
+  check_launch("upconv_post_fused_h");
 }
 
 extern "C" void cv_fused_a1_h_kernel_wrapper(int b, int n, int s, int k, const float *xyz1, const float *u,
@@ -871,32 +825,16 @@ extern "C" void cv_fused_a1_h_kernel_wrapper(int b, int n, int s, int k, const f
   PWCLO_REQUIRE(rows_fit_32bit((long long)b * max(n, s * 32)), "cv_fused_a1_h: batch too large for 32-bit offsets (b=%d)", b);
   CVHArgs a{xyz1, u, xyz2, v, nullptr, idx, packed_w, pix, b, n, s, k};
   const int kp = pix_slots;
-  constexpr int lds = 4 * (layer_floats(1, 8) + layer_floats(8, 4) + layer_floats(4, 4));
-  constexpr int lds3 = 4 * (layer_floats(1, 8) + layer_floats_bf3(8, 4) + layer_floats_bf3(4, 4));
-  static bool a32 = false, a16 = false, a8 = false, a6 = false, b32 = false, b16 = false, b8 = false, b6 = false;
-  constexpr int lds2 = 4 * (layer_floats(1, 8) + layer_floats_bf16(8, 4) + layer_floats_bf16(4, 4));
-  PWCLO_REQUIRE_PACKED("cv_fused_a1_h", wfmt, packed_floats, lds / 4, lds3 / 4, lds2 / 4);
-  if (wfmt == PWCLO_WFMT_BF16X3) {
-    if (kp == 6) launch_h<16>(cv_a1_h_kernel<6, 1, 16, 1>, b6, lds3, tiles_h(b, s, 6, 1), a);
-    else if (kp == 32) launch_h<16>(cv_a1_h_kernel<32, 1, 16, 1>, b32, lds3, tiles_h(b, s, 32, 1), a);
-    else if (kp == 16) launch_h<16>(cv_a1_h_kernel<16, 1, 16, 1>, b16, lds3, tiles_h(b, s, 16, 1), a);
-    else launch_h<16>(cv_a1_h_kernel<8, 1, 16, 1>, b8, lds3, tiles_h(b, s, 8, 1), a);
-    check_launch("cv_fused_a1_h");
-    return;
-  }
-  if (wfmt == PWCLO_WFMT_BF16) {
-    static bool c32 = false, c16 = false, c8 = false, c6 = false;
-    if (kp == 6) launch_h<16>(cv_a1_h_kernel<6, 1, 16, 2>, c6, lds2, tiles_h(b, s, 6, 1), a);
-    else if (kp == 32) launch_h<16>(cv_a1_h_kernel<32, 1, 16, 2>, c32, lds2, tiles_h(b, s, 32, 1), a);
-    else if (kp == 16) launch_h<16>(cv_a1_h_kernel<16, 1, 16, 2>, c16, lds2, tiles_h(b, s, 16, 1), a);
-    else launch_h<16>(cv_a1_h_kernel<8, 1, 16, 2>, c8, lds2, tiles_h(b, s, 8, 1), a);
-    check_launch("cv_fused_a1_h");
-    return;
-  }
-  if (kp == 6) launch_h<16>(cv_a1_h_kernel<6, 1, 16>, a6, lds, tiles_h(b, s, 6, 1), a);
-  else if (kp == 32) launch_h<16>(cv_a1_h_kernel<32, 1, 16>, a32, lds, tiles_h(b, s, 32, 1), a);
-  else if (kp == 16) launch_h<16>(cv_a1_h_kernel<16, 1, 16>, a16, lds, tiles_h(b, s, 16, 1), a);
-  else launch_h<16>(cv_a1_h_kernel<8, 1, 16>, a8, lds, tiles_h(b, s, 8, 1), a);
+  using St = Stack<1, 8, 8, 4, 4, 4>;
+  PWCLO_REQUIRE_PACKED("cv_fused_a1_h", wfmt, packed_floats, St);
+  with_format(wfmt, [&](auto fmt) {
+    constexpr int FMT = decltype(fmt)::value;
+    constexpr int lds = St::bytes<FMT>();
+    if (kp == 6) launch_persistent<cv_a1_h_kernel<6, 1, 16, FMT>, 16>(lds, stack_tiles(b, s, 6, 1), a);
+    else if (kp == 32) launch_persistent<cv_a1_h_kernel<32, 1, 16, FMT>, 16>(lds, stack_tiles(b, s, 32, 1), a);
+    else if (kp == 16) launch_persistent<cv_a1_h_kernel<16, 1, 16, FMT>, 16>(lds, stack_tiles(b, s, 16, 1), a);
+    else launch_persistent<cv_a1_h_kernel<8, 1, 16, FMT>, 16>(lds, stack_tiles(b, s, 8, 1), a);
+  });
   check_launch("cv_fused_a1_h");
 }
 
@@ -906,8 +844,7 @@ extern "C" void cv_fused_a_lane6_kernel_wrapper(int b, int n, int s, const float
                                                 float *v2, int a1_floats, int a2_floats, int v2_floats) {
   if (b <= 0 || s <= 0) return;
   PWCLO_REQUIRE(rows_fit_32bit((long long)b * max(n, s * 6)), "cv_fused_a_lane6: batch too large for 32-bit offsets (b=%d)", b);
-  constexpr int fa1 = layer_floats(1, 8) + layer_floats(8, 4) + layer_floats(4, 4);
-  constexpr int fa2 = layer_floats(1, 4) + layer_floats(8, 8) + layer_floats(8, 4);
+  constexpr int fa1 = Stack<1, 8, 8, 4, 4, 4>::floats(), fa2 = Stack<1, 4, 8, 8, 8, 4>::floats();
   PWCLO_REQUIRE(a1_floats == fa1 && a2_floats == fa2, "cv_fused_a_lane6: packed stacks hold %d / %d floats, need %d / %d (fp32 tiles)",
                 a1_floats, a2_floats, fa1, fa2);
   PWCLO_REQUIRE((packed_v2 == nullptr) == (v2 == nullptr) && (packed_v2 == nullptr || v2_floats == layer_floats(4, 8)),
@@ -916,11 +853,10 @@ extern "C" void cv_fused_a_lane6_kernel_wrapper(int b, int n, int s, const float
   constexpr int lds = 4 * (fa1 + fa2);
   static_assert(lds <= 160 * 1024, "both stages' weights must fit the 160 KiB of LDS");
   const long long t16 = (long long)b * ((s + 15) / 16);
-  static bool attr = false, attr_v = false, attr_v4 = false;
   // a coarse level's few hundred tiles: 4-wave workgroups spread them over twice the CUs
-  if (packed_v2 != nullptr && t16 <= 1024) launch_h<4>(cv_a_lane6_kernel<4, true>, attr_v4, lds, t16, a);
-  else if (packed_v2 != nullptr) launch_h<8>(cv_a_lane6_kernel<8, true>, attr_v, lds, t16, a);
-  else launch_h<8>(cv_a_lane6_kernel<8, false>, attr, lds, t16, a);
+  if (packed_v2 != nullptr && t16 <= 1024) launch_persistent<cv_a_lane6_kernel<4, true>, 4>(lds, t16, a);
+  else if (packed_v2 != nullptr) launch_persistent<cv_a_lane6_kernel<8, true>, 8>(lds, t16, a);
+  else launch_persistent<cv_a_lane6_kernel<8, false>, 8>(lds, t16, a);
   check_launch("cv_fused_a_lane6");
 }
 
@@ -931,20 +867,14 @@ extern "C" void cv_fused_b_h_kernel_wrapper(int b, int s, int k, const float *xy
   PWCLO_REQUIRE(k >= 1 && k <= 4, "cv_fused_b_h: nsample=%d outside [1,4]", k);
   PWCLO_REQUIRE(rows_fit_32bit((long long)b * s * 4), "cv_fused_b_h: batch too large for 32-bit offsets (b=%d)", b);
   CVHArgs a{xyz1, u2, xyz1, v2, first, idx, packed_w, out, b, s, s, k};
-  static bool attr = false;
-  constexpr int lds = 4 * (layer_floats(1, 4) + layer_floats(4, 8) + layer_floats(8, 4));
-  static bool attr_s = false, attr3 = false, attr3_s = false;
-  constexpr int lds3 = 4 * (layer_floats(1, 4) + layer_floats_bf3(4, 8) + layer_floats_bf3(8, 4));
-  static const int coarse_w4 = fh_tuning("PWCLO_COARSE_W4", 1);
-  const bool small = coarse_w4 && tiles_h(b, s, 4, 1) <= coarse_tiles_h();
-  constexpr int lds2 = 4 * (layer_floats(1, 4) + layer_floats_bf16(4, 8) + layer_floats_bf16(8, 4));
-  static bool attr2 = false, attr2_s = false;
-  PWCLO_REQUIRE_PACKED("cv_fused_b_h", wfmt, packed_floats, lds / 4, lds3 / 4, lds2 / 4);
-  if (wfmt == PWCLO_WFMT_BF16X3 && small) launch_h<4>(cv_b_h_kernel<4, 1, 4, 1>, attr3_s, lds3, tiles_h(b, s, 4, 1), a);
-  else if (wfmt == PWCLO_WFMT_BF16X3) launch_h<16>(cv_b_h_kernel<4, 1, 16, 1>, attr3, lds3, tiles_h(b, s, 4, 1), a);
-  else if (wfmt == PWCLO_WFMT_BF16 && small) launch_h<4>(cv_b_h_kernel<4, 1, 4, 2>, attr2_s, lds2, tiles_h(b, s, 4, 1), a);
-  else if (wfmt == PWCLO_WFMT_BF16) launch_h<16>(cv_b_h_kernel<4, 1, 16, 2>, attr2, lds2, tiles_h(b, s, 4, 1), a);
-  else if (small) launch_h<4>(cv_b_h_kernel<4, 1, 4>, attr_s, lds, tiles_h(b, s, 4, 1), a);
-  else launch_h<16>(cv_b_h_kernel<4, 1, 16>, attr, lds, tiles_h(b, s, 4, 1), a);
+  using St = Stack<1, 4, 4, 8, 8, 4>;
+  PWCLO_REQUIRE_PACKED("cv_fused_b_h", wfmt, packed_floats, St);
+  const long long tiles = stack_tiles(b, s, 4, 1);
+  const bool small = coarse_w4() && tiles <= coarse_tiles();
+  with_format(wfmt, [&](auto fmt) {
+    constexpr int FMT = decltype(fmt)::value;
+    if (small) launch_persistent<cv_b_h_kernel<4, 1, 4, FMT>, 4>(St::bytes<FMT>(), tiles, a);
+    else launch_persistent<cv_b_h_kernel<4, 1, 16, FMT>, 16>(St::bytes<FMT>(), tiles, a);
+  });
   check_launch("cv_fused_b_h");
 }

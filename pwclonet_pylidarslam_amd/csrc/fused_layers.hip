@@ -12,10 +12,12 @@
 //          -> softmax over the neighbours -> sum_k w * gathered first     ("second aggregate", :146-188)
 // The only materialised intermediate is cv_a1's 64-channel per-pixel feature (written once, read
 // once); the reference materialises > 10 (B,C,S,K) tensors for the same result.
+//
+// Launch policy (tuning variables, stack sizes per weight format, persistent grid, the per-kernel LDS attribute) lives
+// in launch.hpp; the wrappers at the end of this file only choose (kernel, workgroup width, tile count).
 #include <math.h>
-#include <stdlib.h>
 
-#include "mlp_core.hpp"
+#include "launch.hpp"
 
 PWCLO_TRACE_TU(fused_layers)
 
@@ -760,39 +762,21 @@ __global__ __launch_bounds__(64 * MP_PARTS) void pose_head_kernel(PoseHeadArgs a
   }
 }
 
-// ---- launch helpers ------------------------------------------------------------------------------------
-static int fl_tuning(const char *name, int dflt) {   // PWCLO_FL_<NAME> overrides (experiments)
-  const char *e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
-
-// Largest launch (in wave tiles) that still takes the 4-wave workgroup variants of the point-wise / coarse-level kernels.  Narrow
-// workgroups reach more CUs -- lower latency of a lone forward (batch 1: +7 %, batch 4: +5 %) -- but every workgroup stages the
-// stack's 100-160 KB of weights again, which costs CU-time: in the pipelined batch-32 run the launches of exactly 2048 tiles
-// (level-2 flow predictors) are better off wide (+0.3 %, profiles/r03/r03_v7_ab_coarse_w4.txt); smaller ones stay narrow.
-static int coarse_tiles() {
-  static const int v = fl_tuning("PWCLO_COARSE_W4_TILES", 2047);
-  return v;
-}
-
-template <int W, typename Kern, typename Args>
-static void launch_persistent(Kern kern, bool &attr_set, int lds_bytes, long long ntiles, const Args &a) {
-  if (lds_bytes > 64 * 1024 && !attr_set) {
-    (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);  // once per kernel: the largest any configuration can ask for
-    attr_set = true;
-  }
-  // Workgroups beyond one resident set queue behind it; >1 "rounds" keeps the kernel balanced when
-  // part of the chip is held by another stream's kernels (e.g. the other in-flight batch's FPS).
-  static const int rounds = fl_tuning("PWCLO_FL_ROUNDS", 1);
-  const int per_cu = (lds_bytes > 80 * 1024 || W > 8) ? 1 : 2;
-  long long grid = (ntiles + W - 1) / W;
-  if (grid > 256LL * per_cu * rounds) grid = 256LL * per_cu * rounds;
-  if (grid < 1) grid = 1;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(W * 64), lds_bytes, current_stream(), a);
-}
-
-static long long tiles_of(int b, int s, int kp, int p) {
-  return (long long)b * (((long long)s * kp + 16 * p - 1) / (16 * p));
+// ---- point-wise launch: the one place that picks pointwise_kernel's workgroup width -----------------------------
+// few tiles (coarse levels): 4-wave workgroups spread them over 4x more CUs; a 16-wave workgroup would run 4 tiles
+// back to back on each SIMD while most of the chip idles.  The stack + tail form (BT > 0) exists on 4- and 16-wave
+// workgroups only.
+template <int NB0, int NB1, int NB2, int B1, int B2, int BT = 0>
+static void launch_pointwise(const PointwiseArgs &a) {
+  constexpr int lds = Stack<NB0 + NB1 + NB2, B1, B1, B2, B2, BT>::bytes();
+  static_assert(lds <= 160 * 1024, "stack and tail must fit the 160 KiB of LDS");
+  const bool wide = BT > 0 || fl_wide();
+  const long long t1 = stack_tiles(a.B, a.S, 1, 1);
+  if (wide && coarse_w4() && t1 <= coarse_tiles())
+    launch_persistent<pointwise_kernel<NB0, NB1, NB2, B1, B2, 1, 4, BT>, 4>(lds, t1, a);
+  else if (wide) launch_persistent<pointwise_kernel<NB0, NB1, NB2, B1, B2, 1, 16, BT>, 16>(lds, t1, a);
+  else if constexpr (BT == 0)
+    launch_persistent<pointwise_kernel<NB0, NB1, NB2, B1, B2, 2, 8>, 8>(lds, stack_tiles(a.B, a.S, 1, 2), a);
 }
 
 }  // namespace pwclo
@@ -804,12 +788,10 @@ extern "C" void upconv_fused_kernel_wrapper(int b, int n, int s, int k, const fl
                                             const float *packed_w, float *out) {
   if (b <= 0 || s <= 0) return;
   PWCLO_REQUIRE(k >= 1 && k <= 8, "upconv_fused: nsample=%d outside [1,8]", k);
-  UpconvArgs a{xyz2, xyz1, feat1, idx, packed_w, out, b, n, s, k, fl_tuning("PWCLO_FL_STAGGER", 0)};
-  static bool attr = false, attr1 = false;
-  static const int wide = fl_tuning("PWCLO_FL_WIDE", 1);
-  constexpr int lds = 4 * (layer_floats(5, 8) + layer_floats(8, 4));
-  if (wide) launch_persistent<16>(upconv_kernel<8, 1, 16>, attr1, lds, tiles_of(b, s, 8, 1), a);
-  else launch_persistent<8>(upconv_kernel<8, 2, 8>, attr, lds, tiles_of(b, s, 8, 2), a);
+  UpconvArgs a{xyz2, xyz1, feat1, idx, packed_w, out, b, n, s, k, fl_stagger()};
+  constexpr int lds = Stack<5, 8, 8, 4>::bytes();
+  if (fl_wide()) launch_persistent<upconv_kernel<8, 1, 16>, 16>(lds, stack_tiles(b, s, 8, 1), a);
+  else launch_persistent<upconv_kernel<8, 2, 8>, 8>(lds, stack_tiles(b, s, 8, 2), a);
   check_launch("upconv_fused");
 }
 
@@ -818,22 +800,10 @@ extern "C" void pointwise_fused_kernel_wrapper(int b, int s, int c0, int c1, int
                                                const float *packed_w, float *out) {
   if (b <= 0 || s <= 0) return;
   PWCLO_REQUIRE(rows_fit_32bit((long long)b * s), "pointwise_fused: batch too large for 32-bit offsets (b=%d)", b);
-  PointwiseArgs a{{src0, src1, src2}, packed_w, out, b, s, fl_tuning("PWCLO_FL_STAGGER", 0), nullptr, nullptr};
+  PointwiseArgs a{{src0, src1, src2}, packed_w, out, b, s, fl_stagger(), nullptr, nullptr};
 #define PW_CASE(C0, C1, C2, A1, A2)                                                                 \
   if (c0 == C0 && c1 == C1 && c2 == C2 && w1 == A1 && w2 == A2) {                                   \
-    static bool attr = false, attr1 = false, attr4 = false;                                         \
-    static const int wide = fl_tuning("PWCLO_FL_WIDE", 1);                                          \
-    constexpr int NBI = (C0 + C1 + C2) / 16;                                                        \
-    constexpr int lds = 4 * (layer_floats(NBI, A1 / 16) + (A2 > 0 ? layer_floats(A1 / 16, A2 / 16) : 0)); \
-    /* few tiles (coarse levels): 4-wave workgroups spread them over 4x more CUs; a 16-wave        \
-       workgroup would run 4 tiles back to back on each SIMD while most of the chip idles */        \
-    if (wide && fl_tuning("PWCLO_COARSE_W4", 1) && tiles_of(b, s, 1, 1) <= coarse_tiles())                  \
-      launch_persistent<4>(pointwise_kernel<C0 / 16, C1 / 16, C2 / 16, A1 / 16, A2 / 16, 1, 4>,      \
-                           attr4, lds, tiles_of(b, s, 1, 1), a);                                    \
-    else if (wide) launch_persistent<16>(pointwise_kernel<C0 / 16, C1 / 16, C2 / 16, A1 / 16, A2 / 16, 1, 16>, \
-                                    attr1, lds, tiles_of(b, s, 1, 1), a);                           \
-    else launch_persistent<8>(pointwise_kernel<C0 / 16, C1 / 16, C2 / 16, A1 / 16, A2 / 16, 2, 8>, attr, lds, \
-                              tiles_of(b, s, 1, 2), a);                                             \
+    launch_pointwise<C0 / 16, C1 / 16, C2 / 16, A1 / 16, A2 / 16>(a);                               \
     check_launch("pointwise_fused");                                                                \
     return;                                                                                         \
   }
@@ -862,17 +832,9 @@ extern "C" void pointwise_tail_fused_kernel_wrapper(int b, int s, int c0, int c1
   PointwiseArgs a{{src0, src1, src2}, packed_w, out, b, s, 0, packed_tail, out_tail};
 #define PWT_CASE(C0, C1, C2, A1, A2, AT)                                                            \
   if (c0 == C0 && c1 == C1 && c2 == C2 && w1 == A1 && w2 == A2 && wt == AT) {                       \
-    static bool attr16 = false, attr4 = false;                                                      \
-    constexpr int NBI = (C0 + C1 + C2) / 16;                                                        \
-    constexpr int lds = 4 * (layer_floats(NBI, A1 / 16) + layer_floats(A1 / 16, A2 / 16) + layer_floats(A2 / 16, AT / 16)); \
-    static_assert(lds <= 160 * 1024, "stack and tail must fit the 160 KiB of LDS");                 \
     PWCLO_REQUIRE(tail_floats == layer_floats(A2 / 16, AT / 16), "pointwise_tail_fused: packed tail holds %d floats, needs %d", \
                   tail_floats, layer_floats(A2 / 16, AT / 16));                                     \
-    if (fl_tuning("PWCLO_COARSE_W4", 1) && tiles_of(b, s, 1, 1) <= coarse_tiles())                        \
-      launch_persistent<4>(pointwise_kernel<C0 / 16, C1 / 16, C2 / 16, A1 / 16, A2 / 16, 1, 4, AT / 16>, \
-                           attr4, lds, tiles_of(b, s, 1, 1), a);                                    \
-    else launch_persistent<16>(pointwise_kernel<C0 / 16, C1 / 16, C2 / 16, A1 / 16, A2 / 16, 1, 16, AT / 16>, \
-                               attr16, lds, tiles_of(b, s, 1, 1), a);                               \
+    launch_pointwise<C0 / 16, C1 / 16, C2 / 16, A1 / 16, A2 / 16, AT / 16>(a);                      \
     check_launch("pointwise_tail_fused");                                                           \
     return;                                                                                         \
   }
@@ -889,15 +851,13 @@ extern "C" void cv_fused_a1_kernel_wrapper(int b, int n, int s, int k, int c, co
   if (b <= 0 || s <= 0) return;
   PWCLO_REQUIRE(k >= 1 && k <= 32, "cv_fused_a1: nsample_q=%d outside [1,32]", k);
   PWCLO_REQUIRE(cv_pix_slots_valid(k, pix_slots), "cv_fused_a1: pix_slots=%d invalid for nsample_q=%d", pix_slots, k);
-  CVArgs a{xyz1, feat1, xyz2, feat2, idx, packed_w, pix, nullptr, b, n, s, k, fl_tuning("PWCLO_FL_STAGGER", 0)};
+  CVArgs a{xyz1, feat1, xyz2, feat2, idx, packed_w, pix, nullptr, b, n, s, k, fl_stagger()};
   const int kp = pix_slots;
 #define A1_CASE(C, KP)                                                                              \
   if (c == C && kp == KP) {                                                                         \
-    static bool attr = false, attr1 = false;                                                        \
-    static const int wide = fl_tuning("PWCLO_FL_WIDE", 1);                                          \
-    constexpr int lds = 4 * (layer_floats(1 + 2 * (C / 16), 8) + layer_floats(8, 4) + layer_floats(4, 4)); \
-    if (wide && KP <= 16) launch_persistent<16>(cv_a1_kernel<C / 16, KP, 1, 16>, attr1, lds, tiles_of(b, s, KP, 1), a); \
-    else launch_persistent<8>(cv_a1_kernel<C / 16, KP, 2, 8>, attr, lds, tiles_of(b, s, KP, 2), a);  \
+    constexpr int lds = Stack<1 + 2 * (C / 16), 8, 8, 4, 4, 4>::bytes();                            \
+    if (fl_wide() && KP <= 16) launch_persistent<cv_a1_kernel<C / 16, KP, 1, 16>, 16>(lds, stack_tiles(b, s, KP, 1), a); \
+    else launch_persistent<cv_a1_kernel<C / 16, KP, 2, 8>, 8>(lds, stack_tiles(b, s, KP, 2), a);    \
     check_launch("cv_fused_a1");                                                                    \
     return;                                                                                         \
   }
@@ -914,53 +874,35 @@ extern "C" void cv_fused_a2_kernel_wrapper(int b, int n, int s, int k, const flo
   PWCLO_REQUIRE(k >= 1 && k <= 32, "cv_fused_a2: nsample_q=%d outside [1,32]", k);
   PWCLO_REQUIRE(cv_pix_slots_valid(k, pix_slots), "cv_fused_a2: pix_slots=%d invalid for nsample_q=%d", pix_slots, k);
   PWCLO_REQUIRE(rows_fit_32bit((long long)b * max(n, s * 32)), "cv_fused_a2: batch too large for 32-bit offsets (b=%d)", b);
-  CVArgs a{xyz1, nullptr, xyz2, nullptr, idx, packed_w, const_cast<float *>(pix), out, b, n, s, k,
-           fl_tuning("PWCLO_FL_STAGGER", 0)};
+  CVArgs a{xyz1, nullptr, xyz2, nullptr, idx, packed_w, const_cast<float *>(pix), out, b, n, s, k, fl_stagger()};
   const int kp = pix_slots;
-  constexpr int lds = 4 * (layer_floats(1, 4) + layer_floats(8, 8) + layer_floats(8, 4));
-  {
-    constexpr int lds3c = 4 * (layer_floats(1, 4) + layer_floats_bf3(8, 8) + layer_floats_bf3(8, 4));
-    constexpr int lds2c = 4 * (layer_floats(1, 4) + layer_floats_bf16(8, 8) + layer_floats_bf16(8, 4));
-    PWCLO_REQUIRE(wfmt == PWCLO_WFMT_F32 || kp == 6 || kp == 32,
-                  "cv_fused_a2: the reduced formats exist for 6 / 32 pixel slots only (got %d)", kp);
-    PWCLO_REQUIRE_PACKED("cv_fused_a2", wfmt, packed_floats, lds / 4, lds3c / 4, lds2c / 4);
-  }
-  static bool attr32 = false, attr16 = false, attr8 = false, attr16w = false, attr8w = false, attr6 = false;
-  static const int wide = fl_tuning("PWCLO_FL_WIDE", 1);
-  static bool attr6s = false;
-  const long long t6 = (long long)b * ((s + 7) / 8);
-  if (wfmt == PWCLO_WFMT_BF16X3) {     // opt-in split path (mlp_core.hpp)
-    constexpr int lds3 = 4 * (layer_floats(1, 4) + layer_floats_bf3(8, 8) + layer_floats_bf3(8, 4));
-    static bool b6 = false, b6s = false, b32 = false;
-    if (kp == 6 && t6 <= 2048) launch_persistent<4>(cv_a2_dense6_kernel<4, 1>, b6s, lds3, t6, a);
-    else if (kp == 6) launch_persistent<8>(cv_a2_dense6_kernel<8, 1>, b6, lds3, t6, a);
-    else launch_persistent<8>(cv_a2_kernel<32, 2, 8, 1>, b32, lds3, tiles_of(b, s, 32, 2), a);
-    check_launch("cv_fused_a2");
-    return;
-  }
-  if (wfmt == PWCLO_WFMT_BF16) {
-    constexpr int lds2 = 4 * (layer_floats(1, 4) + layer_floats_bf16(8, 8) + layer_floats_bf16(8, 4));
-    static bool c6 = false, c6s = false, c32 = false;
-    if (kp == 6 && t6 <= 2048) launch_persistent<4>(cv_a2_dense6_kernel<4, 2>, c6s, lds2, t6, a);
-    else if (kp == 6) launch_persistent<8>(cv_a2_dense6_kernel<8, 2>, c6, lds2, t6, a);
-    else launch_persistent<8>(cv_a2_kernel<32, 2, 8, 2>, c32, lds2, tiles_of(b, s, 32, 2), a);
-    check_launch("cv_fused_a2");
-    return;
-  }
-  static const int lane6 = fl_tuning("PWCLO_LANE6", 1);
-  static bool attrl = false;
-  const long long t16 = (long long)b * ((s + 15) / 16);
-  // in-lane softmax for the large levels; a coarse level has too few 16-query tiles to fill the chip (measured:
-  // 48 us against 31 us for the dense-6 kernel on 4-wave workgroups at S = 256)
-  if (kp == 6 && lane6 && t16 > 1024) launch_persistent<8>(cv_a2_lane6_kernel<8>, attrl, lds, t16, a);
-  else if (kp == 6 && t6 <= 2048 && fl_tuning("PWCLO_COARSE_W4", 1))   // coarse level: 4-wave workgroups reach twice as many CUs
-    launch_persistent<4>(cv_a2_dense6_kernel<4>, attr6s, lds, t6, a);
-  else if (kp == 6) launch_persistent<8>(cv_a2_dense6_kernel<8>, attr6, lds, t6, a);
-  else if (kp == 32) launch_persistent<8>(cv_a2_kernel<32, 2, 8>, attr32, lds, tiles_of(b, s, 32, 2), a);
-  else if (kp == 16 && wide) launch_persistent<16>(cv_a2_kernel<16, 1, 16>, attr16w, lds, tiles_of(b, s, 16, 1), a);
-  else if (kp == 16) launch_persistent<8>(cv_a2_kernel<16, 2, 8>, attr16, lds, tiles_of(b, s, 16, 2), a);
-  else if (wide) launch_persistent<16>(cv_a2_kernel<8, 1, 16>, attr8w, lds, tiles_of(b, s, 8, 1), a);
-  else launch_persistent<8>(cv_a2_kernel<8, 2, 8>, attr8, lds, tiles_of(b, s, 8, 2), a);
+  using St = Stack<1, 4, 8, 8, 8, 4>;
+  PWCLO_REQUIRE(wfmt == PWCLO_WFMT_F32 || kp == 6 || kp == 32,
+                "cv_fused_a2: the reduced formats exist for 6 / 32 pixel slots only (got %d)", kp);
+  PWCLO_REQUIRE_PACKED("cv_fused_a2", wfmt, packed_floats, St);
+  static const int lane6 = tuning("PWCLO_LANE6", 1);
+  const long long t6 = (long long)b * ((s + 7) / 8), t16 = (long long)b * ((s + 15) / 16);
+  with_format(wfmt, [&](auto fmt) {
+    constexpr int FMT = decltype(fmt)::value;
+    constexpr int lds = St::bytes<FMT>();
+    // the reduced formats (opt-in, mlp_core.hpp) take the 4-wave dense-6 kernel whatever PWCLO_COARSE_W4 says
+    const bool w4 = FMT != PWCLO_WFMT_F32 || coarse_w4();
+    if constexpr (FMT == PWCLO_WFMT_F32) {
+      // in-lane softmax for the large levels; a coarse level has too few 16-query tiles to fill the chip (measured:
+      // 48 us against 31 us for the dense-6 kernel on 4-wave workgroups at S = 256)
+      if (kp == 6 && lane6 && t16 > 1024) return launch_persistent<cv_a2_lane6_kernel<8>, 8>(lds, t16, a);
+    }
+    if (kp == 6 && t6 <= 2048 && w4)   // coarse level: 4-wave workgroups reach twice as many CUs
+      launch_persistent<cv_a2_dense6_kernel<4, FMT>, 4>(lds, t6, a);
+    else if (kp == 6) launch_persistent<cv_a2_dense6_kernel<8, FMT>, 8>(lds, t6, a);
+    else if (kp == 32) launch_persistent<cv_a2_kernel<32, 2, 8, FMT>, 8>(lds, stack_tiles(b, s, 32, 2), a);
+    else if constexpr (FMT == PWCLO_WFMT_F32) {   // 16 / 8 pixel slots: fp32 tiles only (required above)
+      if (kp == 16 && fl_wide()) launch_persistent<cv_a2_kernel<16, 1, 16>, 16>(lds, stack_tiles(b, s, 16, 1), a);
+      else if (kp == 16) launch_persistent<cv_a2_kernel<16, 2, 8>, 8>(lds, stack_tiles(b, s, 16, 2), a);
+      else if (fl_wide()) launch_persistent<cv_a2_kernel<8, 1, 16>, 16>(lds, stack_tiles(b, s, 8, 1), a);
+      else launch_persistent<cv_a2_kernel<8, 2, 8>, 8>(lds, stack_tiles(b, s, 8, 2), a);
+    }
+  });
   check_launch("cv_fused_a2");
 }
 
@@ -969,14 +911,12 @@ extern "C" void cv_fused_b_kernel_wrapper(int b, int s, int k, int c, const floa
                                           const float *packed_w, float *out) {
   if (b <= 0 || s <= 0) return;
   PWCLO_REQUIRE(k >= 1 && k <= 4, "cv_fused_b: nsample=%d outside [1,4]", k);
-  CVArgs a{xyz1, feat1, xyz1, first, idx, packed_w, nullptr, out, b, s, s, k, fl_tuning("PWCLO_FL_STAGGER", 0)};
+  CVArgs a{xyz1, feat1, xyz1, first, idx, packed_w, nullptr, out, b, s, s, k, fl_stagger()};
 #define B_CASE(C)                                                                                   \
   if (c == C) {                                                                                     \
-    static bool attr = false, attr1 = false;                                                        \
-    static const int wide = fl_tuning("PWCLO_FL_WIDE", 1);                                          \
-    constexpr int lds = 4 * (layer_floats(1, 4) + layer_floats(8 + C / 16, 8) + layer_floats(8, 4)); \
-    if (wide) launch_persistent<16>(cv_b_kernel<C / 16, 4, 1, 16>, attr1, lds, tiles_of(b, s, 4, 1), a); \
-    else launch_persistent<8>(cv_b_kernel<C / 16, 4, 2, 8>, attr, lds, tiles_of(b, s, 4, 2), a);     \
+    constexpr int lds = Stack<1, 4, 8 + C / 16, 8, 8, 4>::bytes();                                  \
+    if (fl_wide()) launch_persistent<cv_b_kernel<C / 16, 4, 1, 16>, 16>(lds, stack_tiles(b, s, 4, 1), a); \
+    else launch_persistent<cv_b_kernel<C / 16, 4, 2, 8>, 8>(lds, stack_tiles(b, s, 4, 2), a);       \
     check_launch("cv_fused_b");                                                                     \
     return;                                                                                         \
   }

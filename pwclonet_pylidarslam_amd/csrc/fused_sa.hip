@@ -7,9 +7,10 @@
 // by ONE kernel whose HBM traffic is the algorithmic minimum: indices + gathered rows in,
 // (B,S,Cout) out.  Feature tensors are point-major (B,N,C) so a neighbour's channels are one
 // contiguous row (16-byte gathers).  See mlp_core.hpp for the register/MFMA layout.
-#include <stdlib.h>
-
-#include "mlp_core.hpp"
+//
+// Launch policy (tuning variables, persistent grid, the per-kernel LDS attribute) lives in launch.hpp; this file
+// keeps the set-abstraction rule SA_GRID (two persistent rounds, workgroups per CU from the LDS size alone).
+#include "launch.hpp"
 
 namespace pwclo {
 
@@ -103,27 +104,6 @@ __global__ __launch_bounds__(SA_WAVES * 64) void sa_kernel(SAArgs a) {
   }
 }
 
-template <int CFB, int B1, int B2, int B3, int KP, int P, bool XYZ_ONLY>
-static void launch_sa(const SAArgs &a) {
-  constexpr int NBI = 1 + CFB;
-  constexpr int lds_bytes = 4 * (layer_floats(NBI, B1) + layer_floats(B1, B2) + layer_floats(B2, B3));
-  static_assert(lds_bytes <= 160 * 1024, "packed weights must fit in LDS");
-  auto kern = sa_kernel<CFB, B1, B2, B3, KP, P, XYZ_ONLY>;
-  static bool attr_set = false;
-  if (lds_bytes > 64 * 1024 && !attr_set) {
-    (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);  // once per kernel: the largest any configuration can ask for
-    attr_set = true;
-  }
-  const long long pix = (long long)a.S * KP;
-  const long long ntiles = (long long)a.B * ((pix + 16 * P - 1) / (16 * P));
-  static int rounds = -1;
-  if (rounds < 0) { const char *e = getenv("PWCLO_FL_ROUNDS"); rounds = e ? atoi(e) : 2; }
-  const int per_cu = lds_bytes > 80 * 1024 ? 1 : 2;
-  long long grid = (ntiles + SA_WAVES - 1) / SA_WAVES;
-  if (grid > 256LL * per_cu * rounds) grid = 256LL * per_cu * rounds;   // persistent workgroups
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(SA_WAVES * 64), lds_bytes, current_stream(), a);
-}
-
 }  // namespace pwclo
 
 using namespace pwclo;
@@ -134,13 +114,14 @@ extern "C" void sa_fused_kernel_wrapper(int b, int n, int s, int k, int c_feat, 
                                         const int *idx, const float *packed_w, float *out) {
   if (b <= 0 || s <= 0) return;
   PWCLO_REQUIRE(k >= 1 && k <= 32, "sa_fused: nsample=%d outside [1,32]", k);
-  static int stagger = -1;
-  if (stagger < 0) { const char *e = getenv("PWCLO_FL_STAGGER"); stagger = e ? atoi(e) : 0; }
-  SAArgs a{xyz, new_xyz, feat, idx, packed_w, out, b, n, s, k, stagger};
+  SAArgs a{xyz, new_xyz, feat, idx, packed_w, out, b, n, s, k, fl_stagger()};
   const int kp = k > 16 ? 32 : 16;
 #define SA_CASE(CF, A1, A2, A3, KP, XYZ)                                                          \
   if (c_feat == CF && c1 == A1 && c2 == A2 && c3 == A3 && kp == KP) {                             \
-    launch_sa<CF / 16, A1 / 16, A2 / 16, A3 / 16, KP, 2, XYZ>(a);                                 \
+    constexpr int lds_bytes = Stack<1 + CF / 16, A1 / 16, A1 / 16, A2 / 16, A2 / 16, A3 / 16>::bytes(); \
+    static_assert(lds_bytes <= 160 * 1024, "packed weights must fit in LDS");                     \
+    launch_persistent<sa_kernel<CF / 16, A1 / 16, A2 / 16, A3 / 16, KP, 2, XYZ>, SA_WAVES>(         \
+        lds_bytes, stack_tiles(b, s, KP, 2), a, SA_GRID);                                         \
     check_launch("sa_fused");                                                                     \
     return;                                                                                       \
   }

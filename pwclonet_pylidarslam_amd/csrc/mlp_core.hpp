@@ -140,7 +140,7 @@ __device__ __forceinline__ void mlp_layer(f32x4 (&out)[NBO][P], const f32x4 (&in
 // lo*lo terms are below 2^-24 relative).  A K = 32 instruction consumes TWO 16-channel blocks: lane group g
 // supplies k = 8g..8g+7, taken as its four registers of block 2*mp and its four of block 2*mp+1, so the
 // accumulator-is-the-next-operand property of the fp32 path carries over; the packed weights hold, per
-// (o, mp) tile, [split][lane][8 bf16] in the matching order (fused.py: pack_layer_bf3).  96 matrix cycles
+// (o, mp) tile, [split][lane][8 bf16] in the matching order (fused.py: pack_layer).  96 matrix cycles
 // per 32 input channels instead of 256, paid for with ~5.5 VALU instructions per split activation.
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
@@ -305,20 +305,9 @@ constexpr int layer_floats_any(int nbi, int nbo) {
          : (FMT == 2 && nbi % 2 == 0) ? layer_floats_bf16(nbi, nbo) : layer_floats(nbi, nbo);
 }
 
-// The format of a packed weight buffer is a property of the BUFFER, fixed when it was packed (fused.py records it
-// on the packed object): the stack launchers take it as an explicit argument `wfmt` together with the buffer's
-// length in floats, and refuse a length that does not match the layout the selected kernel will index
-// (a buffer packed in one format and launched as the other would otherwise be read out of bounds, silently).
+// The packed-weight format of a stack as the launchers receive it (`wfmt`; the values are the FMT template argument).
+// launch.hpp: PWCLO_REQUIRE_PACKED checks a buffer's length against it.
 enum : int { PWCLO_WFMT_F32 = 0, PWCLO_WFMT_BF16X3 = 1, PWCLO_WFMT_BF16 = 2 };
-#define PWCLO_REQUIRE_PACKED(what, wfmt, packed_floats, floats_f32, floats_bf3, floats_bf16)                     \
-  do {                                                                                                           \
-    PWCLO_REQUIRE((wfmt) >= PWCLO_WFMT_F32 && (wfmt) <= PWCLO_WFMT_BF16, what ": unknown weight format %d",        \
-                  (int)(wfmt));                                                                                  \
-    const int expect_ = (wfmt) == PWCLO_WFMT_BF16X3 ? (int)(floats_bf3)                                           \
-                        : (wfmt) == PWCLO_WFMT_BF16 ? (int)(floats_bf16) : (int)(floats_f32);                      \
-    PWCLO_REQUIRE((packed_floats) == expect_, what ": packed weights hold %d floats, format %d needs %d",          \
-                  (int)(packed_floats), (int)(wfmt), expect_);                                                   \
-  } while (0)
 
 // Hoisting.  The first layer of a grouped MLP is linear in its concatenated input
 // [geometry(q,p) | feat_centre[s] | feat_nbr[n]], and the feature parts depend on ONE point, not on

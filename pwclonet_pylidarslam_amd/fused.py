@@ -31,34 +31,6 @@ def fold_conv_bn(layer):
     return w.float(), b.float()
 
 
-def pack_layer(w, b, phys_map, nbo=None, kmajor_out=False):
-    """Pack one folded layer.  ``phys_map``: for every physical input channel (length multiple of
-    16) the original input channel, or -1 for padding.  Output channels are padded to 16*nbo.
-    ``kmajor_out`` (cout <= 16): output channel c is produced on row 4*(c % 4) + c // 4, i.e. in lane group c % 4,
-    accumulator register c // 4 -- the "k-step major" order in which the NEXT layer needs only ceil(cout / 4) of its
-    four MFMA k-steps (its phys_map must be ``kstep_major_map(cout)``)."""
-    cout, _ = w.shape
-    nbi = len(phys_map) // 16
-    assert len(phys_map) == 16 * nbi
-    nbo = nbo or (cout + 15) // 16
-    if kmajor_out:
-        assert cout <= 16 and nbo == 1
-        rows = torch.tensor([4 * (c % 4) + c // 4 for c in range(cout)], dtype=torch.long, device=w.device)
-        w_perm = torch.zeros((16, w.shape[1]), dtype=w.dtype, device=w.device)
-        b_perm = torch.zeros((16,), dtype=b.dtype, device=b.device)
-        w_perm[rows], b_perm[rows] = w, b
-        w, b, cout = w_perm, b_perm, 16
-    pm = torch.as_tensor(phys_map, dtype=torch.long, device=w.device)
-    wphys = torch.zeros((16 * nbo, 16 * nbi), dtype=torch.float32, device=w.device)
-    valid = pm >= 0
-    wphys[:cout, valid] = w[:, pm[valid]]
-    # (o,row,m,g,r) -> (o,m,g,row,r): lane = 16*g + row
-    wp = wphys.view(nbo, 16, nbi, 4, 4).permute(0, 2, 3, 1, 4).reshape(-1)
-    bias = torch.zeros(16 * nbo, dtype=torch.float32, device=w.device)
-    bias[:cout] = b
-    return torch.cat((wp, bias)).contiguous()
-
-
 WFMT_F32, WFMT_BF16X3, WFMT_BF16 = 0, 1, 2     # include/pwclo_ops.h: packed-weight format of a stack (csrc/mlp_core.hpp)
 _DTYPE_WFMT = {"f32": WFMT_F32, "fp32": WFMT_F32, "float32": WFMT_F32, "bf16x3": WFMT_BF16X3, "bf16": WFMT_BF16,
                "bfloat16": WFMT_BF16}
@@ -86,12 +58,65 @@ def default_wfmt():
     return WFMT_BF16X3 if os.environ.get("PWCLO_BF16X3", "0") != "0" else WFMT_F32
 
 
+def pack_layer(w, b, phys_map, nbo=None, wfmt=WFMT_F32, kmajor_out=False):
+    """Pack one folded layer.  ``phys_map``: for every physical input channel (length multiple of
+    16) the original input channel, or -1 for padding.  Output channels are padded to 16*nbo.
+    ``wfmt`` selects the tile layout (csrc/mlp_core.hpp); the bias is fp32 in all of them:
+      WFMT_F32     per (o, m) tile [lane][4 floats] as in the module docstring (``mlp_layer``);
+      WFMT_BF16X3  per (o, mp) tile [split][lane][8 bf16], lane = 16*g + row, element t of lane group g = physical
+                   channel 16*(2*mp + t//4) + 4*g + t%4; the three splits are the round-to-nearest bf16 terms hi, mid,
+                   lo of every weight (``mlp_layer_bf3``);
+      WFMT_BF16    per (o, mp) tile [lane][8 bf16] in the same element order, every weight rounded once to bf16
+                   (round to nearest even; ``mlp_layer_bf16``).
+    The reduced formats consume input blocks in pairs: a layer with an odd number of them is packed fp32 whatever
+    ``wfmt`` says (csrc/mlp_core.hpp: mlp_layer_any / layer_floats_any).  Returned as float32 storage.
+    ``kmajor_out`` (cout <= 16): output channel c is produced on row 4*(c % 4) + c // 4, i.e. in lane group c % 4,
+    accumulator register c // 4 -- the "k-step major" order in which the NEXT layer needs only ceil(cout / 4) of its
+    four MFMA k-steps (its phys_map must be ``kstep_major_map(cout)``)."""
+    cout, _ = w.shape
+    nbi = len(phys_map) // 16
+    assert len(phys_map) == 16 * nbi
+    nbo = nbo or (cout + 15) // 16
+    if kmajor_out:
+        assert cout <= 16 and nbo == 1
+        rows = torch.tensor([4 * (c % 4) + c // 4 for c in range(cout)], dtype=torch.long, device=w.device)
+        w_perm = torch.zeros((16, w.shape[1]), dtype=w.dtype, device=w.device)
+        b_perm = torch.zeros((16,), dtype=b.dtype, device=b.device)
+        w_perm[rows], b_perm[rows] = w, b
+        w, b, cout = w_perm, b_perm, 16
+    pm = torch.as_tensor(phys_map, dtype=torch.long, device=w.device)
+    wphys = torch.zeros((16 * nbo, 16 * nbi), dtype=torch.float32, device=w.device)
+    valid = pm >= 0
+    wphys[:cout, valid] = w[:, pm[valid]]
+    bias = torch.zeros(16 * nbo, dtype=torch.float32, device=w.device)
+    bias[:cout] = b
+    if wfmt == WFMT_F32 or nbi % 2:
+        # (o,row,m,g,r) -> (o,m,g,row,r): lane = 16*g + row
+        tiles = wphys.view(nbo, 16, nbi, 4, 4).permute(0, 2, 3, 1, 4).reshape(-1)
+    else:
+        # (o, row, mp, half, g, r) -> (o, mp, g, row, half, r): element t = 4*half + r of lane 16*g + row
+        wt = wphys.view(nbo, 16, nbi // 2, 2, 4, 4).permute(0, 2, 4, 1, 3, 5).reshape(nbo, nbi // 2, 64, 8)
+        hi = wt.to(torch.bfloat16)
+        if wfmt == WFMT_BF16X3:
+            r1 = wt - hi.float()
+            mid = r1.to(torch.bfloat16)
+            lo = (r1 - mid.float()).to(torch.bfloat16)
+            hi = torch.stack((hi, mid, lo), dim=2)                        # (o, mp, split, lane, 8)
+        tiles = hi.contiguous().view(torch.int16).reshape(-1).view(torch.float32)
+    return torch.cat((tiles, bias)).contiguous()
+
+
+# ---- kernel names for _lib.annotate(kernel=...) ----------------------------------------------------------
+# bench.py keys the committed PMC files (profiles/pmc_*.json) by the kernel name as rocprofv3 prints it, so Python has
+# to name the kernel a wrapper is about to pick.  Each function mirrors the dispatch of ONE wrapper of csrc/ (named
+# beside it) for the cases the fused forward reaches; a change to a wrapper's `if` chain is a change here.
+
 def _kname(name, wfmt, split_capable=True):
-    """Kernel name as rocprofv3 prints it: the stack kernels carry a trailing `int FMT` template argument."""
+    """The stack kernels carry a trailing `int FMT` template argument."""
     return name[:-1] + (", %d>" % (wfmt if split_capable else 0))
 
 
-def _a2_kernel_name(kp, B, S, wfmt):
+def _a2_kernel_name(kp, B, S, wfmt):                         # fused_layers.hip: cv_fused_a2_kernel_wrapper
     if kp == 6 and wfmt == WFMT_F32 and os.environ.get("PWCLO_LANE6", "1") != "0" and B * ((S + 15) // 16) > 1024:
         return "cv_a2_lane6_kernel<8>"
     if kp == 6:
@@ -100,47 +125,29 @@ def _a2_kernel_name(kp, B, S, wfmt):
                   wfmt, split_capable=kp == 32)
 
 
-def pack_layer_bf3(w, b, phys_map, nbo=None):
-    """Pack one folded layer for ``mlp_layer_bf3`` (csrc/mlp_core.hpp): per (o, mp) tile [split][lane][8 bf16],
-    lane = 16*g + row, element t of lane group g = physical channel 16*(2*mp + t//4) + 4*g + t%4; the three
-    splits are the round-to-nearest bf16 terms hi, mid, lo of every weight.  Returned as float32 storage."""
-    cout, _ = w.shape
-    nbi = len(phys_map) // 16
-    assert len(phys_map) == 16 * nbi and nbi % 2 == 0
-    nbo = nbo or (cout + 15) // 16
-    pm = torch.as_tensor(phys_map, dtype=torch.long, device=w.device)
-    wphys = torch.zeros((16 * nbo, 16 * nbi), dtype=torch.float32, device=w.device)
-    valid = pm >= 0
-    wphys[:cout, valid] = w[:, pm[valid]]
-    # (o, row, mp, half, g, r) -> (o, mp, g, row, half, r): element t = 4*half + r of lane 16*g + row
-    wt = wphys.view(nbo, 16, nbi // 2, 2, 4, 4).permute(0, 2, 4, 1, 3, 5).reshape(nbo, nbi // 2, 64, 8)
-    hi = wt.to(torch.bfloat16)
-    r1 = wt - hi.float()
-    mid = r1.to(torch.bfloat16)
-    lo = (r1 - mid.float()).to(torch.bfloat16)
-    tiles = torch.stack((hi, mid, lo), dim=2).contiguous()            # (o, mp, split, lane, 8)
-    packed = tiles.view(torch.int16).reshape(-1).view(torch.float32)
-    bias = torch.zeros(16 * nbo, dtype=torch.float32, device=w.device)
-    bias[:cout] = b
-    return torch.cat((packed, bias)).contiguous()
+def _upconv_h_kernel_name(B, S, wfmt):                       # fused_hoisted.hip: upconv_fused_h_kernel_wrapper
+    if wfmt == WFMT_F32 and os.environ.get("PWCLO_LANE_UP", "1") != "0" and B * ((S + 15) // 16) > 2048:
+        return "upconv_lane_kernel<16>"
+    return _kname("upconv_h_kernel<8, 1, 16>", wfmt)
 
 
-def pack_layer_bf16(w, b, phys_map, nbo=None):
-    """Pack one folded layer for ``mlp_layer_bf16`` (csrc/mlp_core.hpp): per (o, mp) tile [lane][8 bf16] in the
-    element order of ``pack_layer_bf3``, every weight rounded once to bf16 (round to nearest even); fp32 bias."""
-    cout, _ = w.shape
-    nbi = len(phys_map) // 16
-    assert len(phys_map) == 16 * nbi and nbi % 2 == 0
-    nbo = nbo or (cout + 15) // 16
-    pm = torch.as_tensor(phys_map, dtype=torch.long, device=w.device)
-    wphys = torch.zeros((16 * nbo, 16 * nbi), dtype=torch.float32, device=w.device)
-    valid = pm >= 0
-    wphys[:cout, valid] = w[:, pm[valid]]
-    wt = wphys.view(nbo, 16, nbi // 2, 2, 4, 4).permute(0, 2, 4, 1, 3, 5).reshape(nbo, nbi // 2, 64, 8)
-    packed = wt.to(torch.bfloat16).contiguous().view(torch.int16).reshape(-1).view(torch.float32)
-    bias = torch.zeros(16 * nbo, dtype=torch.float32, device=w.device)
-    bias[:cout] = b
-    return torch.cat((packed, bias)).contiguous()
+def _upconv_post_kernel_name(njobs, B, S, c2):               # fused_hoisted.hip: upconv_post_fused_h_kernel_wrapper
+    tiles = njobs * B * ((S + 15) // 16)
+    return "upconv_lane_post_kernel<%d, %d>" % (c2 // 16, 16 if tiles >= 4096 else 8 if tiles >= 2048 else 4)
+
+
+def _a1_h_kernel_name(kp, wfmt):                             # fused_hoisted.hip: cv_fused_a1_h_kernel_wrapper
+    return _kname("cv_a1_h_kernel<%d, 1, 16>" % kp, wfmt)
+
+
+def _a_lane6_kernel_name(B, S, fold_v2):                     # fused_hoisted.hip: cv_fused_a_lane6_kernel_wrapper
+    return "cv_a_lane6_kernel<%d, %s>" % (4 if fold_v2 and B * ((S + 15) // 16) <= 1024 else 8,
+                                          "true" if fold_v2 else "false")
+
+
+def _b_h_kernel_name(B, S, wfmt):                            # fused_hoisted.hip: cv_fused_b_h_kernel_wrapper
+    small = B * ((S * 4 + 15) // 16) <= int(os.environ.get("PWCLO_COARSE_W4_TILES", "2047"))
+    return _kname("cv_b_h_kernel<4, 1, %d>" % (4 if small else 16), wfmt)
 
 
 def chain_map(cout_prev, nb):
@@ -158,16 +165,17 @@ def stack_macs(shared_mlp):
     return sum(int(l.conv.weight.shape[0]) * int(l.conv.weight.shape[1]) for l in shared_mlp)
 
 
-def pack_stack(shared_mlp, first_map, wfmt=WFMT_F32):
-    """Pack every layer of a SharedMLP whose first layer reads the physical order `first_map`.
-    Returns (packed float tensor, [padded widths]).  ``wfmt`` = WFMT_BF16X3: layers with an even number of
-    input blocks use the bf16x3 format (kernels built on mlp_layer_any)."""
+def pack_stack(layers, first_map=None, wfmt=WFMT_F32, cout_prev=None):
+    """Pack every layer of a SharedMLP (or of a slice of one).  The first of them reads the physical order
+    ``first_map``, or -- ``cout_prev`` given instead -- the padded output of a previous layer with that many real
+    channels; every further layer reads its predecessor's padded output.  ``wfmt``: tile format of the layers with
+    an even number of input blocks (``pack_layer``).  Returns (packed float tensor, [padded widths])."""
     parts, widths = [], []
-    pm = first_map
-    for layer in shared_mlp:
+    pm = first_map if cout_prev is None else chain_map(cout_prev, (cout_prev + 15) // 16)
+    for layer in layers:
         w, b = fold_conv_bn(layer)
         nbo = (w.shape[0] + 15) // 16
-        parts.append(pack_layer_any(w, b, pm, nbo, wfmt))
+        parts.append(pack_layer(w, b, pm, nbo, wfmt))
         widths.append(16 * nbo)
         pm = chain_map(w.shape[0], nbo)
     return torch.cat(parts).contiguous(), widths
@@ -564,28 +572,6 @@ def _zeros_like_bias(w):
     return torch.zeros(w.shape[0], dtype=w.dtype, device=w.device)
 
 
-def pack_layer_any(w, b, phys_map, nbo=None, wfmt=WFMT_F32):
-    """``pack_layer_bf3`` for the split format when the layer has an even number of 16-channel input
-    blocks (csrc/mlp_core.hpp: mlp_layer_any / layer_floats_any), ``pack_layer`` otherwise."""
-    if wfmt == WFMT_BF16X3 and (len(phys_map) // 16) % 2 == 0:
-        return pack_layer_bf3(w, b, phys_map, nbo)
-    if wfmt == WFMT_BF16 and (len(phys_map) // 16) % 2 == 0:
-        return pack_layer_bf16(w, b, phys_map, nbo)
-    return pack_layer(w, b, phys_map, nbo)
-
-
-def _pack_rest(layers, cout_prev, wfmt):
-    """Pack layers 2.. of a stack fed by a previous layer with `cout_prev` real outputs."""
-    parts, widths = [], []
-    for layer in layers:
-        w, b = fold_conv_bn(layer)
-        nbo = (w.shape[0] + 15) // 16
-        parts.append(pack_layer_any(w, b, chain_map(cout_prev, (cout_prev + 15) // 16), nbo, wfmt))
-        widths.append(16 * nbo)
-        cout_prev = w.shape[0]
-    return parts, widths
-
-
 class FusedSAHoisted:
     """``PointnetSAModulePWCLONet`` with the feature part of layer 1 hoisted to a per-point map."""
 
@@ -613,12 +599,12 @@ class FusedSAHoisted:
             wb2, wb3 = fold_conv_bn(layers[1]), fold_conv_bn(layers[2])
             second = pack_layer(wb2[0], wb2[1], kstep_major_map(w1.shape[0]), 1, kmajor_out=True)
             third = pack_layer(wb3[0], wb3[1], kstep_major_map(w2), (wb3[0].shape[0] + 15) // 16)
-            rest, widths = [second, third], [16, 16 * ((wb3[0].shape[0] + 15) // 16)]
+            rest, widths = torch.cat((second, third)), [16, 16 * ((wb3[0].shape[0] + 15) // 16)]
         else:
             if not self.c_feat:
                 first = pack_layer(w1, b1, kstep_major_map(6), nbo1)
-            rest, widths = _pack_rest(layers[1:], w1.shape[0], self.wfmt)
-        self.packed = torch.cat([first] + rest).contiguous()
+            rest, widths = pack_stack(layers[1:], wfmt=self.wfmt, cout_prev=w1.shape[0])
+        self.packed = torch.cat((first, rest)).contiguous()
         self.widths = [16 * nbo1] + widths
         self.c_out = layers[-1].conv.weight.shape[0]
         self.macs = stack_macs(module.mlp_module) - self.c_feat * w1.shape[0]   # per pixel, after hoisting
@@ -657,9 +643,9 @@ class FusedUpconvHoisted:
         self.wfmt = default_wfmt()
         self.pre_job = LinearJob(w1[:, :64], b1, out_bf16=self.wfmt == WFMT_BF16)   # original order [feat(64), diff(3)], :490
         first = pack_layer(w1[:, 64:67], _zeros_like_bias(w1), kstep_major_map(3), 8)
-        rest, widths = _pack_rest(layers[1:], 128, self.wfmt)
+        rest, widths = pack_stack(layers[1:], wfmt=self.wfmt, cout_prev=128)
         assert widths == [64]
-        self.packed = torch.cat([first] + rest).contiguous()
+        self.packed = torch.cat((first, rest)).contiguous()
         c2 = list(module.post_mlp)[0].conv.weight.shape[1] - 64
         self.post = FusedPointwise(module.post_mlp, [64, c2])
         self.macs = stack_macs(module.mlp)
@@ -671,8 +657,7 @@ class FusedUpconvHoisted:
         B, S, _ = xyz2.shape
         N, K = xyz1.shape[1], idx.shape[2]
         pooled = torch.empty((B, S, 64), dtype=torch.float32, device=xyz2.device)
-        lane = (self.wfmt == WFMT_F32 and os.environ.get("PWCLO_LANE_UP", "1") != "0" and B * ((S + 15) // 16) > 2048)
-        _lib.annotate(family="mlp", kernel="upconv_lane_kernel<16>" if lane else _kname("upconv_h_kernel<8, 1, 16>", self.wfmt),
+        _lib.annotate(family="mlp", kernel=_upconv_h_kernel_name(B, S, self.wfmt),
                       flops=2.0 * B * S * K * (self.macs - 64 * 128),
                       bytes=4.0 * B * (S * K * (1 + 3 + 128) + 3 * S + 64 * S))
         _lib.call("upconv_fused_h_kernel_wrapper", xyz2.device, B, N, S, K, _p(xyz2), _p(xyz1), _p(pre),
@@ -697,8 +682,7 @@ def run_upconv_post(ups, xyz2, xyz1, feat2, pres, idx):
     c2 = feat2.shape[2]
     outs = [torch.empty((B, S, 64), dtype=torch.float32, device=xyz2.device) for _ in ups]
     pa = lambda v: (ctypes.c_void_p * n)(*v)
-    tiles = n * B * ((S + 15) // 16)
-    _lib.annotate(family="mlp", kernel="upconv_lane_post_kernel<%d, %d>" % (c2 // 16, 16 if tiles >= 4096 else 8 if tiles >= 2048 else 4),
+    _lib.annotate(family="mlp", kernel=_upconv_post_kernel_name(n, B, S, c2),
                   flops=sum(2.0 * B * S * (K * (u.macs - 64 * 128) + u.post.macs) for u in ups),
                   bytes=4.0 * n * B * (S * K * (1 + 3 + 128) + 3 * S + S * c2 + 64 * S))
     _lib.call("upconv_post_fused_h_kernel_wrapper", xyz2.device, n, B, N, S, K, c2, _p(xyz2), _p(xyz1), _p(idx), _p(feat2),
@@ -727,9 +711,9 @@ class FusedCostVolumeHoisted:
         self.job_u = LinearJob(w1[:, 10:10 + c], b1, out_bf16=h16)
         self.job_v = LinearJob(w1[:, 10 + c:10 + 2 * c], _zeros_like_bias(w1), out_bf16=h16)
         first = pack_layer(w1[:, :10], _zeros_like_bias(w1), kstep_major_map(10), 8)
-        rest, widths = _pack_rest(la[1:], 128, self.wfmt)
+        rest, widths = pack_stack(la[1:], wfmt=self.wfmt, cout_prev=128)
         assert widths == [64, 64]
-        self.w_a1 = torch.cat([first] + rest).contiguous()
+        self.w_a1 = torch.cat((first, rest)).contiguous()
         wx1, wd = pack_stack(module.mlp_conv_xyz_1, geo)
         w2, wd2 = pack_stack(module.mlp2_convs, list(range(128)), self.wfmt_a2)
         assert wd == [64] and wd2 == [128, 64]
@@ -739,10 +723,10 @@ class FusedCostVolumeHoisted:
         w3, b3 = fold_conv_bn(lb[0])                                   # [enc2 (64) | feat1 (C) | first (64)]
         self.job_u2 = LinearJob(w3[:, 64:64 + c], b3, out_bf16=h16)
         self.job_v2 = LinearJob(w3[:, 64 + c:], _zeros_like_bias(w3), out_bf16=h16)
-        first_b = pack_layer_any(w3[:, :64], _zeros_like_bias(w3), list(range(64)), 8, self.wfmt)
-        rest_b, wdb = _pack_rest(lb[1:], 128, self.wfmt)
+        first_b = pack_layer(w3[:, :64], _zeros_like_bias(w3), list(range(64)), 8, self.wfmt)
+        rest_b, wdb = pack_stack(lb[1:], wfmt=self.wfmt, cout_prev=128)
         assert wdb == [64]
-        self.w_b = torch.cat([wx2, first_b] + rest_b).contiguous()
+        self.w_b = torch.cat((wx2, first_b, rest_b)).contiguous()
         self.macs_a1 = stack_macs(module.mlp_convs)
         self.macs_a2 = stack_macs(module.mlp_conv_xyz_1) + stack_macs(module.mlp2_convs)
         self.macs_b = stack_macs(module.mlp_conv_xyz_2) + stack_macs(module.mlp3_convs)
@@ -765,7 +749,7 @@ class FusedCostVolumeHoisted:
         if merged:
             return self._merged(xyz1, xyz2, u, v, u2, idx_q, idx, taps, tap)
         pix = torch.empty((B, S * kp, 64), dtype=torch.bfloat16 if self.wfmt == WFMT_BF16 else torch.float32, device=dev)
-        _lib.annotate(family="mlp", kernel=_kname("cv_a1_h_kernel<%d, 1, 16>" % kp, self.wfmt),
+        _lib.annotate(family="mlp", kernel=_a1_h_kernel_name(kp, self.wfmt),
                       flops=2.0 * B * S * kq * (self.macs_a1 - 2 * c * 128),
                       bytes=4.0 * B * (S * kq * (1 + 3 + 128 + 64) + S * (3 + 128)))
         _lib.call("cv_fused_a1_h_kernel_wrapper", dev, B, N, S, kq, _p(xyz1), _p(u), _p(xyz2), _p(v), _p(idx_q),
@@ -791,8 +775,7 @@ class FusedCostVolumeHoisted:
         fold_v2 = os.environ.get("PWCLO_CV_V2", "1") != "0" and not self.job_v2.out_bf16
         first = torch.empty((B, S, 64), dtype=torch.float32, device=dev)
         v2 = torch.empty((B, S, 128), dtype=torch.float32, device=dev) if fold_v2 else None
-        _lib.annotate(family="mlp", kernel="cv_a_lane6_kernel<%d, %s>" % (4 if fold_v2 and B * ((S + 15) // 16) <= 1024 else 8,
-                                                                          "true" if fold_v2 else "false"),
+        _lib.annotate(family="mlp", kernel=_a_lane6_kernel_name(B, S, fold_v2),
                       flops=2.0 * B * S * (6 * (self.macs_a1 - 2 * self.c * 128 + self.macs_a2) + (64 * 128 if fold_v2 else 0)),
                       bytes=4.0 * B * (S * 6 * (1 + 3 + 128) + S * (3 + 3 * 128 + 64 + (128 if fold_v2 else 0))))
         _lib.call("cv_fused_a_lane6_kernel_wrapper", dev, B, N, S, _p(xyz1), _p(u), _p(xyz2), _p(v), _p(idx_q),
@@ -810,7 +793,7 @@ class FusedCostVolumeHoisted:
         B, S, _ = xyz1.shape
         dev, k, c = xyz1.device, self.nsample, self.c
         out = torch.empty((B, S, 64), dtype=torch.float32, device=dev)
-        _lib.annotate(family="mlp", kernel=_kname("cv_b_h_kernel<4, 1, %d>" % (4 if B * ((S * 4 + 15) // 16) <= int(os.environ.get("PWCLO_COARSE_W4_TILES", "2047")) else 16), self.wfmt),
+        _lib.annotate(family="mlp", kernel=_b_h_kernel_name(B, S, self.wfmt),
                       flops=2.0 * B * S * k * (self.macs_b - (c + 64) * 128),
                       bytes=4.0 * B * (S * k * (1 + 3 + 128 + 64) + S * (3 + 128 + 64)))
         _lib.call("cv_fused_b_h_kernel_wrapper", dev, B, S, k, _p(xyz1), _p(u2), _p(v2), _p(first), _p(idx),

@@ -133,6 +133,82 @@ def test_bn_folding_and_weight_packing_layout():
     torch.testing.assert_close(h2, ref2[0, :, :, 0], rtol=1e-5, atol=1e-5)
 
 
+def _unpack_reduced_stack(wfmt):
+    """The seeded stack of the fp32 layout test packed in a reduced format and read back by the element order
+    csrc/mlp_core.hpp documents: per (o, mp) tile [split][lane][8 bf16], lane = 16*g + row, element t of lane group g =
+    physical input channel 16*(2*mp + t//4) + 4*g + t%4 of output channel 16*o + row; then 16*nbo fp32 biases.
+    Yields per layer (folded weights in physical order, bf16 terms (nsplit, rows, channels), packed bias, folded bias)."""
+    from pwclonet_pylidarslam_amd import fused
+    from pwclonet_pylidarslam_amd.pointnet2_ops import pytorch_utils as pt
+    torch.manual_seed(0)
+    mlp = pt.SharedMLP([19, 24, 32], bn=True).eval()
+    for layer in mlp:
+        layer.bn.bn.running_mean.uniform_(-1, 1)
+        layer.bn.bn.running_var.uniform_(0.5, 2)
+        layer.bn.bn.weight.data.uniform_(0.5, 1.5)
+        layer.bn.bn.bias.data.uniform_(-1, 1)
+    pm = fused.sa_first_map(16)
+    packed, widths = fused.pack_stack(mlp, pm, wfmt)
+    assert widths == [32, 32] and packed.dtype == torch.float32
+    nsplit = 3 if wfmt == fused.WFMT_BF16X3 else 1
+    off, out = 0, []
+    for layer in mlp:
+        w, b = fused.fold_conv_bn(layer)
+        cout, nbi, nbo = w.shape[0], len(pm) // 16, (w.shape[0] + 15) // 16
+        assert nbi % 2 == 0
+        wphys = torch.zeros(16 * nbo, 16 * nbi)
+        for p, c in enumerate(pm):
+            if c >= 0:
+                wphys[:cout, p] = w[:, c]
+        nfloats = nbo * (nbi // 2) * nsplit * 64 * 8 // 2          # two bf16 per float of storage
+        tiles = packed[off:off + nfloats].view(torch.bfloat16).view(nbo, nbi // 2, nsplit, 64, 8)
+        terms = torch.zeros(nsplit, 16 * nbo, 16 * nbi, dtype=torch.bfloat16)
+        for o in range(nbo):
+            for mp in range(nbi // 2):
+                for lane in range(64):
+                    row, g = lane % 16, lane // 16
+                    for t in range(8):
+                        terms[:, 16 * o + row, 16 * (2 * mp + t // 4) + 4 * g + t % 4] = tiles[o, mp, :, lane, t]
+        bias = packed[off + nfloats:off + nfloats + 16 * nbo]
+        off += nfloats + 16 * nbo
+        out.append((wphys, terms, bias, torch.cat((b, torch.zeros(16 * nbo - cout)))))
+        pm = fused.chain_map(cout, nbo)
+    assert off == packed.numel()
+    return out
+
+
+def test_weight_packing_layout_bf16():
+    """wfmt = bf16: every tile element is the folded weight rounded once to bfloat16; the bias stays fp32."""
+    from pwclonet_pylidarslam_amd import fused
+    for wphys, terms, bias, b in _unpack_reduced_stack(fused.WFMT_BF16):
+        assert torch.equal(terms[0], wphys.to(torch.bfloat16))
+        assert torch.equal(bias, b)
+
+
+def test_weight_packing_layout_bf16x3():
+    """wfmt = bf16x3: the three round-to-nearest bf16 terms of a weight, added in fp32 as (hi + mid) + lo, give the
+    folded fp32 weight back exactly (3 x 8 significant bits cover fp32's 24); the bias stays fp32."""
+    from pwclonet_pylidarslam_amd import fused
+    for wphys, terms, bias, b in _unpack_reduced_stack(fused.WFMT_BF16X3):
+        hi, mid, lo = terms.float()
+        assert torch.equal((hi + mid) + lo, wphys)
+        assert (hi != 0).any() and (mid != 0).any() and (lo != 0).any()
+        assert torch.equal(bias, b)
+
+
+def test_weight_packing_odd_input_blocks_stay_fp32():
+    """The reduced formats consume input blocks in pairs: a layer with an odd number of them is packed as fp32 tiles
+    whatever format is asked for (csrc/mlp_core.hpp: layer_floats_any)."""
+    from pwclonet_pylidarslam_amd import fused
+    torch.manual_seed(1)
+    w, b = torch.randn(20, 10), torch.randn(20)
+    geo = list(range(10)) + [-1] * 6
+    ref = fused.pack_layer(w, b, geo, 2)
+    assert ref.numel() == fused.layer_floats(1, 2)
+    for wfmt in (fused.WFMT_BF16X3, fused.WFMT_BF16):
+        assert torch.equal(fused.pack_layer(w, b, geo, 2, wfmt), ref)
+
+
 def test_synthetic_generators():
     from pwclonet_pylidarslam_amd import synthetic
     a1, a2, q, t = synthetic.kitti_like_pair(5, 2048, 2)
