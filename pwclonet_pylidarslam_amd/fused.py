@@ -58,6 +58,21 @@ def default_wfmt():
     return WFMT_BF16X3 if os.environ.get("PWCLO_BF16X3", "0") != "0" else WFMT_F32
 
 
+def layer_wfmt(wfmt, nbi):
+    """Tile format a layer with ``nbi`` 16-channel input blocks is packed and run in when its stack asks for ``wfmt``:
+    the reduced formats consume input blocks in pairs, so an odd layer -- a lone geometry block, all of psa_1 and
+    psa_2 -- stays fp32 (csrc/mlp_core.hpp: mlp_layer_any / layer_floats_any)."""
+    return WFMT_F32 if nbi % 2 else wfmt
+
+
+def cv_stack_wfmt(kp, wfmt, hoisted=True):
+    """Format of a cost volume's stacks for ``kp`` pixel slots: cv_a2 has reduced formats for 6 / 32 pixel slots only,
+    and the un-hoisted cv_a1 writes fp32 per-pixel features (bf16 rows belong to the hoisted set)."""
+    if kp not in (6, 32) or (not hoisted and wfmt == WFMT_BF16):
+        return WFMT_F32
+    return wfmt
+
+
 def pack_layer(w, b, phys_map, nbo=None, wfmt=WFMT_F32, kmajor_out=False):
     """Pack one folded layer.  ``phys_map``: for every physical input channel (length multiple of
     16) the original input channel, or -1 for padding.  Output channels are padded to 16*nbo.
@@ -90,7 +105,7 @@ def pack_layer(w, b, phys_map, nbo=None, wfmt=WFMT_F32, kmajor_out=False):
     wphys[:cout, valid] = w[:, pm[valid]]
     bias = torch.zeros(16 * nbo, dtype=torch.float32, device=w.device)
     bias[:cout] = b
-    if wfmt == WFMT_F32 or nbi % 2:
+    if layer_wfmt(wfmt, nbi) == WFMT_F32:
         # (o,row,m,g,r) -> (o,m,g,row,r): lane = 16*g + row
         tiles = wphys.view(nbo, 16, nbi, 4, 4).permute(0, 2, 3, 1, 4).reshape(-1)
     else:
@@ -116,13 +131,19 @@ def _kname(name, wfmt, split_capable=True):
     return name[:-1] + (", %d>" % (wfmt if split_capable else 0))
 
 
+def _switch(name):                                           # csrc/launch.hpp: fl_wide() / coarse_w4(), default on
+    return os.environ.get(name, "1") != "0"
+
+
 def _a2_kernel_name(kp, B, S, wfmt):                         # fused_layers.hip: cv_fused_a2_kernel_wrapper
     if kp == 6 and wfmt == WFMT_F32 and os.environ.get("PWCLO_LANE6", "1") != "0" and B * ((S + 15) // 16) > 1024:
         return "cv_a2_lane6_kernel<8>"
     if kp == 6:
-        return _kname("cv_a2_dense6_kernel<%d>" % (8 if B * ((S + 7) // 8) > 2048 else 4), wfmt)
-    return _kname({32: "cv_a2_kernel<32, 2, 8>", 16: "cv_a2_kernel<16, 1, 16>", 8: "cv_a2_kernel<8, 1, 16>"}[kp],
-                  wfmt, split_capable=kp == 32)
+        w4 = B * ((S + 7) // 8) <= 2048 and (wfmt != WFMT_F32 or _switch("PWCLO_COARSE_W4"))
+        return _kname("cv_a2_dense6_kernel<%d>" % (4 if w4 else 8), wfmt)
+    if kp == 32:
+        return _kname("cv_a2_kernel<32, 2, 8>", wfmt)
+    return _kname("cv_a2_kernel<%d, %s>" % (kp, "1, 16" if _switch("PWCLO_FL_WIDE") else "2, 8"), wfmt, split_capable=False)
 
 
 def _upconv_h_kernel_name(B, S, wfmt):                       # fused_hoisted.hip: upconv_fused_h_kernel_wrapper
@@ -146,7 +167,7 @@ def _a_lane6_kernel_name(B, S, fold_v2):                     # fused_hoisted.hip
 
 
 def _b_h_kernel_name(B, S, wfmt):                            # fused_hoisted.hip: cv_fused_b_h_kernel_wrapper
-    small = B * ((S * 4 + 15) // 16) <= int(os.environ.get("PWCLO_COARSE_W4_TILES", "2047"))
+    small = _switch("PWCLO_COARSE_W4") and B * ((S * 4 + 15) // 16) <= int(os.environ.get("PWCLO_COARSE_W4_TILES", "2047"))
     return _kname("cv_b_h_kernel<4, 1, %d>" % (4 if small else 16), wfmt)
 
 
@@ -422,9 +443,7 @@ class FusedCostVolume:
         self.c = c1
         self.nsample, self.nsample_q = module.nsample, module.nsample_q
         self.kp = cv_pix_slots(module.nsample_q)               # per-pixel buffer layout, fixed at pack time
-        self.wfmt_a2 = default_wfmt() if self.kp in (6, 32) else WFMT_F32
-        if self.wfmt_a2 == WFMT_BF16:
-            self.wfmt_a2 = WFMT_F32        # the un-hoisted cv_a1 writes fp32 per-pixel features; bf16 rows belong to the hoisted set
+        self.wfmt_a2 = cv_stack_wfmt(self.kp, default_wfmt(), hoisted=False)
         geo = list(range(10)) + [-1] * 6
         # mlp_convs input (costvolume.py:105-110): [geometry10, feat1 (C), feat2 gathered (C)]
         self.w_a1, w = pack_stack(module.mlp_convs, geo + [10 + c for c in range(2 * c1)])
@@ -700,9 +719,7 @@ class FusedCostVolumeHoisted:
         self.c = c = c1
         self.nsample, self.nsample_q = module.nsample, module.nsample_q
         self.kp = cv_pix_slots(module.nsample_q)               # per-pixel buffer layout, fixed at pack time
-        self.wfmt = default_wfmt()
-        if self.kp not in (6, 32) and self.wfmt != WFMT_F32:
-            self.wfmt = WFMT_F32                               # cv_a2 has reduced formats for 6 / 32 pixel slots only
+        self.wfmt = cv_stack_wfmt(self.kp, default_wfmt())
         self.wfmt_a2 = self.wfmt
         h16 = self.wfmt == WFMT_BF16                           # hoisted rows and the per-pixel buffer stored as bf16
         geo = list(range(10)) + [-1] * 6
