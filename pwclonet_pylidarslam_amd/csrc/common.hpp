@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 
 #include "../../include/pwclo_ops.h"
 
@@ -33,6 +34,13 @@ unsigned *device_error_word();
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
+// PWCLO_<NAME> override of a launch parameter (experiments; README.md lists them).  Callers keep the value in a
+// function-local static: every variable is read once per process.
+static inline int tuning(const char *name, int dflt) {
+  const char *e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+
 // The reference's block-size rule (cuda_utils.h:15-19): 2^floor(log2(work)) clamped to [1,512].
 // Integer form; agrees with the reference's double log() evaluation for every work_size >= 1
 // that this library accepts (checked against the oracle in tests/test_host_logic.py).
@@ -61,8 +69,28 @@ void trace_set_knn(const TraceBuf &b);
 void trace_set_sampling(const TraceBuf &b);
 void trace_set_warp(const TraceBuf &b);
 
-// ---- device helpers ------------------------------------------------------------------------
 #if defined(__HIPCC__)
+
+// ---- launch helpers ------------------------------------------------------------------------
+// A kernel that asks for more than the default 64 KiB of dynamic LDS needs hipFuncAttributeMaxDynamicSharedMemorySize
+// raised first, once per kernel: the flag that remembers it is this function's own static, so there is exactly one per
+// instantiation (per kernel) and no caller can pair a kernel with another kernel's flag.
+template <auto Kern>
+static void raise_lds_limit(int bytes) {
+  static bool attr_set = false;
+  if (attr_set) return;
+  (void)hipFuncSetAttribute((const void *)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  attr_set = true;
+}
+
+// Launches Kern (workgroups of W waves) with lds_bytes of dynamic LDS on the library's stream.
+template <auto Kern, int W, typename... Args>
+static void launch_grid(dim3 grid, int lds_bytes, const Args &...a) {
+  if (lds_bytes > 64 * 1024) raise_lds_limit<Kern>(160 * 1024);   // the largest any configuration can ask for
+  hipLaunchKernelGGL(Kern, grid, dim3(W * 64), lds_bytes, current_stream(), a...);
+}
+
+// ---- device helpers ------------------------------------------------------------------------
 
 // One copy per translation unit (no relocatable device code in this build); the TU's trace_set_*() fills it.
 static __device__ __attribute__((unused)) TraceBuf g_trace = {nullptr, nullptr, 0u};

@@ -1,20 +1,14 @@
 // Host-side launch policy of the fused stack kernels (fused_layers.hip, fused_hoisted.hip, fused_sa.hip): the
-// PWCLO_* tuning reader, the size of a packed stack per weight format, the runtime-format -> template-argument
-// dispatch and the persistent-grid launcher.  No device code lives here.
+// PWCLO_* switches, the size of a packed stack per weight format, the runtime-format -> template-argument
+// dispatch and the persistent-grid launcher (on launch_grid, common.hpp).  No device code lives here.
 #pragma once
-#include <stdlib.h>
 #include <type_traits>
 
 #include "mlp_core.hpp"
 
 namespace pwclo {
 
-// PWCLO_<NAME> override of a launch parameter (experiments; README.md lists them).  Callers keep the value in a
-// function-local static: every variable is read once per process.
-static inline int tuning(const char *name, int dflt) {
-  const char *e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
+// PWCLO_* switches of the stack kernels (tuning(): common.hpp), each read once per process.
 static inline int fl_wide() { static const int v = tuning("PWCLO_FL_WIDE", 1); return v; }        // 16-wave workgroups
 static inline int fl_stagger() { static const int v = tuning("PWCLO_FL_STAGGER", 0); return v; }  // mlp_core.hpp: stagger_start
 static inline int coarse_w4() { static const int v = tuning("PWCLO_COARSE_W4", 1); return v; }
@@ -64,20 +58,6 @@ template <typename F> static inline void with_format(int wfmt, F &&f) {
     PWCLO_REQUIRE((packed_floats) == expect_, what ": packed weights hold %d floats, format %d needs %d",          \
                   (int)(packed_floats), (int)(wfmt), expect_);                                                   \
   } while (0)
-
-// Launches Kern (workgroups of W waves) with lds_bytes of dynamic LDS on the library's stream.  A kernel that asks for
-// more than the default 64 KiB needs hipFuncAttributeMaxDynamicSharedMemorySize raised first, once per kernel: the
-// flag that remembers it is this function's own static, so there is exactly one per instantiation (per kernel) and
-// no caller can pair a kernel with another kernel's flag.
-template <auto Kern, int W, typename Args>
-static void launch_grid(dim3 grid, int lds_bytes, const Args &a) {
-  static bool attr_set = false;
-  if (lds_bytes > 64 * 1024 && !attr_set) {
-    (void)hipFuncSetAttribute((const void *)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);  // the largest any configuration can ask for
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(Kern, grid, dim3(W * 64), lds_bytes, current_stream(), a);
-}
 
 // Persistent grid over ntiles wave tiles: one workgroup per W tiles, at most 256 CUs x per_cu resident workgroups x
 // rounds.  Workgroups beyond one resident set queue behind it; >1 "rounds" keeps the kernel balanced when part of the

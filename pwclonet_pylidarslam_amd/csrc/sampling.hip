@@ -36,6 +36,50 @@ __device__ __forceinline__ unsigned fps_bitrev(unsigned v, int bits) {
   return bits == 0 ? 0u : (__brev(v) >> (32 - bits));
 }
 
+// ---- the pieces every sampler shares: one copy of the tie rule, the key layout and the eligibility test --------------
+// Sampling priority of point k (smaller wins a tie): bitrev_{log2 bs}(k mod bs) << 23 | (k div bs).  K is the caller's
+// index type (int or unsigned, k >= 0 either way).
+template <typename K>
+__device__ __forceinline__ unsigned fps_priority(K k, int bs, int log2bs) {
+  return (fps_bitrev((unsigned)(k & (K)(bs - 1)), log2bs) << PRI_SHIFT) | (unsigned)(k >> log2bs);
+}
+
+// Arg-max key of a candidate: distance bits + 1 above the INVERTED priority, so that one unsigned 64-bit maximum picks
+// the largest distance and, among equals, the smallest priority.  0 = no candidate (bits + 1 keeps a distance of +0.0
+// distinct from it).  Built in place by the three kernels that use it (wmax == 0 ? 0 : wmax << 32 | ~wpri).
+// The index of the point a (non-zero) key stands for.
+__device__ __forceinline__ int fps_key_index(unsigned long long key, int bs, int log2bs) {
+  const unsigned p = 0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull);
+  return (int)fps_bitrev(p >> PRI_SHIFT, log2bs) + bs * (int)(p & ((1u << PRI_SHIFT) - 1u));
+}
+
+// sampling.cpp:74-76: a point with |p|^2 <= 1e-3 is never sampled (the comparison runs in double, the sum in fp32,
+// term by term).
+__device__ __forceinline__ bool fps_eligible(float x, float y, float z) {
+  const float mag = (x * x) + (y * y) + (z * z);
+  return !((double)mag <= 1e-3);
+}
+
+// Distance along one axis from the sample coordinate s to the box [lo, hi], in the update's own arithmetic.
+__device__ __forceinline__ float fps_box_gap(float lo, float hi, float s) {
+  return fmaxf(fmaxf(lo - s, s - hi), 0.f);
+}
+
+// Workgroup arg-max over three rotating u64 LDS slots: iteration `it` posts into slot it % 3 (one ds_max_u64 per wave),
+// one barrier, one broadcast read.  Slot (it + 2) % 3 = (it - 1) % 3 is cleared right after barrier `it`: every wave
+// has read it before arriving there, and nobody adds to it before barrier it + 1.
+struct SlotArgMax {
+  unsigned long long *slots;
+  __device__ __forceinline__ void init() const { slots[0] = 0ull; slots[1] = 0ull; slots[2] = 0ull; }   // one thread
+  // a wave's contribution to iteration `it`; returns the slot, to be read after the barrier
+  __device__ __forceinline__ unsigned long long *post(int it, unsigned long long key, int lane) const {
+    unsigned long long *slot = slots + (it % 3);
+    if (lane == 0) atomicMax(slot, key);
+    return slot;
+  }
+  __device__ __forceinline__ void retire(int it) const { slots[(it + 2) % 3] = 0ull; }                  // one thread
+};
+
 // T threads; a thread owns PPT = I << E points.  The reference partitions the cloud over
 // bs = opt_n_threads(n) threads by k mod bs.  Here
 //   * T >= bs (E = 0): thread tid owns residue tid mod bs, points k = tid + T*i, i < I;
@@ -75,35 +119,21 @@ __device__ __forceinline__ unsigned fps_bitrev(unsigned v, int bits) {
 constexpr int FPS_CHAIN_INTS = 12;    // [0] fallback flag, [1] number of events, [2..9] event iterations
 constexpr int FPS_CHAIN_MAXEV = 8;
 
-// XCHG (round 3, multi-wave kernels with the LDS table): the winner's coordinates travel WITH the exchange instead of
-// being looked up after it.  Every lane requests the coordinates of its own best candidate from the LDS table right after
-// the update loop -- the read's latency hides under the two wave reductions -- and the lane that wins its wave stores them
-// in the wave's slot of a double-buffered 8-entry table before the barrier; after the barrier the slot key and the eight
-// coordinate slots are read in ONE round trip and the winner's are picked with v_readlane (its wave follows from the key).
-// Removes the dependent table read (key -> index -> coordinates) from the head of the next iteration.  Same arithmetic,
-// same winner: bit-identical output (tests/test_gpu_ops.py FPS cases run both forms).
-// CPW = 2 (round 3, tools/fps_pair_probe.py): TWO clouds per workgroup, T threads each, every cloud's eight waves meeting
-// at their OWN barrier -- an LDS counter the waves add to and poll -- so that the two dependent chains run side by side on
-// one CU and fill each other's exchange stalls (one chain leaves a third of the CU's issue slots idle: co-resident chains
-// measured -17 % CU-time per cloud at two, -28 % at four per CU).  Needs the global winner lookup (LDS_TABLE = false: two
-// 131 KB tables do not fit) and neither `prefix_in` nor `done` (their early exits are per cloud).  Same arithmetic, same
-// winner: bit-identical output.
-template <int T, int E, int I, bool LDS_TABLE, bool XCHG = false, int CPW = 1>
-__global__ __launch_bounds__(T * CPW) void fps_reg_kernel(int n, int m, int bs, int log2bs,
+// The chain log of one cloud in LDS (fps_reg_kernel, fps_slab_kernel): cvals / cstat = winning value and tie status
+// (0 = unique arg-max, 1 = tie, 2 = no candidate) of iterations 0..tie_iters+1, noted inside the loop and judged once
+// after it; cmeta = [0] events, [1] fallback, in the slot header.  The two kernels spell these few lines out: wrapped
+// in a function or struct they compile to a different instruction schedule (profiles/sampling_refactor/README.md).
+template <int T, int E, int I, bool LDS_TABLE>
+__global__ __launch_bounds__(T) void fps_reg_kernel(int n, int m, int bs, int log2bs,
                                                     const float *__restrict__ dataset,
                                                     int *__restrict__ idxs,
                                                     float *__restrict__ new_xyz,
                                                     int *__restrict__ tie_out, int tie_iters,
-                                                    const int *__restrict__ prefix_in,
-                                                    const int *__restrict__ done = nullptr) {
+                                                    const int *__restrict__ prefix_in) {
   TraceScope trace_scope_(TK_FPS);
   constexpr int PPT = I << E;
-  constexpr int NW_ = T / 64;
-  static_assert(CPW == 1 || (CPW == 2 && !LDS_TABLE && !XCHG), "two clouds per workgroup: global winner lookup only");
-  const int half = CPW == 1 ? 0 : (int)(threadIdx.x / T);          // which of the workgroup's clouds (wave-uniform)
-  const int cloud = (int)blockIdx.x * CPW + half;
-  if (CPW == 1 && done != nullptr && done[blockIdx.x] != 0) return;   // this cloud was sampled by fps_slab_kernel (workgroup-uniform)
-  if (CPW == 1 && prefix_in != nullptr && prefix_in[blockIdx.x * FPS_CHAIN_INTS] == 0) {       // workgroup-uniform
+  const int cloud = (int)blockIdx.x;
+  if (prefix_in != nullptr && prefix_in[blockIdx.x * FPS_CHAIN_INTS] == 0) {       // workgroup-uniform
     const int *rec = prefix_in + blockIdx.x * FPS_CHAIN_INTS;
     const int nev = rec[1];
     const float *src = dataset + (size_t)blockIdx.x * n * 3;
@@ -112,10 +142,7 @@ __global__ __launch_bounds__(T * CPW) void fps_reg_kernel(int n, int m, int bs, 
       for (int e = 0; e < nev; ++e) {
         const int it = rec[2 + e];                 // tie between list positions it and it+1
         if ((t == it || t == it + 1) && it + 1 < n) {
-          const unsigned p0 = (fps_bitrev((unsigned)(it & (bs - 1)), log2bs) << PRI_SHIFT) | (unsigned)(it >> log2bs);
-          const unsigned p1 = (fps_bitrev((unsigned)((it + 1) & (bs - 1)), log2bs) << PRI_SHIFT) |
-                              (unsigned)((it + 1) >> log2bs);
-          const int first = p0 < p1 ? it : it + 1;
+          const int first = fps_priority(it, bs, log2bs) < fps_priority(it + 1, bs, log2bs) ? it : it + 1;
           pick = t == it ? first : (first == it ? it + 1 : it);
         }
       }
@@ -130,19 +157,15 @@ __global__ __launch_bounds__(T * CPW) void fps_reg_kernel(int n, int m, int bs, 
   // a sampler wave is one link of a long dependent chain: whenever it can issue, it should, ahead of
   // the throughput kernels of other in-flight batches that may share its SIMD
   __builtin_amdgcn_s_setprio(3);
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_all[];
-  // CPW == 2: each cloud has its own slot header + chain log, one after the other
-  unsigned char *smem = smem_all + (CPW == 1 ? 0 : (size_t)half * ((FPS_SLOT_BYTES + (size_t)(tie_out ? (tie_iters + 2) * 8 : 0) + 15) & ~(size_t)15));
-  unsigned *arrive = reinterpret_cast<unsigned *>(smem + 48);                // CPW == 2: this cloud's barrier counter
-  unsigned long long *slots = reinterpret_cast<unsigned long long *>(smem);  // [3] rotating
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const SlotArgMax wgmax{reinterpret_cast<unsigned long long *>(smem)};
   float4 *table = reinterpret_cast<float4 *>(smem + FPS_SLOT_BYTES);         // [n] when LDS_TABLE
-  // chain log (only when tie_out): winning value and tie status of iterations 0..tie_iters+1, judged
-  // once after the loop instead of inside it
+  // chain log (only when tie_out), judged once after the loop instead of inside it
   unsigned *cvals = reinterpret_cast<unsigned *>(smem + FPS_SLOT_BYTES + (LDS_TABLE ? (size_t)n * 16 : 0));
   int *cstat = reinterpret_cast<int *>(cvals + (tie_iters + 2));
-  int *cmeta = reinterpret_cast<int *>(smem + 32);                           // [0] events, [1] fallback (slot header)
+  int *cmeta = reinterpret_cast<int *>(smem + 32);
 
-  const int tid = CPW == 1 ? (int)threadIdx.x : (int)(threadIdx.x % T);
+  const int tid = (int)threadIdx.x;
   const int lane = tid & 63;
   constexpr int NW = T / 64;
   const float *pts = dataset + (size_t)cloud * n * 3;
@@ -163,7 +186,7 @@ __global__ __launch_bounds__(T * CPW) void fps_reg_kernel(int n, int m, int bs, 
       py = pts[k * 3 + 1];
       pz = pts[k * 3 + 2];
       const float mag = (px * px) + (py * py) + (pz * pz);
-      if (!((double)mag <= 1e-3)) t0 = 1e10f;  // sampling.cpp:74-76 initial temp
+      if (!((double)mag <= 1e-3)) t0 = 1e10f;  // fps_eligible, written out: the helper changes this kernel's schedule
       if (LDS_TABLE) table[k] = make_float4(px, py, pz, 0.f);
     }
     x[j] = px; y[j] = py; z[j] = pz; td[j] = __float_as_int(t0);
@@ -174,21 +197,13 @@ __global__ __launch_bounds__(T * CPW) void fps_reg_kernel(int n, int m, int bs, 
   const unsigned qstep = E == 0 ? (unsigned)(T / bs) : 1u;
   if (tid == 0) {
     out[0] = 0;
-    slots[0] = 0ull; slots[1] = 0ull; slots[2] = 0ull;
+    wgmax.init();
     cmeta[0] = 0; cmeta[1] = 0;
-    if (CPW > 1) *arrive = 0u;
   }
   if (tie_out != nullptr)
     for (int i = tid; i < tie_iters + 2; i += T) { cstat[i] = 0; cvals[i] = 0u; }
   __syncthreads();
 
-  constexpr bool XC = XCHG && LDS_TABLE && NW_ > 1;
-  __shared__ float4 wxyz[2][XC ? NW_ : 1];      // [iteration parity][wave]: coordinates of each wave's local winner
-  float nx1 = 0.f, ny1 = 0.f, nz1 = 0.f;        // XC: coordinates of the current sample, carried over from the exchange
-  if (XC) {
-    const float4 p0 = table[0];
-    nx1 = p0.x; ny1 = p0.y; nz1 = p0.z;
-  }
   int old = 0;
   // One iteration; TRACK additionally records whether the arg-max was unique.  Two instantiations run
   // back to back (iterations < tie_iters, then the rest) rather than one loop with a branch inside:
@@ -196,9 +211,7 @@ __global__ __launch_bounds__(T * CPW) void fps_reg_kernel(int n, int m, int bs, 
   auto iteration = [&](auto track_tag, int it) {
     constexpr bool TRACK = decltype(track_tag)::value;
     float x1, y1, z1;
-    if (XC) {
-      x1 = nx1; y1 = ny1; z1 = nz1;
-    } else if (LDS_TABLE) {
+    if (LDS_TABLE) {
       const float4 p = table[old];
       x1 = p.x; y1 = p.y; z1 = p.z;
     } else {
@@ -222,12 +235,6 @@ __global__ __launch_bounds__(T * CPW) void fps_reg_kernel(int n, int m, int bs, 
       bestj = better ? j : bestj;
       best = better ? d2 : best;
     }
-    float4 mycand = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (XC) {   // coordinates of this lane's own candidate: requested now, needed after the wave reductions
-      const int u = E == 0 ? 0 : (int)(__brev((unsigned)(bestj / I)) >> (32 - (E == 0 ? 1 : E)));
-      const int kc = tid + T * u + kstride * (bestj % I);
-      mycand = table[kc < n ? kc : 0];
-    }
     const bool lane_tie = TRACK && best >= 0 && best2 == best;
     // 0 = no candidate; otherwise bits+1 so that a legitimate distance of +0.0 stays distinct
     const unsigned mine = best < 0 ? 0u : (unsigned)best + 1u;
@@ -245,38 +252,10 @@ __global__ __launch_bounds__(T * CPW) void fps_reg_kernel(int n, int m, int bs, 
       tie = (hm & (hm - 1ull)) != 0ull || __ballot(holds && lane_tie) != 0ull;
     }
     if (NW > 1) {
-      unsigned long long *slot = slots + (it % 3);
-      if (lane == 0) atomicMax(slot, key);
-      if (XC && holds && mypri == wpri) wxyz[it & 1][tid >> 6] = mycand;     // exactly one lane per wave with a candidate
-      if (CPW == 1) {
-        __syncthreads();
-      } else {
-        // this cloud's own barrier: a wave's LDS operations execute in order, so once the counter shows 8 arrivals for
-        // this iteration all eight arg-max updates above are in the slot
-        if (lane == 0) __hip_atomic_fetch_add(arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        const unsigned want = (unsigned)NW * (unsigned)it;
-        while (__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(arrive, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) <
-               (int)want)
-          __builtin_amdgcn_s_sleep(1);
-        asm volatile("" ::: "memory");
-      }
+      unsigned long long *slot = wgmax.post(it, key, lane);
+      __syncthreads();
       key = *slot;
-      float4 all = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (XC) all = wxyz[it & 1][lane & (NW - 1)];                           // same round trip as the key
-      if (tid == 0) slots[(it + 2) % 3] = 0ull;
-      if (XC) {
-        if (key == 0ull) {                       // no candidate anywhere: the reference falls back to index 0
-          const float4 p0 = table[0];
-          nx1 = p0.x; ny1 = p0.y; nz1 = p0.z;
-        } else {
-          const unsigned pw = 0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull);
-          const int kw = (int)fps_bitrev(pw >> PRI_SHIFT, log2bs) + bs * (int)(pw & ((1u << PRI_SHIFT) - 1u));
-          const int wsel = __builtin_amdgcn_readfirstlane((kw & (T - 1)) >> 6);   // the wave that owns point kw
-          nx1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(all.x), wsel));
-          ny1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(all.y), wsel));
-          nz1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(all.z), wsel));
-        }
-      }
+      if (tid == 0) wgmax.retire(it);
       // another wave reached the same maximal distance with a different point
       if (TRACK) tie = tie || (wmax != 0u && wmax == (unsigned)(key >> 32) && wkey != key);
     }
@@ -284,12 +263,7 @@ __global__ __launch_bounds__(T * CPW) void fps_reg_kernel(int n, int m, int bs, 
       if (lane == 0 && (tie || key == 0ull)) cstat[it] = key == 0ull ? 2 : 1;
       if (tid == 0) cvals[it] = (unsigned)(key >> 32);
     }
-    if (key == 0ull) {
-      old = 0;
-    } else {
-      const unsigned p = 0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull);
-      old = (int)fps_bitrev(p >> PRI_SHIFT, log2bs) + bs * (int)(p & ((1u << PRI_SHIFT) - 1u));
-    }
+    old = key == 0ull ? 0 : fps_key_index(key, bs, log2bs);
     if (tid == 0) out[it] = old;
   };
   int it = 1;
@@ -302,12 +276,11 @@ __global__ __launch_bounds__(T * CPW) void fps_reg_kernel(int n, int m, int bs, 
     oxyz[(m - 1) * 3 + 1] = pts[old * 3 + 1];
     oxyz[(m - 1) * 3 + 2] = pts[old * 3 + 2];
   }
-  (void)nx1; (void)ny1; (void)nz1;
+  // Judge the log: a tie at iteration i < tie_iters is a simple event iff iteration i+1 had no tie and won with the
+  // same value (the other tied point, alone at V); anything else -> fallback.  (fps_slab_kernel: the same block.)
   if (tie_out != nullptr) {
-    // Judge the log: a tie at iteration i < tie_iters is a simple event iff iteration i+1 had no tie
-    // and won with the same value (the other tied point, alone at V); anything else -> fallback.
     int *rec = tie_out + cloud * FPS_CHAIN_INTS;
-    const bool enough = m >= tie_iters + 2;                 // decisions tie_iters-1 and tie_iters both made
+    const bool enough = m >= tie_iters + 2;
     __syncthreads();
     if (enough) {
       for (int i = 1 + tid; i < tie_iters; i += T) {
@@ -346,17 +319,13 @@ __global__ __launch_bounds__(T * CPW) void fps_reg_kernel(int n, int m, int bs, 
 // ~4 of 128 per iteration, ~9 during the first 200) and re-reduces their summaries; a wave with an empty mask reuses
 // its cached arg-max.  Priorities derive from the ORIGINAL index each sorted row carries, hence the same winner as
 // fps_reg_kernel for every input (tests: lattice clouds, zero padding, chain records, benchmark clouds bit for bit).
-// LDS_TABLE = false: the winner's coordinates come from the original cloud in global memory (L2-resident) instead of a
-// 16-byte-per-point LDS copy: the workgroup then needs ~8 KiB of LDS instead of 139 KiB, so that SEVERAL pruned chains
-// can share a CU (each uses well under half of its issue slots; round 3 experiment, tools/fps_pair_probe.py).
-template <int T, int I, bool LDS_TABLE = true>
+template <int T, int I>
 __global__ __launch_bounds__(T) void fps_slab_kernel(int n, int m, int bs, int log2bs, int nblk,
                                                      const float4 *__restrict__ rows_all,
                                                      const int *__restrict__ slab_tab,
                                                      int *__restrict__ idxs, float *__restrict__ new_xyz,
                                                      int *__restrict__ tie_out, int tie_iters,
-                                                     int *__restrict__ status, int dbg,
-                                                     const float *__restrict__ dataset = nullptr) {
+                                                     int *__restrict__ status) {
   TraceScope trace_scope_(TK_FPS);
   constexpr int NW = T / 64;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -369,12 +338,11 @@ __global__ __launch_bounds__(T) void fps_slab_kernel(int n, int m, int bs, int l
   if (tid == 0) status[blockIdx.x] = 1;
   __builtin_amdgcn_s_setprio(3);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  unsigned long long *slots = reinterpret_cast<unsigned long long *>(smem);  // [3] rotating
-  float4 *table = reinterpret_cast<float4 *>(smem + FPS_SLOT_BYTES);         // [n], by ORIGINAL index (LDS_TABLE)
-  unsigned *cvals = reinterpret_cast<unsigned *>(smem + FPS_SLOT_BYTES + (LDS_TABLE ? (size_t)n * 16 : 0));
+  const SlotArgMax wgmax{reinterpret_cast<unsigned long long *>(smem)};
+  float4 *table = reinterpret_cast<float4 *>(smem + FPS_SLOT_BYTES);         // [n], by ORIGINAL index
+  unsigned *cvals = reinterpret_cast<unsigned *>(smem + FPS_SLOT_BYTES + (size_t)n * 16);
   int *cstat = reinterpret_cast<int *>(cvals + (tie_iters + 2));
   int *cmeta = reinterpret_cast<int *>(smem + 32);
-  const float *opts = LDS_TABLE ? nullptr : dataset + (size_t)blockIdx.x * n * 3;
 
   const float4 *rows = rows_all + (size_t)blockIdx.x * nblk * 64;
   int *out = idxs + (size_t)blockIdx.x * m;
@@ -400,13 +368,12 @@ __global__ __launch_bounds__(T) void fps_slab_kernel(int n, int m, int bs, int l
       const float4 c = rows[row];
       px = c.x; py = c.y; pz = c.z;
       const unsigned k = __float_as_uint(c.w);              // original index
-      pr = (fps_bitrev(k & (unsigned)(bs - 1), log2bs) << PRI_SHIFT) | (k >> log2bs);
-      const float mag = (px * px) + (py * py) + (pz * pz);
-      if (!((double)mag <= 1e-3)) {                         // never-eligible points stay outside the box
+      pr = fps_priority(k, bs, log2bs);
+      if (fps_eligible(px, py, pz)) {                       // never-eligible points stay outside the box
         t0 = 1e10f;
         lx = hx = px; ly = hy = py; lz = hz = pz;
       }
-      if (LDS_TABLE) table[k] = make_float4(px, py, pz, 0.f);
+      table[k] = make_float4(px, py, pz, 0.f);
     }
     x[j] = px; y[j] = py; z[j] = pz; td[j] = __float_as_int(t0); pri[j] = pr;
     lx = wave_allreduce_f32(lx, [](float a, float b) { return fminf(a, b); });
@@ -419,7 +386,7 @@ __global__ __launch_bounds__(T) void fps_slab_kernel(int n, int m, int bs, int l
   }
   if (tid == 0) {
     out[0] = 0;
-    slots[0] = 0ull; slots[1] = 0ull; slots[2] = 0ull;
+    wgmax.init();
     cmeta[0] = 0; cmeta[1] = 0;
   }
   if (tie_out != nullptr)
@@ -440,23 +407,15 @@ __global__ __launch_bounds__(T) void fps_slab_kernel(int n, int m, int bs, int l
   int old = 0;
   auto iteration = [&](auto track_tag, int it) {
     constexpr bool TRACK = decltype(track_tag)::value;
-    float x1, y1, z1;
-    if (LDS_TABLE) {
-      const float4 p1 = table[old];
-      x1 = p1.x; y1 = p1.y; z1 = p1.z;
-    } else {
-      x1 = opts[old * 3 + 0]; y1 = opts[old * 3 + 1]; z1 = opts[old * 3 + 2];
-    }
+    const float4 p1 = table[old];
+    const float x1 = p1.x, y1 = p1.y, z1 = p1.z;
     if (oxyz && tid == 0) {
       oxyz[(it - 1) * 3 + 0] = x1; oxyz[(it - 1) * 3 + 1] = y1; oxyz[(it - 1) * 3 + 2] = z1;
     }
     // lane j: lower bound of d(p, sample) over bucket j's box, in the update's own arithmetic
-    const float gx = fmaxf(fmaxf(blox - x1, x1 - bhix), 0.f);
-    const float gy = fmaxf(fmaxf(bloy - y1, y1 - bhiy), 0.f);
-    const float gz = fmaxf(fmaxf(bloz - z1, z1 - bhiz), 0.f);
+    const float gx = fps_box_gap(blox, bhix, x1), gy = fps_box_gap(bloy, bhiy, y1), gz = fps_box_gap(bloz, bhiz, z1);
     const float bd = gx * gx + gy * gy + gz * gz;
     unsigned long long todo = __ballot(lane < I && (unsigned)__float_as_int(bd) + 1u < gmax);
-    if (dbg == 1 && it > 1) todo = 0ull;                    // timing probe: overhead floor (wrong results)
     if (todo != 0ull) {
       auto update = [&](auto jtag) {
         constexpr int j = decltype(jtag)::value;
@@ -501,14 +460,10 @@ __global__ __launch_bounds__(T) void fps_slab_kernel(int n, int m, int bs, int l
     }
     const unsigned long long wkey =
         wmax == 0u ? 0ull : (((unsigned long long)wmax << 32) | (unsigned long long)(0xFFFFFFFFu - wpri));
-    unsigned long long key = wkey;
-    {
-      unsigned long long *slot = slots + (it % 3);
-      if (lane == 0) atomicMax(slot, key);
-      __syncthreads();
-      key = *slot;
-      if (tid == 0) slots[(it + 2) % 3] = 0ull;
-    }
+    unsigned long long *slot = wgmax.post(it, wkey, lane);
+    __syncthreads();
+    const unsigned long long key = *slot;
+    if (tid == 0) wgmax.retire(it);
     gmax = (unsigned)(key >> 32);                          // bits + 1 of the winner's distance: bounds every point
     if (TRACK) {
       // a tie = the GLOBAL maximum attained by two points: inside this wave (wtie) or by another wave (wkey != key)
@@ -517,12 +472,7 @@ __global__ __launch_bounds__(T) void fps_slab_kernel(int n, int m, int bs, int l
       if (lane == 0 && (tie || key == 0ull)) cstat[it] = key == 0ull ? 2 : 1;
       if (tid == 0) cvals[it] = (unsigned)(key >> 32);
     }
-    if (key == 0ull) {
-      old = 0;
-    } else {
-      const unsigned p = 0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull);
-      old = (int)fps_bitrev(p >> PRI_SHIFT, log2bs) + bs * (int)(p & ((1u << PRI_SHIFT) - 1u));
-    }
+    old = key == 0ull ? 0 : fps_key_index(key, bs, log2bs);
     if (tid == 0) out[it] = old;
   };
   int it = 1;
@@ -530,14 +480,11 @@ __global__ __launch_bounds__(T) void fps_slab_kernel(int n, int m, int bs, int l
   for (; it < tracked_end; ++it) iteration(std::true_type{}, it);
   for (; it < m; ++it) iteration(std::false_type{}, it);
   if (oxyz && tid == 0) {
-    if (LDS_TABLE) {
-      const float4 p = table[old];
-      oxyz[(m - 1) * 3 + 0] = p.x; oxyz[(m - 1) * 3 + 1] = p.y; oxyz[(m - 1) * 3 + 2] = p.z;
-    } else {
-      oxyz[(m - 1) * 3 + 0] = opts[old * 3 + 0]; oxyz[(m - 1) * 3 + 1] = opts[old * 3 + 1]; oxyz[(m - 1) * 3 + 2] = opts[old * 3 + 2];
-    }
+    const float4 p = table[old];
+    oxyz[(m - 1) * 3 + 0] = p.x; oxyz[(m - 1) * 3 + 1] = p.y; oxyz[(m - 1) * 3 + 2] = p.z;
   }
-  if (tie_out != nullptr) {      // judge the log exactly as fps_reg_kernel does
+  // judge the log exactly as fps_reg_kernel does (same block; see the note at FPS_CHAIN_INTS)
+  if (tie_out != nullptr) {
     int *rec = tie_out + blockIdx.x * FPS_CHAIN_INTS;
     const bool enough = m >= tie_iters + 2;
     __syncthreads();
@@ -593,8 +540,7 @@ __global__ __launch_bounds__(T) void fps_stream_kernel(int n, int m, int bs, int
     unsigned bestpri = 0xFFFFFFFFu;
     for (int k = tid; k < n; k += T) {
       const float px = pts[k * 3 + 0], py = pts[k * 3 + 1], pz = pts[k * 3 + 2];
-      const float mag = (px * px) + (py * py) + (pz * pz);
-      if ((double)mag <= 1e-3) continue;
+      if (!fps_eligible(px, py, pz)) continue;
       const float dx = px - x1, dy = py - y1, dz = pz - z1;
       const float d = dx * dx + dy * dy + dz * dz;
       const float d2 = fminf(d, tmp[k]);
@@ -618,12 +564,7 @@ __global__ __launch_bounds__(T) void fps_stream_kernel(int n, int m, int bs, int
       const unsigned long long o = slots[it & 1][w];
       kmax = o > kmax ? o : kmax;
     }
-    if (kmax == 0ull) {
-      old = 0;
-    } else {
-      const unsigned p = 0xFFFFFFFFu - (unsigned)(kmax & 0xFFFFFFFFull);
-      old = (int)fps_bitrev(p >> PRI_SHIFT, log2bs) + bs * (int)(p & ((1u << PRI_SHIFT) - 1u));
-    }
+    old = kmax == 0ull ? 0 : fps_key_index(kmax, bs, log2bs);
     if (tid == 0) out[it] = old;
   }
   if (oxyz && tid == 0) {
@@ -694,7 +635,7 @@ __global__ __launch_bounds__(COOP_T) void fps_coop_kernel(int n, int m, int bs, 
                                                           const int *__restrict__ perm,
                                                           const float *__restrict__ orig_dataset) {
   extern __shared__ __attribute__((aligned(16))) unsigned pri_lds[];   // SORTED: [I][COOP_T] priorities
-  __shared__ unsigned long long slots[3];
+  __shared__ unsigned long long slots[3];   // workgroup-local arg-max
   __shared__ unsigned long long bcast;      // winning key, ~0 = timed out
   __shared__ float bxyz[3];                 // its coordinates
   // 1-D grid of 8 * G * ceil(clouds / 8) workgroups.  Blocks are dealt round-robin over the 8 XCDs (observed, not a
@@ -704,7 +645,7 @@ __global__ __launch_bounds__(COOP_T) void fps_coop_kernel(int n, int m, int bs, 
   const int rclass = blockIdx.x & 7, q = blockIdx.x >> 3;
   const int cloud = rclass + 8 * (q / G), g = q % G;
   if (cloud >= nclouds) return;
-  if (holdback == 1 && g == G - 1) return;            // 2, 3: timing probes (results meaningless), see coop_launch
+  if (holdback == 1 && g == G - 1) return;
   const int tid = threadIdx.x, lane = tid & 63;
   const int vtid = g * COOP_T + tid, ttotal = G * COOP_T;
   const float *pts = dataset + (size_t)cloud * n * 3;
@@ -729,8 +670,7 @@ __global__ __launch_bounds__(COOP_T) void fps_coop_kernel(int n, int m, int bs, 
     unsigned pr = 0xFFFFFFFFu;
     if (k < n) {
       px = pts[(size_t)k * 3 + 0]; py = pts[(size_t)k * 3 + 1]; pz = pts[(size_t)k * 3 + 2];
-      const float mag = (px * px) + (py * py) + (pz * pz);
-      if (!((double)mag <= 1e-3)) {
+      if (fps_eligible(px, py, pz)) {
         t0 = 1e10f;
         if (SORTED) {
           lox = fminf(lox, px); hix = fmaxf(hix, px);
@@ -738,10 +678,7 @@ __global__ __launch_bounds__(COOP_T) void fps_coop_kernel(int n, int m, int bs, 
           loz = fminf(loz, pz); hiz = fmaxf(hiz, pz);
         }
       }
-      if (SORTED) {
-        const unsigned o = (unsigned)permc[k];
-        pr = (fps_bitrev(o & (unsigned)(bs - 1), log2bs) << PRI_SHIFT) | (o >> log2bs);
-      }
+      if (SORTED) pr = fps_priority((unsigned)permc[k], bs, log2bs);
     }
     if (SORTED) pri_lds[i * COOP_T + tid] = pr;
     x[i] = px; y[i] = py; z[i] = pz; td[i] = __float_as_int(t0);
@@ -756,8 +693,9 @@ __global__ __launch_bounds__(COOP_T) void fps_coop_kernel(int n, int m, int bs, 
   }
   const unsigned pri_base = (fps_bitrev((unsigned)(vtid & (bs - 1)), log2bs) << PRI_SHIFT) | (unsigned)(vtid / bs);
   const unsigned qstep = (unsigned)(ttotal / bs);
+  const SlotArgMax wgmax{slots};
   if (tid == 0) {
-    slots[0] = 0ull; slots[1] = 0ull; slots[2] = 0ull;
+    wgmax.init();
     if (g == 0) out[0] = 0;
   }
   // sample 0 is ORIGINAL point 0 (in sorted mode pts[0] is some other point)
@@ -784,7 +722,7 @@ __global__ __launch_bounds__(COOP_T) void fps_coop_kernel(int n, int m, int bs, 
           w0 = __hip_atomic_load(qs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           ready = (unsigned)w0 == 0xFFFFFFFFu;
         }
-        if (__ballot(ready) == ~0ull || holdback == 3) { done = true; break; }   // probe 3: one poll, never wait
+        if (__ballot(ready) == ~0ull) { done = true; break; }
         if ((spin & 63) == 63 && __hip_atomic_load(errw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0ull) break;
         __builtin_amdgcn_s_sleep(1);
       }
@@ -803,13 +741,10 @@ __global__ __launch_bounds__(COOP_T) void fps_coop_kernel(int n, int m, int bs, 
   for (int it = 1; it < m && !failed; ++it) {
     bool active = true;
     if (SORTED) {
-      const float gx = fmaxf(fmaxf(lox - x1, x1 - hix), 0.f);
-      const float gy = fmaxf(fmaxf(loy - y1, y1 - hiy), 0.f);
-      const float gz = fmaxf(fmaxf(loz - z1, z1 - hiz), 0.f);
+      const float gx = fps_box_gap(lox, hix, x1), gy = fps_box_gap(loy, hiy, y1), gz = fps_box_gap(loz, hiz, z1);
       const float bd = gx * gx + gy * gy + gz * gz;            // the update's own expression on the box gap
       active = __builtin_amdgcn_readfirstlane((int)((unsigned)__float_as_int(bd) + 1u < gmax)) != 0;
     }
-    if (holdback == 2) active = false;                  // probe: exchange + barriers only
     if (active) {
       int best = __float_as_int(-1.0f);
       bestj = 0;
@@ -831,8 +766,7 @@ __global__ __launch_bounds__(COOP_T) void fps_coop_kernel(int n, int m, int bs, 
     }
     const unsigned long long key =
         wmax == 0u ? 0ull : (((unsigned long long)wmax << 32) | (unsigned long long)(0xFFFFFFFFu - wpri));
-    unsigned long long *slot = slots + (it % 3);
-    if (lane == 0) atomicMax(slot, key);
+    unsigned long long *slot = wgmax.post(it, key, lane);
     __syncthreads();
     const unsigned long long lkey = *slot;
     unsigned long long *mys = gws + ((size_t)(it & 1) * COOP_MAX_G + g) * COOP_SLOT_WORDS;
@@ -850,7 +784,7 @@ __global__ __launch_bounds__(COOP_T) void fps_coop_kernel(int n, int m, int bs, 
       coop_post(mys + 0, (unsigned)(lkey >> 32), tag, local);
     }
     if (tid == 0) {
-      slots[(it + 2) % 3] = 0ull;
+      wgmax.retire(it);
       if (lkey == 0ull)                                  // no candidate in this workgroup: value 0
         for (int w = 0; w < COOP_SLOT_WORDS; ++w) coop_post(mys + w, 0u, tag, local);
     }
@@ -872,7 +806,7 @@ __global__ __launch_bounds__(COOP_T) void fps_coop_kernel(int n, int m, int bs, 
           ready = (unsigned)w0 == tag && (unsigned)w1 == tag && (unsigned)w2 == tag && (unsigned)w3 == tag &&
                   (unsigned)w4 == tag;
         }
-        if (__ballot(ready) == ~0ull || holdback == 3) { done = true; break; }   // probe 3: one poll, never wait
+        if (__ballot(ready) == ~0ull) { done = true; break; }
         if ((spin & 63) == 63 &&
             __hip_atomic_load(errw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0ull) break;
         __builtin_amdgcn_s_sleep(1);
@@ -906,8 +840,7 @@ __global__ __launch_bounds__(COOP_T) void fps_coop_kernel(int n, int m, int bs, 
     } else if (kmax == 0ull) {       // nothing left to sample anywhere: index 0 again, like the reference
       x1 = first[0]; y1 = first[1]; z1 = first[2];
     } else {
-      const unsigned p = 0xFFFFFFFFu - (unsigned)(kmax & 0xFFFFFFFFull);
-      old = (int)fps_bitrev(p >> PRI_SHIFT, log2bs) + bs * (int)(p & ((1u << PRI_SHIFT) - 1u));
+      old = fps_key_index(kmax, bs, log2bs);
       x1 = bxyz[0]; y1 = bxyz[1]; z1 = bxyz[2];
     }
     gmax = failed ? 0u : (unsigned)(kmax >> 32);
@@ -918,76 +851,56 @@ __global__ __launch_bounds__(COOP_T) void fps_coop_kernel(int n, int m, int bs, 
   }
 }
 
-// Per-cloud "already sampled" flags of the launch being dispatched (set by the slab wrapper around fps_dispatch).
-static thread_local const int *t_done_flags = nullptr;
+// bs = opt_n_threads(n) of the reference and its log2: the thread partition every sampler's tie rule is written in.
+struct FpsGeometry { int bs, log2bs; };
+static FpsGeometry fps_geometry(int n) {
+  FpsGeometry g{ref_opt_n_threads(n), 0};
+  while ((1 << g.log2bs) < g.bs) ++g.log2bs;
+  return g;
+}
+
+// PWCLO_FPS_* switches (README.md), each read once per process.
+static int fps_use_table() { static const int v = tuning("PWCLO_FPS_TABLE", 1); return v; }
+static int fps_use_coop() { static const int v = tuning("PWCLO_FPS_COOP", 1); return v; }
+static int fps_coop_poll_delay() { static const int v = tuning("PWCLO_FPS_COOP_POLL_DELAY", 12); return v; }   // 12 x 64 cycles: swept 0..32 on configs[4]
+static int fps_coop_xcd_local_default() { static const int v = tuning("PWCLO_FPS_COOP_XCD_LOCAL", 1); return v; }
+static int fps_coop_launch_default() { static const int v = tuning("PWCLO_FPS_COOP_LAUNCH", 1); return v; }
 
 template <int T, int E, int I>
 static void launch_fps_reg(int b, int n, int m, int bs, int log2bs, const float *dataset, int *idxs,
                            float *new_xyz, int *tie_out, int tie_iters, const int *prefix_in) {
   const size_t chain_bytes = tie_out ? (size_t)(tie_iters + 2) * 8 : 0;
   const size_t table_bytes = FPS_SLOT_BYTES + (size_t)n * sizeof(float4) + chain_bytes;
-  hipStream_t st = current_stream();
-  static int use_table = -1;
-  if (use_table < 0) { const char *e = getenv("PWCLO_FPS_TABLE"); use_table = e ? atoi(e) : 1; }
-  static int use_pair = -1;
-  if (use_pair < 0) { const char *e = getenv("PWCLO_FPS_PAIR"); use_pair = e ? atoi(e) : 0; }   // opt-in: -15 % CU-time per cloud but 1.7x the chain latency (profiles/r03)
-  if constexpr (T == 512 && E == 0 && I == 16) {
-    // two clouds per 1024-thread workgroup, each with its own LDS barrier (see the kernel): the pyramid's first level
-    if (use_pair && (b % 2) == 0 && prefix_in == nullptr && t_done_flags == nullptr) {
-      auto kern = fps_reg_kernel<512, 0, 16, false, false, 2>;
-      // a dynamic-LDS request of 72 KiB (the kernel uses ~17 of them): two such workgroups may share a CU, the MFMA
-      // workgroups of other in-flight batches (>= 40 KiB of weights each) may not move in beside the chains
-      static bool attr = false;
-      if (!attr) { (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024); attr = true; }
-      hipLaunchKernelGGL(kern, dim3(b / 2), dim3(1024), 72 * 1024, st, n, m, bs, log2bs, dataset, idxs, new_xyz, tie_out,
-                         tie_iters, prefix_in, t_done_flags);
-      return;
-    }
-  }
-  static int use_xchg = -1;
-  if (use_xchg < 0) { const char *e = getenv("PWCLO_FPS_XCHG"); use_xchg = e ? atoi(e) : 0; }   // measured SLOWER (profiles/r03/r03_fps_exchange_variant.txt): opt-in
-  if (table_bytes + 512 <= 160 * 1024 && T > 64 && use_xchg && (use_table || table_bytes <= 64 * 1024)) {
-    auto kern = fps_reg_kernel<T, E, I, true, true>;       // coordinates travel with the exchange
-    static bool big_lds_enabled = false;
-    if (table_bytes > 60 * 1024 && !big_lds_enabled) {
-      (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512);
-      big_lds_enabled = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(b), dim3(T), table_bytes, st, n, m, bs, log2bs, dataset, idxs, new_xyz, tie_out,
-                       tie_iters, prefix_in, t_done_flags);
-  } else if (table_bytes <= 160 * 1024 && (use_table || table_bytes <= 64 * 1024)) {
-    auto kern = fps_reg_kernel<T, E, I, true>;
-    static bool big_lds_enabled = false;  // per instantiation; raises the 64 KiB dynamic-LDS default
-    if (table_bytes > 64 * 1024 && !big_lds_enabled) {
-      (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024);
-      big_lds_enabled = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(b), dim3(T), table_bytes, st, n, m, bs, log2bs, dataset, idxs, new_xyz, tie_out,
-                       tie_iters, prefix_in, t_done_flags);
+  const int use_table = fps_use_table();
+  if (table_bytes <= 160 * 1024 && (use_table || table_bytes <= 64 * 1024)) {
+    launch_grid<fps_reg_kernel<T, E, I, true>, T / 64>(dim3(b), (int)table_bytes, n, m, bs, log2bs, dataset, idxs, new_xyz,
+                                                       tie_out, tie_iters, prefix_in);
   } else {
-    hipLaunchKernelGGL((fps_reg_kernel<T, E, I, false>), dim3(b), dim3(T), FPS_SLOT_BYTES + chain_bytes, st, n, m,
-                       bs, log2bs, dataset, idxs, new_xyz, tie_out, tie_iters, prefix_in, t_done_flags);
+    launch_grid<fps_reg_kernel<T, E, I, false>, T / 64>(dim3(b), (int)(FPS_SLOT_BYTES + chain_bytes), n, m, bs, log2bs, dataset,
+                                                        idxs, new_xyz, tie_out, tie_iters, prefix_in);
   }
+  check_launch("furthest_point_sampling");
 }
 
 // Threads per cloud as a function of n (measured on MI355X, tools/microbench.py).
-// PWCLO_FPS_THREADS=<64|128|256|512|1024> overrides it for experiments.
-static int fps_pick_threads(int n, int bs) {
-  static int forced = -1;
-  if (forced < 0) {
-    const char *e = getenv("PWCLO_FPS_THREADS");
-    forced = e ? atoi(e) : 0;
-  }
-  int T;
-  if (forced == 64 || forced == 128 || forced == 256 || forced == 512 || forced == 1024) T = forced;
-  else if (n <= 256) T = 64;     // single wave: no LDS exchange, no barrier (342 ns/iter at n=256)
-  else if (n <= 4096) T = 256;   // 505 ns/iter at n=2048 (512 threads: 573, 128: 671)
-  else T = 512;                  // 916 ns/iter at n=8192 (1024 threads: 988, 256: 1010)
-  if (T > 512 && n <= 512) T = 512;
-  (void)bs;
-  return T;
+static int fps_pick_threads(int n) {
+  if (n <= 256) return 64;     // single wave: no LDS exchange, no barrier (342 ns/iter at n=256)
+  if (n <= 4096) return 256;   // 505 ns/iter at n=2048 (512 threads: 573, 128: 671)
+  return 512;                  // 916 ns/iter at n=8192 (1024 threads: 988, 256: 1010)
 }
+
+// The instantiations of fps_reg_kernel: every (T, E, I) that fps_pick_threads and the reference's block size select for
+// some n <= 24576, I being the largest points-per-residue count of its row (tests/test_host_cpu.py re-derives the list).
+// Rows of one (T, E) stand in ascending order of I: fps_dispatch takes the first that fits.
+struct FpsRow {
+  int T, E, I;
+  void (*launch)(int, int, int, int, int, const float *, int *, float *, int *, int, const int *);
+};
+template <int T, int E, int I> constexpr FpsRow fps_row() { return {T, E, I, launch_fps_reg<T, E, I>}; }
+static const FpsRow FPS_ROWS[] = {
+    fps_row<64, 0, 1>(),  fps_row<64, 0, 2>(),  fps_row<64, 1, 1>(),  fps_row<64, 1, 2>(),  fps_row<64, 2, 1>(),
+    fps_row<256, 0, 2>(), fps_row<256, 1, 1>(), fps_row<256, 1, 2>(), fps_row<256, 1, 4>(), fps_row<256, 1, 8>(),
+    fps_row<512, 0, 16>(), fps_row<512, 0, 48>()};
 
 // out[b,c,j] = points[b,c,idx[b,j]]; grid (ceil(m/256), c, b) so that small m still fills CUs.
 __global__ __launch_bounds__(256) void gather_points_kernel(int c, int n, int m,
@@ -1028,8 +941,8 @@ extern "C" void group_points_grad_kernel_wrapper(int b, int c, int n, int npoint
 // CUs: bench.py --config 5) selects the plain launch with pwclo_fps_large_cloud_launch(0) (or PWCLO_FPS_COOP_LAUNCH=0):
 // co-residency then holds by construction as long as at most 256 workgroups of this kernel are in flight and the other
 // kernels on the device are short -- and a violation still ends in PWCLO_ECOOP_TIMEOUT, never in wrong indices.
-static std::atomic<int> g_xcd_local{-1};    // -1: not decided (PWCLO_FPS_COOP_XCD_LOCAL, default 1); set by pwclo_fps_large_cloud_exchange
-static std::atomic<int> g_coop_api{-1};     // -1: not decided (PWCLO_FPS_COOP_LAUNCH, default 1); set by pwclo_fps_large_cloud_launch
+static std::atomic<int> g_xcd_local{-1};    // -1: as PWCLO_FPS_COOP_XCD_LOCAL says (default 1); set by pwclo_fps_large_cloud_exchange
+static std::atomic<int> g_coop_api{-1};     // -1: as PWCLO_FPS_COOP_LAUNCH says (default 1); set by pwclo_fps_large_cloud_launch
 
 static void coop_launch(int b, int n, int m, int bs, int log2bs, int G, const float *dataset,
                         unsigned long long *ws, int *idxs, float *new_xyz, const int *perm,
@@ -1038,24 +951,15 @@ static void coop_launch(int b, int n, int m, int bs, int log2bs, int G, const fl
   unsigned *host_err = device_error_word();            // a timeout inside the kernel reaches pwclo_last_error()
   if (host_err == nullptr) return;
   const char *dbg = getenv("PWCLO_FPS_COOP_DEBUG_TIMEOUT");   // test hook of the failure path (read per call)
-  int holdback = dbg ? atoi(dbg) : 0;
+  int holdback = (dbg && atoi(dbg) == 1) ? 1 : 0;
   int spin_limit = holdback == 1 ? 256 : (1 << 21);
   int xcd_local = g_xcd_local.load();
-  if (xcd_local < 0) {
-    const char *e = getenv("PWCLO_FPS_COOP_XCD_LOCAL");
-    xcd_local = e ? atoi(e) : 1;
-    g_xcd_local.store(xcd_local);
-  }
-  static int poll_delay = -1;
-  if (poll_delay < 0) { const char *e = getenv("PWCLO_FPS_COOP_POLL_DELAY"); poll_delay = e ? atoi(e) : 12; }   // 12 x 64 cycles: swept 0..32 on configs[4] (tools/scratch/poll_delay.sh)
+  if (xcd_local < 0) xcd_local = fps_coop_xcd_local_default();
+  int poll_delay = fps_coop_poll_delay();
   hipLaunchKernelGGL(fps_coop_init_kernel, dim3(ceil_div(b * COOP_WS_WORDS, 256)), dim3(256), 0, st, ws,
                      b * COOP_WS_WORDS);
   int coop_api = g_coop_api.load();
-  if (coop_api < 0) {
-    const char *e = getenv("PWCLO_FPS_COOP_LAUNCH");
-    coop_api = e ? atoi(e) : 1;
-    g_coop_api.store(coop_api);
-  }
+  if (coop_api < 0) coop_api = fps_coop_launch_default();
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   (void)hipStreamIsCapturing(st, &cap);
   const bool use_coop_api = coop_api && cap == hipStreamCaptureStatusNone;
@@ -1063,11 +967,7 @@ static void coop_launch(int b, int n, int m, int bs, int log2bs, int G, const fl
   const size_t lds = sorted ? (size_t)16 * COOP_T * sizeof(unsigned) : 0;
   const void *kern = sorted ? reinterpret_cast<const void *>(fps_coop_kernel<16, true>)
                             : reinterpret_cast<const void *>(fps_coop_kernel<16, false>);
-  static bool lds_attr = false;
-  if (sorted && !lds_attr) {
-    (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    lds_attr = true;
-  }
+  if (sorted) raise_lds_limit<fps_coop_kernel<16, true>>((int)lds);
   int per_launch = (224 * (1024 / COOP_T)) / G;         // plain launch: workgroups that are certainly co-resident on an idle device
   if (per_launch >= 8) per_launch &= ~7;                // whole groups of 8 clouds: the grid is padded to 8 * G * ceil(clouds / 8)
   for (int c0 = 0; c0 < b; c0 += per_launch) {
@@ -1106,49 +1006,26 @@ static void fps_dispatch(int b, int n, int m, const float *dataset, float *temp,
   if (b <= 0 || m <= 0) return;
   PWCLO_REQUIRE(n >= 1, "furthest_point_sampling: n=%d must be >= 1", n);
   PWCLO_REQUIRE((long long)n < (1ll << PRI_SHIFT) * 1ll, "furthest_point_sampling: n=%d too large", n);
-  const int bs = ref_opt_n_threads(n);
-  int log2bs = 0;
-  while ((1 << log2bs) < bs) ++log2bs;
-  int T = fps_pick_threads(n, bs);
-  int E = 0;
-  while ((T << E) < bs) ++E;                  // T < bs: a thread owns 2^E residues
-  int I = ceil_div(n, E == 0 ? T : bs);       // points per residue per thread
-  if (T == 1024 && I > 16) { T = 512; E = 0; I = ceil_div(n, 512); }   // VGPR budget at 16 waves
-#define FPS_CASE(TT, EE, II)                                               \
-  if (T == TT && E == EE && I <= II) {                                     \
-    launch_fps_reg<TT, EE, II>(b, n, m, bs, log2bs, dataset, idxs, new_xyz, tie_out, tie_iters, prefix_in); \
-    check_launch("furthest_point_sampling");                              \
-    return;                                                                \
-  }
-  if (T == 1024) { FPS_CASE(1024, 0, 8) FPS_CASE(1024, 0, 16) }
-  if (T == 512) { FPS_CASE(512, 0, 1) FPS_CASE(512, 0, 2) FPS_CASE(512, 0, 4) FPS_CASE(512, 0, 8)
-                  FPS_CASE(512, 0, 16) FPS_CASE(512, 0, 48) }
-  if (T == 256) { FPS_CASE(256, 0, 1) FPS_CASE(256, 0, 2)
-                  FPS_CASE(256, 1, 1) FPS_CASE(256, 1, 2) FPS_CASE(256, 1, 4) FPS_CASE(256, 1, 8)
-                  FPS_CASE(256, 1, 16) FPS_CASE(256, 1, 32) }
-  if (T == 128) { FPS_CASE(128, 0, 1) FPS_CASE(128, 0, 2)
-                  FPS_CASE(128, 1, 1) FPS_CASE(128, 1, 2)
-                  FPS_CASE(128, 2, 1) FPS_CASE(128, 2, 2) FPS_CASE(128, 2, 4) FPS_CASE(128, 2, 8)
-                  FPS_CASE(128, 2, 16) }
-  if (T == 64) { FPS_CASE(64, 0, 1) FPS_CASE(64, 0, 2)
-                 FPS_CASE(64, 1, 1) FPS_CASE(64, 1, 2)
-                 FPS_CASE(64, 2, 1) FPS_CASE(64, 2, 2)
-                 FPS_CASE(64, 3, 1) FPS_CASE(64, 3, 2) FPS_CASE(64, 3, 4) FPS_CASE(64, 3, 8) }
-#undef FPS_CASE
-  if (n <= 24576) {  // register-resident fallback (large clouds, or a forced T without a case)
-    launch_fps_reg<512, 0, 48>(b, n, m, bs, log2bs, dataset, idxs, new_xyz, tie_out, tie_iters, prefix_in);
-    check_launch("furthest_point_sampling");
+  const auto [bs, log2bs] = fps_geometry(n);
+  if (n <= 24576) {                               // one workgroup per cloud, every point in a register
+    const int T = fps_pick_threads(n);
+    int E = 0;
+    while ((T << E) < bs) ++E;                  // T < bs: a thread owns 2^E residues
+    const int I = ceil_div(n, E == 0 ? T : bs);   // points per residue per thread
+    const FpsRow *row = nullptr;
+    for (const FpsRow &r : FPS_ROWS)   // the first fit is the smallest: rows of one (T, E) are listed by ascending I
+      if (r.T == T && r.E == E && I <= r.I) { row = &r; break; }
+    PWCLO_REQUIRE(row != nullptr, "furthest_point_sampling: n=%d needs (T, E, I) = (%d, %d, %d), which has no kernel", n, T, E, I);
+    row->launch(b, n, m, bs, log2bs, dataset, idxs, new_xyz, tie_out, tie_iters, prefix_in);
     return;
   }
   PWCLO_REQUIRE(temp != nullptr,
                 "furthest_point_sampling: n=%d needs the (b,n) temp buffer pre-filled with 1e10", n);
   if (tie_out != nullptr)   // the large-cloud samplers keep no tie record: later levels run in full
     hipLaunchKernelGGL(fps_fill_flag_kernel, dim3(ceil_div(b, 256)), dim3(256), 0, current_stream(), tie_out, b, 1);
-  static int coop = -1;
-  if (coop < 0) { const char *e = getenv("PWCLO_FPS_COOP"); coop = e ? atoi(e) : 1; }
   const int G = ceil_div(n, COOP_T * 16);                // workgroups per cloud, <= 16 points per thread
   // (8 points per thread on twice the workgroups was measured slower: 3.2 vs 2.9 us per iteration at n = 120k)
-  if (coop && G <= COOP_MAX_G && (reinterpret_cast<uintptr_t>(temp) & 7) == 0 && (size_t)COOP_WS_WORDS * 2 <= (size_t)n) {
+  if (fps_use_coop() && G <= COOP_MAX_G && (reinterpret_cast<uintptr_t>(temp) & 7) == 0 && (size_t)COOP_WS_WORDS * 2 <= (size_t)n) {
     // cooperative multi-workgroup sampler; `temp` doubles as its (re-zeroed) exchange workspace
     coop_launch(b, n, m, bs, log2bs, G, dataset, reinterpret_cast<unsigned long long *>(temp), idxs, new_xyz,
                 nullptr, nullptr);
@@ -1187,9 +1064,7 @@ extern "C" void furthest_point_sampling_sorted_kernel_wrapper(int b, int n, int 
   PWCLO_REQUIRE(n > 24576 && (long long)n < (1ll << PRI_SHIFT), "furthest_point_sampling(sorted): n=%d outside (24576, 2^23)", n);
   PWCLO_REQUIRE(dataset != nullptr && sorted != nullptr && perm != nullptr && temp != nullptr,
                 "furthest_point_sampling(sorted): dataset, sorted copy, permutation and temp are required");
-  const int bs = ref_opt_n_threads(n);
-  int log2bs = 0;
-  while ((1 << log2bs) < bs) ++log2bs;
+  const auto [bs, log2bs] = fps_geometry(n);
   const int G = ceil_div(n, COOP_T * 16);
   PWCLO_REQUIRE(G <= COOP_MAX_G && (reinterpret_cast<uintptr_t>(temp) & 7) == 0 && (size_t)COOP_WS_WORDS * 2 <= (size_t)n,
                 "furthest_point_sampling(sorted): n=%d needs %d workgroups per cloud (max %d) / an 8-byte aligned temp", n, G,
@@ -1228,7 +1103,7 @@ __global__ __launch_bounds__(256) void so_bbox_kernel(int n, const float *__rest
   unsigned lo[3] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu}, hi[3] = {0u, 0u, 0u};
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
     const float px = p[(size_t)i * 3], py = p[(size_t)i * 3 + 1], pz = p[(size_t)i * 3 + 2];
-    if ((double)((px * px) + (py * py) + (pz * pz)) <= 1e-3) continue;     // never-eligible rows stay outside the box
+    if (!fps_eligible(px, py, pz)) continue;     // never-eligible rows stay outside the box
     const float v[3] = {px, py, pz};
 #pragma unroll
     for (int a = 0; a < 3; ++a) { const unsigned c = so_code(v[a]); lo[a] = min(lo[a], c); hi[a] = max(hi[a], c); }
@@ -1291,8 +1166,7 @@ __global__ __launch_bounds__(256) void so_hist_kernel(int n, const float *__rest
   }
   // rows the sampler never selects (|p|^2 <= 1e-3: the zero padding behind a frame's survivors, sampling.cpp:74-76) go
   // behind every real cell: mixed into the origin's cell they would smear its few real points over dozens of blocks
-  const float mag = (p[0] * p[0]) + (p[1] * p[1]) + (p[2] * p[2]);
-  if ((double)mag <= 1e-3) c = (unsigned)SO_CELLS;
+  if (!fps_eligible(p[0], p[1], p[2])) c = (unsigned)SO_CELLS;
   cell[(size_t)b * n + i] = (int)c;
   atomicAdd(hist + (size_t)b * SO_BINS + c, 1);
 }
@@ -1335,8 +1209,7 @@ __global__ __launch_bounds__(1024) void so_block_sort_kernel(int n, int bs, int 
   unsigned long long k = ~0ull;
   if (pos < n) {
     const unsigned o = (unsigned)order[(size_t)b * n + pos];
-    const unsigned pri = (fps_bitrev(o & (unsigned)(bs - 1), log2bs) << PRI_SHIFT) | (o >> log2bs);
-    k = ((unsigned long long)pri << 32) | o;
+    k = ((unsigned long long)fps_priority(o, bs, log2bs) << 32) | o;
   }
   key[t] = k;
   __syncthreads();
@@ -1372,9 +1245,7 @@ extern "C" void fps_spatial_order_kernel_wrapper(int b, int n, const float *poin
   PWCLO_REQUIRE(workspace != nullptr && points != nullptr && sorted != nullptr && perm != nullptr,
                 "fps_spatial_order: points, outputs and workspace are required%s", "");
   PWCLO_REQUIRE(b <= 65535 && (long long)n < (1ll << PRI_SHIFT), "fps_spatial_order: b=%d n=%d out of range", b, n);
-  const int bs = ref_opt_n_threads(n);
-  int log2bs = 0;
-  while ((1 << log2bs) < bs) ++log2bs;
+  const auto [bs, log2bs] = fps_geometry(n);
   unsigned *box = reinterpret_cast<unsigned *>(workspace);
   int *cell = reinterpret_cast<int *>(box + (size_t)b * 8);
   int *order = cell + (size_t)b * n;
@@ -1395,9 +1266,10 @@ extern "C" int knn_point_slabs(int n);
 extern "C" long long knn_point_build_bytes(int b, int n);
 
 // Level-1 sampler of the fused pipeline: `knn_workspace` / `slab_tab` come from knn_build_kernel_wrapper on the
-// same cloud (the neighbour search of that level needs the build anyway).  Clouds whose slabs fit are sampled by
-// fps_slab_kernel (exact pruning of the distance update), the others by the register-resident kernel, which
-// runs second and skips the clouds flagged in `status` (b ints, device).  Same outputs as the chain wrapper.
+// same cloud (the neighbour search of that level needs the build anyway).  Every cloud is sampled by fps_slab_kernel
+// (exact pruning of the distance update), which flags it in `status` (b ints, device); an n outside the kernel's
+// range is refused.  `dataset` is not read: the kernel takes the points from the workspace's rows.  Same outputs as
+// the chain wrapper.
 extern "C" void furthest_point_sampling_slab_kernel_wrapper(int b, int n, int m, const float *dataset, int *idxs,
                                                             float *new_xyz, int *tie_out, int tie_iters,
                                                             const void *knn_workspace, const int *slab_tab,
@@ -1405,46 +1277,21 @@ extern "C" void furthest_point_sampling_slab_kernel_wrapper(int b, int n, int m,
   if (b <= 0 || m <= 0) return;
   PWCLO_REQUIRE(knn_workspace != nullptr && slab_tab != nullptr && status != nullptr,
                 "furthest_point_sampling(slab): workspace, slab table and status buffer are required");
-  const int bs = ref_opt_n_threads(n);
-  int log2bs = 0;
-  while ((1 << log2bs) < bs) ++log2bs;
+  const auto [bs, log2bs] = fps_geometry(n);
   const size_t chain_bytes = tie_out ? (size_t)(tie_iters + 2) * 8 : 0;
   const size_t lds = FPS_SLOT_BYTES + (size_t)n * sizeof(float4) + chain_bytes;
   PWCLO_REQUIRE(knn_point_slabs(n) == 8 && n >= 4096 && n <= 8 * 18 * 64 && lds <= 160 * 1024,
                 "furthest_point_sampling(slab): n=%d is outside the slab sampler's range (8 slabs, LDS table)", n);
   const int nblk = (n + 63) / 64 + 8;
   const int per = (n + 7) / 8;
-  const char *dbg_e = getenv("PWCLO_FPS_SLAB_DBG");
-  const int dbg = dbg_e ? atoi(dbg_e) : 0;
-  static int lds_table = -1;
-  if (lds_table < 0) { const char *e = getenv("PWCLO_FPS_SLAB_TABLE"); lds_table = e ? atoi(e) : 1; }
-  if (!lds_table) {        // winner coordinates from the original cloud in global memory: a few KiB of LDS per workgroup
-    const size_t small = FPS_SLOT_BYTES + chain_bytes;
-    if (per <= 16 * 64)
-      hipLaunchKernelGGL((fps_slab_kernel<512, 16, false>), dim3(b), dim3(512), small, current_stream(), n, m, bs, log2bs,
-                         nblk, reinterpret_cast<const float4 *>(knn_workspace), slab_tab, idxs, new_xyz, tie_out, tie_iters,
-                         status, dbg, dataset);
-    else
-      hipLaunchKernelGGL((fps_slab_kernel<512, 18, false>), dim3(b), dim3(512), small, current_stream(), n, m, bs, log2bs,
-                         nblk, reinterpret_cast<const float4 *>(knn_workspace), slab_tab, idxs, new_xyz, tie_out, tie_iters,
-                         status, dbg, dataset);
-    check_launch("furthest_point_sampling(slab)");
-    return;
-  }
-  static bool big16 = false, big18 = false;
-#define SLAB_LAUNCH(II, FLAG)                                                                                   \
-  {                                                                                                             \
-    auto kern = fps_slab_kernel<512, II>;                                                                       \
-    if (!FLAG) {                                                                                                \
-      (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);    \
-      FLAG = true;                                                                                              \
-    }                                                                                                           \
-    hipLaunchKernelGGL(kern, dim3(b), dim3(512), lds, current_stream(), n, m, bs, log2bs, nblk,                 \
-                       reinterpret_cast<const float4 *>(knn_workspace), slab_tab, idxs, new_xyz, tie_out,       \
-                       tie_iters, status, dbg, dataset);                                                        \
-  }
-  if (per <= 16 * 64) SLAB_LAUNCH(16, big16) else SLAB_LAUNCH(18, big18)
-#undef SLAB_LAUNCH
+  (void)dataset;
+  const auto rows = reinterpret_cast<const float4 *>(knn_workspace);
+  if (per <= 16 * 64)
+    launch_grid<fps_slab_kernel<512, 16>, 8>(dim3(b), (int)lds, n, m, bs, log2bs, nblk, rows, slab_tab, idxs, new_xyz, tie_out,
+                                             tie_iters, status);
+  else
+    launch_grid<fps_slab_kernel<512, 18>, 8>(dim3(b), (int)lds, n, m, bs, log2bs, nblk, rows, slab_tab, idxs, new_xyz, tie_out,
+                                             tie_iters, status);
   check_launch("furthest_point_sampling(slab)");
 }
 

@@ -28,7 +28,11 @@ def rand_cloud(seed, b, n, scale=20.0):
 # ---------------------------------------------------------------- furthest point sampling
 FPS_SHAPES = [(2, 8192, 2048), (2, 2048, 1024), (3, 1024, 256), (3, 256, 64), (2, 1024, 2048),
               (2, 100, 50), (2, 63, 20), (1, 5000, 300), (2, 16384, 128), (1, 20000, 64),
-              (1, 30000, 12), (2, 1, 3), (2, 129, 129), (2, 511, 40), (2, 4096, 512), (1, 4097, 300)]
+              (1, 30000, 12), (2, 1, 3), (2, 129, 129), (2, 511, 40), (2, 4096, 512), (1, 4097, 300),
+              # the dispatch rows no other shape reaches (n = 128: one wave, two residues per thread; n = 512 on a random
+              # cloud), the last n with the LDS point table and the first without it, the largest single-workgroup
+              # cloud (48 points per thread exactly) and the first cooperative one (two workgroups)
+              (2, 128, 40), (2, 512, 40), (1, 10236, 24), (1, 10237, 24), (1, 24576, 16), (1, 24577, 16)]
 
 
 @pytest.mark.parametrize("b,n,m", FPS_SHAPES)
@@ -39,7 +43,7 @@ def test_fps_random(cuda, b, n, m):
     assert torch.equal(out, ref)
 
 
-@pytest.mark.parametrize("n,m", [(512, 300), (1000, 700), (8192, 512), (64, 64), (300, 200)])
+@pytest.mark.parametrize("n,m", [(512, 300), (1000, 700), (8192, 512), (64, 64), (300, 200), (8192, 2048)])
 def test_fps_exact_ties_lattice(cuda, n, m):
     """Integer lattice + duplicates: almost every arg-max is an exact tie, so the result is
     decided by the reference's tie rule (bit-reversed k mod bs, then k div bs)."""

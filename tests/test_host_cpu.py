@@ -489,3 +489,36 @@ def test_conv_blocks_on_cpu_are_plain_torch():
     assert not conv1x1.supported(x, mlp[0].conv)            # CPU tensor: never routed to the kernels
     assert conv1x1._wgrad_split(192, 128) and conv1x1._wgrad_split(6, 8)
     assert not conv1x1._wgrad_split(160, 144)               # 9 x 10 tiles: no 8-worker split with <= 4 x 4 per wave
+
+
+def test_fps_dispatch_rows_cover_every_single_workgroup_cloud():
+    """csrc/sampling.hip instantiates the register-resident sampler for twelve (T, E, I) rows and nothing else.  For
+    every n a single workgroup samples (1..24576) the launch parameters follow from the reference's block-size rule
+    (oracle: opt_n_threads) by the rule fps_dispatch documents -- T threads by n, E = log2(bs / T) when T < bs,
+    I = points per residue per thread; the rule is re-stated here, only the row list is read from the source, so a
+    change of the C thresholds shows in the GPU shapes of tests/test_gpu_ops.py, not here -- and must select exactly
+    one row of the table in the source; the n range of every row is the documented one."""
+    from oracle import ops as O
+    src = open(os.path.join(ROOT, "pwclonet_pylidarslam_amd", "csrc", "sampling.hip")).read()
+    rows = [tuple(int(v) for v in r) for r in re.findall(r"fps_row<(\d+), (\d+), (\d+)>\(\)", src)]
+    documented = {(64, 0, 1): (1, 64), (64, 0, 2): (65, 127), (64, 1, 1): (128, 128), (64, 1, 2): (129, 255),
+                  (64, 2, 1): (256, 256), (256, 0, 2): (257, 511), (256, 1, 1): (512, 512), (256, 1, 2): (513, 1024),
+                  (256, 1, 4): (1025, 2048), (256, 1, 8): (2049, 4096), (512, 0, 16): (4097, 8192),
+                  (512, 0, 48): (8193, 24576)}
+    assert len(rows) == 12 and set(rows) == set(documented)
+    seen = {}
+    for n in range(1, 24577):
+        bs = O.opt_n_threads(n)
+        T = 64 if n <= 256 else (256 if n <= 4096 else 512)
+        E = 0
+        while (T << E) < bs:
+            E += 1
+        per = T if E == 0 else bs
+        I = (n + per - 1) // per
+        fit = [r for r in rows if r[0] == T and r[1] == E and I <= r[2]]
+        assert fit, "n=%d: (T, E, I) = (%d, %d, %d) has no kernel" % (n, T, E, I)
+        row = min(fit, key=lambda r: r[2])                   # the dispatch takes the first (smallest) I that fits
+        assert sum(1 for r in fit if r[2] == row[2]) == 1
+        lo, hi = seen.get(row, (n, n))
+        seen[row] = (min(lo, n), max(hi, n))
+    assert seen == documented

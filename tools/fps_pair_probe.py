@@ -3,8 +3,9 @@
 
 Times the level-1 call (8192 -> 2048) for 64 / 256 / 512 / 1024 clouds: with ONE workgroup per cloud and 256 CUs, 256 clouds are
 one chain per CU; 512 / 1024 clouds are two / four per CU when the kernel's LDS / registers allow them to be co-resident,
-otherwise the extra workgroups queue and the time doubles.  Variants: the register-resident kernel (LDS table / global
-table) and the bucket-pruned slab kernel (LDS table / global table)."""
+otherwise the extra workgroups queue and the time doubles.  Variants: the register-resident kernel (LDS table, or global
+table with PWCLO_FPS_TABLE=0) and the bucket-pruned slab kernel (LDS table; its global-table form was removed with the
+other round-3 sampler experiments)."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -28,5 +29,5 @@ for nb in (64, 256, 512, 1024):
         ms = timeit(lambda: fused.fps_slab_with_xyz(x, 2048))
     else:
         ms = timeit(lambda: fused.fps_with_xyz(x, 2048))
-    print("%s table=%s/%s clouds %4d: %8.3f ms  (%.3f ms per 256 clouds)" % (which, os.environ.get("PWCLO_FPS_TABLE", "1"),
-          os.environ.get("PWCLO_FPS_SLAB_TABLE", "1"), nb, ms, ms * 256 / max(nb, 256)))
+    table = "1" if which == "slab" else os.environ.get("PWCLO_FPS_TABLE", "1")
+    print("%s table=%s clouds %4d: %8.3f ms  (%.3f ms per 256 clouds)" % (which, table, nb, ms, ms * 256 / max(nb, 256)))
