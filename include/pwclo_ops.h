@@ -417,6 +417,28 @@ void train_batch_sample_kernel_wrapper(int B, int R, int npoints, int dataset, c
                                        const double *t_trans, int augmented, float *xyz_f1, float *xyz_f2, int *indices,
                                        int *counts);
 
+/* Flat gradient bucket and Adam over a list of n fp32 tensors (flat_step.FlatAdam).  The list is
+ * read from HOST arrays at launch time -- tensors[t] (device pointer, 4-byte aligned), counts[t] values, offsets[t] = first
+ * value in the bucket, a multiple of 64 (256 bytes) with offsets[t] + round_up(counts[t], 64) <= total - 1 -- and travels to
+ * the kernels by value, flat_step_entries_per_launch() tensors per launch, so a captured graph holds it without host
+ * memory.  Spans of different tensors must not overlap (flat_step.bucket_layout lays them back to back).  bucket: total
+ * fp32 values, 16-byte aligned; its LAST value is the count of non-finite inputs. */
+int flat_step_entries_per_launch(void);
+/* bucket[offsets[t] + i] = tensors[t][i] * scale (scale 1.0f: the bits as they are); the padding up to round_up(count, 64)
+ * is written as zero; bucket[total - 1] = number of NaN / +-Inf values read, as fp32 (exact below 2^24). */
+void flat_pack_kernel_wrapper(int n, void *const *tensors, const long long *counts, const long long *offsets, float scale,
+                              float *bucket, long long total);
+/* torch.optim.Adam (decoupled == 0: weight_decay is L2, added to the gradient) or AdamW (decoupled != 0) without amsgrad /
+ * maximize over tensors[t] = the PARAMETERS; gradient = bucket, exp_avg, exp_avg_sq: total fp32 values each at the same
+ * offsets.  step (1) i64 and lr (1) f64 live in DEVICE memory; coef (4) f64 is scratch of the launch group.  A one-thread
+ * launch goes first: bucket[total - 1] == 0 -> step += 1 and coef = {1, lr / (1 - beta1^step), sqrt(1 - beta2^step), lr};
+ * otherwise coef[0] = 0 and the update launches leave parameters, moments and step as they were.  Every value is computed
+ * in fp64 from the fp32 inputs and rounded once. */
+void flat_adam_kernel_wrapper(int n, void *const *tensors, const long long *counts, const long long *offsets,
+                              const float *bucket, float *exp_avg, float *exp_avg_sq, long long total, long long *step,
+                              const double *lr, double *coef, double beta1, double beta2, double eps, double weight_decay,
+                              int decoupled);
+
 /* ---- 3b. module-path layers: training-mode BatchNorm, stack tails, pointwise convolution ---- */
 
 /* Training-mode BatchNorm over x (b, c, l) f32 (l = product of the trailing dimensions), the statistics pass of

@@ -69,6 +69,11 @@ SIGNATURES = {
     "train_batch_pose_kernel_wrapper": ([_i, _i, _i, _F, _F, _F, _F, _F, _F], None),
     "train_batch_sample_kernel_wrapper": ([_i, _i, _i, _i, _F, _F, _F, ctypes.c_float, ctypes.c_float, _F, _F, _i, _F, _F, _F,
                                            _F], None),
+    "flat_step_entries_per_launch": ([], _i),
+    "flat_pack_kernel_wrapper": ([_i, ctypes.POINTER(ctypes.c_void_p)] + [ctypes.POINTER(ctypes.c_longlong)] * 2
+                                 + [ctypes.c_float, _F, ctypes.c_longlong], None),
+    "flat_adam_kernel_wrapper": ([_i, ctypes.POINTER(ctypes.c_void_p)] + [ctypes.POINTER(ctypes.c_longlong)] * 2
+                                 + [_F, _F, _F, ctypes.c_longlong, _F, _F, _F] + [ctypes.c_double] * 4 + [_i], None),
     "batchnorm_train_workspace_bytes": ([_i], ctypes.c_longlong),
     "batchnorm_train_forward_kernel_wrapper": ([_i, _i, _i, _F, _F, _F, ctypes.c_float, ctypes.c_float, _F, _F, _F, _F,
                                                 _F, _F, _i], None),

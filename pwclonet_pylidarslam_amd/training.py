@@ -11,6 +11,8 @@ drifts to its own loss weights and then to its own network.  ``PWCLONetWithLoss`
 import torch
 import torch.nn as nn
 
+from .flat_step import FlatAdam, FlatTrainStep  # noqa: F401  (the data-parallel step that replays as graphs)
+
 
 class PWCLONetWithLoss(nn.Module):
     """``forward(xyz_f1 (B,3,N), xyz_f2 (B,3,N), gt_params (B,7)) -> (loss, pose_params (B,4,7), log_dict)``."""

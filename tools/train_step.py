@@ -3,12 +3,15 @@
 
     python tools/train_step.py [--batch 8] [--steps 10]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 tools/train_step.py --gpus N
+    python tools/train_step.py --flat --graph [--gpus N]
 
 One process per GPU; the reference-shaped module graph in TRAIN mode (BatchNorm batch statistics,
 dropout; torch conv/BN autograd + the HIP gather/group forward and backward kernels), the
 reference's supervised loss (pwclonet_pylidarslam_amd.loss), Adam, and -- for N > 1 --
 DistributedDataParallel over RCCL: one 3.1 MB gradient all-reduce per step, BN buffers not
-broadcast.  Not the headline benchmark (bench.py measures forward pairs/s); prints one JSON line.
+broadcast.  --flat replaces DDP + torch's Adam by flat_step.FlatAdam / FlatTrainStep: one flat gradient bucket, one
+eager all-reduce, one HIP Adam launch group -- the data-parallel step that replays as graphs (--gpus N --graph).
+Not the headline benchmark (bench.py measures forward pairs/s); prints one JSON line.
 """
 import argparse, json, os, sys, time
 
@@ -22,7 +25,8 @@ import bench  # noqa: E402
 from pwclonet_pylidarslam_amd import dist_util  # noqa: E402
 from pwclonet_pylidarslam_amd.loss import PWCLONetLossModule  # noqa: E402
 from pwclonet_pylidarslam_amd.pwclonet import PWCLONet  # noqa: E402
-from pwclonet_pylidarslam_amd.training import PWCLONetWithLoss, TrainStep, ddp_wrap, gradient_bucket_values  # noqa: E402
+from pwclonet_pylidarslam_amd.training import (FlatAdam, FlatTrainStep, PWCLONetWithLoss, TrainStep, ddp_wrap,  # noqa: E402
+                                               gradient_bucket_values)
 
 
 def main():
@@ -35,6 +39,9 @@ def main():
     ap.add_argument("--fused-adam", action="store_true", help="torch.optim.Adam(fused=True): one multi-tensor kernel")
     ap.add_argument("--graph", action="store_true",
                     help="capture forward + loss + backward + Adam into one hipGraph (single GPU only)")
+    ap.add_argument("--flat", action="store_true",
+                    help="flat_step.FlatAdam + FlatTrainStep: flat gradient bucket, eager all-reduce, HIP Adam; with it --graph "
+                         "is allowed for --gpus N (two graphs around the collective); --gpus 1 runs the world-1 collective too")
     ap.add_argument("--sample-ahead", action="store_true",
                     help="draw the next batch's furthest-point samples on a second stream while this batch's step runs "
                          "(training.TrainStep(sample_ahead=True); the synthetic batch is the same every step)")
@@ -44,6 +51,7 @@ def main():
     a = ap.parse_args()
     if a.gpus > 1 and not dist_util.launched_by_torchrun():      # supervise N fresh ranks; no GPU call made here
         sys.exit(dist_util.spawn_ranks(os.path.abspath(__file__), sys.argv[1:], a.gpus))
+    explicit_gpus = any(x == "--gpus" or x.startswith("--gpus=") for x in sys.argv[1:])
     rank, local_rank, world = dist_util.env_world()
     assert world == a.gpus, "WORLD_SIZE=%d but --gpus %d" % (world, a.gpus)
     dev = torch.device("cuda", local_rank)
@@ -57,17 +65,32 @@ def main():
     # network + loss in ONE module: the all-reduce carries the 775 068 network gradients and the loss module's two
     # learnable weights -- with the network alone under DDP the replicas' loss weights drift
     unit = PWCLONetWithLoss(net, loss_mod)
-    model = ddp_wrap(unit, dev) if world > 1 else unit
-    opt = torch.optim.Adam(unit.parameters(), lr=1e-4, capturable=a.graph, fused=True if a.fused_adam else None)
+    group = None
+    if a.flat:
+        assert not (a.fused_adam or a.sample_ahead), "--flat brings its own Adam kernel; not combined with --fused-adam / --sample-ahead"
+        if explicit_gpus:                                  # --gpus given: the collective runs, also at world size 1
+            import torch.distributed as dist
+            if not dist.is_initialized():
+                os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+                os.environ.setdefault("MASTER_PORT", "29533")
+                dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
+            group = dist.group.WORLD
+        model, opt = unit, FlatAdam(unit.parameters(), lr=1e-4)
+    else:
+        model = ddp_wrap(unit, dev) if world > 1 else unit
+        opt = torch.optim.Adam(unit.parameters(), lr=1e-4, capturable=a.graph, fused=True if a.fused_adam else None)
     x1, x2 = bench.make_batch(a.batch, a.npoints, 2000 + rank, dev)
     g = torch.Generator().manual_seed(3 + rank)
     gt = torch.randn(a.batch, 7, generator=g) * 0.1
     gt[:, 3:] = torch.nn.functional.normalize(gt[:, 3:] + torch.tensor([1.0, 0, 0, 0]), dim=1)
     gt = gt.to(dev)
 
-    if a.graph:
-        assert world == 1, "--graph is the single-GPU variant (DDP's bucketed all-reduce is not captured here)"
-    step = TrainStep(model, opt, x1, x2, gt, graph=a.graph, sample_ahead=a.sample_ahead).step
+    if a.flat:
+        step = FlatTrainStep(unit, opt, x1, x2, gt, graph=a.graph, process_group=group).step
+    else:
+        if a.graph:
+            assert world == 1, "--graph is the single-GPU variant (DDP's bucketed all-reduce is not captured here; --flat is)"
+        step = TrainStep(model, opt, x1, x2, gt, graph=a.graph, sample_ahead=a.sample_ahead).step
     if a.raw_batches:
         assert not a.sample_ahead, "--raw-batches rewrites the step's tensors every step; not combined with --sample-ahead"
         from pwclonet_pylidarslam_amd import batches
@@ -79,7 +102,7 @@ def main():
         if a.graph:                                        # one capture serves every step: the counter lives on the device
             torch.cuda.synchronize(dev)
             feed_graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(feed_graph):
+            with torch.cuda.graph(feed_graph, **(FlatTrainStep.capture_kw(group) if a.flat else {})):
                 feed()
             feed = feed_graph.replay
         train = step
@@ -100,11 +123,16 @@ def main():
         print(json.dumps({"metric": "PWCLO-Net training frame-pairs/sec (fwd+bwd+Adam), 2x%d-pt pairs" % a.npoints,
                           "value": world * a.batch * a.steps / dt, "unit": "frame-pairs/s", "n_gpus": world,
                           "ms_per_step": 1e3 * dt / a.steps, "batch_per_gpu": a.batch, "dtype": "f32",
-                          "launch": ("one hipGraph per step" if a.graph else "eager (module graph, torch autograd)")
+                          "launch": (("two hipGraphs per step around the eager all-reduce" if a.flat and group is not None
+                                      else "one hipGraph per step") if a.graph else "eager (module graph, torch autograd)")
+                          + (", flat gradient bucket + HIP Adam" if a.flat else "")
                           + (", next batch's sampling chain on a second stream" if a.sample_ahead else "")
                           + (", every batch built from raw sweeps on the device" if a.raw_batches else ""), "loss_first_last": [losses[0], losses[-1]],
-                          "collective": ("DDP all-reduce of %d fp32 gradient values (network + loss weights), one bucket"
-                                         % gradient_bucket_values(unit)) if world > 1 else "none"}), flush=True)
+                          "collective": ("eager all-reduce of the flat bucket (%d fp32 values: %d gradients, padding, the "
+                                         "non-finite count), world size %d" % (opt.total, gradient_bucket_values(unit), world))
+                          if group is not None else
+                          ("DDP all-reduce of %d fp32 gradient values (network + loss weights), one bucket"
+                           % gradient_bucket_values(unit)) if world > 1 else "none"}), flush=True)
     dist_util.finish()
 
 
