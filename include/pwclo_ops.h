@@ -611,6 +611,34 @@ void softmax_wsum_forward_kernel_wrapper(long long rows, int k, const float *x, 
 void softmax_wsum_backward_kernel_wrapper(long long rows, int k, const float *x, const float *v, const float *dout,
                                           float *dx, float *dv);
 
+/* ---- 4c. module path (training): the pose head with replayable dropout masks ------------
+ * PW/pose_calculator.py:47-86 in train() mode from the mask LOGITS: p = softmax_n(logits), pooled = sum_n emb p,
+ * big = w_qt pooled + b_qt, big_q / big_t = big under two keep masks (kept: times exactly 2.0f, dropped: +0.0f),
+ * q = w_q big_q + b_q normalised as q / (sqrt(sum q^2 + 1e-10) + 1e-10), t = w_t big_t + b_t.
+ * emb, logits (B,64,N) f32 channel-major, 16-byte aligned, N >= 1; w_qt (256,64) 16-byte aligned, b_qt (256), w_q (4,256),
+ * b_q (4), w_t (3,256), b_t (3).  state = {seed, next step, step in flight} i64 in DEVICE memory.
+ * Keep bit of unit c of cloud b = top bit of Philox4x32-10 output word 0, key (seed low, seed high), counter
+ * (b * 256 + c, rank * 8 + head * 2 + branch, step in flight mod 2^32, 3); branch 0 = q, 1 = t; rank in [0, 2^28), head 0..3.
+ * begin: one thread, state[2] = state[1]; state[1] += 1 (once per network forward, before the four heads).
+ * forward reads state[0] and state[2]; writes q (B,4), t (B,3) and what backward needs: rowmax, rinv (B,64) = the row
+ * maximum and 1 / sum of exp(x - max); pooled (B,64); big (B,256); keep (B,256) u8, bit 0 = q kept, bit 1 = t kept;
+ * q_raw (B,4) before the norm.  keep_log (B,256) u8 or NULL receives the same keep bytes (the stream's record).
+ * backward never reads the state: g_q (B,4), g_t (B,3) -> d_emb = g p, d_logits = g p (emb - pooled) with g = g_pooled
+ * (B,64) and p recomputed; the six parameter gradients summed over the batch in batch order (no atomics); g_qraw (B,4),
+ * g_big (B,256), g_pooled (B,64) are workspaces the caller owns. */
+void pose_head_train_begin_kernel_wrapper(long long *state);
+void pose_head_train_forward_kernel_wrapper(int B, int N, const float *emb, const float *logits, const float *w_qt,
+                                            const float *b_qt, const float *w_q, const float *b_q, const float *w_t,
+                                            const float *b_t, const long long *state, int rank, int head, float *rowmax,
+                                            float *rinv, float *pooled, float *big, unsigned char *keep,
+                                            unsigned char *keep_log, float *q_raw, float *q, float *t);
+void pose_head_train_backward_kernel_wrapper(int B, int N, const float *emb, const float *logits, const float *w_qt,
+                                             const float *w_q, const float *w_t, const float *rowmax, const float *rinv,
+                                             const float *pooled, const float *big, const unsigned char *keep,
+                                             const float *q_raw, const float *g_q, const float *g_t, float *g_qraw,
+                                             float *g_big, float *g_pooled, float *d_emb, float *d_logits, float *d_w_qt,
+                                             float *d_b_qt, float *d_w_q, float *d_b_q, float *d_w_t, float *d_b_t);
+
 /* ---- 5. KITTI odometry evaluation of predicted poses ---------------------------
  * Replaces the per-sample host loops of /root/reference/train.py:866-893 (pose row -> 4x4 via quat2mat :762-795),
  * slam/common/kitti360_utils.py:406-431 (relative -> absolute poses), evaluation.py:198-215 (trajectory distances)

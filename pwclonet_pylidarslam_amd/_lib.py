@@ -64,6 +64,9 @@ SIGNATURES = {
     "softmax_wsum_supported_k": ([_i], _i),
     "softmax_wsum_forward_kernel_wrapper": ([ctypes.c_longlong, _i, _F, _F, _F], None),
     "softmax_wsum_backward_kernel_wrapper": ([ctypes.c_longlong, _i, _F, _F, _F, _F, _F], None),
+    "pose_head_train_begin_kernel_wrapper": ([_F], None),
+    "pose_head_train_forward_kernel_wrapper": ([_i, _i] + [_F] * 9 + [_i, _i] + [_F] * 9, None),
+    "pose_head_train_backward_kernel_wrapper": ([_i, _i] + [_F] * 24, None),
     "compact_frames_scan_kernel_wrapper": ([_i, _i, _i, _F, _F, _F, _F], None),
     "sweep_filter_compact_kernel_wrapper": ([_i, _i, _i, _F, _F, _i, _F, ctypes.c_float, ctypes.c_float, _F, _F], None),
     "train_batch_pose_kernel_wrapper": ([_i, _i, _i, _F, _F, _F, _F, _F, _F], None),

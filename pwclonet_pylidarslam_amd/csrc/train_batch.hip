@@ -13,37 +13,10 @@
 #include <stdint.h>
 
 #include "common.hpp"
+#include "philox.hpp"
 #include "rows.hpp"
 
 namespace pwclo {
-
-constexpr unsigned TB_SELECT = 0u;    // purpose words of the counter (c3)
-constexpr unsigned TB_REPLACE = 1u;
-constexpr unsigned TB_AUGMENT = 2u;
-
-// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11), counter (c0..c3), key (k0, k1).
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
-                                              unsigned out[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    c0 = hi1 ^ c1 ^ k0;
-    c1 = lo1;
-    c2 = hi0 ^ c3 ^ k1;
-    c3 = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
-__device__ __forceinline__ unsigned philox_word(unsigned index, unsigned unit, unsigned step, unsigned purpose, unsigned k0,
-                                                unsigned k1) {
-  unsigned o[4];
-  philox4x32_10(index, unit, step, purpose, k0, k1, o);
-  return o[0];
-}
 
 // c = a . b for 3x3 row-major matrices, every entry summed left to right.
 __device__ __forceinline__ void mat3_mul(const double a[9], const double b[9], double c[9]) {

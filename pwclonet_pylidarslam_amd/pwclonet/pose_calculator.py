@@ -31,3 +31,21 @@ class PoseCalculator(nn.Module):
         if self.squeeze:
             q, t = q.squeeze(2), t.squeeze(2)
         return q, t
+
+    def from_logits(self, embedding_features, mask_logits):
+        """``self(embedding_features, F.softmax(mask_logits, dim=2))`` -- exactly that while no
+        ``training.DropoutStream`` is attached, in ``eval()`` and for tensors the kernels do not cover.  With a stream
+        attached and in ``train()`` mode the whole head, soft-max included, is one hand-written kernel pair each way
+        (``..pose_head``) and its two dropout masks come from the stream's counter-based generator."""
+        attached = getattr(self, "_dropout_stream", None)
+        if attached is not None and self.training:
+            from .. import pose_head
+            stream, head = attached
+            qt, q_, t_ = self.conv1d_q_t.conv, self.conv1d_q.conv, self.conv1d_t.conv
+            weights = (qt.weight, qt.bias, q_.weight, q_.bias, t_.weight, t_.bias)
+            if pose_head.supported(embedding_features, mask_logits, weights):
+                q, t, _keep = pose_head.pose_head_train(embedding_features, mask_logits, *weights, stream.state_on(
+                    embedding_features.device), stream.rank, head, stream.keep_log(head, embedding_features.shape[0],
+                                                                                  embedding_features.device))
+                return (q, t) if self.squeeze else (q.unsqueeze(2), t.unsqueeze(2))
+        return self(embedding_features, F.softmax(mask_logits, dim=2))

@@ -1,7 +1,6 @@
 """Pose warp-refinement level, ``PW/pose_warp_refinement.py:25-158``."""
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
 from ..pointnet2_ops.pointnet2_modules import PointnetFPModulePWCLONet
 from . import PWCLO_utils as pwclo
@@ -59,7 +58,7 @@ class PoseWarpRefinement(nn.Module):
             embedding_mask = self.flow_predictor_mask(coarse_masks, embedding_features, points_f1)
         else:
             embedding_mask = coarse_masks
-        q_det, t_det = self.pose_calculator(embedding_features, F.softmax(embedding_mask, dim=2))
+        q_det, t_det = self.pose_calculator.from_logits(embedding_features, embedding_mask)
         q = pwclo.mul_point_q(q_det, q_coarse).squeeze(2)        # pose_warp_refinement.py:139
         t = pwclo.warp(t_coarse, q_det, t_det).squeeze(2)        # :148
         return q, t, embedding_features, embedding_mask

@@ -263,6 +263,9 @@ class PWCLONet(nn.Module):
         """The reference-shaped forward (PW/pwclo_net.py:109-207) on the HIP ops."""
         cf = lambda z: z.permute(0, 2, 1).contiguous()
         B = xyz_f1.size(0)
+        dropout_stream = getattr(self, "_dropout_stream", None)
+        if dropout_stream is not None and self.training and xyz_f1.is_cuda:
+            dropout_stream.begin(xyz_f1.device)  # one launch: this forward's four heads draw the masks of the next step
         if samples is not None:                  # every level's samples drawn by the caller (sample_pyramid)
             l1 = self._pyramid(cf(xyz_f1), points_f1, samples[0])
             l2 = self._pyramid(cf(xyz_f2), points_f2, samples[1])
@@ -295,7 +298,7 @@ class PWCLONet(nn.Module):
         x14 = cf(x14t)
 
         mask4 = self.l4_flow_predictor(p14, emb4)
-        q4, t4 = self.pose_calculator_4(emb4, F.softmax(mask4, dim=2))
+        q4, t4 = self.pose_calculator_4.from_logits(emb4, mask4)
 
         q3, t3, emb3, mask3 = self.pose_warp_refinement_3(x13, p13, x23, p23, x14, emb4, mask4, q4, t4)
         q2, t2, emb2, mask2 = self.pose_warp_refinement_2(x12, p12, x22, p22, x13, emb3, mask3, q3, t3)

@@ -167,3 +167,120 @@ class TrainStep:
         for dst, src in zip(self.samples, self.next_samples):
             torch._foreach_copy_(dst, src)
         return loss
+
+
+class DropoutStream:
+    """Replayable dropout for the four pose heads: while attached, a training-mode
+    ``PWCLONet.forward`` on the GPU advances the step counter with one launch and every ``PoseCalculator`` in ``train()``
+    mode runs ``pose_head.pose_head_train`` -- the head as hand-written kernels -- with keep masks that are a function of
+    ``(seed, step, rank, head, branch, cloud, unit)``: Philox4x32-10 under the 64-bit ``seed``, the generator of
+    ``batches.TrainBatchBuilder`` with purpose word 3.  The reference's ``F.dropout`` stream is not reproduced, its law is
+    (p = 0.5: kept values doubled, dropped ones zero), identically on any device.
+
+    Seed, step and rank enter the kernels from device memory and launch arguments only, so the stream works inside
+    ``TrainStep(graph=True)`` / ``FlatTrainStep(graph=True)`` and every replay advances the step.  ``rank`` separates the
+    masks of data-parallel replicas (0 .. 2^28 - 1).  ``detach()`` restores the heads' plain ``F.dropout`` path."""
+
+    HEADS = ("pose_calculator_4", "pose_warp_refinement_3.pose_calculator", "pose_warp_refinement_2.pose_calculator",
+             "pose_warp_refinement_1.pose_calculator")        # forward order: head 0 .. 3 of the counter
+
+    def __init__(self, net, seed=0, rank=0):
+        seed, rank = int(seed), int(rank)
+        if not -(1 << 63) <= seed < (1 << 64):
+            raise ValueError("dropout stream: seed=%d does not fit 64 bits" % seed)
+        if not 0 <= rank < (1 << 28):
+            raise ValueError("dropout stream: rank=%d outside [0, 2^28)" % rank)
+        self.seed, self.rank = seed & ((1 << 64) - 1), rank
+        self._step_host = 0
+        self._state = None
+        self._log = None
+        self.net = None
+        self.attach(net)
+
+    # ---- attachment ----------------------------------------------------------------------------------------------------
+    def attach(self, net):
+        if self.net is not None:
+            raise RuntimeError("dropout stream: already attached (detach() first)")
+        if not hasattr(net, "get_submodule"):
+            raise TypeError("dropout stream: needs the PWCLONet module, got %s" % type(net).__name__)
+        try:
+            heads = [net.get_submodule(name) for name in self.HEADS]
+        except AttributeError as e:
+            raise TypeError("dropout stream: the module has no pose head %s" % e) from e
+        if any(not hasattr(h, "from_logits") for h in heads):
+            raise TypeError("dropout stream: the pose heads must be this package's PoseCalculator")
+        if getattr(net, "_dropout_stream", None) is not None:
+            raise RuntimeError("dropout stream: the network already has a stream attached")
+        for i, h in enumerate(heads):
+            h._dropout_stream = (self, i)
+        net._dropout_stream = self
+        self.net = net
+        first = next(net.parameters(), None)
+        if first is not None and first.is_cuda:
+            self.state_on(first.device)          # made here, outside any capture
+        return self
+
+    def detach(self):
+        """Today's behaviour again: the heads call ``F.dropout`` and no begin launch is issued."""
+        if self.net is not None:
+            for name in self.HEADS:
+                self.net.get_submodule(name)._dropout_stream = None
+            self.net._dropout_stream = None
+            self.net = None
+
+    # ---- device state (used by the network and the heads) ---------------------------------------------------------------
+    def state_on(self, device):
+        """The (3,) int64 device state {seed, next step, step in flight}, made on first use."""
+        if self._state is None or self._state.device != device:
+            if self._state is not None:
+                self._step_host = int(self._state[1].item())
+            signed = self.seed - (1 << 64) if self.seed >= (1 << 63) else self.seed
+            self._state = torch.tensor([signed, self._step_host, self._step_host], dtype=torch.int64).to(device)
+            self._log = None
+        return self._state
+
+    def keep_log(self, head, batch, device):
+        """Head ``head``'s (B,256) uint8 slot of the record ``masks()`` reads."""
+        if self._log is None or self._log.shape[1] != batch or self._log.device != device:
+            self._log = torch.zeros((4, batch, 256), dtype=torch.uint8, device=device)
+        return self._log[head]
+
+    def begin(self, device):
+        """One launch: step in flight = next step, next step += 1."""
+        from . import _lib
+        _lib.call("pose_head_train_begin_kernel_wrapper", device, self.state_on(device).data_ptr())
+
+    # ---- the step counter ------------------------------------------------------------------------------------------------
+    def step_index(self):
+        """The step the next training forward (or replay) will use."""
+        return self._step_host if self._state is None else int(self._state[1].item())
+
+    def set_step(self, k):
+        k = int(k)
+        if not 0 <= k < (1 << 62):
+            raise ValueError("dropout stream: step=%d outside [0, 2^62)" % k)
+        self._step_host = k
+        if self._state is not None:
+            self._state[1:2].fill_(k)
+
+    def masks(self):
+        """(4, 2, B, 256) bool: the keep masks of the last training forward -- [head, branch (0 = q, 1 = t), cloud, unit]."""
+        if self._log is None:
+            raise RuntimeError("dropout stream: no training forward has run yet")
+        return torch.stack(((self._log & 1) != 0, (self._log & 2) != 0), dim=1)
+
+    def state_dict(self):
+        return {"seed": self.seed, "rank": self.rank, "step": self.step_index()}
+
+    def load_state_dict(self, sd):
+        """Seed and step are written to the device state, which a captured graph re-reads; the rank is a launch argument:
+        load it before capturing."""
+        seed, rank = int(sd["seed"]), int(sd["rank"])
+        if not -(1 << 63) <= seed < (1 << 64):
+            raise ValueError("dropout stream: seed=%d does not fit 64 bits" % seed)
+        if not 0 <= rank < (1 << 28):
+            raise ValueError("dropout stream: rank=%d outside [0, 2^28)" % rank)
+        self.seed, self.rank = seed & ((1 << 64) - 1), rank
+        self.set_step(sd["step"])
+        if self._state is not None:
+            self._state[0:1].fill_(self.seed - (1 << 64) if self.seed >= (1 << 63) else self.seed)

@@ -4,6 +4,7 @@
     python tools/train_step.py [--batch 8] [--steps 10]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 tools/train_step.py --gpus N
     python tools/train_step.py --flat --graph [--gpus N]
+    python tools/train_step.py --graph --fused-adam --dropout-stream [SEED]
 
 One process per GPU; the reference-shaped module graph in TRAIN mode (BatchNorm batch statistics,
 dropout; torch conv/BN autograd + the HIP gather/group forward and backward kernels), the
@@ -25,8 +26,8 @@ import bench  # noqa: E402
 from pwclonet_pylidarslam_amd import dist_util  # noqa: E402
 from pwclonet_pylidarslam_amd.loss import PWCLONetLossModule  # noqa: E402
 from pwclonet_pylidarslam_amd.pwclonet import PWCLONet  # noqa: E402
-from pwclonet_pylidarslam_amd.training import (FlatAdam, FlatTrainStep, PWCLONetWithLoss, TrainStep, ddp_wrap,  # noqa: E402
-                                               gradient_bucket_values)
+from pwclonet_pylidarslam_amd.training import (DropoutStream, FlatAdam, FlatTrainStep, PWCLONetWithLoss, TrainStep,  # noqa: E402
+                                               ddp_wrap, gradient_bucket_values)
 
 
 def main():
@@ -48,6 +49,9 @@ def main():
     ap.add_argument("--raw-batches", action="store_true",
                     help="every step trains on a fresh batch built from raw synthetic sweeps by batches.TrainBatchBuilder "
                          "(filter, random choice, augmentation, ground truth on the device), written into the step's tensors")
+    ap.add_argument("--dropout-stream", type=int, nargs="?", const=0, default=None, metavar="SEED",
+                    help="training.DropoutStream(net, seed=SEED, rank=rank): replayable dropout masks and the pose heads as "
+                         "hand-written kernels (without it the heads call F.dropout: torch's stream)")
     a = ap.parse_args()
     if a.gpus > 1 and not dist_util.launched_by_torchrun():      # supervise N fresh ranks; no GPU call made here
         sys.exit(dist_util.spawn_ranks(os.path.abspath(__file__), sys.argv[1:], a.gpus))
@@ -65,6 +69,7 @@ def main():
     # network + loss in ONE module: the all-reduce carries the 775 068 network gradients and the loss module's two
     # learnable weights -- with the network alone under DDP the replicas' loss weights drift
     unit = PWCLONetWithLoss(net, loss_mod)
+    stream = DropoutStream(net, seed=a.dropout_stream, rank=rank) if a.dropout_stream is not None else None
     group = None
     if a.flat:
         assert not (a.fused_adam or a.sample_ahead), "--flat brings its own Adam kernel; not combined with --fused-adam / --sample-ahead"
@@ -127,7 +132,10 @@ def main():
                                       else "one hipGraph per step") if a.graph else "eager (module graph, torch autograd)")
                           + (", flat gradient bucket + HIP Adam" if a.flat else "")
                           + (", next batch's sampling chain on a second stream" if a.sample_ahead else "")
-                          + (", every batch built from raw sweeps on the device" if a.raw_batches else ""), "loss_first_last": [losses[0], losses[-1]],
+                          + (", every batch built from raw sweeps on the device" if a.raw_batches else ""),
+                          "dropout": ("DropoutStream(seed=%d): counter-based masks, HIP pose heads, next step %d"
+                                      % (a.dropout_stream, stream.step_index())) if stream is not None else "F.dropout",
+                          "loss_first_last": [losses[0], losses[-1]],
                           "collective": ("eager all-reduce of the flat bucket (%d fp32 values: %d gradients, padding, the "
                                          "non-finite count), world size %d" % (opt.total, gradient_bucket_values(unit), world))
                           if group is not None else
