@@ -548,6 +548,25 @@ void conv1x1_affine_maxk_forward_kernel_wrapper(int b, int cin, int cout, int s,
 long long conv1x1_wgrad_workspace_bytes(int b, int cin, int cout, int p);
 void conv1x1_wgrad_kernel_wrapper(int b, int cin, int cout, int p, const float *dy, const float *x, float *dw,
                                   void *workspace);
+/* Host only (no launch): which kernel instantiation and grid the entry point `kind` selects for (b, cin, cout, p) given
+ * as that entry point takes them, answered by the launchers' own planning code.  cus = 0: the current device's CU count;
+ * cus > 0 stands in for it, and no HIP call is made (usable without a GPU).  out receives
+ *   kinds FORWARD .. POOLED: {nbo, gy, gx, lean, stats}: conv1x1_kernel<nbo, stats, lean> on a (gx, gy) grid
+ *                            (FORWARD also stands for conv1x1_bnrelu_forward, POOLED for any k; p = s * k there);
+ *   kind WGRAD:              {ro, rm, ph, wo, wm, cp, grid}: conv1x1_wgrad_kernel<ro, rm, .> with ph pixel phases of wo x wm
+ *                            workers on chunks of cp pixels (the same plan with and without the input transform).
+ * Returns 0 when the plan is one the launcher runs, 1 when the launcher refuses it with PWCLO_EINVAL (LDS beyond the limit,
+ * more than 4 blocks for DGRAD_SUMS, no rectangle for WGRAD; out is filled all the same), -1 for an unknown kind or a
+ * non-positive size.  The launchers' checks that do not depend on the plan (p % 4, alignment, tensors below 4 GiB) are
+ * not repeated here. */
+#define PWCLO_PLAN_FORWARD 0     /* conv1x1_forward(transposed = 0), conv1x1_bnrelu_forward */
+#define PWCLO_PLAN_DGRAD 1       /* conv1x1_forward(transposed = 1) for the layer (cin, cout): the kernel writes cin rows */
+#define PWCLO_PLAN_STATS 2       /* conv1x1_forward_bnstats */
+#define PWCLO_PLAN_DGRAD_SUMS 3  /* conv1x1_dgrad_bnstats for the layer (cin, cout) */
+#define PWCLO_PLAN_AFFINE 4      /* conv1x1_affine_forward */
+#define PWCLO_PLAN_POOLED 5      /* conv1x1_affine_maxk_forward */
+#define PWCLO_PLAN_WGRAD 6       /* conv1x1_wgrad, conv1x1_bnrelu_wgrad */
+int conv1x1_plan_query(int kind, int b, int cin, int cout, int p, int cus, int *out);
 
 /* ---- 4. hoisted variants of section 3 ----------------------------------------------------------
  * The first layer of every grouped MLP is linear in [geometry | feat_centre[s] | feat_nbr[n]]; the

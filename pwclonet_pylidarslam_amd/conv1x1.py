@@ -78,6 +78,24 @@ def _wgrad_split(cin, cout):
     return any(-(-nbo // wo) <= 4 and -(-nbi // (8 // wo)) <= 4 for wo in (1, 2, 4, 8))
 
 
+PLAN_KINDS = {"forward": 0, "dgrad": 1, "stats": 2, "dgrad_sums": 3, "affine": 4, "pooled": 5, "wgrad": 6}   # PWCLO_PLAN_*
+_PLAN_FIELDS = (("nbo", "gy", "gx", "lean", "stats"), ("ro", "rm", "ph", "wo", "wm", "cp", "grid"))
+
+
+def plan(kind, b, cin, cout, p, cus=0):
+    """conv1x1_plan_query: the kernel instantiation and grid the entry point ``kind`` (a key of ``PLAN_KINDS``) selects
+    for the sizes as that entry point takes them -> dict of the fields documented in include/pwclo_ops.h plus
+    ``accepted`` (False: the launcher refuses the shape).  ``cus`` > 0 stands in for the device's CU count; the call is
+    then host-only and works without a GPU."""
+    import ctypes
+    out = (ctypes.c_int * 8)()
+    rc = _lib.load().conv1x1_plan_query(PLAN_KINDS[kind], b, cin, cout, p, cus, out)
+    if rc < 0:
+        raise ValueError("conv1x1_plan_query(%s, %d, %d, %d, %d, %d)" % (kind, b, cin, cout, p, cus))
+    fields = _PLAN_FIELDS[kind == "wgrad"]
+    return dict(zip(fields, out[:len(fields)]), accepted=rc == 0)
+
+
 def _forward(x, w2d, transposed, cin, cout):
     B = x.shape[0]
     P = x.numel() // (B * cin)

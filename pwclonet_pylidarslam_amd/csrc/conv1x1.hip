@@ -566,7 +566,9 @@ __global__ __launch_bounds__(512) void conv1x1_wgrad_reduce_kernel(int n, int np
   if (rg == 0 && e < n) dw[e] = part[0][el];
 }
 
-static int conv_grid_x() {
+// CUs of the current device; cus_override > 0 stands in for it (conv1x1_plan_query: no HIP call then)
+static int conv_grid_x(int cus_override = 0) {
+  if (cus_override > 0) return cus_override;
   static int cus = 0;
   if (cus == 0) {
     int dev = 0;
@@ -582,7 +584,7 @@ struct WgradPlan { int cp, ph, wo, wm, ro, rm, grid; size_t lds; };
 // Split of the 8 waves: `ph` pixel phases when there are fewer than 5 tiles (one tile per worker then), else
 // wo x wm = 8 workers over the (nbo, nbi) tile grid with the fewest operand reads per MFMA; ro in {1,2,4},
 // rm in {1,2,3,4} (the instantiated rectangles).  ro = 0: not covered.
-static WgradPlan wgrad_plan(int b, int cin, int cout, int p) {
+static WgradPlan wgrad_plan(int b, int cin, int cout, int p, int cus = 0) {
   WgradPlan pl;
   const int rows = cin + cout;
   const int nbo = ceil_div(cout, 16), nbi = ceil_div(cin, 16), ntiles = nbo * nbi;
@@ -620,7 +622,7 @@ static WgradPlan wgrad_plan(int b, int cin, int cout, int p) {
   if (pl.ph > 1 && pl.lds < (size_t)pl.ph * tgw * 64 * 16) pl.lds = (size_t)pl.ph * tgw * 64 * 16;
   const long long chunks = (long long)b * ceil_div(p, cp);
   const int per_cu = ((size_t)2 * pl.lds <= (size_t)150 * 1024 && pl.ro * pl.rm <= 2) ? 2 : 1;
-  const long long want = (long long)conv_grid_x() * per_cu;
+  const long long want = (long long)conv_grid_x(cus) * per_cu;
   pl.grid = (int)(chunks < want ? chunks : want);
   return pl;
 }
@@ -666,7 +668,7 @@ using namespace pwclo;
 
 // Launch shape of the forward / input-gradient kernel: gy groups of nbo output blocks, gx persistent tile workers.
 struct ConvGrid { int nbi, nbo, gy; long long gx; size_t lds; };
-static ConvGrid conv_grid(int b, int cin, int cout, int p, bool stats, bool lean = false, bool bwd_sums = false) {
+static ConvGrid conv_grid(int b, int cin, int cout, int p, bool stats, bool lean = false, bool bwd_sums = false, int cus = 0) {
   ConvGrid cg;
   cg.nbi = ceil_div(cin, 16);
   const int nbo_all = ceil_div(cout, 16);
@@ -681,7 +683,7 @@ static ConvGrid conv_grid(int b, int cin, int cout, int p, bool stats, bool lean
     static int split_env = -1;
     if (split_env < 0) { const char *e = getenv("PWCLO_CONV_SPLIT"); split_env = e ? atoi(e) : 1; }
     // (measured: worth it while the launch is under HALF a workgroup per CU; at 192 of 256 the split only adds input re-reads)
-    while (split_env && cg.gy < nbo_all && 2 * one_tile_per_wave * cg.gy <= conv_grid_x()) cg.gy = min(nbo_all, cg.gy * 2);
+    while (split_env && cg.gy < nbo_all && 2 * one_tile_per_wave * cg.gy <= conv_grid_x(cus)) cg.gy = min(nbo_all, cg.gy * 2);
   }
   cg.nbo = ceil_div(nbo_all, cg.gy);
   cg.gy = ceil_div(nbo_all, cg.nbo);
@@ -692,11 +694,25 @@ static ConvGrid conv_grid(int b, int cin, int cout, int p, bool stats, bool lean
   // workgroups a CU can hold (LDS, registers): the short-epilogue kernels without statistics stay under 128 VGPRs at every
   // width (4 waves per SIMD), with statistics up to 4 output blocks, the general epilogue up to 3
   const int per_cu = (cg.lds <= 72 * 1024 && (cg.nbo <= 3 || (lean && !stats) || (stats && cg.nbo <= 4))) ? 2 : 1;
-  cg.gx = (long long)conv_grid_x() * per_cu / cg.gy;
+  cg.gx = (long long)conv_grid_x(cus) * per_cu / cg.gy;
   const long long need = (tiles + CONV_WAVES - 1) / CONV_WAVES;
   if (cg.gx > need) cg.gx = need;
   if (cg.gx < 1) cg.gx = 1;
   return cg;
+}
+
+// Which conv1x1_kernel<NBO, STATS, LEAN> a call runs and on what grid: the launcher and conv1x1_plan_query both ask here.
+// stats: 0 none, 1 batch statistics of y, 2 the BatchNorm-backward sums of an input gradient.
+struct ConvForm { ConvGrid cg; bool lean; int stats; unsigned y_bytes; };
+static ConvForm conv_form(int b, int cin, int cout, int p, bool affine, int pool, int stats, int cus = 0) {
+  ConvForm f;
+  // y through 32-bit offsets where it fits (0: the general epilogue with 64-bit addresses)
+  const long long yb64 = (long long)b * cout * p * 4;
+  f.y_bytes = (pool == 0 && yb64 < (1ll << 32) - 16) ? (unsigned)yb64 : 0u;
+  f.lean = !affine && pool == 0 && f.y_bytes != 0u;
+  f.stats = stats;
+  f.cg = conv_grid(b, cin, cout, p, stats != 0, f.lean, stats == 2, cus);
+  return f;
 }
 
 static void conv1x1_launch(int b, int cin, int cout, int p, const float *x, const float *w, int transposed, float *y,
@@ -711,13 +727,12 @@ static void conv1x1_launch(int b, int cin, int cout, int p, const float *x, cons
                 "conv1x1_forward: pooled rows of k=%d pixels need k in {4,8,16,32} dividing p=%d", pool, p);
   // transposed = 1: w is stored (cin, cout) row-major -- the input-gradient pass of a layer whose weight it is.
   const long long ld_o = transposed ? 1 : cin, ld_i = transposed ? cout : 1;
-  // y through 32-bit offsets where it fits (0: the general epilogue with 64-bit addresses)
-  const long long yb64 = (long long)b * cout * p * 4;
-  const unsigned y_bytes = (pool == 0 && yb64 < (1ll << 32) - 16) ? (unsigned)yb64 : 0u;
-  const bool lean = scale == nullptr && pool == 0 && y_bytes != 0u;
+  const ConvForm form = conv_form(b, cin, cout, p, scale != nullptr, pool, stats == nullptr ? 0 : bx != nullptr ? 2 : 1);
+  const unsigned y_bytes = form.y_bytes;
+  const bool lean = form.lean;
   PWCLO_REQUIRE(stats == nullptr || lean, "conv1x1_forward_bnstats: output of %lld bytes (the statistics epilogue addresses y with "
-                "32-bit byte offsets)", yb64);
-  const ConvGrid cg = conv_grid(b, cin, cout, p, stats != nullptr, lean, bx != nullptr);
+                "32-bit byte offsets)", (long long)b * cout * p * 4);
+  const ConvGrid cg = form.cg;
   const int nbi = cg.nbi, nbo = cg.nbo, gy = cg.gy;
   const size_t lds = cg.lds;
   const long long gx = cg.gx;
@@ -735,7 +750,8 @@ static void conv1x1_launch(int b, int cin, int cout, int p, const float *x, cons
 #define PWCLO_CONV_LAUNCH(N)                                                                                     \
   case N:                                                                                                        \
     if (stats != nullptr && bx != nullptr) {                                                                     \
-      if (N <= 4) { PWCLO_CONV_LAUNCH_S((N <= 4 ? N : 1), 2, true) }                                             \
+      PWCLO_REQUIRE(N <= 4, "conv1x1_dgrad_bnstats: %d output blocks per workgroup, the sums epilogue is built for 1..4", N); \
+      PWCLO_CONV_LAUNCH_S((N <= 4 ? N : 1), 2, true)                                                             \
     }                                                                                                            \
     else if (stats != nullptr) { PWCLO_CONV_LAUNCH_S(N, 1, true) }                                               \
     else if (lean) { PWCLO_CONV_LAUNCH_S(N, 0, true) }                                                           \
@@ -884,4 +900,31 @@ extern "C" void conv1x1_bnrelu_wgrad_kernel_wrapper(int b, int cin, int cout, in
                                                     void *workspace) {
   PWCLO_REQUIRE(in_mean != nullptr && in_invstd != nullptr, "conv1x1_bnrelu_wgrad: in_mean and in_invstd are required%s", "");
   conv1x1_wgrad_launch(b, cin, cout, p, dy, x, dw, workspace, in_mean, in_invstd, in_gamma, in_beta);
+}
+
+// Host-only: the launch plan of the entry point `kind` for (b, cin, cout, p) as that entry point takes them, from the
+// same conv_grid() / wgrad_plan() the launchers call.  cus > 0 stands in for the device's CU count (no HIP call then).
+extern "C" int conv1x1_plan_query(int kind, int b, int cin, int cout, int p, int cus, int *out) {
+  if (out == nullptr || b <= 0 || cin <= 0 || cout <= 0 || p <= 0 || cus < 0) return -1;
+  if (kind == PWCLO_PLAN_WGRAD) {
+    const WgradPlan pl = wgrad_plan(b, cin, cout, p, cus);
+    const int v[7] = {pl.ro, pl.rm, pl.ph, pl.wo, pl.wm, pl.cp, pl.grid};
+    for (int i = 0; i < 7; ++i) out[i] = v[i];
+    return (pl.ro > 0 && pl.lds <= 150 * 1024 &&
+            (long long)(cin + cout) * (pl.cp / 4) <= (long long)WGRAD_MAXV * CONV_THREADS) ? 0 : 1;
+  }
+  ConvForm f;
+  switch (kind) {
+    case PWCLO_PLAN_FORWARD: f = conv_form(b, cin, cout, p, false, 0, 0, cus); break;
+    case PWCLO_PLAN_DGRAD: f = conv_form(b, cout, cin, p, false, 0, 0, cus); break;       // the kernel's output rows are cin
+    case PWCLO_PLAN_STATS: f = conv_form(b, cin, cout, p, false, 0, 1, cus); break;
+    case PWCLO_PLAN_DGRAD_SUMS: f = conv_form(b, cout, cin, p, false, 0, 2, cus); break;
+    case PWCLO_PLAN_AFFINE: f = conv_form(b, cin, cout, p, true, 0, 0, cus); break;
+    case PWCLO_PLAN_POOLED: f = conv_form(b, cin, cout, p, true, 4, 0, cus); break;      // (the row length k does not enter)
+    default: return -1;
+  }
+  const int v[5] = {f.cg.nbo, f.cg.gy, (int)f.cg.gx, f.lean ? 1 : 0, f.stats};
+  for (int i = 0; i < 5; ++i) out[i] = v[i];
+  const bool ok = f.cg.lds <= 154 * 1024 && (f.stats == 0 || f.lean) && (f.stats != 2 || f.cg.nbo <= 4);
+  return ok ? 0 : 1;
 }

@@ -1,7 +1,8 @@
 """Pointwise convolution kernels of the module path (csrc/conv1x1.hip) against a float64
 restatement of torch.nn.functional.conv2d (what P2/pytorch_utils.py:114-167 runs) -- forward, input gradient and
 weight gradient for every (cin, cout) the network's SharedMLPs hold, ragged pixel counts, determinism, and the drop-in
-through the Conv2d building block."""
+through the Conv2d building block.  These shapes are small: nearly all of them run the NBO = 1 instantiation;
+tests/test_gpu_conv_variants.py covers every instantiation the dispatch can select."""
 import numpy as np
 import pytest
 import torch
@@ -41,6 +42,10 @@ def _check(got, ref, what, rel=1e-5):
 
 @pytest.mark.parametrize("cin,cout", NET_SHAPES)
 def test_conv1x1_forward_and_gradients_match_float64(cuda, cin, cout):
+    """Every (cin, cout) of the network, forward and both gradients against float64 -- all of them as NBO = 1: at 3 x 65
+    tiles the few-pixel channel split of conv_grid() gives every workgroup one 16-channel output block.  The wider
+    instantiations (NBO 2..8, the statistics and general epilogues, every weight-gradient rectangle) are reached, and
+    asserted to be reached, by tests/test_gpu_conv_variants.py."""
     g = torch.Generator().manual_seed(cin * 1000 + cout)
     B, P = 3, 2052                                           # 2052 = 32 tiles of 64 + a ragged tail of 4 pixels
     x = torch.randn(B, cin, P, generator=g).to(cuda)
