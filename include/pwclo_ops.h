@@ -621,6 +621,34 @@ void cv_fused_b_h_kernel_wrapper(int b, int s, int k, const float *xyz1, const f
                                  const float *v2, const float *first, const int *idx,
                                  const float *packed_w, float *out, int wfmt, int packed_floats);
 
+/* ---- 4a. in-place refresh of the packed weights (pack_plan.PackPlan) ---------------------
+ * One job per packed layer: everything needed to redo fused.py's fold_conv_bn -> column slice -> row padding -> pack_layer
+ * from the live module tensors.  All pointers are device pointers; the table itself lives in device memory.
+ *   w          conv weight (cout, cin) fp32 row-major; columns [col0, ...) are the ones the layer uses
+ *   conv_bias  (cout) or NULL;  gamma, beta, mean, var (cout): eval-mode BatchNorm, all four NULL without one;  eps: its eps
+ *   phys_map   16 * nbi ints: per physical input channel the column (relative to col0) it reads, or -1 for padding
+ *   dst        the layer inside its packed buffer, 16-byte aligned: nbo * nbi operand tiles of 256 floats (fmt 0), or
+ *              nbo * nbi / 2 tiles of 256 (fmt 2: bf16) / 768 (fmt 1: three bf16 terms) floats, then 16 * nbo fp32 biases
+ *              (the layouts of csrc/mlp_core.hpp; fmt is the format the layer really has: odd nbi is always 0)
+ *   use_bias   0: the biases are written as zeros (hoisted layers whose bias another job carries)
+ *   kmajor     output channel c sits on row 4 * (c % 4) + c / 4 (cout <= 16, nbo == 1)
+ *   tile0      first tile of this job in the launch's grid; the job owns nbo * nbi (fmt 0) or nbo * nbi / 2 tiles + 1
+ * Rows >= cout and padding channels are written as zeros.  W' = W * gamma / sqrt(var + eps) and
+ * b' = (b - mean) * gamma / sqrt(var + eps) + beta in fp64, rounded to fp32 once; bf16 = round to nearest even;
+ * bf16x3 terms hi, mid = bf16(w - hi), lo = bf16((w - hi) - mid) with fp32 differences.  Bit for bit fused.py's result. */
+typedef struct PwcloPackJob {
+  const float *w, *conv_bias, *gamma, *beta, *mean, *var;
+  const int *phys_map;
+  float *dst;
+  double eps;
+  int cout, cin, col0, use_bias;
+  int nbo, nbi, fmt, kmajor;
+  int tile0, reserved;
+} PwcloPackJob;
+/* jobs: DEVICE table of njobs jobs with ascending tile0 (jobs[0].tile0 == 0), total_tiles = the sum of their tiles.  One
+ * launch on the calling thread's stream (pwclo_set_stream), one wave per tile, every destination element written once. */
+void pwclo_pack_layers_kernel_wrapper(const PwcloPackJob *jobs, int njobs, int total_tiles);
+
 /* ---- 4b. module path (training): softmax over K + weighted sum as one pass each way ---------------------------
  * out[r] = sum_k softmax_k(x[r,:]) * v[r,k] for rows = B*C*S contiguous rows of K logits / values (PW/costvolume.py:139-141,
  * 181-183 on (B,C,S,K) tensors); backward recomputes the probabilities: dv = dout p, dx = p dout (v - out).

@@ -124,6 +124,7 @@ SIGNATURES = {
     "cv_fused_a1_h_kernel_wrapper": ([_i] * 4 + [_F] * 7 + [_i] * 3, None),
     "cv_fused_a_lane6_kernel_wrapper": ([_i] * 3 + [_F] * 10 + [_i] * 3, None),
     "cv_fused_b_h_kernel_wrapper": ([_i] * 3 + [_F] * 7 + [_i] * 2, None),
+    "pwclo_pack_layers_kernel_wrapper": ([_F, _i, _i], None),
     "odom_rows_to_transforms_kernel_wrapper": ([_i, _i, _F, _F, _i], None),
     "odom_accumulate_kernel_wrapper": ([_i, _F, _F, _F], None),
     "odom_cumulative_distance_kernel_wrapper": ([_i, _F, _F, _F], None),

@@ -13,7 +13,7 @@ import os
 
 import torch
 
-from . import _lib
+from . import _lib, pack_plan
 
 
 def fold_conv_bn(layer):
@@ -28,7 +28,30 @@ def fold_conv_bn(layer):
         s = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
         w = w * s[:, None]
         b = (b - bn.running_mean.detach().double()) * s + bn.bias.detach().double()
-    return w.float(), b.float()
+    w, b = w.float(), b.float()
+    # provenance for the pack plan (pack_plan.py): (source layer, first column) / (source layer, bias in use).  It rides
+    # on the tensors so that ``pack_layer(*fold_conv_bn(layer), ...)`` keeps its signature; a plain attribute does not
+    # survive a tensor op, so ONLY _cols / _pad_rows / _zeros_like_bias may stand between here and pack_layer in a
+    # constructor -- anything else (.clone(), .contiguous(), a bare slice) loses it and pack_layer raises while a plan is
+    # being recorded (pack_plan._Recorder.add), i.e. in every FusedPWCLONet constructor, on the CPU as well.
+    w._pack_src, b._pack_src = (layer, 0), (layer, True)
+    return w, b
+
+
+def _cols(w, lo, hi=None):
+    """``w[:, lo:hi]`` of a folded weight; the slice keeps its provenance."""
+    out = w[:, lo:hi]
+    src = getattr(w, "_pack_src", None)
+    if src is not None:
+        out._pack_src = (src[0], src[1] + lo)
+    return out
+
+
+def _cat(parts):
+    """``torch.cat(parts).contiguous()`` of packed layers; the pack plan learns where each part went."""
+    out = torch.cat(parts).contiguous()
+    pack_plan.note_cat(parts, out)
+    return out
 
 
 WFMT_F32, WFMT_BF16X3, WFMT_BF16 = 0, 1, 2     # include/pwclo_ops.h: packed-weight format of a stack (csrc/mlp_core.hpp)
@@ -89,6 +112,7 @@ def pack_layer(w, b, phys_map, nbo=None, wfmt=WFMT_F32, kmajor_out=False):
     accumulator register c // 4 -- the "k-step major" order in which the NEXT layer needs only ceil(cout / 4) of its
     four MFMA k-steps (its phys_map must be ``kstep_major_map(cout)``)."""
     cout, _ = w.shape
+    w_src, b_src = w, b
     nbi = len(phys_map) // 16
     assert len(phys_map) == 16 * nbi
     nbo = nbo or (cout + 15) // 16
@@ -118,7 +142,9 @@ def pack_layer(w, b, phys_map, nbo=None, wfmt=WFMT_F32, kmajor_out=False):
             lo = (r1 - mid.float()).to(torch.bfloat16)
             hi = torch.stack((hi, mid, lo), dim=2)                        # (o, mp, split, lane, 8)
         tiles = hi.contiguous().view(torch.int16).reshape(-1).view(torch.float32)
-    return torch.cat((tiles, bias)).contiguous()
+    out = torch.cat((tiles, bias)).contiguous()
+    pack_plan.note_layer(w_src, b_src, phys_map, nbo, layer_wfmt(wfmt, nbi), kmajor_out, out)
+    return out
 
 
 # ---- kernel names for _lib.annotate(kernel=...) ----------------------------------------------------------
@@ -199,7 +225,7 @@ def pack_stack(layers, first_map=None, wfmt=WFMT_F32, cout_prev=None):
         parts.append(pack_layer(w, b, pm, nbo, wfmt))
         widths.append(16 * nbo)
         pm = chain_map(w.shape[0], nbo)
-    return torch.cat(parts).contiguous(), widths
+    return _cat(parts), widths
 
 
 def _p(t):
@@ -451,11 +477,11 @@ class FusedCostVolume:
         wx1, wd = pack_stack(module.mlp_conv_xyz_1, geo)
         w2, wd2 = pack_stack(module.mlp2_convs, list(range(128)), self.wfmt_a2)     # [enc (64) | feat (64)], :133
         assert wd == [64] and wd2 == [128, 64]
-        self.w_a2 = torch.cat((wx1, w2)).contiguous()
+        self.w_a2 = _cat((wx1, w2))
         wx2, _ = pack_stack(module.mlp_conv_xyz_2, geo)
         w3, wd3 = pack_stack(module.mlp3_convs, list(range(128 + c1)))  # [enc2 | feat1 | first], :176
         assert wd3 == [128, 64]
-        self.w_b = torch.cat((wx2, w3)).contiguous()
+        self.w_b = _cat((wx2, w3))
         self.macs_a1 = stack_macs(module.mlp_convs)
         self.macs_a2 = stack_macs(module.mlp_conv_xyz_1) + stack_macs(module.mlp2_convs)
         self.macs_b = stack_macs(module.mlp_conv_xyz_2) + stack_macs(module.mlp3_convs)
@@ -588,7 +614,10 @@ def kstep_major_map(n):
 
 
 def _zeros_like_bias(w):
-    return torch.zeros(w.shape[0], dtype=w.dtype, device=w.device)
+    out = torch.zeros(w.shape[0], dtype=w.dtype, device=w.device)
+    if hasattr(w, "_pack_src"):
+        out._pack_src = (w._pack_src[0], False)      # pack plan: this layer's bias is written as zeros
+    return out
 
 
 class FusedSAHoisted:
@@ -603,9 +632,9 @@ class FusedSAHoisted:
         self.wfmt = default_wfmt()
         if self.c_feat:
             # original order [xyz_diff(3), feat(C)] (pointnet2_modules.py:222)
-            self.pre_job = LinearJob(_pad_rows(w1[:, 3:], 16 * nbo1), _pad_rows(b1, 16 * nbo1),
+            self.pre_job = LinearJob(_pad_rows(_cols(w1, 3), 16 * nbo1), _pad_rows(b1, 16 * nbo1),
                                      out_bf16=self.wfmt == WFMT_BF16)
-            first = pack_layer(w1[:, :3], _zeros_like_bias(w1), kstep_major_map(3), nbo1)
+            first = pack_layer(_cols(w1, 0, 3), _zeros_like_bias(w1), kstep_major_map(3), nbo1)
         else:
             self.pre_job = None
         # level 0 (6 -> 8 -> 8 -> 16): 8-channel layers on 16-wide MFMA blocks.  Producing them k-step major lets the
@@ -618,12 +647,12 @@ class FusedSAHoisted:
             wb2, wb3 = fold_conv_bn(layers[1]), fold_conv_bn(layers[2])
             second = pack_layer(wb2[0], wb2[1], kstep_major_map(w1.shape[0]), 1, kmajor_out=True)
             third = pack_layer(wb3[0], wb3[1], kstep_major_map(w2), (wb3[0].shape[0] + 15) // 16)
-            rest, widths = torch.cat((second, third)), [16, 16 * ((wb3[0].shape[0] + 15) // 16)]
+            rest, widths = _cat((second, third)), [16, 16 * ((wb3[0].shape[0] + 15) // 16)]
         else:
             if not self.c_feat:
                 first = pack_layer(w1, b1, kstep_major_map(6), nbo1)
             rest, widths = pack_stack(layers[1:], wfmt=self.wfmt, cout_prev=w1.shape[0])
-        self.packed = torch.cat((first, rest)).contiguous()
+        self.packed = _cat((first, rest))
         self.widths = [16 * nbo1] + widths
         self.c_out = layers[-1].conv.weight.shape[0]
         self.macs = stack_macs(module.mlp_module) - self.c_feat * w1.shape[0]   # per pixel, after hoisting
@@ -648,7 +677,10 @@ def _pad_rows(t, rows):
     if t.shape[0] == rows:
         return t
     pad = torch.zeros((rows - t.shape[0],) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
-    return torch.cat((t, pad), dim=0)
+    out = torch.cat((t, pad), dim=0)
+    if hasattr(t, "_pack_src"):
+        out._pack_src = t._pack_src
+    return out
 
 
 class FusedUpconvHoisted:
@@ -660,11 +692,11 @@ class FusedUpconvHoisted:
         w1, b1 = fold_conv_bn(layers[0])
         assert w1.shape == (128, 67), "set-upconv kernel is built for 64-channel coarse features"
         self.wfmt = default_wfmt()
-        self.pre_job = LinearJob(w1[:, :64], b1, out_bf16=self.wfmt == WFMT_BF16)   # original order [feat(64), diff(3)], :490
-        first = pack_layer(w1[:, 64:67], _zeros_like_bias(w1), kstep_major_map(3), 8)
+        self.pre_job = LinearJob(_cols(w1, 0, 64), b1, out_bf16=self.wfmt == WFMT_BF16)   # original order [feat(64), diff(3)], :490
+        first = pack_layer(_cols(w1, 64, 67), _zeros_like_bias(w1), kstep_major_map(3), 8)
         rest, widths = pack_stack(layers[1:], wfmt=self.wfmt, cout_prev=128)
         assert widths == [64]
-        self.packed = torch.cat((first, rest)).contiguous()
+        self.packed = _cat((first, rest))
         c2 = list(module.post_mlp)[0].conv.weight.shape[1] - 64
         self.post = FusedPointwise(module.post_mlp, [64, c2])
         self.macs = stack_macs(module.mlp)
@@ -725,25 +757,25 @@ class FusedCostVolumeHoisted:
         geo = list(range(10)) + [-1] * 6
         la = list(module.mlp_convs)
         w1, b1 = fold_conv_bn(la[0])                                   # [geo(10) | feat1 (C) | feat2 (C)]
-        self.job_u = LinearJob(w1[:, 10:10 + c], b1, out_bf16=h16)
-        self.job_v = LinearJob(w1[:, 10 + c:10 + 2 * c], _zeros_like_bias(w1), out_bf16=h16)
-        first = pack_layer(w1[:, :10], _zeros_like_bias(w1), kstep_major_map(10), 8)
+        self.job_u = LinearJob(_cols(w1, 10, 10 + c), b1, out_bf16=h16)
+        self.job_v = LinearJob(_cols(w1, 10 + c, 10 + 2 * c), _zeros_like_bias(w1), out_bf16=h16)
+        first = pack_layer(_cols(w1, 0, 10), _zeros_like_bias(w1), kstep_major_map(10), 8)
         rest, widths = pack_stack(la[1:], wfmt=self.wfmt, cout_prev=128)
         assert widths == [64, 64]
-        self.w_a1 = torch.cat((first, rest)).contiguous()
+        self.w_a1 = _cat((first, rest))
         wx1, wd = pack_stack(module.mlp_conv_xyz_1, geo)
         w2, wd2 = pack_stack(module.mlp2_convs, list(range(128)), self.wfmt_a2)
         assert wd == [64] and wd2 == [128, 64]
-        self.w_a2 = torch.cat((wx1, w2)).contiguous()
+        self.w_a2 = _cat((wx1, w2))
         wx2, _ = pack_stack(module.mlp_conv_xyz_2, kstep_major_map(10))
         lb = list(module.mlp3_convs)
         w3, b3 = fold_conv_bn(lb[0])                                   # [enc2 (64) | feat1 (C) | first (64)]
-        self.job_u2 = LinearJob(w3[:, 64:64 + c], b3, out_bf16=h16)
-        self.job_v2 = LinearJob(w3[:, 64 + c:], _zeros_like_bias(w3), out_bf16=h16)
-        first_b = pack_layer(w3[:, :64], _zeros_like_bias(w3), list(range(64)), 8, self.wfmt)
+        self.job_u2 = LinearJob(_cols(w3, 64, 64 + c), b3, out_bf16=h16)
+        self.job_v2 = LinearJob(_cols(w3, 64 + c), _zeros_like_bias(w3), out_bf16=h16)
+        first_b = pack_layer(_cols(w3, 0, 64), _zeros_like_bias(w3), list(range(64)), 8, self.wfmt)
         rest_b, wdb = pack_stack(lb[1:], wfmt=self.wfmt, cout_prev=128)
         assert wdb == [64]
-        self.w_b = torch.cat((wx2, first_b, rest_b)).contiguous()
+        self.w_b = _cat((wx2, first_b, rest_b))
         self.macs_a1 = stack_macs(module.mlp_convs)
         self.macs_a2 = stack_macs(module.mlp_conv_xyz_1) + stack_macs(module.mlp2_convs)
         self.macs_b = stack_macs(module.mlp_conv_xyz_2) + stack_macs(module.mlp3_convs)
@@ -915,7 +947,8 @@ class FusedPWCLONet:
     """Eval-mode forward of a ``PWCLONet`` on the fused kernels (point-major activations).
 
     Built from (and sharing nothing mutable with) an existing module: weights are folded and
-    packed once; call again after loading a new ``state_dict``.  The siamese pyramid runs both
+    packed once; after the module's weights changed, build again or call ``refresh()``, which redoes the
+    recorded pack plan (``self.plan``, pack_plan.py) in place with one launch.  The siamese pyramid runs both
     frames as one batch, the level-4 FPS of ``flow_feature_encoding`` reuses ``psa_4``'s (same
     cloud, same result: SURVEY.md appendix B) and the two set-upconvs of a level share one
     neighbour search (identical inputs).
@@ -926,8 +959,57 @@ class FusedPWCLONet:
     one pair and frame 1 of the next."""
 
     def __init__(self, net):
-        from .pwclonet import PWCLO_utils as pw
         assert not net.training, "the fused path implements eval-mode semantics"
+        with pack_plan.recording() as rec:        # one job per pack_layer call below (pack_plan.py)
+            self._pack(net)
+        heads = [(self.l4_head, net.pose_calculator_4, "pose_calculator_4")]
+        heads += [(d["head"], m.pose_calculator, "pose_warp_refinement_%d.pose_calculator" % lvl) for d, (lvl, m) in
+                  zip(self.pwr, ((3, net.pose_warp_refinement_3), (2, net.pose_warp_refinement_2),
+                                 (1, net.pose_warp_refinement_1)))]
+        self.plan = pack_plan.PackPlan(rec, net, heads)
+
+    def refresh(self):
+        """Bring the packed weights up to date with the module they were packed from, IN PLACE: one launch of
+        csrc/pack_refresh.hip re-folds and re-packs every layer from the live parameters and BatchNorm buffers into the
+        existing packed buffers -- bit for bit what a new ``FusedPWCLONet`` would hold, while no buffer address and no
+        Python object changes, so captured graphs that read the buffers stay valid.
+
+        Ordering: the launch is ordered on the CURRENT stream.  A forward or graph replay submitted to that stream
+        afterwards sees all new weights, one submitted before sees all old ones; work in flight on OTHER streams
+        (``PipelinedSequence`` / ``StagedPipeline`` slots) must be drained first.  May itself be captured into a graph.
+        The device job table is rewritten only when a source tensor's storage moved (``param.data = ...``); that is a
+        host-to-device copy and raises RuntimeError naming the tensor while a stream is capturing.  The pose heads have
+        no packed copy: they, and graphs captured over them, read the parameters in place, so a pose-head parameter
+        whose storage was swapped raises RuntimeError here, under capture or not (``PWCLONet.refresh_fused`` packs
+        again instead: a new object, which graph holders notice or must be told about)."""
+        self.plan.refresh()
+        return self
+
+    def packed_buffers(self):
+        """{name: tensor} of every packed weight buffer the kernels read (the pose heads read the parameters)."""
+        out = {}
+
+        def add(prefix, obj):
+            if obj is None:
+                return
+            for attr in ("packed", "w_a1", "w_a2", "w_b"):
+                if isinstance(getattr(obj, attr, None), torch.Tensor):
+                    out[prefix + "." + attr] = getattr(obj, attr)
+            for attr in ("pre_job", "post", "job_u", "job_v", "job_u2", "job_v2"):
+                add(prefix + "." + attr, getattr(obj, attr, None))
+
+        for i, m in enumerate(self.sa):
+            add("sa%d" % (i + 1), m)
+        add("cv3", self.cv3)
+        add("ffe", self.ffe)
+        add("l4_pred", self.l4_pred)
+        for lvl, d in zip((3, 2, 1), self.pwr):
+            for key in ("up_f", "up_m", "cv", "pred_f", "pred_m"):
+                add("pwr%d.%s" % (lvl, key), d[key])
+        return out
+
+    def _pack(self, net):
+        from .pwclonet import PWCLO_utils as pw
         import os
         self.branch = os.environ.get("PWCLO_BRANCH", "1") != "0"   # fork/join streams under graph capture
         # hoisted first layers (per-point partial products, csrc/fused_hoisted.hip); 0 = section-3 kernels

@@ -8,7 +8,8 @@ work is scheduled:
     (``..fused.FusedPWCLONet``: BatchNorm folded, activations point-major, 75 launches): the weights are packed on the
     first such call (``config["fused"] = "auto"``, the default -- a user of the reference who only swaps the import gets the
     fast path; ``"off"`` keeps the module graph, ``prepare_fused(dtype=...)`` packs explicitly); ``train()``,
-    ``load_state_dict()`` and ``.to()`` drop the packed weights again, in-place parameter edits re-pack;
+    ``load_state_dict()`` and ``.to()`` drop the packed weights again, in-place parameter edits re-pack
+    (``prepare_fused(persistent=True)``: the copy stays and is refreshed in place, captured graphs survive);
   * ``log_dict`` is the reference's (host tensors, forces a D2H sync, pwclo_net.py:186-193) by
     default -- soft-max and norm computed on the device, their result copied (the reference copies the mask and
     computes on the host: 71 ms per batch of 32); ``log_mode="device"`` keeps the same values on the GPU without a sync and
@@ -127,9 +128,10 @@ class PWCLONet(nn.Module):
                                                          last_pose_estimation=True, **common)
 
         self._fused = None
+        self._fused_persistent = False
 
     # ---- fused eval-mode path ---------------------------------------------------------------------
-    def prepare_fused(self, dtype=None):
+    def prepare_fused(self, dtype=None, persistent=False):
         """Fold BatchNorm and pack the weights for the fused kernels (eval mode only).  ``dtype``: "f32" (default:
         fp32 MFMA, the parity path), "bf16" (BASELINE configs[4]: stack layers on v_mfma_f32_16x16x32_bf16 with weights
         and activations rounded to bf16, fp32 accumulation; coordinates, distances, FPS indices and neighbour lists
@@ -137,14 +139,48 @@ class PWCLONet(nn.Module):
         to the parameters it was made from: ``train()``, ``load_state_dict()``, ``.to()`` / ``.cuda()`` /
         ``.float()`` (anything that goes through ``_apply``) drop it, and an in-place edit of any parameter or
         buffer (optimizer step, ``copy_``) is noticed through the tensors' version counters at the next eager
-        forward, which re-packs."""
+        forward, which re-packs.
+
+        ``persistent=True`` keeps the packed copy across ``train()`` and ``load_state_dict()`` (which copies into the
+        existing parameters, so their storage is stable) and brings it up to date IN PLACE: the next eval-mode no-grad
+        use of the fused path whose version counters differ calls ``refresh_fused()`` (one kernel launch) instead of
+        packing again -- the ``_fused`` object and every packed buffer stay where they are, so captured graphs
+        (``GraphedForward``, ``StreamingOdometry``, ...) keep replaying, with the new weights.  As before, nothing
+        happens while a stream is capturing.  ``_apply`` (``.to()``, ``.float()``, ...) still drops the copy, because
+        the storage moves; a parameter whose storage was swapped (``param.data = ...``, ``load_state_dict(assign=True)``)
+        makes the next use pack again from scratch (a new ``_fused``: graphs are captured again).  A training loop that
+        validates on the fast path every epoch, or an odometry that takes a new checkpoint, wants this.
+
+        Persistence is a property of the LAST call: a later ``prepare_fused()`` without ``persistent=True`` packs again
+        and ends it (``train()`` and ``load_state_dict()`` drop the copy again).  Like every call of this method it puts
+        the module into eval mode."""
         from ..fused import FusedPWCLONet, packing_dtype
+        self._fused_persistent = bool(persistent)
         self.eval()
         if dtype is not None:
             self._fused_dtype = dtype
         with packing_dtype(getattr(self, "_fused_dtype", None)):
             self._fused = FusedPWCLONet(self)
         self._fused_tensors = list(self.parameters()) + list(self.buffers())
+        self._fused_versions = self._state_versions()
+        return self
+
+    def refresh_fused(self):
+        """Bring the packed weights up to date with the parameters and BatchNorm buffers in place.  The packed copy has
+        eval-mode semantics, so this PUTS THE MODULE INTO EVAL MODE (``self.eval()``, as ``prepare_fused`` does): a
+        module that was training is no longer afterwards -- call ``train()`` again to go on training.  Then
+        ``FusedPWCLONet.refresh()`` runs -- one launch on the current stream, no buffer address and no object identity
+        changed, so captured graphs survive -- and the tensors' version counters are recorded.  Ordering: a forward or replay
+        submitted to the current stream afterwards sees all new weights, one submitted before sees all old ones; users
+        of the multi-stream pipelines (``PipelinedSequence``, ``StagedPipeline``) drain their slots first.  Raises when
+        nothing is packed.  A parameter whose storage was swapped makes this a full ``prepare_fused()`` (new object)
+        outside capture and a RuntimeError under capture."""
+        if self._fused is None:
+            raise RuntimeError("refresh_fused: the fused weights are not packed (call prepare_fused() first)")
+        self.eval()
+        if self._fused.plan.moved() and not torch.cuda.is_current_stream_capturing():
+            return self.prepare_fused(persistent=self._fused_persistent)
+        self._fused.refresh()
         self._fused_versions = self._state_versions()
         return self
 
@@ -162,12 +198,16 @@ class PWCLONet(nn.Module):
         return LazyLogDict(inter["mask1"], inter["x11"], self.log_mode == "host")
 
     def train(self, mode=True):
-        if mode:
+        if mode and not self._fused_persistent:
             self._fused = None      # packed weights would go stale
         return super().train(mode)
 
     def load_state_dict(self, *args, **kwargs):
-        self._fused = None
+        # nn.Module.load_state_dict(state_dict, strict=True, assign=False): assign=True swaps the parameters themselves.
+        # Whatever gets past this test, a swapped storage is caught by plan.moved() at the next use (refresh_fused).
+        assign = kwargs["assign"] if "assign" in kwargs else (args[2] if len(args) > 2 else False)
+        if not self._fused_persistent or assign:
+            self._fused = None
         return super().load_state_dict(*args, **kwargs)
 
     def _pyramid(self, xyz_t, points, samples=None):
@@ -201,11 +241,15 @@ class PWCLONet(nn.Module):
         call (``fused="auto"``) and re-packs after an in-place parameter / buffer edit (not while a graph is captured)."""
         if self._fused is None and self.fuse_mode == "auto" and not self.training and not torch.is_grad_enabled() \
                 and x.is_cuda and not torch.cuda.is_current_stream_capturing():
-            self.prepare_fused()        # inference call of a drop-in user: same results within 1e-5, five times the speed
+            # inference call of a drop-in user: same results within 1e-5, five times the speed
+            self.prepare_fused(persistent=self._fused_persistent)
         if self._fused is None or self.training or torch.is_grad_enabled():
             return False
         if not torch.cuda.is_current_stream_capturing() and self._state_versions() != self._fused_versions:
-            self.prepare_fused()            # a parameter / buffer was edited in place since packing
+            if self._fused_persistent:
+                self.refresh_fused()        # in place (packs again by itself if a parameter's storage was swapped)
+            else:
+                self.prepare_fused()        # a parameter / buffer was edited in place since packing
         return True
 
     def forward_sequence(self, frames, num_points=None):
