@@ -438,6 +438,12 @@ void flat_adam_kernel_wrapper(int n, void *const *tensors, const long long *coun
                               const float *bucket, float *exp_avg, float *exp_avg_sq, long long total, long long *step,
                               const double *lr, double *coef, double beta1, double beta2, double eps, double weight_decay,
                               int decoupled);
+/* The same, and skipped (1) i64 in DEVICE memory counts the steps not applied: the one-thread launch adds 1 to it whenever
+ * it finds bucket[total - 1] != 0.  Nothing resets it (flat_pack zeroes the bucket's count, not this). */
+void flat_adam_skipped_kernel_wrapper(int n, void *const *tensors, const long long *counts, const long long *offsets,
+                                      const float *bucket, float *exp_avg, float *exp_avg_sq, long long total,
+                                      long long *step, const double *lr, double *coef, double beta1, double beta2,
+                                      double eps, double weight_decay, int decoupled, long long *skipped);
 
 /* ---- 3b. module-path layers: training-mode BatchNorm, stack tails, pointwise convolution ---- */
 
@@ -455,6 +461,15 @@ void batchnorm_train_forward_kernel_wrapper(int b, int c, int l, const float *x,
                                             const float *beta, float eps, float momentum, float *running_mean,
                                             float *running_var, float *y, float *save_mean, float *save_invstd,
                                             void *workspace, int relu);
+/* The *_devmom siblings of the three entry points that take `float momentum` read it from DEVICE memory instead:
+ * momentum_dev (1) f32, loaded by the one lane per channel that writes running_*, same arithmetic ((1 - (double)m) *
+ * running + (double)m * value, rounded once), so a cell holding m gives the bits the argument m gives.  A launch argument
+ * is baked into a captured graph's kernel node; the cell is re-read by every replay, so a momentum schedule needs no
+ * recapture.  momentum_dev == NULL with running_mean != NULL is a caller error (PWCLO_EINVAL). */
+void batchnorm_train_forward_devmom_kernel_wrapper(int b, int c, int l, const float *x, const float *gamma,
+                                                   const float *beta, float eps, const float *momentum_dev,
+                                                   float *running_mean, float *running_var, float *y, float *save_mean,
+                                                   float *save_invstd, void *workspace, int relu);
 /* dx (b, c, l), dgamma (c), dbeta (c) from dy (the gradient w.r.t. the forward's output) and the saved statistics. */
 void batchnorm_train_backward_kernel_wrapper(int b, int c, int l, const float *x, const float *dy,
                                              const float *gamma, const float *beta, const float *save_mean,
@@ -472,6 +487,12 @@ void batchnorm_train_relu_maxk_forward_kernel_wrapper(int b, int c, int s, int k
                                                       float *running_mean, float *running_var, float *pooled,
                                                       unsigned char *arg, float *xsel, float *save_mean,
                                                       float *save_invstd, void *workspace);
+void batchnorm_train_relu_maxk_forward_devmom_kernel_wrapper(int b, int c, int s, int k, const float *x,
+                                                             const float *gamma, const float *beta, float eps,
+                                                             const float *momentum_dev, float *running_mean,
+                                                             float *running_var, float *pooled, unsigned char *arg,
+                                                             float *xsel, float *save_mean, float *save_invstd,
+                                                             void *workspace);
 /* dx (b, c, s, k), dgamma (c), dbeta (c) from dpool (b, c, s), the gradient w.r.t. pooled: the dense gradient of the
  * activation (dpool at arg where the pooled value was positive, 0 elsewhere) is never written. */
 void batchnorm_train_relu_maxk_backward_kernel_wrapper(int b, int c, int s, int k, const float *x, const float *dpool,
@@ -519,6 +540,11 @@ void conv1x1_forward_bnstats_kernel_wrapper(int b, int cin, int cout, int p, con
                                             const float *in_beta, float *y, float eps, float momentum,
                                             float *running_mean, float *running_var, float *save_mean,
                                             float *save_invstd, void *workspace);
+void conv1x1_forward_bnstats_devmom_kernel_wrapper(int b, int cin, int cout, int p, const float *x, const float *w,
+                                                   const float *in_mean, const float *in_invstd, const float *in_gamma,
+                                                   const float *in_beta, float *y, float eps, const float *momentum_dev,
+                                                   float *running_mean, float *running_var, float *save_mean,
+                                                   float *save_invstd, void *workspace);
 /* Training mode, input gradient through conv <- ReLU <- BatchNorm: da (b, cin, p) = W^T dy -- the gradient w.r.t. the
  * rectified, normalised input of the convolution -- AND dgamma / dbeta (cin) of the BatchNorm in front of it, summed in the
  * convolution's epilogue from da and bn_x (b, cin, p), the BatchNorm's input: the reduction pass of

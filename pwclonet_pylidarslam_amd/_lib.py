@@ -77,12 +77,18 @@ SIGNATURES = {
                                  + [ctypes.c_float, _F, ctypes.c_longlong], None),
     "flat_adam_kernel_wrapper": ([_i, ctypes.POINTER(ctypes.c_void_p)] + [ctypes.POINTER(ctypes.c_longlong)] * 2
                                  + [_F, _F, _F, ctypes.c_longlong, _F, _F, _F] + [ctypes.c_double] * 4 + [_i], None),
+    "flat_adam_skipped_kernel_wrapper": ([_i, ctypes.POINTER(ctypes.c_void_p)] + [ctypes.POINTER(ctypes.c_longlong)] * 2
+                                         + [_F, _F, _F, ctypes.c_longlong, _F, _F, _F] + [ctypes.c_double] * 4 + [_i, _F], None),
     "batchnorm_train_workspace_bytes": ([_i], ctypes.c_longlong),
     "batchnorm_train_forward_kernel_wrapper": ([_i, _i, _i, _F, _F, _F, ctypes.c_float, ctypes.c_float, _F, _F, _F, _F,
                                                 _F, _F, _i], None),
+    "batchnorm_train_forward_devmom_kernel_wrapper": ([_i, _i, _i, _F, _F, _F, ctypes.c_float, _F, _F, _F, _F, _F, _F, _F,
+                                                       _i], None),
     "batchnorm_train_backward_kernel_wrapper": ([_i, _i, _i] + [_F] * 10 + [_i], None),
     "batchnorm_train_relu_maxk_forward_kernel_wrapper": ([_i, _i, _i, _i, _F, _F, _F, ctypes.c_float, ctypes.c_float]
                                                          + [_F] * 8, None),
+    "batchnorm_train_relu_maxk_forward_devmom_kernel_wrapper": ([_i, _i, _i, _i, _F, _F, _F, ctypes.c_float, _F] + [_F] * 8,
+                                                                None),
     "batchnorm_train_relu_maxk_backward_kernel_wrapper": ([_i, _i, _i, _i] + [_F] * 12, None),
     "conv1x1_forward_kernel_wrapper": ([_i, _i, _i, _i, _F, _F, _i, _F], None),
     "conv1x1_affine_forward_kernel_wrapper": ([_i, _i, _i, _i, _F, _F, _F, _F, _i, _F], None),
@@ -94,6 +100,7 @@ SIGNATURES = {
     "conv1x1_dgrad_bnstats_kernel_wrapper": ([_i, _i, _i, _i] + [_F] * 11, None),
     "batchnorm_train_backward_apply_kernel_wrapper": ([_i, _i, _i] + [_F] * 9 + [_i], None),
     "conv1x1_forward_bnstats_kernel_wrapper": ([_i, _i, _i, _i] + [_F] * 7 + [ctypes.c_float, ctypes.c_float] + [_F] * 5, None),
+    "conv1x1_forward_bnstats_devmom_kernel_wrapper": ([_i, _i, _i, _i] + [_F] * 7 + [ctypes.c_float, _F] + [_F] * 5, None),
     "batchnorm_train_apply_kernel_wrapper": ([_i, _i, _i] + [_F] * 6 + [_i], None),
     "batchnorm_train_relu_maxk_apply_kernel_wrapper": ([_i, _i, _i, _i] + [_F] * 8, None),
     "conv1x1_wgrad_kernel_wrapper": ([_i, _i, _i, _i, _F, _F, _F, _F], None),

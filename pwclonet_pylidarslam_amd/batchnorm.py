@@ -48,6 +48,73 @@ def count_batch(bn):
         _pending[id(t)] = (t, (ent[1] if ent else 0) + 1)
 
 
+CELL_ATTR = "_pwclo_bn_momentum"      # plain attribute (no buffer, no parameter: ``state_dict()`` does not see it)
+
+
+class BNMomentumCell:
+    """The BatchNorm momentum of a model as ONE fp32 value in device memory.  A launch argument is
+    baked into a captured graph's kernel nodes; while a cell is attached (``pytorch_utils.attach_bn_momentum``) the
+    training kernels read the momentum from ``tensor`` instead, so a replay follows ``set()``.  ``value`` is the host
+    copy; every module's ``.momentum`` is kept equal to it and the call sites refuse a module whose ``.momentum`` was
+    assigned behind the cell's back."""
+
+    def __init__(self, model, modules, momentum, device):
+        self.model, self.modules = model, list(modules)
+        self.value = float(momentum)
+        self.tensor = torch.full((1,), self.value, dtype=torch.float32, device=device)
+        self._hooks = [m.register_forward_pre_hook(self._torch_path) for m in self.modules]
+        for m in [model] + self.modules:
+            object.__setattr__(m, CELL_ATTR, self)
+
+    def set(self, momentum):
+        """Every module's ``.momentum`` and the device value (a fill on the current stream: no host synchronisation)."""
+        self.value = float(momentum)
+        for m in self.modules:
+            m.momentum = self.value
+        self.tensor.fill_(self.value)
+
+    def detach(self):
+        """Remove every trace from the model: the launch-argument path of a model that never had a cell."""
+        for h in self._hooks:
+            h.remove()
+        self._hooks = []
+        for m in [self.model] + self.modules:
+            m.__dict__.pop(CELL_ATTR, None)
+
+    def check(self, bn, device):
+        if self.tensor.device != device:
+            raise RuntimeError("BatchNorm momentum cell lives on %s, the input on %s (attach the cell after moving the "
+                               "model)" % (self.tensor.device, device))
+        if bn.momentum != self.value:
+            raise RuntimeError("BatchNorm momentum %r was assigned behind the attached cell (which holds %r): use "
+                               "cell.set() or BNMomentumScheduler.step()" % (bn.momentum, self.value))
+
+    @staticmethod
+    def _torch_path(bn, args):
+        # torch's own forward (PWCLO_HIP_BN=0, a shape ``supported()`` rejects, ...) takes the momentum as a host float
+        # that a capture bakes in: the very thing the cell exists to avoid
+        if bn.training and args and args[0].is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("a BatchNorm with a momentum cell reached torch's batch_norm inside a graph capture: that "
+                               "path cannot read the momentum from device memory, replays would keep the capture's value")
+
+
+def momentum_of(bn, x):
+    """``bn.momentum`` as the training kernels take it: the float, or -- checked against ``x`` and the module -- the
+    attached ``BNMomentumCell``."""
+    cell = bn.__dict__.get(CELL_ATTR)
+    if cell is None:
+        return bn.momentum
+    cell.check(bn, x.device)
+    return cell
+
+
+def _momentum_entry(name, momentum):
+    """(entry point, argument) of a launch that takes the momentum: the ``_devmom`` sibling with the cell's pointer."""
+    if isinstance(momentum, BNMomentumCell):
+        return name.replace("_kernel_wrapper", "_devmom_kernel_wrapper"), momentum.tensor.data_ptr()
+    return name, float(momentum)
+
+
 def _touch(*tensors):
     """The kernels update running_mean / running_var through raw pointers: bump their version counters so that
     anything keyed on them (conv1x1._folded) sees the write."""
@@ -79,8 +146,9 @@ class _BatchNormTrain(Function):
             save_mean = torch.empty((C,), dtype=torch.float32, device=x.device)
             save_invstd = torch.empty((C,), dtype=torch.float32, device=x.device)
             ws = _workspace(C, x.device)
-            _lib.call("batchnorm_train_forward_kernel_wrapper", x.device, B, C, L, p(x), p(weight), p(bias), float(eps),
-                      float(momentum), p(running_mean), p(running_var), p(y), p(save_mean), p(save_invstd), p(ws), int(relu))
+            name, mom = _momentum_entry("batchnorm_train_forward_kernel_wrapper", momentum)
+            _lib.call(name, x.device, B, C, L, p(x), p(weight), p(bias), float(eps), mom, p(running_mean), p(running_var),
+                      p(y), p(save_mean), p(save_invstd), p(ws), int(relu))
         ctx.save_for_backward(x, weight, bias, save_mean, save_invstd)
         ctx.relu = bool(relu)
         return y
@@ -117,10 +185,11 @@ def batch_norm_train(x, bn, relu=False, stats=None):
     already updated the running statistics and the counter): only the apply pass runs."""
     if stats is not None:
         return _BatchNormTrain.apply(x, bn.weight, bn.bias, None, None, bn.momentum, bn.eps, relu, stats[0], stats[1])
+    momentum = momentum_of(bn, x)
     count_batch(bn)
     rm = bn.running_mean if bn.track_running_stats else None
     rv = bn.running_var if bn.track_running_stats else None
-    y = _BatchNormTrain.apply(x, bn.weight, bn.bias, rm, rv, bn.momentum, bn.eps, relu)
+    y = _BatchNormTrain.apply(x, bn.weight, bn.bias, rm, rv, momentum, bn.eps, relu)
     _touch(rm, rv)
     return y
 
@@ -146,9 +215,9 @@ class _BatchNormReluMaxK(Function):
             save_mean = torch.empty((C,), dtype=torch.float32, device=x.device)
             save_invstd = torch.empty((C,), dtype=torch.float32, device=x.device)
             ws = _workspace(C, x.device)
-            _lib.call("batchnorm_train_relu_maxk_forward_kernel_wrapper", x.device, B, C, S, K, p(x), p(weight), p(bias),
-                      float(eps), float(momentum), p(running_mean), p(running_var), p(pooled), p(arg), p(xsel),
-                      p(save_mean), p(save_invstd), p(ws))
+            name, mom = _momentum_entry("batchnorm_train_relu_maxk_forward_kernel_wrapper", momentum)
+            _lib.call(name, x.device, B, C, S, K, p(x), p(weight), p(bias), float(eps), mom, p(running_mean),
+                      p(running_var), p(pooled), p(arg), p(xsel), p(save_mean), p(save_invstd), p(ws))
         ctx.save_for_backward(x, weight, bias, save_mean, save_invstd, arg, xsel)
         return pooled
 
@@ -178,9 +247,10 @@ def batch_norm_train_relu_max(x, bn, stats=None):
     pooled pass, nothing of shape (B, C, S, K) written.  ``stats``: see ``batch_norm_train``."""
     if stats is not None:
         return _BatchNormReluMaxK.apply(x, bn.weight, bn.bias, None, None, bn.momentum, bn.eps, stats[0], stats[1])
+    momentum = momentum_of(bn, x)
     count_batch(bn)
     rm = bn.running_mean if bn.track_running_stats else None
     rv = bn.running_var if bn.track_running_stats else None
-    y = _BatchNormReluMaxK.apply(x, bn.weight, bn.bias, rm, rv, bn.momentum, bn.eps)
+    y = _BatchNormReluMaxK.apply(x, bn.weight, bn.bias, rm, rv, momentum, bn.eps)
     _touch(rm, rv)
     return y

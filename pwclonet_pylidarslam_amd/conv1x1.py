@@ -155,8 +155,10 @@ def _forward_stats(x, w, cin, cout, in_tf, rm, rv, momentum, eps):
     ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=x.device)
     p = lambda t: t.data_ptr() if t is not None else 0
     tf = in_tf if in_tf is not None else (None, None, None, None)
-    _lib.call("conv1x1_forward_bnstats_kernel_wrapper", x.device, B, cin, cout, P, p(x), p(w), p(tf[0]), p(tf[1]), p(tf[2]),
-              p(tf[3]), p(y), float(eps), float(momentum), p(rm), p(rv), p(mean), p(invstd), p(ws))
+    from . import batchnorm as hb
+    name, mom = hb._momentum_entry("conv1x1_forward_bnstats_kernel_wrapper", momentum)
+    _lib.call(name, x.device, B, cin, cout, P, p(x), p(w), p(tf[0]), p(tf[1]), p(tf[2]), p(tf[3]), p(y), float(eps), mom,
+              p(rm), p(rv), p(mean), p(invstd), p(ws))
     return y, mean, invstd
 
 
@@ -196,9 +198,10 @@ def conv1x1_stats(x, conv, bn):
     """``conv(x)`` plus the batch statistics of the result for the training-mode module ``bn`` that follows ``conv`` in
     its block: -> (y, (mean, invstd)); ``bn``'s running statistics and counter are updated as ``bn(y)`` would."""
     from . import batchnorm as hb
+    momentum = hb.momentum_of(bn, x)
     hb.count_batch(bn)
     rm, rv = _bn_buffers(bn)
-    y, mean, invstd = _Conv1x1Stats.apply(x, conv.weight, rm, rv, bn.momentum, bn.eps)
+    y, mean, invstd = _Conv1x1Stats.apply(x, conv.weight, rm, rv, momentum, bn.eps)
     touch_running_stats(rm, rv)
     return y, (mean, invstd)
 
@@ -286,8 +289,9 @@ class _BNReluConv(Function):
             mean = torch.empty((cin,), dtype=torch.float32, device=x.device)
             invstd = torch.empty((cin,), dtype=torch.float32, device=x.device)
             ws = hb._workspace(cin, x.device)
-            _lib.call("batchnorm_train_forward_kernel_wrapper", x.device, B, cin, P, p(x), p(gamma), p(beta), float(eps),
-                      float(momentum), p(running_mean), p(running_var), 0, p(mean), p(invstd), p(ws), 1)
+            name, mom = hb._momentum_entry("batchnorm_train_forward_kernel_wrapper", momentum)
+            _lib.call(name, x.device, B, cin, P, p(x), p(gamma), p(beta), float(eps), mom, p(running_mean),
+                      p(running_var), 0, p(mean), p(invstd), p(ws), 1)
         ctx.save_for_backward(x, gamma, beta, mean, invstd, weight)
         if out_stats is not None:
             y, mean_y, invstd_y = _forward_stats(x, w, cin, cout, (mean, invstd, gamma, beta), *out_stats)
@@ -350,6 +354,8 @@ def bn_relu_conv(x, bn, conv, stats=None, next_bn=None):
     this function with ``next_bn``; the running statistics were updated there).  ``next_bn``: the training-mode BatchNorm
     that follows ``conv``; the result is then (y, (mean_y, invstd_y)) and ``next_bn``'s buffers are updated."""
     from . import batchnorm as hb
+    momentum = hb.momentum_of(bn, x) if stats is None else bn.momentum        # (with stats given it is not used)
+    next_momentum = hb.momentum_of(next_bn, x) if next_bn is not None else None
     if stats is None:
         hb.count_batch(bn)
         rm, rv = _bn_buffers(bn)
@@ -360,8 +366,8 @@ def bn_relu_conv(x, bn, conv, stats=None, next_bn=None):
     if next_bn is not None:
         hb.count_batch(next_bn)
         nrm, nrv = _bn_buffers(next_bn)
-        out_stats = (nrm, nrv, next_bn.momentum, next_bn.eps)
-    out = _BNReluConv.apply(x, bn.weight, bn.bias, rm, rv, bn.momentum, bn.eps, conv.weight, given[0], given[1], out_stats)
+        out_stats = (nrm, nrv, next_momentum, next_bn.eps)
+    out = _BNReluConv.apply(x, bn.weight, bn.bias, rm, rv, momentum, bn.eps, conv.weight, given[0], given[1], out_stats)
     touch_running_stats(rm, rv)
     if next_bn is not None:
         touch_running_stats(nrm, nrv)

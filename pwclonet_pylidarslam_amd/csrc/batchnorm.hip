@@ -119,7 +119,10 @@ __device__ __forceinline__ void bn_fold(const double *__restrict__ partial, int 
   s1 = bn_wave_sum(s1);
 }
 
+// momentum_dev (nullable): the momentum in device memory -- a captured graph then follows a schedule (the argument is
+// baked into the graph's kernel node); only the lane that writes the running statistics reads it.
 __global__ __launch_bounds__(256) void bn_forward_finish_kernel(int C, int nsplit, long long M, float eps, float momentum,
+                                                                const float *__restrict__ momentum_dev,
                                                                 const double *__restrict__ partial,
                                                                 float *__restrict__ running_mean,
                                                                 float *__restrict__ running_var,
@@ -137,6 +140,7 @@ __global__ __launch_bounds__(256) void bn_forward_finish_kernel(int C, int nspli
   save_invstd[ch] = (float)(1.0 / sqrt(var + (double)eps));
   if (running_mean != nullptr) {
     const double unbiased = M > 1 ? var * (double)M / (double)(M - 1) : var;
+    if (momentum_dev != nullptr) momentum = *momentum_dev;
     running_mean[ch] = (float)((1.0 - (double)momentum) * (double)running_mean[ch] + (double)momentum * mean);
     running_var[ch] = (float)((1.0 - (double)momentum) * (double)running_var[ch] + (double)momentum * unbiased);
   }
@@ -297,10 +301,11 @@ static int bn_splits(int c, long long M, long long *per_split) {
 }
 
 // for conv1x1.hip: the statistics of a convolution's output from the partial sums its epilogue left
-void bn_forward_finish_launch(int c, int nsplit, long long M, float eps, float momentum, const double *partial,
-                              float *running_mean, float *running_var, float *save_mean, float *save_invstd) {
+void bn_forward_finish_launch(int c, int nsplit, long long M, float eps, float momentum, const float *momentum_dev,
+                              const double *partial, float *running_mean, float *running_var, float *save_mean,
+                              float *save_invstd) {
   hipLaunchKernelGGL(bn_forward_finish_kernel, dim3(ceil_div(c, 4)), dim3(256), 0, current_stream(), c, nsplit, M, eps,
-                     momentum, partial, running_mean, running_var, save_mean, save_invstd);
+                     momentum, momentum_dev, partial, running_mean, running_var, save_mean, save_invstd);
   check_launch("bn_forward_finish");
 }
 
@@ -330,11 +335,10 @@ static void bn_launch_apply(bool vec, int b, int c, int l, float inv_m, const fl
                        st, c, l, inv_m, x, dy, gamma, beta, mean, invstd, dgamma, dbeta, out);
 }
 
-extern "C" void batchnorm_train_forward_kernel_wrapper(int b, int c, int l, const float *x, const float *gamma,
-                                                       const float *beta, float eps, float momentum,
-                                                       float *running_mean, float *running_var, float *y,
-                                                       float *save_mean, float *save_invstd, void *workspace,
-                                                       int relu) {
+// momentum_dev != nullptr: the *_devmom entry point (momentum read from device memory, the argument unused)
+static void bn_train_forward(int b, int c, int l, const float *x, const float *gamma, const float *beta, float eps,
+                             float momentum, const float *momentum_dev, float *running_mean, float *running_var, float *y,
+                             float *save_mean, float *save_invstd, void *workspace, int relu) {
   if (b <= 0 || c <= 0 || l <= 0) return;
   PWCLO_REQUIRE(b <= 65535 && c <= 65535, "batchnorm_train_forward: b=%d c=%d exceed the grid limits", b, c);
   PWCLO_REQUIRE((running_mean == nullptr) == (running_var == nullptr),
@@ -352,13 +356,33 @@ extern "C" void batchnorm_train_forward_kernel_wrapper(int b, int c, int l, cons
   hipLaunchKernelGGL((bn_partial_kernel<0, false>), dim3(nsplit, c), dim3(BN_THREADS), 0, st, c, l, M, per_split, x,
                      none, none, none, none, none, partial);
   hipLaunchKernelGGL(bn_forward_finish_kernel, dim3(ceil_div(c, 4)), dim3(256), 0, st, c, nsplit, M, eps, momentum,
-                     partial, running_mean, running_var, save_mean, save_invstd);
+                     momentum_dev, partial, running_mean, running_var, save_mean, save_invstd);
   if (stats_only) {
   } else if (relu)
     bn_launch_apply<0, true>(vec, b, c, l, 0.f, x, none, gamma, beta, save_mean, save_invstd, none, none, y, st);
   else
     bn_launch_apply<0, false>(vec, b, c, l, 0.f, x, none, gamma, beta, save_mean, save_invstd, none, none, y, st);
   check_launch("batchnorm_train_forward");
+}
+
+extern "C" void batchnorm_train_forward_kernel_wrapper(int b, int c, int l, const float *x, const float *gamma,
+                                                       const float *beta, float eps, float momentum,
+                                                       float *running_mean, float *running_var, float *y,
+                                                       float *save_mean, float *save_invstd, void *workspace,
+                                                       int relu) {
+  bn_train_forward(b, c, l, x, gamma, beta, eps, momentum, nullptr, running_mean, running_var, y, save_mean, save_invstd,
+                   workspace, relu);
+}
+
+extern "C" void batchnorm_train_forward_devmom_kernel_wrapper(int b, int c, int l, const float *x, const float *gamma,
+                                                              const float *beta, float eps, const float *momentum_dev,
+                                                              float *running_mean, float *running_var, float *y,
+                                                              float *save_mean, float *save_invstd, void *workspace,
+                                                              int relu) {
+  PWCLO_REQUIRE(momentum_dev != nullptr || running_mean == nullptr,
+                "batchnorm_train_forward_devmom: momentum_dev is required with running statistics%s", "");
+  bn_train_forward(b, c, l, x, gamma, beta, eps, 0.f, momentum_dev, running_mean, running_var, y, save_mean, save_invstd,
+                   workspace, relu);
 }
 
 extern "C" void batchnorm_train_backward_kernel_wrapper(int b, int c, int l, const float *x, const float *dy,
@@ -441,12 +465,10 @@ extern "C" void batchnorm_train_backward_apply_kernel_wrapper(int b, int c, int 
     default: CALL(32); break;           \
   }
 
-extern "C" void batchnorm_train_relu_maxk_forward_kernel_wrapper(int b, int c, int s, int k, const float *x,
-                                                                 const float *gamma, const float *beta, float eps,
-                                                                 float momentum, float *running_mean,
-                                                                 float *running_var, float *pooled,
-                                                                 unsigned char *arg, float *xsel, float *save_mean,
-                                                                 float *save_invstd, void *workspace) {
+static void bn_train_relu_maxk_forward(int b, int c, int s, int k, const float *x, const float *gamma, const float *beta,
+                                       float eps, float momentum, const float *momentum_dev, float *running_mean,
+                                       float *running_var, float *pooled, unsigned char *arg, float *xsel, float *save_mean,
+                                       float *save_invstd, void *workspace) {
   if (b <= 0 || c <= 0 || s <= 0) return;
   PWCLO_REQUIRE(k == 4 || k == 8 || k == 16 || k == 32, "batchnorm_train_relu_maxk_forward: k=%d not in {4,8,16,32}", k);
   PWCLO_REQUIRE(b <= 65535 && c <= 65535, "batchnorm_train_relu_maxk_forward: b=%d c=%d exceed the grid limits", b, c);
@@ -463,7 +485,7 @@ extern "C" void batchnorm_train_relu_maxk_forward_kernel_wrapper(int b, int c, i
   hipLaunchKernelGGL((bn_partial_kernel<0, false>), dim3(nsplit, c), dim3(BN_THREADS), 0, st, c, l, M, per_split, x,
                      none, none, none, none, none, partial);
   hipLaunchKernelGGL(bn_forward_finish_kernel, dim3(ceil_div(c, 4)), dim3(256), 0, st, c, nsplit, M, eps, momentum,
-                     partial, running_mean, running_var, save_mean, save_invstd);
+                     momentum_dev, partial, running_mean, running_var, save_mean, save_invstd);
   const dim3 grid(ceil_div(l / 4, BN_THREADS), c, b);
 #define PWCLO_CALL(KK)                                                                                              \
   hipLaunchKernelGGL((bn_apply_relu_maxk_kernel<KK>), grid, dim3(BN_THREADS), 0, st, c, s, x, gamma, beta, save_mean, \
@@ -471,6 +493,28 @@ extern "C" void batchnorm_train_relu_maxk_forward_kernel_wrapper(int b, int c, i
   PWCLO_BN_MAXK_DISPATCH(k, PWCLO_CALL)
 #undef PWCLO_CALL
   check_launch("batchnorm_train_relu_maxk_forward");
+}
+
+extern "C" void batchnorm_train_relu_maxk_forward_kernel_wrapper(int b, int c, int s, int k, const float *x,
+                                                                 const float *gamma, const float *beta, float eps,
+                                                                 float momentum, float *running_mean,
+                                                                 float *running_var, float *pooled,
+                                                                 unsigned char *arg, float *xsel, float *save_mean,
+                                                                 float *save_invstd, void *workspace) {
+  bn_train_relu_maxk_forward(b, c, s, k, x, gamma, beta, eps, momentum, nullptr, running_mean, running_var, pooled, arg,
+                             xsel, save_mean, save_invstd, workspace);
+}
+
+extern "C" void batchnorm_train_relu_maxk_forward_devmom_kernel_wrapper(int b, int c, int s, int k, const float *x,
+                                                                        const float *gamma, const float *beta, float eps,
+                                                                        const float *momentum_dev, float *running_mean,
+                                                                        float *running_var, float *pooled,
+                                                                        unsigned char *arg, float *xsel, float *save_mean,
+                                                                        float *save_invstd, void *workspace) {
+  PWCLO_REQUIRE(momentum_dev != nullptr || running_mean == nullptr,
+                "batchnorm_train_relu_maxk_forward_devmom: momentum_dev is required with running statistics%s", "");
+  bn_train_relu_maxk_forward(b, c, s, k, x, gamma, beta, eps, 0.f, momentum_dev, running_mean, running_var, pooled, arg,
+                             xsel, save_mean, save_invstd, workspace);
 }
 
 // The pooled pass alone, with GIVEN batch statistics (see batchnorm_train_apply_kernel_wrapper).

@@ -799,11 +799,10 @@ extern "C" long long conv1x1_stats_workspace_bytes(int b, int cin, int cout, int
   return (long long)cout * cg.gx * 2 * (long long)sizeof(double);
 }
 
-extern "C" void conv1x1_forward_bnstats_kernel_wrapper(int b, int cin, int cout, int p, const float *x, const float *w,
-                                                       const float *in_mean, const float *in_invstd,
-                                                       const float *in_gamma, const float *in_beta, float *y, float eps,
-                                                       float momentum, float *running_mean, float *running_var,
-                                                       float *save_mean, float *save_invstd, void *workspace) {
+static void conv1x1_forward_bnstats(int b, int cin, int cout, int p, const float *x, const float *w, const float *in_mean,
+                                    const float *in_invstd, const float *in_gamma, const float *in_beta, float *y, float eps,
+                                    float momentum, const float *momentum_dev, float *running_mean, float *running_var,
+                                    float *save_mean, float *save_invstd, void *workspace) {
   if (b <= 0 || cin <= 0 || cout <= 0 || p <= 0) return;
   PWCLO_REQUIRE(workspace != nullptr && save_mean != nullptr && save_invstd != nullptr,
                 "conv1x1_forward_bnstats: workspace, save_mean and save_invstd are required%s", "");
@@ -813,8 +812,30 @@ extern "C" void conv1x1_forward_bnstats_kernel_wrapper(int b, int cin, int cout,
   PWCLO_REQUIRE(cg.lds <= 154 * 1024, "conv1x1_forward_bnstats: cin=%d cout=%d need %zu bytes of LDS", cin, cout, cg.lds);
   double *partial = reinterpret_cast<double *>(workspace);
   conv1x1_launch(b, cin, cout, p, x, w, 0, y, nullptr, nullptr, 0, 0, in_mean, in_invstd, in_gamma, in_beta, partial);
-  bn_forward_finish_launch(cout, (int)cg.gx, (long long)b * p, eps, momentum, partial, running_mean, running_var, save_mean,
-                           save_invstd);
+  bn_forward_finish_launch(cout, (int)cg.gx, (long long)b * p, eps, momentum, momentum_dev, partial, running_mean, running_var,
+                           save_mean, save_invstd);
+}
+
+extern "C" void conv1x1_forward_bnstats_kernel_wrapper(int b, int cin, int cout, int p, const float *x, const float *w,
+                                                       const float *in_mean, const float *in_invstd,
+                                                       const float *in_gamma, const float *in_beta, float *y, float eps,
+                                                       float momentum, float *running_mean, float *running_var,
+                                                       float *save_mean, float *save_invstd, void *workspace) {
+  conv1x1_forward_bnstats(b, cin, cout, p, x, w, in_mean, in_invstd, in_gamma, in_beta, y, eps, momentum, nullptr, running_mean,
+                          running_var, save_mean, save_invstd, workspace);
+}
+
+// The same with the momentum read from device memory (see batchnorm_train_forward_devmom_kernel_wrapper).
+extern "C" void conv1x1_forward_bnstats_devmom_kernel_wrapper(int b, int cin, int cout, int p, const float *x, const float *w,
+                                                              const float *in_mean, const float *in_invstd,
+                                                              const float *in_gamma, const float *in_beta, float *y,
+                                                              float eps, const float *momentum_dev, float *running_mean,
+                                                              float *running_var, float *save_mean, float *save_invstd,
+                                                              void *workspace) {
+  PWCLO_REQUIRE(momentum_dev != nullptr || running_mean == nullptr,
+                "conv1x1_forward_bnstats_devmom: momentum_dev is required with running statistics%s", "");
+  conv1x1_forward_bnstats(b, cin, cout, p, x, w, in_mean, in_invstd, in_gamma, in_beta, y, eps, 0.f, momentum_dev, running_mean,
+                          running_var, save_mean, save_invstd, workspace);
 }
 
 // Input gradient of a layer that follows a training-mode BatchNorm (+ ReLU): da = W^T dy (w stored (cout, cin) like the

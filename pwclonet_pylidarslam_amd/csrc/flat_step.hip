@@ -67,11 +67,14 @@ __global__ __launch_bounds__(FLAT_THREADS) void flat_pack_kernel(FlatTable tab, 
 
 // One thread, BEFORE the update launches: the only writer of the counter and of coef, which those launches only read.
 // coef = {apply (1 / 0), lr / (1 - beta1^t), sqrt(1 - beta2^t), lr}.
+// skipped (nullable): the cumulative count of steps not applied, which no pack resets.
 __global__ void flat_adam_head_kernel(const float *__restrict__ slot, long long *__restrict__ step,
-                                      const double *__restrict__ lr, double *__restrict__ coef, double beta1, double beta2) {
+                                      const double *__restrict__ lr, double *__restrict__ coef, double beta1, double beta2,
+                                      long long *__restrict__ skipped) {
   if (threadIdx.x != 0) return;
   if (!(*slot == 0.0f)) {                                // non-finite gradients somewhere: this step is not applied
     coef[0] = 0.0;
+    if (skipped != nullptr) *skipped = *skipped + 1;
     return;
   }
   const long long t = *step + 1;
@@ -207,10 +210,9 @@ extern "C" void flat_pack_kernel_wrapper(int n, void *const *tensors, const long
   check_launch("flat_pack");
 }
 
-extern "C" void flat_adam_kernel_wrapper(int n, void *const *tensors, const long long *counts, const long long *offsets,
-                                         const float *bucket, float *exp_avg, float *exp_avg_sq, long long total,
-                                         long long *step, const double *lr, double *coef, double beta1, double beta2,
-                                         double eps, double weight_decay, int decoupled) {
+static void flat_adam(int n, void *const *tensors, const long long *counts, const long long *offsets, const float *bucket,
+                      float *exp_avg, float *exp_avg_sq, long long total, long long *step, const double *lr, double *coef,
+                      double beta1, double beta2, double eps, double weight_decay, int decoupled, long long *skipped) {
   FLAT_COMMON_CHECKS("flat_adam");
   PWCLO_REQUIRE(exp_avg != nullptr && exp_avg_sq != nullptr && (reinterpret_cast<uintptr_t>(exp_avg) & 15u) == 0u &&
                 (reinterpret_cast<uintptr_t>(exp_avg_sq) & 15u) == 0u,
@@ -224,7 +226,7 @@ extern "C" void flat_adam_kernel_wrapper(int n, void *const *tensors, const long
   unsigned max_span[FLAT_MAX_TENSORS / FLAT_ENTRIES] = {};
   if (!flat_tables("flat_adam", n, tensors, counts, offsets, total, tabs, max_span)) return;
   hipLaunchKernelGGL(flat_adam_head_kernel, dim3(1), dim3(64), 0, current_stream(), bucket + (total - 1), step, lr, coef,
-                     beta1, beta2);
+                     beta1, beta2, skipped);
   for (int l = 0; l < launches; ++l) {
     const int entries = n - l * FLAT_ENTRIES < FLAT_ENTRIES ? n - l * FLAT_ENTRIES : FLAT_ENTRIES;
     const dim3 grid = flat_grid(max_span[l], entries);
@@ -236,4 +238,22 @@ extern "C" void flat_adam_kernel_wrapper(int n, void *const *tensors, const long
                          exp_avg_sq, coef, beta1, beta2, eps, weight_decay);
   }
   check_launch("flat_adam");
+}
+
+extern "C" void flat_adam_kernel_wrapper(int n, void *const *tensors, const long long *counts, const long long *offsets,
+                                         const float *bucket, float *exp_avg, float *exp_avg_sq, long long total,
+                                         long long *step, const double *lr, double *coef, double beta1, double beta2,
+                                         double eps, double weight_decay, int decoupled) {
+  flat_adam(n, tensors, counts, offsets, bucket, exp_avg, exp_avg_sq, total, step, lr, coef, beta1, beta2, eps, weight_decay,
+            decoupled, nullptr);
+}
+
+extern "C" void flat_adam_skipped_kernel_wrapper(int n, void *const *tensors, const long long *counts,
+                                                 const long long *offsets, const float *bucket, float *exp_avg,
+                                                 float *exp_avg_sq, long long total, long long *step, const double *lr,
+                                                 double *coef, double beta1, double beta2, double eps, double weight_decay,
+                                                 int decoupled, long long *skipped) {
+  PWCLO_REQUIRE(skipped != nullptr, "flat_adam_skipped: skipped is required%s", "");
+  flat_adam(n, tensors, counts, offsets, bucket, exp_avg, exp_avg_sq, total, step, lr, coef, beta1, beta2, eps, weight_decay,
+            decoupled, skipped);
 }

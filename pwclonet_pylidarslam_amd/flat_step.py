@@ -50,9 +50,10 @@ class FlatAdam:
 
     Owns the flat gradient ``bucket`` (``total`` fp32 values, the last one the count of non-finite gradient values of
     the last ``pack`` -- ``nonfinite`` is a view of it), the two moment buffers at the same offsets, and the device
-    scalars ``step_count`` (int64) and ``lr`` (float64).  The parameters are neither re-pointed nor copied: the model
-    and its ``state_dict`` stay as they are.  ``step()`` applies nothing -- parameters, moments and counter keep their
-    bits -- while the count is not zero (the reference raises on a NaN loss; a replayed graph cannot)."""
+    scalars ``step_count`` (int64), ``skipped`` (int64) and ``lr`` (float64).  The parameters are neither re-pointed nor
+    copied: the model and its ``state_dict`` stay as they are.  ``step()`` applies nothing -- parameters, moments and
+    counter keep their bits -- while the count is not zero (the reference raises on a NaN loss; a replayed graph cannot)
+    and adds 1 to ``skipped``, which no ``pack()`` resets: read it once after an epoch of replays."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=False):
         self.params = [p for p in params if p.requires_grad]
@@ -78,6 +79,7 @@ class FlatAdam:
         self.exp_avg_sq = torch.zeros_like(self.bucket)
         self.nonfinite = self.bucket[self.total - 1:]
         self.step_count = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.skipped = torch.zeros(1, dtype=torch.int64, device=dev)
         self.lr = torch.full((1,), float(lr), dtype=torch.float64, device=dev)
         self._lr_host = float(lr)
         self._coef = torch.zeros(4, dtype=torch.float64, device=dev)
@@ -108,10 +110,10 @@ class FlatAdam:
 
     def step(self):
         """One Adam update of every parameter from the bucket (skipped as a whole while ``nonfinite`` is not zero)."""
-        _lib.call("flat_adam_kernel_wrapper", self.device, len(self.params), self._param_ptrs, self._counts, self._offsets,
-                  self.bucket.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.total,
+        _lib.call("flat_adam_skipped_kernel_wrapper", self.device, len(self.params), self._param_ptrs, self._counts,
+                  self._offsets, self.bucket.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.total,
                   self.step_count.data_ptr(), self.lr.data_ptr(), self._coef.data_ptr(), self.betas[0], self.betas[1],
-                  self.eps, self.weight_decay, int(self.decoupled))
+                  self.eps, self.weight_decay, int(self.decoupled), self.skipped.data_ptr())
 
     def set_lr(self, lr):
         """Write the device scalar the kernel reads: a schedule needs no recapture."""
@@ -133,7 +135,8 @@ class FlatAdam:
 
     def state_dict(self):
         """``torch.optim.Adam.state_dict()``'s layout: per-parameter ``step`` / ``exp_avg`` / ``exp_avg_sq`` and one
-        parameter group; ``torch.optim.Adam(...).load_state_dict`` accepts it."""
+        parameter group; ``torch.optim.Adam(...).load_state_dict`` accepts it (and carries the group's extra
+        ``flat_skipped`` entry, the cumulative skipped-step count, along without reading it)."""
         step = int(self.step_count.item())
         state = {}
         if step > 0:
@@ -143,7 +146,8 @@ class FlatAdam:
                             "exp_avg_sq": self.view(self.exp_avg_sq, i).clone()}
         group = {"lr": self._lr_host, "betas": self.betas, "eps": self.eps, "weight_decay": self.weight_decay,
                  "amsgrad": False, "maximize": False, "foreach": None, "capturable": False, "differentiable": False,
-                 "fused": None, "decoupled_weight_decay": self.decoupled, "params": list(range(len(self.params)))}
+                 "fused": None, "decoupled_weight_decay": self.decoupled, "flat_skipped": int(self.skipped.item()),
+                 "params": list(range(len(self.params)))}
         return {"state": state, "param_groups": [group]}
 
     def load_state_dict(self, sd):
@@ -182,6 +186,7 @@ class FlatAdam:
         if len(steps) > 1:
             raise ValueError("FlatAdam keeps ONE step counter; the checkpoint's parameters are at steps %s" % sorted(steps))
         self.step_count.fill_(steps.pop() if steps else 0)
+        self.skipped.fill_(int(g0.get("flat_skipped", 0)))         # (torch's own checkpoints have no such entry)
 
 
 class FlatTrainStep:

@@ -292,8 +292,37 @@ def set_bn_momentum_default(bn_momentum):
     return fn
 
 
+BNMomentumCell = _hip_bn.BNMomentumCell
+_BN_TYPES = (nn.BatchNorm1d, nn.BatchNorm2d, nn.BatchNorm3d)
+
+
+def _common_momentum(modules):
+    values = {m.momentum for m in modules}
+    if len(values) != 1 or None in values:
+        raise ValueError("a BatchNorm momentum cell holds ONE value; the model's BatchNorm layers have momentum %s"
+                         % sorted(values, key=repr))
+    return values.pop()
+
+
+def attach_bn_momentum(model):
+    """Make the BatchNorm momentum of ``model`` a device value that captured training steps follow (DESIGN.md section
+    17): one fp32 element on the model's device, initialised from the layers' common ``momentum`` (``ValueError`` when
+    they differ or one is ``None``) and recorded as a plain attribute on the model and on every BatchNorm below it --
+    ``state_dict()`` is unchanged.  Returns the ``BNMomentumCell``: ``set(m)``, ``value``, ``detach()``."""
+    if getattr(model, _hip_bn.CELL_ATTR, None) is not None:
+        raise RuntimeError("the model already has a BatchNorm momentum cell (detach() it first)")
+    modules = [m for m in model.modules() if isinstance(m, _BN_TYPES)]
+    if not modules:
+        raise ValueError("attach_bn_momentum: the model has no BatchNorm layer")
+    if any(m.__dict__.get(_hip_bn.CELL_ATTR) is not None for m in modules):
+        raise RuntimeError("a BatchNorm layer of the model already belongs to another momentum cell")
+    tensors = list(model.parameters()) + list(model.buffers())
+    return BNMomentumCell(model, modules, _common_momentum(modules), tensors[0].device)
+
+
 class BNMomentumScheduler(object):
-    """pytorch_utils.py:319-349."""
+    """pytorch_utils.py:319-349.  When the model carries a ``BNMomentumCell``, ``step`` also brings the cell to the value
+    the setter wrote."""
 
     def __init__(self, model, bn_lambda, last_epoch=-1, setter=set_bn_momentum_default):
         if not isinstance(model, nn.Module):
@@ -311,3 +340,6 @@ class BNMomentumScheduler(object):
         self.last_epoch = epoch
         self.last_momentum = self.lmbd(epoch)
         self.model.apply(self.setter(self.lmbd(epoch)))
+        cell = getattr(self.model, _hip_bn.CELL_ATTR, None)
+        if cell is not None:
+            cell.set(_common_momentum(cell.modules))

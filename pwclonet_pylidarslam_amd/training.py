@@ -169,6 +169,65 @@ class TrainStep:
         return loss
 
 
+class EpochSchedule:
+    """The reference trainer's two per-epoch schedules (slam/training/trainer.py:469-482) tied to the device values a
+    captured step reads: the learning rate (``FlatAdam.lr`` / a tensor ``lr`` of a capturable torch optimizer) and the
+    BatchNorm momentum (``pytorch_utils.attach_bn_momentum``), DESIGN.md section 17.
+
+    ``lr_scheduler_factory(opt) -> LRScheduler`` is called with a private one-parameter ``torch.optim.SGD`` whose ``lr``
+    is ``optimizer``'s current learning rate, so any torch scheduler class constructs and steps on it unchanged
+    (``FlatAdam`` is not a ``torch.optim.Optimizer``).  ``bn_scheduler``: a ``pytorch_utils.BNMomentumScheduler``.
+
+    ``epoch_end()`` steps the learning-rate scheduler and pushes ``get_last_lr()[0]`` into ``optimizer`` -- every
+    group's ``lr`` of a torch optimizer, filled in place where it is a tensor -- then steps the BatchNorm scheduler with
+    ``epoch``, the number of epochs finished: the epoch the value is used for.  (The reference passes the 0-based index
+    of the epoch just finished, so its momentum trails its own lambda by one epoch; shift the lambda to reproduce that.)"""
+
+    def __init__(self, optimizer, lr_scheduler_factory=None, bn_scheduler=None):
+        self.opt, self.bn_scheduler = optimizer, bn_scheduler
+        self.epoch = 0
+        self.lr_scheduler = self._proxy = None
+        if lr_scheduler_factory is not None:
+            lr = optimizer._lr_host if isinstance(optimizer, FlatAdam) else float(optimizer.param_groups[0]["lr"])
+            self._proxy = torch.optim.SGD([nn.Parameter(torch.zeros(1))], lr=lr)
+            self.lr_scheduler = lr_scheduler_factory(self._proxy)
+
+    def _push(self):
+        if self.lr_scheduler is not None:
+            lr = float(self.lr_scheduler.get_last_lr()[0])
+            if isinstance(self.opt, FlatAdam):
+                self.opt.set_lr(lr)
+            else:
+                for g in self.opt.param_groups:
+                    if torch.is_tensor(g["lr"]):
+                        g["lr"].fill_(lr)
+                    else:
+                        g["lr"] = lr
+
+    def epoch_end(self):
+        self.epoch += 1
+        if self.lr_scheduler is not None:
+            self._proxy.step()                   # (nothing to update; torch warns when a scheduler steps first)
+            self.lr_scheduler.step()
+            self._push()
+        if self.bn_scheduler is not None:
+            self.bn_scheduler.step(self.epoch)
+
+    def state_dict(self):
+        return {"epoch": self.epoch,
+                "lr_scheduler": self.lr_scheduler.state_dict() if self.lr_scheduler is not None else None}
+
+    def load_state_dict(self, sd):
+        """Resume: the epoch and the learning-rate scheduler's state; both values go to the device again."""
+        self.epoch = int(sd["epoch"])
+        if self.lr_scheduler is not None:
+            self.lr_scheduler.load_state_dict(sd["lr_scheduler"])
+            self._proxy.param_groups[0]["lr"] = self.lr_scheduler.get_last_lr()[0]      # the recursive forms start from it
+            self._push()
+        if self.bn_scheduler is not None:
+            self.bn_scheduler.step(self.epoch)
+
+
 class DropoutStream:
     """Replayable dropout for the four pose heads: while attached, a training-mode
     ``PWCLONet.forward`` on the GPU advances the step counter with one launch and every ``PoseCalculator`` in ``train()``

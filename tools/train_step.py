@@ -5,6 +5,7 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 tools/train_step.py --gpus N
     python tools/train_step.py --flat --graph [--gpus N]
     python tools/train_step.py --graph --fused-adam --dropout-stream [SEED]
+    python tools/train_step.py --flat --graph --bn-cell --epochs 3 --steps-per-epoch 10
 
 One process per GPU; the reference-shaped module graph in TRAIN mode (BatchNorm batch statistics,
 dropout; torch conv/BN autograd + the HIP gather/group forward and backward kernels), the
@@ -25,9 +26,17 @@ import torch  # noqa: E402
 import bench  # noqa: E402
 from pwclonet_pylidarslam_amd import dist_util  # noqa: E402
 from pwclonet_pylidarslam_amd.loss import PWCLONetLossModule  # noqa: E402
+from pwclonet_pylidarslam_amd.pointnet2_ops.pytorch_utils import BNMomentumScheduler, attach_bn_momentum  # noqa: E402
 from pwclonet_pylidarslam_amd.pwclonet import PWCLONet  # noqa: E402
-from pwclonet_pylidarslam_amd.training import (DropoutStream, FlatAdam, FlatTrainStep, PWCLONetWithLoss, TrainStep,  # noqa: E402
-                                               ddp_wrap, gradient_bucket_values)
+from pwclonet_pylidarslam_amd.training import (DropoutStream, EpochSchedule, FlatAdam, FlatTrainStep, PWCLONetWithLoss,  # noqa: E402
+                                               TrainStep, ddp_wrap, gradient_bucket_values)
+
+
+def _momentum(model):
+    """The BatchNorm layers' common momentum."""
+    values = {m.momentum for m in model.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm)}
+    assert len(values) == 1, values
+    return values.pop()
 
 
 def main():
@@ -52,6 +61,14 @@ def main():
     ap.add_argument("--dropout-stream", type=int, nargs="?", const=0, default=None, metavar="SEED",
                     help="training.DropoutStream(net, seed=SEED, rank=rank): replayable dropout masks and the pose heads as "
                          "hand-written kernels (without it the heads call F.dropout: torch's stream)")
+    ap.add_argument("--bn-cell", action="store_true",
+                    help="pytorch_utils.attach_bn_momentum before the step is built: the training kernels read the BatchNorm "
+                         "momentum from device memory, so replays follow the momentum schedule")
+    ap.add_argument("--epochs", type=int, default=0,
+                    help="with --steps-per-epoch K: time E blocks of K steps with training.EpochSchedule.epoch_end() between "
+                         "them (the reference's BatchNorm momentum lambda stepping every epoch, MultiStepLR(milestones=[1, 2], gamma=0.5)) "
+                         "instead of --steps steps")
+    ap.add_argument("--steps-per-epoch", type=int, default=10)
     a = ap.parse_args()
     if a.gpus > 1 and not dist_util.launched_by_torchrun():      # supervise N fresh ranks; no GPU call made here
         sys.exit(dist_util.spawn_ranks(os.path.abspath(__file__), sys.argv[1:], a.gpus))
@@ -70,6 +87,7 @@ def main():
     # learnable weights -- with the network alone under DDP the replicas' loss weights drift
     unit = PWCLONetWithLoss(net, loss_mod)
     stream = DropoutStream(net, seed=a.dropout_stream, rank=rank) if a.dropout_stream is not None else None
+    cell = attach_bn_momentum(unit) if a.bn_cell else None
     group = None
     if a.flat:
         assert not (a.fused_adam or a.sample_ahead), "--flat brings its own Adam kernel; not combined with --fused-adam / --sample-ahead"
@@ -84,6 +102,15 @@ def main():
     else:
         model = ddp_wrap(unit, dev) if world > 1 else unit
         opt = torch.optim.Adam(unit.parameters(), lr=1e-4, capturable=a.graph, fused=True if a.fused_adam else None)
+    schedule = None
+    if a.epochs:
+        assert not a.graph or (a.flat and a.bn_cell), \
+            "--epochs with --graph needs --flat (a device learning rate) and --bn-cell (a device momentum): replays ignore the rest"
+        from torch.optim.lr_scheduler import MultiStepLR
+        # the reference's lambda (train.py:322; init 0.5, rate 0.5, max 0.99) with a decay step of ONE epoch: a short run moves
+        bn_sched = BNMomentumScheduler(unit, lambda it: min(1 - 0.5 * 0.5 ** int(it / 1), 0.99))
+        schedule = EpochSchedule(opt, lambda o: MultiStepLR(o, milestones=[1, 2], gamma=0.5), bn_sched)
+        a.steps = a.epochs * a.steps_per_epoch
     x1, x2 = bench.make_batch(a.batch, a.npoints, 2000 + rank, dev)
     g = torch.Generator().manual_seed(3 + rank)
     gt = torch.randn(a.batch, 7, generator=g) * 0.1
@@ -119,7 +146,9 @@ def main():
     losses = [step().item() for _ in range(a.warmup)]
     dist_util.fence(dev)
     t0 = time.perf_counter()
-    for _ in range(a.steps):
+    for k in range(a.steps):
+        if schedule is not None and k and k % a.steps_per_epoch == 0:
+            schedule.epoch_end()
         loss = step()
     dist_util.fence(dev)
     dt = dist_util.max_over_ranks(time.perf_counter() - t0, dev)
@@ -136,6 +165,9 @@ def main():
                           "dropout": ("DropoutStream(seed=%d): counter-based masks, HIP pose heads, next step %d"
                                       % (a.dropout_stream, stream.step_index())) if stream is not None else "F.dropout",
                           "loss_first_last": [losses[0], losses[-1]],
+                          "skipped": int(opt.skipped.item()) if a.flat else None,
+                          "bn_momentum": _momentum(unit), "bn_cell": cell is not None,
+                          "epoch_ends": schedule.epoch if schedule is not None else 0,
                           "collective": ("eager all-reduce of the flat bucket (%d fp32 values: %d gradients, padding, the "
                                          "non-finite count), world size %d" % (opt.total, gradient_bucket_values(unit), world))
                           if group is not None else
