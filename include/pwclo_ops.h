@@ -148,6 +148,10 @@ void knn_point_kernel_wrapper(int b, int n, int s, int nsample, const float *xyz
  * `workspace` may be NULL; also used when s < 256, where the build does not amortise).
  * Bit-identical output to knn_point_kernel_wrapper. */
 long long knn_point_workspace_bytes(int b, int n);
+/* The workspace's two cloud-major sections, rows then boxes: out[0..3] = (rows offset, rows bytes per cloud, boxes
+ * offset, boxes bytes per cloud), so that rows offset + b * rows bytes = boxes offset and boxes offset + b * boxes bytes =
+ * knn_point_workspace_bytes(b, n).  Returns 1; 0 with out all zero where there is no workspace (exhaustive kernel). */
+int knn_point_workspace_sections(int b, int n, long long *out);
 /* The two passes of the pruned search separately, so that ONE build of a cloud's search structure serves several
  * searches and the slab-pruned sampler below: workspace of knn_point_build_bytes(b, n) bytes (64 <= n <= 16384);
  * slab_tab (optional, b*32 ints): (padded first row, row count) of the cloud's knn_point_slabs(n) <= 16 x-slabs. */
@@ -732,6 +736,27 @@ void odom_accumulate_kernel_wrapper(int nseq, const int *seq_start, const double
  * rows unused): rel[0, i] = abs_out[0, i] = I and *count = 1.  k >= capacity: nothing written, *overflow = 1. */
 void odom_stream_append_kernel_wrapper(int S, int capacity, int prime, const float *rows, int row_stride, double *rel,
                                        double *abs_out, int *count, int *overflow);
+/* Streaming odometry with per-stream dropouts and restarts.  All pointers DEVICE memory.
+ * One workgroup, one thread per stream (S <= 1024).  active / restart: S ints, this call's masks.  pose: (S,4,7) fp32
+ * contiguous, rows [tx ty tz qw qx qy qz].  Persistent: have_prev / count / valid (S ints each), rel / abs_out
+ * (capacity, S, 4, 4) fp64, overflow (one int).  Per stream: idle (!active): valid = 0 and nothing else; prime (active
+ * and (restart or !have_prev)): rel[0,s] = abs_out[0,s] = I, count = 1, have_prev = 1, valid = 0; pair (otherwise):
+ * k = count, rel[k,s] = the transform of the level-1 row, abs_out[k,s] = abs_out[k-1,s] . rel[k,s], count = k + 1,
+ * valid = 1 (k == capacity: nothing written to the trajectories, *overflow = 1).  Streams that are not pair get the
+ * identity pose (0,0,0, 1,0,0,0) in their four rows of `pose`. */
+void stream_append_masked_kernel_wrapper(int S, int capacity, const int *active, const int *restart, float *pose,
+                                         double *rel, double *abs_out, int *have_prev, int *count, int *valid,
+                                         int *overflow);
+/* One launch that copies, for every stream s with active[s] != 0 (S ints, DEVICE), bytes[i] bytes from
+ * src[i] + s * src_stride[i] to dst[i] + s * dst_stride[i] for each of nseg <= stream_handover_max_segments() segments;
+ * inactive streams' bytes are not touched.  dst / src / bytes / strides: HOST arrays of nseg entries (device addresses
+ * in dst / src); the strides may be NULL (= bytes: densely packed streams).  The table travels to the kernel by value, so
+ * a captured graph holds it without host memory.  Addresses, sizes and strides must be multiples of 4; segments where
+ * all are multiples of 16 move 16 bytes per lane. */
+int stream_handover_max_segments(void);
+void stream_handover_masked_kernel_wrapper(int nseg, void *const *dst, const void *const *src, const long long *bytes,
+                                           const long long *dst_stride, const long long *src_stride, int S,
+                                           const int *active);
 /* dist[f] = sum_{i<=f} |p[i] - p[i-1]| (dist[first] = 0) from the translations of `poses`. */
 void odom_cumulative_distance_kernel_wrapper(int nseq, const int *seq_start, const double *poses, double *dist);
 /* One slot per (sequence, first frame in 0,step,2*step.., segment length): slot_start (nseq+1 ints, DEVICE) with

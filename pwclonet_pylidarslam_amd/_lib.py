@@ -39,6 +39,7 @@ SIGNATURES = {
     "three_interpolate_grad_kernel_wrapper": ([_i, _i, _i, _i, _F, _F, _F, _F], None),
     "knn_point_kernel_wrapper": ([_i, _i, _i, _i, _F, _F, _F, _F], None),
     "knn_point_workspace_bytes": ([_i, _i], ctypes.c_longlong),
+    "knn_point_workspace_sections": ([_i, _i, ctypes.POINTER(ctypes.c_longlong)], _i),
     "knn_point_ws_kernel_wrapper": ([_i, _i, _i, _i, _F, _F, _F, _F, _F], None),
     "knn_point_build_bytes": ([_i, _i], ctypes.c_longlong),
     "knn_point_slabs": ([_i], _i),
@@ -136,6 +137,10 @@ SIGNATURES = {
     "odom_accumulate_kernel_wrapper": ([_i, _F, _F, _F], None),
     "odom_cumulative_distance_kernel_wrapper": ([_i, _F, _F, _F], None),
     "odom_stream_append_kernel_wrapper": ([_i, _i, _i, _F, _i, _F, _F, _F, _F], None),
+    "stream_append_masked_kernel_wrapper": ([_i, _i] + [_F] * 9, None),
+    "stream_handover_max_segments": ([], _i),
+    "stream_handover_masked_kernel_wrapper": ([_i] + [ctypes.POINTER(ctypes.c_void_p)] * 2
+                                              + [ctypes.POINTER(ctypes.c_longlong)] * 3 + [_i, _F], None),
     "odom_sequence_errors_kernel_wrapper": ([_i, _i] + [_F] * 5 + [_i, _i] + [_F] * 3, None),
 }
 

@@ -796,6 +796,21 @@ extern "C" long long knn_point_workspace_bytes(int b, int n) {
   return (long long)b * nblk * (64 * 16 + 32);
 }
 
+// The two cloud-major sections of that workspace (knn_build_launch below lays them out): rows[b][nblk * 64] float4, then
+// boxes[b][nblk] of 32 bytes -> out = (rows offset, rows bytes per cloud, boxes offset, boxes bytes per cloud).  A
+// caller that moves single clouds of a kept structure (stream_handover_masked_kernel) asks here and never restates
+// the layout.  Returns 0 and zeros where knn_point_workspace_bytes(b, n) is 0 (exhaustive kernel: no workspace).
+extern "C" int knn_point_workspace_sections(int b, int n, long long *out) {
+  if (out == nullptr) return 0;
+  out[0] = out[1] = out[2] = out[3] = 0;
+  if (b <= 0 || knn_point_workspace_bytes(b, n) == 0) return 0;
+  const long long nblk = (n + 63) / 64 + knn_slabs(n);
+  out[1] = nblk * 64 * (long long)sizeof(float4);
+  out[2] = (long long)b * out[1];
+  out[3] = nblk * 2 * (long long)sizeof(float4);
+  return 1;
+}
+
 // Build pass alone: sorted rows + block boxes into `workspace` (knn_point_workspace_bytes(b, n) bytes) and, when
 // slab_tab != NULL, 32 ints per cloud: (padded first row, row count) of up to 16 x-slabs.
 static bool knn_build_launch(int b, int n, const float *xyz, void *workspace, int *slab_tab) {

@@ -9,6 +9,7 @@ BatchNorm folded into the 1x1 convolution) and ``phys`` maps the kernel's physic
 channel order (16-channel blocks, one source per block) to the layer's original input channels.
 """
 import contextlib
+import ctypes
 import os
 
 import torch
@@ -941,6 +942,54 @@ class FrameState:
         for d, s_ in zip(dst, srcs):
             d.copy_(s_)
         return self
+
+    def frame1_segments(self, dst_state):
+        """What ``copy_frame1_`` moves from this state into ``dst_state``, cut so that every piece is cloud-major:
+        a list of ``(dst_ptr, src_ptr, bytes_per_stream)`` over ``frame1_tensors()``, each kept search structure as
+        its two sections (sorted rows, block boxes; ``knn_point_workspace_sections`` knows where they lie)."""
+        clouds = self.x[0].shape[0]
+        kept = [self.built[lvl] for lvl in self.FRAME1_BUILT if lvl in self.built]
+        srcs, dsts = self.frame1_tensors(), dst_state.frame1_tensors()
+        assert len(srcs) == len(dsts)
+        first_ws = len(self.x) + len(self.f) + 1
+        segs = []
+        for i, (s_, d) in enumerate(zip(srcs, dsts)):
+            assert s_.is_contiguous() and d.is_contiguous() and s_.dtype == d.dtype and s_.shape == d.shape
+            if first_ws <= i < first_ws + len(kept):
+                _, b, n = kept[i - first_ws]
+                out = (ctypes.c_longlong * 4)()
+                assert b == clouds and _lib.load().knn_point_workspace_sections(b, n, out) == 1
+                assert out[2] + b * out[3] == s_.numel() * s_.element_size()
+                segs += [(d.data_ptr() + out[0], s_.data_ptr() + out[0], int(out[1])),
+                         (d.data_ptr() + out[2], s_.data_ptr() + out[2], int(out[3]))]
+            else:
+                nbytes = s_.numel() * s_.element_size()
+                assert s_.shape[0] == clouds and nbytes % clouds == 0
+                segs.append((d.data_ptr(), s_.data_ptr(), nbytes // clouds))
+        return segs
+
+    def copy_frame1_masked_(self, src, active):
+        """``copy_frame1_`` for the clouds s with ``active[s] != 0`` only (int32 (C,) on the device, read there): one
+        launch of ``stream_handover_masked_kernel`` over ``src.frame1_segments(self)``; the other clouds of this state
+        keep every byte."""
+        masked_copy(src.frame1_segments(self), active)
+        return self
+
+
+def masked_copy(segments, active, dst_strides=None, src_strides=None):
+    """One ``stream_handover_masked_kernel`` launch on the current stream: for every stream s with ``active[s] != 0``
+    copy each segment ``(dst_ptr, src_ptr, bytes_per_stream)``'s bytes of stream s.  Strides default to the byte count."""
+    n = len(segments)
+    if n > _lib.load().stream_handover_max_segments():
+        raise ValueError("masked_copy: %d segments exceed the kernel's table of %d"
+                         % (n, _lib.load().stream_handover_max_segments()))
+    assert active.dtype == torch.int32 and active.is_contiguous()
+    ptrs, lls = ctypes.c_void_p * n, ctypes.c_longlong * n
+    _lib.annotate(family="handover", bytes=2.0 * active.numel() * sum(s[2] for s in segments))
+    _lib.call("stream_handover_masked_kernel_wrapper", active.device, n, ptrs(*[s[0] for s in segments]),
+              ptrs(*[s[1] for s in segments]), lls(*[s[2] for s in segments]),
+              lls(*dst_strides) if dst_strides is not None else None,
+              lls(*src_strides) if src_strides is not None else None, int(active.numel()), _p(active))
 
 
 class FusedPWCLONet:

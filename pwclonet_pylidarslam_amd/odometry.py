@@ -10,6 +10,10 @@ Every step appends its level-1 poses to trajectories kept on the device (``odom_
 ``relative_poses()[k]`` = quat2mat of pair (k-1, k)'s row (``evaluation.rows_to_transforms``, not inverted),
 ``trajectory()[k]`` = their product (``evaluation.compute_absolute_poses``), row 0 the identity in both.
 
+``per_stream=True`` lifts the lock step: every call says which streams delivered a frame and which
+of those start a new sequence; a state machine on the device keeps one frame counter per stream and the handover moves
+only the streams that advanced, all inside one captured graph.
+
 ``PWCLONetOdometry`` mirrors the reference's ``PoseNetOdometry`` / ``OdometryAlgorithm`` interface for one stream
 (``init``, ``process_next_frame``, ``get_relative_poses``, ...); Hydra / OmegaConf configs stay out of scope.
 """
@@ -44,9 +48,28 @@ class StreamingOdometry:
     ``[:lengths[s]]``, and runs filter + compaction + exact sampling to ``num_points`` (default 8192) inside the same
     prime / step graphs: one capture of each serves every length.  The clouds are bit for bit
     those of ``preprocess.frames_to_clouds(sweep[None, :length], num_points, dataset, cap=capacity)``;
-    ``survivor_counts()`` tells a caller which streams kept fewer than ``num_points`` points."""
+    ``survivor_counts()`` tells a caller which streams kept fewer than ``num_points`` points.
 
-    def __init__(self, net, streams=1, num_points=None, max_frames=4096, graph=True, warmup=1, sweeps=None):
+    Per-stream mode (``per_stream=True``): ``step(frames, active=None, restart=None)`` and ``step_sweeps(sweeps, lengths,
+    active=None, restart=None)`` take two (S,) masks, bool or integer, host sequences or device tensors (device tensors
+    are read on the device, without a sync); ``None`` = all active, none restarting.  ``active[s]``: stream s delivered a
+    frame in this call (the rows of the other streams are ignored; raw mode: their lengths too, though they must be
+    well-formed); ``restart[s]``: that frame starts a new sequence.  Every call returns the static (S, 4, 7) pose, never
+    ``None``: a stream's first delivered frame primes that stream alone, and rows that are no real pair (idle or primed
+    streams; ``valid()`` tells) hold the identity pose (0,0,0, 1,0,0,0).  A stream that skips calls is paired, when it
+    comes back, with the last frame it delivered.  ``frame_counts()``: frames per stream; ``relative_poses(stream=i)`` /
+    ``trajectory(stream=i)``: (count_i, 4, 4) of one stream (they read one counter from the device, which may sync);
+    without ``stream=`` they raise here, because the streams differ in length.  ``reset(streams=...)`` restarts some
+    streams on their next delivered frame.  ``max_frames`` bounds the number of CALLS since the last full ``reset()``:
+    the host cannot know the per-stream counts without a sync, and calls >= every count.  One captured graph per input
+    shape serves priming, pairs and idling alike: masks, counters and trajectories are device memory that the graph reads.
+    Cost: the graph has one shape, so an idle stream costs what an active one does (its row is recomputed from the frame
+    it delivered last and discarded); what is gained is correctness under dropouts and restarts with no new capture.  The
+    first call (and the first call of every new input shape) needs at least one active stream: idle streams' input rows
+    start as copies of the first active stream's, so that no step ever reads an uninitialised buffer."""
+
+    def __init__(self, net, streams=1, num_points=None, max_frames=4096, graph=True, warmup=1, sweeps=None,
+                 per_stream=False):
         if not 1 <= int(streams) <= MAX_STREAMS:
             raise ValueError("StreamingOdometry: streams=%d outside [1, %d]" % (int(streams), MAX_STREAMS))
         if int(max_frames) < 1:
@@ -63,6 +86,10 @@ class StreamingOdometry:
         self._fused_id = None
         self._rel = self._abs = self._count = self._overflow = None
         self.handover_bytes = 0     # bytes the captured step copies into the persistent previous frame
+        self.per_stream = bool(per_stream)
+        self.captures = 0           # per-stream mode: graphs captured so far
+        self._static = {}           # per-stream eager mode: input shape -> static frames (graph mode: in _graphs)
+        self._active = self._restart = self._have_prev = self._counts = self._valid = None    # (S,) int32, device
         self._front = None          # raw mode: preprocess.SweepFrontEnd (persistent sweep, lengths, tr, sampler buffers)
         if sweeps is not None:
             if self.num_points is None:
@@ -110,11 +137,29 @@ class StreamingOdometry:
 
     # ---- public interface ----------------------------------------------------------------------------------------
 
-    def reset(self, tr=None):
+    def reset(self, streams=None, tr=None):
         """Start new sequences on all S streams: the next ``step`` primes and returns None.  ``tr``: raw KITTI mode, the
-        new sequences' calibration (as ``set_calibration``)."""
+        new sequences' calibration (as ``set_calibration``).  Per-stream mode: ``streams`` restarts those streams alone on
+        their next delivered frame, as if that call's ``restart`` named them.  The dtype decides how it is read: integers
+        are stream indices (host sequence), booleans an (S,) mask (host sequence or device tensor; a device tensor of
+        integers is refused as ambiguous).  Only the streams' ``have_prev`` word is cleared, on the device and without a
+        sync, so the mark survives calls in which they idle, and ``frame_counts()``, ``valid()`` and
+        ``trajectory(stream=i)`` keep showing the old sequence until that frame arrives.  ``streams=None`` restarts all
+        streams at once: counters, ``valid`` and the host call counter that ``max_frames`` bounds are zeroed now."""
+        if streams is not None:
+            if not self.per_stream:
+                raise ValueError("StreamingOdometry: reset(streams=...) needs per_stream=True")
+            mask = self._stream_mask(streams)                   # before anything changes
+            if tr is not None:
+                self.set_calibration(tr)
+            if self._have_prev is not None:
+                self._have_prev.mul_(1 - mask.to(self._have_prev.device))
+            return
         if tr is not None:
             self.set_calibration(tr)
+        if self._have_prev is not None:
+            for t in (self._have_prev, self._counts, self._valid):
+                t.zero_()
         self.frames_seen = 0
         self._prev = None
         if self._overflow is not None:
@@ -134,7 +179,11 @@ class StreamingOdometry:
             return None
         return self._front.bufs["counts"]
 
-    def step(self, frames):
+    def step(self, frames, active=None, restart=None):
+        if self.per_stream:
+            return self._step_masked(frames, active, restart)
+        if active is not None or restart is not None:
+            raise ValueError("StreamingOdometry: active / restart masks need per_stream=True")
         num_points = self._check(frames)
         if self.num_points is None:
             self.num_points = num_points       # fixed from the first frame on: the persistent state has its shapes
@@ -153,7 +202,7 @@ class StreamingOdometry:
         self.frames_seen += 1
         return pose
 
-    def step_sweeps(self, sweeps, lengths):
+    def step_sweeps(self, sweeps, lengths, active=None, restart=None):
         """Raw mode: sweeps (S, R <= capacity, 4) fp32 on the GPU, lengths (S,) host integers in [1, R] or a device
         integer tensor (read on the device; clamped to [0, R] there) -> pose as ``step``.  The host copies the rows
         ``[:R]`` and the lengths into static buffers; filter, compaction and sampling run inside the captured graphs."""
@@ -162,6 +211,10 @@ class StreamingOdometry:
         if front is None:
             raise RuntimeError("%s: step_sweeps needs raw mode (StreamingOdometry(..., sweeps=dict(dataset=..., "
                                "capacity=...)))" % what)
+        if self.per_stream:
+            return self._step_sweeps_masked(sweeps, lengths, active, restart)
+        if active is not None or restart is not None:
+            raise ValueError("%s: active / restart masks need per_stream=True" % what)
         self._check_room(what)
         host_lengths = front.check(sweeps, lengths, what)
         self._check_net(sweeps, what)
@@ -178,13 +231,25 @@ class StreamingOdometry:
         self.frames_seen += 1
         return pose
 
-    def relative_poses(self):
-        """(frames_seen, S, 4, 4) fp64 device view: row 0 the identity, row k the transform of pair (k-1, k)."""
-        return self._view(self._rel)
+    def relative_poses(self, stream=None):
+        """(frames_seen, S, 4, 4) fp64 device view: row 0 the identity, row k the transform of pair (k-1, k).
+        Per-stream mode: ``stream=i`` is required and gives that stream's (count_i, 4, 4)."""
+        return self._view(self._rel, stream)
 
-    def trajectory(self):
-        """(frames_seen, S, 4, 4) fp64 device view: the absolute poses, products of ``relative_poses()``."""
-        return self._view(self._abs)
+    def trajectory(self, stream=None):
+        """(frames_seen, S, 4, 4) fp64 device view: the absolute poses, products of ``relative_poses()``; ``stream=i``
+        as there."""
+        return self._view(self._abs, stream)
+
+    def valid(self):
+        """Per-stream mode: (S,) int32 device view, 1 where the last call's pose row is a real pair.  None before the
+        first call."""
+        return self._valid
+
+    def frame_counts(self):
+        """Per-stream mode: (S,) int32 device view of the frames recorded per stream since its last restart.  None
+        before the first call."""
+        return self._counts
 
     def overflowed(self):
         """Whether the device ever refused an append for lack of capacity (the host check makes this unreachable)."""
@@ -197,6 +262,7 @@ class StreamingOdometry:
         fused = self.net._fused
         if id(fused) != self._fused_id:        # re-packed weights (load_state_dict, prepare_fused): capture again
             self._graphs.clear()
+            self._static.clear()
             self._fused_id = id(fused)
         if self._rel is None:
             self._alloc(device)
@@ -211,10 +277,22 @@ class StreamingOdometry:
         self._append(pose)
         return pose
 
-    def _view(self, buf):
+    def _view(self, buf, stream=None):
+        if stream is None:
+            if self.per_stream:
+                raise ValueError("StreamingOdometry: per-stream mode keeps trajectories of different lengths; ask for "
+                                 "one with stream=i")
+            if buf is None:
+                return torch.empty((0, self.streams, 4, 4), dtype=torch.float64)
+            return buf[:self.frames_seen]
+        if not self.per_stream:
+            raise ValueError("StreamingOdometry: stream= needs per_stream=True (lock-step trajectories are (frames, S, 4, 4))")
+        i = int(stream)
+        if not 0 <= i < self.streams:
+            raise ValueError("StreamingOdometry: stream=%d outside [0, %d)" % (i, self.streams))
         if buf is None:
-            return torch.empty((0, self.streams, 4, 4), dtype=torch.float64)
-        return buf[:self.frames_seen]
+            return torch.empty((0, 4, 4), dtype=torch.float64)
+        return buf[:int(self._counts[i].item()), i]
 
     def _alloc(self, device):
         shape = (self.max_frames, self.streams, 4, 4)
@@ -222,6 +300,9 @@ class StreamingOdometry:
         self._abs = torch.zeros(shape, dtype=torch.float64, device=device)
         self._count = torch.zeros((1,), dtype=torch.int32, device=device)
         self._overflow = torch.zeros((1,), dtype=torch.int32, device=device)
+        if self.per_stream:
+            z = lambda: torch.zeros((self.streams,), dtype=torch.int32, device=device)
+            self._active, self._restart, self._have_prev, self._counts, self._valid = z(), z(), z(), z(), z()
 
     def _append(self, pose):
         """One launch: prime (pose None) or append the level-1 rows of pose (S,4,7) to the device trajectories."""
@@ -282,6 +363,156 @@ class StreamingOdometry:
             return None
         graph, pose = entry["step"]
         graph.replay()
+        return pose
+
+    # ---- per-stream mode ------------------------------------------------------------------------
+
+    def _stream_mask(self, mask, what="streams"):
+        """An (S,) bool or integer mask, host sequence or device tensor -> (S,) int32 0 / 1 tensor where the caller's
+        data lives.  ``what == "streams"`` (``reset``): integers are stream indices (host sequences only), booleans a mask.
+        Raises ValueError before anything is launched."""
+        S = self.streams
+        if isinstance(mask, torch.Tensor) and mask.is_cuda:
+            if what == "streams" and mask.dtype != torch.bool:
+                raise ValueError("StreamingOdometry: reset(streams=...) takes a device mask as bool (integers are stream "
+                                 "indices and belong in a host list), got %s" % mask.dtype)
+            if mask.shape != (S,) or mask.dtype.is_floating_point or mask.dtype.is_complex:
+                raise ValueError("StreamingOdometry: %s must be a (%d,) bool or integer mask, got %s %s"
+                                 % (what, S, mask.dtype, tuple(mask.shape)))
+            return mask.ne(0).to(torch.int32)
+        arr = np.asarray(mask.numpy() if isinstance(mask, torch.Tensor) else mask)
+        if what == "streams" and arr.ndim == 1 and (arr.dtype.kind in "iu" or arr.size == 0):
+            arr = arr.astype(np.int64)
+            if arr.size and (arr.min() < 0 or arr.max() >= S):
+                raise ValueError("StreamingOdometry: streams %s outside [0, %d)" % (arr.tolist(), S))
+            out = np.zeros((S,), dtype=np.int32)
+            out[arr] = 1
+            return torch.from_numpy(out)
+        if arr.shape != (S,) or arr.dtype.kind not in "biu":
+            raise ValueError("StreamingOdometry: %s must be a (%d,) bool or integer mask, got %s %s"
+                             % (what, S, arr.dtype, arr.shape))
+        return torch.from_numpy((arr != 0).astype(np.int32))
+
+    def _masks(self, active, restart):
+        """The call's masks, checked (ValueError before any launch) -> ((S,) int32 tensors or None, None)."""
+        act = None if active is None else self._stream_mask(active, "active")
+        rst = None if restart is None else self._stream_mask(restart, "restart")
+        return act, rst
+
+    def _first_active(self, act):
+        """New static inputs need every row initialised: -> (host bool mask of the active streams, index of the first),
+        reading a device mask once.  ValueError when no stream is active."""
+        host = np.ones((self.streams,), dtype=bool) if act is None else act.cpu().numpy() != 0
+        if not host.any():
+            raise ValueError("StreamingOdometry: the first call (of an input shape) needs at least one active stream: "
+                             "idle streams' inputs start as copies of the first active stream's")
+        return host, int(np.flatnonzero(host)[0])
+
+    def _load_masks(self, act, rst):
+        dev = self._active.device
+        if act is None:
+            self._active.fill_(1)
+        else:
+            self._active.copy_(act)
+        if rst is None:
+            self._restart.zero_()
+        else:
+            self._restart.copy_(rst)
+        return dev
+
+    def _append_masked(self, pose):
+        """One launch: the per-stream state machine over this call's masks; non-pair rows of ``pose`` become identity."""
+        assert pose.is_contiguous() and pose.shape == (self.streams, 4, 7)
+        _lib.call("stream_append_masked_kernel_wrapper", pose.device, self.streams, self.max_frames, _p(self._active),
+                  _p(self._restart), _p(pose), _p(self._rel), _p(self._abs), _p(self._have_prev), _p(self._counts),
+                  _p(self._valid), _p(self._overflow))
+
+    def _masked_body(self, fused, source):
+        """The launches of one per-stream call, captured or eager: source, the step against the persistent previous
+        frame, the masked append, the masked handover (ordered after every reader of the previous frame: the pair
+        stage has joined its side streams by the time it returns)."""
+        pose, new = fused.stream_step(self._slot, source(), self.num_points)
+        self._append_masked(pose)
+        self._slot.copy_frame1_masked_(new, self._active)
+        return pose
+
+    def _run_masked(self, fused, entry, source):
+        """``entry``: dict(step=(graph, pose) | None) of this input shape.  Creates the persistent previous frame from a
+        real state on the very first call, captures once per entry, replays (or runs the same launches eagerly)."""
+        n = self.num_points
+        if self._slot is None:
+            prime = lambda: fused.stream_prime(source(), n)
+            first = self._warm(prime) if self.graph else prime()
+            self._slot = first.frame1_buffers().copy_frame1_(first)
+            self.handover_bytes = self._slot.frame1_bytes()
+        if not self.graph:
+            return self._masked_body(fused, source)
+        if entry["step"] is None:
+            self._warm(lambda: fused.stream_step(self._slot, source(), n))
+            entry["step"] = self._capture(lambda: self._masked_body(fused, source))
+            self.captures += 1
+        graph, pose = entry["step"]
+        graph.replay()
+        return pose
+
+    def _step_masked(self, frames, active, restart):
+        from . import fused as fused_mod
+        num_points = self._check(frames)
+        act, rst = self._masks(active, restart)
+        key = (tuple(frames.shape), frames.device)
+        store = self._graphs if self.graph else self._static
+        filled = None
+        if self._fused_id != id(self.net._fused) or key not in store:
+            host, j = self._first_active(act)               # new static rows: idle streams start from an active one
+            filled = frames.clone()
+            if not host.all():
+                filled[torch.from_numpy(~host).to(frames.device)] = frames[j]
+        if self.num_points is None:
+            self.num_points = num_points
+        fused = self._begin(frames.device)
+        self._load_masks(act, rst)
+        entry = store.get(key)
+        if entry is None:
+            entry = store[key] = dict(static=filled, step=None)
+        else:
+            static, src = entry["static"], frames.contiguous()
+            per = static[0].numel() * static.element_size()
+            fused_mod.masked_copy([(static.data_ptr(), src.data_ptr(), per)], self._active)
+        static = entry["static"]
+        pose = self._run_masked(fused, entry, lambda: static)
+        self.frames_seen += 1
+        return pose
+
+    def _step_sweeps_masked(self, sweeps, lengths, active, restart):
+        what = "StreamingOdometry"
+        front = self._front
+        self._check_room(what)
+        host_lengths = front.check(sweeps, lengths, what)
+        self._check_net(sweeps, what)
+        act, rst = self._masks(active, restart)
+        if front.bufs is None:
+            host, j = self._first_active(act)
+            if not host.all():
+                idle = torch.from_numpy(~host).to(sweeps.device)
+                sweeps = sweeps.clone()
+                sweeps[idle] = sweeps[j]
+                if host_lengths is None:
+                    lengths = lengths.clone()
+                    lengths[idle] = lengths[j]
+                else:
+                    host_lengths = [v if a else host_lengths[j] for v, a in zip(host_lengths, host)]
+        fused = self._begin(sweeps.device)
+        self._load_masks(act, rst)
+        if front.bufs is None:
+            front.load(sweeps, lengths, host_lengths)
+        else:
+            front.load_masked(sweeps, lengths, host_lengths, self._active)
+        store = self._graphs if self.graph else self._static
+        entry = store.get("sweeps")
+        if entry is None:
+            entry = store["sweeps"] = dict(static=None, step=None)
+        pose = self._run_masked(fused, entry, front.run)
+        self.frames_seen += 1
         return pose
 
 

@@ -200,6 +200,20 @@ class SweepFrontEnd:
         else:
             b["lengths"].copy_(torch.tensor(host_lengths, dtype=torch.int32), non_blocking=False)
 
+    def load_masked(self, sweeps, lengths, host_lengths, active):
+        """``load`` for the streams s with ``active[s] != 0`` only ((S,) int32 on the device, read there; no sync): the
+        other streams' static rows and lengths keep the sweep they delivered last.  One launch."""
+        from . import fused
+        b, cap = self.bufs, self.capacity
+        src = sweeps.contiguous()
+        rows = src.shape[1] * 16
+        if host_lengths is None:
+            new_len = lengths.to(torch.int32).contiguous()
+        else:
+            new_len = torch.tensor(host_lengths, dtype=torch.int32).to(src.device)
+        fused.masked_copy([(b["sweeps"].data_ptr(), src.data_ptr(), rows), (b["lengths"].data_ptr(), new_len.data_ptr(), 4)],
+                          active, dst_strides=[cap * 16, 4], src_strides=[rows, 4])
+
     def _alloc(self, device):
         S, cap, m = self.streams, self.capacity, self.npoints
         e = lambda shape, dt: torch.empty(shape, dtype=dt, device=device)

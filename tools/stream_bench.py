@@ -13,10 +13,18 @@
     captured step copies into the persistent previous frame and the time of that copy alone (eager, HIP events).
 Check: the streamed rows equal the pair forward's at the same batch bit for bit.
 
-    python tools/stream_bench.py [--frames F] [--repeats R] [--steps32 K] [--trace-only]
+    python tools/stream_bench.py [--frames F] [--repeats R] [--steps32 K] [--trace-only] [--per-stream]
 
 ``--trace-only``: only the S = 1 graphed stream over the frames, for ``rocprofv3 --kernel-trace --stats -- python
 tools/stream_bench.py --trace-only`` (a run of its own).
+
+``--per-stream``: instead of (a)-(c), the masked step of ``StreamingOdometry(per_stream=True)``
+against the lock-step step, alternated repeat by repeat in this process: S = 1 per-frame time (all active), S = 32
+frames/s with all streams active and with every other stream active (steps x S per second in both: an idle stream costs
+what an active one does), and at S = 32 the masked handover launch alone against the lock-step copies (HIP events,
+bytes read + written per second).  ``--per-stream --trace-only``: only 30 masked handover launches at S = 32, all streams
+active, for ``rocprofv3 --kernel-trace --stats -- python tools/stream_bench.py --per-stream --trace-only`` (a run of its own):
+the kernel's device time without launch latency.
 """
 import argparse
 import json
@@ -94,6 +102,99 @@ def _region_ms(dev, fn, steps):
     return s.elapsed_time(e)
 
 
+def _per_stream(a, dev, net, clouds, res):
+    """``--per-stream``: masked step against lock-step step, same frames, alternated."""
+    F = a.frames
+    if a.trace_only:
+        S = 32
+        fs = net._fused
+        batch = clouds[torch.tensor([(5 * i) % F for i in range(S)], device=dev)]
+        new = fs.stream_prime(batch, a.npoints)
+        slot = new.frame1_buffers()
+        ones = torch.ones((S,), dtype=torch.int32, device=dev)
+        for _ in range(30):
+            slot.copy_frame1_masked_(new, ones)
+        torch.cuda.synchronize(dev)
+        print(json.dumps({"tool": "stream_bench", "mode": "per_stream", "trace_only": True, "launches": 30,
+                          "bytes": slot.frame1_bytes()}))
+        return
+    lock = StreamingOdometry(net, streams=1, max_frames=F + 1, graph=True)
+    per = StreamingOdometry(net, streams=1, max_frames=F + 1, graph=True, per_stream=True)
+
+    def run1(so):
+        so.reset()
+        so.step(clouds[0:1])
+        return _per_frame_ms(dev, lambda k: so.step(clouds[k:k + 1]), F)
+
+    lock.reset(), per.reset()
+    lock.step(clouds[0:1]), per.step(clouds[0:1])
+    same = all(torch.equal(per.step(clouds[k:k + 1]), lock.step(clouds[k:k + 1])) for k in range(1, min(F, 20)))
+    run1(lock), run1(per)
+    tl, tm = [], []
+    for _ in range(a.repeats):
+        tl.append(run1(lock))
+        tm.append(run1(per))
+    res["s1_lockstep_ms_per_frame"], res["s1_masked_ms_per_frame"] = _stats(tl), _stats(tm)
+    res["s1_rows_bitwise_equal_lockstep"] = bool(same)
+
+    S, K = 32, a.steps32
+    idx = [[(k + 5 * i) % F for i in range(S)] for k in range(K + 1)]
+    batches = [clouds[torch.tensor(r, device=dev)] for r in idx]
+    lock32 = StreamingOdometry(net, streams=S, max_frames=K + 2, graph=True)
+    per32 = StreamingOdometry(net, streams=S, max_frames=K + 2, graph=True, per_stream=True)
+    half = torch.tensor([i % 2 == 0 for i in range(S)], device=dev)
+
+    def run32(so, mask=None):
+        so.reset()
+        so.step(batches[0])
+        step = (lambda k: so.step(batches[k + 1])) if mask is None else (lambda k: so.step(batches[k + 1], active=mask))
+        return S * K / (_region_ms(dev, step, K) / 1e3)
+
+    lock32.reset(), per32.reset()
+    lock32.step(batches[0]), per32.step(batches[0])
+    same32 = all(torch.equal(per32.step(batches[k]), lock32.step(batches[k])) for k in range(1, 4))
+    run32(lock32), run32(per32), run32(per32, half)
+    rl, ra, rh = [], [], []
+    for _ in range(a.repeats):
+        rl.append(run32(lock32))
+        ra.append(run32(per32))
+        rh.append(run32(per32, half))
+    res["s32_lockstep_frames_per_s"] = _stats(rl)
+    res["s32_masked_all_active_frames_per_s"] = _stats(ra)
+    res["s32_masked_half_active_stream_steps_per_s"] = _stats(rh)
+    res["s32_rows_bitwise_equal_lockstep"] = bool(same32)
+
+    # the handover alone at S = 32: one masked launch (all active, half active) against the lock-step copies
+    fs = net._fused
+    prev = fs.stream_prime(batches[0], a.npoints)
+    _, new = fs.stream_step(prev, batches[1], a.npoints)
+    slot = new.frame1_buffers()
+    ones = torch.ones((S,), dtype=torch.int32, device=dev)
+    halfi = half.to(torch.int32)
+
+    def timed(fn):
+        out = []
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize(dev)
+        for _ in range(30):
+            s.record()
+            fn()
+            e.record()
+            e.synchronize()
+            out.append(s.elapsed_time(e))
+        return _stats(out[5:])
+
+    nbytes = slot.frame1_bytes()
+    t_copy, t_all, t_half = (timed(lambda: slot.copy_frame1_(new)), timed(lambda: slot.copy_frame1_masked_(new, ones)),
+                             timed(lambda: slot.copy_frame1_masked_(new, halfi)))
+    res["handover_s32"] = {"bytes": nbytes, "segments": len(new.frame1_segments(slot)),
+                           "copies_lockstep": len(slot.frame1_tensors()), "lockstep_copies_ms": t_copy,
+                           "masked_all_active_ms": t_all, "masked_half_active_ms": t_half,
+                           "masked_all_active_read_plus_write_TBps": 2.0 * nbytes / (t_all["median"] * 1e-3) / 1e12,
+                           "masked_half_active_read_plus_write_TBps": nbytes / (t_half["median"] * 1e-3) / 1e12}
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=201, help="frames of the S = 1 sequence (pairs = frames - 1)")
@@ -102,6 +203,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--steps32", type=int, default=20, help="steps per timed region at S = 32")
     ap.add_argument("--trace-only", action="store_true")
+    ap.add_argument("--per-stream", action="store_true", help="masked step against lock-step step (section 18)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     base = torch.from_numpy(synthetic.kitti_like_sequence(2024, a.npoints, a.base)[0]).to(dev)   # (base, N, 4)
@@ -114,6 +216,9 @@ def main():
     res = {"tool": "stream_bench", "npoints": a.npoints, "frames": a.frames, "base": a.base, "repeats": a.repeats,
            "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES")}
     torch.set_grad_enabled(False)
+    if a.per_stream:
+        res["mode"] = "per_stream"
+        return _per_stream(a, dev, net, clouds, res)
 
     # ---- (a) S = 1 ----
     so = StreamingOdometry(net, streams=1, max_frames=a.frames + 1, graph=True)
