@@ -598,6 +598,23 @@ void conv1x1_wgrad_kernel_wrapper(int b, int cin, int cout, int p, const float *
 #define PWCLO_PLAN_WGRAD 6       /* conv1x1_wgrad, conv1x1_bnrelu_wgrad */
 int conv1x1_plan_query(int kind, int b, int cin, int cout, int p, int cus, int *out);
 
+/* Host only (no launch, no device needed): which scatter-add kernel group_points_grad (dense and strided; gather_points_grad
+ * with n <= 32768 is the same call with p = npoints) and three_interpolate_grad select for a shape, answered by the
+ * launchers' own planning code.  p = npoints * nsample.  aligned: grad_out and idx are 16-byte aligned (what the launcher
+ * reads off its pointers).  use_lds: the PWCLO_GRAD_LDS switch, 0 / 1, or -1 for the environment's value as the launcher
+ * takes it.  out receives {form, ct, slices, splits, per_split, vec4, ranges}:
+ *   form      PWCLO_SCATTER_ATOMIC (global fp32 atomics, one thread per position) or PWCLO_SCATTER_LDS;
+ *   ct        channels of one slice (LDS form: a workgroup's accumulators are ct x n floats), slices = ceil(c / ct);
+ *   splits    position ranges the launcher asks for, per_split positions each;
+ *   ranges    position ranges launched (grid x = ceil(p / per_split)): 1 = the slice's sole owner adds its totals with a
+ *             plain read-modify-write, more = every range flushes with global atomics;
+ *   vec4      16-byte loads of idx and grad_out (group_points_grad only).
+ * Returns 0, or -1 for a non-positive size. */
+#define PWCLO_SCATTER_ATOMIC 0
+#define PWCLO_SCATTER_LDS 1
+int group_points_grad_plan_query(int b, int c, int n, int p, int aligned, int use_lds, int *out);
+int three_interpolate_grad_plan_query(int b, int c, int n, int m, int use_lds, int *out);
+
 /* ---- 4. hoisted variants of section 3 ----------------------------------------------------------
  * The first layer of every grouped MLP is linear in [geometry | feat_centre[s] | feat_nbr[n]]; the
  * feature parts depend on one point only, so W_feat . feat[point] (+ bias) is computed once per

@@ -36,6 +36,10 @@ unsigned *device_error_word();
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
+// Host-side decision of a scatter-add gradient launcher (group_points.hip: gp_grad_plan, interpolate.hip: ti_grad_plan), in
+// the order the *_grad_plan_query entry points report it (include/pwclo_ops.h).
+struct ScatterGradPlan { int form, ct, slices, splits, per_split, vec4, ranges; };
+
 // PWCLO_<NAME> override of a launch parameter (experiments; README.md lists them).  Callers keep the value in a
 // function-local static: every variable is read once per process.
 static inline int tuning(const char *name, int dflt) {

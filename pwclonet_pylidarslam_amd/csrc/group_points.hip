@@ -482,6 +482,38 @@ static void gp_forward(int b, int c, int n, int npoints, int nsample, const floa
   check_launch("group_points");
 }
 
+// Which scatter-add kernel gp_grad launches and how it cuts the work: the launcher and group_points_grad_plan_query both ask
+// here.  `aligned`: grad_out and idx are 16-byte aligned (with P % 4 == 0 that is the vec4 path).
+static ScatterGradPlan gp_grad_plan(int b, int c, int n, int P, bool use_lds, bool aligned) {
+  ScatterGradPlan pl = {PWCLO_SCATTER_ATOMIC, GP_CH_PER_BLOCK, ceil_div(c, GP_CH_PER_BLOCK), 1, P, 0, ceil_div(P, GP_THREADS)};
+  if (!(use_lds && (long long)n * 4 <= GG_LDS_BYTES)) return pl;
+  int ct = 8;
+  while ((long long)ct * n * 4 > GG_LDS_BYTES) ct >>= 1;
+  if (ct > c) ct = c;
+  while (ct > 1 && b * ceil_div(c, ct) < 256) ct >>= 1;        // narrower slices before splitting positions
+  const int slices = ceil_div(c, ct);
+  int splits = b * slices >= 64 ? 1 : ceil_div(256, b * slices);   // split ranges flush with global atomics
+  splits = max(1, min(splits, ceil_div(P, 4 * GG_THREADS)));
+  const int per_split = ceil_div(ceil_div(P, splits), 4) * 4;
+  pl.form = PWCLO_SCATTER_LDS;
+  pl.ct = ct;
+  pl.slices = slices;
+  pl.splits = splits;
+  pl.per_split = per_split;
+  pl.vec4 = (P % 4 == 0) && aligned;
+  pl.ranges = ceil_div(P, per_split);
+  return pl;
+}
+
+extern "C" int group_points_grad_plan_query(int b, int c, int n, int p, int aligned, int use_lds, int *out) {
+  if (b <= 0 || c <= 0 || n <= 0 || p <= 0 || out == nullptr) return -1;
+  if (use_lds < 0) { const char *e = getenv("PWCLO_GRAD_LDS"); use_lds = e ? atoi(e) : 1; }
+  const ScatterGradPlan pl = gp_grad_plan(b, c, n, p, use_lds != 0, aligned != 0);
+  out[0] = pl.form; out[1] = pl.ct; out[2] = pl.slices; out[3] = pl.splits; out[4] = pl.per_split; out[5] = pl.vec4;
+  out[6] = pl.ranges;
+  return 0;
+}
+
 extern "C" void group_points_grad_kernel_wrapper(int b, int c, int n, int npoints, int nsample,
                                                  const float *grad_out, const int *idx,
                                                  float *grad_points) {
@@ -497,25 +529,18 @@ static void gp_grad(int b, int c, int n, int npoints, int nsample, const float *
   const int P = (int)P64;
   static int use_lds = -1;
   if (use_lds < 0) { const char *e = getenv("PWCLO_GRAD_LDS"); use_lds = e ? atoi(e) : 1; }
-  if (use_lds && (long long)n * 4 <= GG_LDS_BYTES) {
-    int ct = 8;
-    while ((long long)ct * n * 4 > GG_LDS_BYTES) ct >>= 1;
-    if (ct > c) ct = c;
-    while (ct > 1 && b * ceil_div(c, ct) < 256) ct >>= 1;        // narrower slices before splitting positions
-    const int slices = ceil_div(c, ct);
-    int splits = b * slices >= 64 ? 1 : ceil_div(256, b * slices);   // split ranges flush with global atomics
-    splits = max(1, min(splits, ceil_div(P, 4 * GG_THREADS)));
-    const int per_split = ceil_div(ceil_div(P, splits), 4) * 4;
-    const int vec4 = (P % 4 == 0) && ((reinterpret_cast<uintptr_t>(grad_out) & 15) == 0) &&
-                     ((reinterpret_cast<uintptr_t>(idx) & 15) == 0);
+  const bool aligned = ((reinterpret_cast<uintptr_t>(grad_out) & 15) == 0) && ((reinterpret_cast<uintptr_t>(idx) & 15) == 0);
+  const ScatterGradPlan pl = gp_grad_plan(b, c, n, P, use_lds != 0, aligned);
+  if (pl.form == PWCLO_SCATTER_LDS) {
     static bool attr_set = false;
     if (!attr_set) {
       (void)hipFuncSetAttribute((const void *)group_points_grad_lds_kernel,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, GG_LDS_BYTES);
       attr_set = true;
     }
-    hipLaunchKernelGGL(group_points_grad_lds_kernel, dim3(ceil_div(P, per_split), slices, b), dim3(GG_THREADS),
-                       (size_t)ct * n * 4, current_stream(), c, n, P, ct, per_split, vec4, grad_out, idx, grad_points, go_bstride);
+    hipLaunchKernelGGL(group_points_grad_lds_kernel, dim3(pl.ranges, pl.slices, b), dim3(GG_THREADS),
+                       (size_t)pl.ct * n * 4, current_stream(), c, n, P, pl.ct, pl.per_split, pl.vec4, grad_out, idx, grad_points,
+                       go_bstride);
     check_launch("group_points_grad");
     return;
   }

@@ -169,6 +169,37 @@ extern "C" void three_interpolate_kernel_wrapper(int b, int c, int m, int n, con
   check_launch("three_interpolate");
 }
 
+// Which kernel three_interpolate_grad launches and how it cuts the work (see gp_grad_plan in group_points.hip): the
+// launcher and three_interpolate_grad_plan_query both ask here.
+static ScatterGradPlan ti_grad_plan(int b, int c, int n, int m, bool use_lds) {
+  ScatterGradPlan pl = {PWCLO_SCATTER_ATOMIC, TI_CH_PER_BLOCK, ceil_div(c, TI_CH_PER_BLOCK), 1, n, 0, ceil_div(n, TI_THREADS)};
+  if (!(use_lds && m > 0 && (long long)m * 4 <= TG_LDS_BYTES)) return pl;
+  int ct = 8;
+  while ((long long)ct * m * 4 > TG_LDS_BYTES) ct >>= 1;
+  if (ct > c) ct = c;
+  while (ct > 1 && b * ceil_div(c, ct) < 256) ct >>= 1;
+  const int slices = ceil_div(c, ct);
+  int splits = b * slices >= 64 ? 1 : ceil_div(256, b * slices);
+  splits = max(1, min(splits, ceil_div(n, 2 * TG_THREADS)));
+  const int per_split = ceil_div(n, splits);
+  pl.form = PWCLO_SCATTER_LDS;
+  pl.ct = ct;
+  pl.slices = slices;
+  pl.splits = splits;
+  pl.per_split = per_split;
+  pl.ranges = ceil_div(n, per_split);
+  return pl;
+}
+
+extern "C" int three_interpolate_grad_plan_query(int b, int c, int n, int m, int use_lds, int *out) {
+  if (b <= 0 || c <= 0 || n <= 0 || m <= 0 || out == nullptr) return -1;
+  if (use_lds < 0) { const char *e = getenv("PWCLO_GRAD_LDS"); use_lds = e ? atoi(e) : 1; }
+  const ScatterGradPlan pl = ti_grad_plan(b, c, n, m, use_lds != 0);
+  out[0] = pl.form; out[1] = pl.ct; out[2] = pl.slices; out[3] = pl.splits; out[4] = pl.per_split; out[5] = pl.vec4;
+  out[6] = pl.ranges;
+  return 0;
+}
+
 extern "C" void three_interpolate_grad_kernel_wrapper(int b, int c, int n, int m,
                                                       const float *grad_out, const int *idx,
                                                       const float *weight, float *grad_points) {
@@ -176,23 +207,16 @@ extern "C" void three_interpolate_grad_kernel_wrapper(int b, int c, int n, int m
   PWCLO_REQUIRE(b <= 65535, "three_interpolate_grad: b=%d exceeds the grid limit", b);
   static int use_lds = -1;
   if (use_lds < 0) { const char *e = getenv("PWCLO_GRAD_LDS"); use_lds = e ? atoi(e) : 1; }
-  if (use_lds && m > 0 && (long long)m * 4 <= TG_LDS_BYTES) {
-    int ct = 8;
-    while ((long long)ct * m * 4 > TG_LDS_BYTES) ct >>= 1;
-    if (ct > c) ct = c;
-    while (ct > 1 && b * ceil_div(c, ct) < 256) ct >>= 1;
-    const int slices = ceil_div(c, ct);
-    int splits = b * slices >= 64 ? 1 : ceil_div(256, b * slices);
-    splits = max(1, min(splits, ceil_div(n, 2 * TG_THREADS)));
-    const int per_split = ceil_div(n, splits);
+  const ScatterGradPlan pl = ti_grad_plan(b, c, n, m, use_lds != 0);
+  if (pl.form == PWCLO_SCATTER_LDS) {
     static bool attr_set = false;
     if (!attr_set) {
       (void)hipFuncSetAttribute((const void *)three_interpolate_grad_lds_kernel,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, TG_LDS_BYTES);
       attr_set = true;
     }
-    hipLaunchKernelGGL(three_interpolate_grad_lds_kernel, dim3(ceil_div(n, per_split), slices, b),
-                       dim3(TG_THREADS), (size_t)ct * m * 4, current_stream(), c, n, m, ct, per_split, grad_out, idx,
+    hipLaunchKernelGGL(three_interpolate_grad_lds_kernel, dim3(pl.ranges, pl.slices, b),
+                       dim3(TG_THREADS), (size_t)pl.ct * m * 4, current_stream(), c, n, m, pl.ct, pl.per_split, grad_out, idx,
                        weight, grad_points);
     check_launch("three_interpolate_grad");
     return;

@@ -243,6 +243,33 @@ def _inverse_index(idx, n):
     return perm, seg
 
 
+_PLAN_FIELDS = ("form", "ct", "slices", "splits", "per_split", "vec4", "ranges")
+_PLAN_FORMS = ("atomic", "lds")          # PWCLO_SCATTER_*
+
+
+def _plan(name, args):
+    import ctypes
+    out = (ctypes.c_int * 8)()
+    if getattr(_lib.load(), name)(*args, out) != 0:
+        raise ValueError("%s%r" % (name, tuple(args)))
+    plan = dict(zip(_PLAN_FIELDS, out[:len(_PLAN_FIELDS)]))
+    plan["form"] = _PLAN_FORMS[plan["form"]]
+    return plan
+
+
+def group_points_grad_plan(b, c, n, p, aligned=True, use_lds=None):
+    """group_points_grad_plan_query: the kernel ``group_points_grad`` / ``group_points_grad_from`` (and ``gather_points_grad``
+    for n <= 32768, p = npoints) selects for grad_out (b, c, p positions) scattered into n source points -> dict of the
+    fields documented in include/pwclo_ops.h, ``form`` as "atomic" / "lds".  ``aligned``: grad_out and idx are 16-byte
+    aligned; ``use_lds``: None = the PWCLO_GRAD_LDS switch as the launcher reads it.  Host only: works without a GPU."""
+    return _plan("group_points_grad_plan_query", (b, c, n, p, int(bool(aligned)), -1 if use_lds is None else int(bool(use_lds))))
+
+
+def three_interpolate_grad_plan(b, c, n, m, use_lds=None):
+    """three_interpolate_grad_plan_query for grad_out (b, c, n) scattered into m coarse points; see ``group_points_grad_plan``."""
+    return _plan("three_interpolate_grad_plan_query", (b, c, n, m, -1 if use_lds is None else int(bool(use_lds))))
+
+
 def _slice_ptr(stack, c_off, c):
     """Address of channel ``c_off`` of cloud 0 of a contiguous (B,Ctot,S,K) tensor + its batch stride in floats."""
     _float(stack, "stack")
