@@ -615,6 +615,31 @@ int conv1x1_plan_query(int kind, int b, int cin, int cout, int p, int cus, int *
 int group_points_grad_plan_query(int b, int c, int n, int p, int aligned, int use_lds, int *out);
 int three_interpolate_grad_plan_query(int b, int c, int n, int m, int use_lds, int *out);
 
+/* Host only (no launch, no device needed): what a knn call launches for xyz (b,n,3), new_xyz (b,s,3) and nsample
+ * neighbours, answered by the launchers' own selection code (csrc/knn.hip: knn_plan).  prebuilt = 0 describes
+ * knn_point_ws_kernel_wrapper with a workspace (knn_point_kernel_wrapper, and a NULL workspace, always take the exhaustive
+ * kernel with the same qpw rule); prebuilt = 1 describes knn_build_kernel_wrapper + knn_point_prebuilt[_slice]_kernel_wrapper,
+ * which have no PWCLO_KNN_MIN_N / PWCLO_KNN_MIN_S gate (64 <= n <= 16384, any s).  use_rows: the PWCLO_KNN_ROWS switch, 0 / 1,
+ * or -1 for the environment's value as the launcher reads it (once per process).
+ * out receives {search, qpw, L, R, build_r, nslab, nblk, grid_x}:
+ *   search    PWCLO_KNN_EXHAUSTIVE: knn_kernel<qpw>, qpw = 2 / 4 / 8 queries per wave by b * s (< 8192, < 65536, more);
+ *             PWCLO_KNN_ROWS: knn_rows_kernel<L, R>, nsample <= 32: L = 16 (nsample <= 16) or 32 lanes per query, R block
+ *             bounds per lane, the smallest of {2,3,5,9,17} (L = 16) / {1,2,3,5,9} (L = 32) with L * R >= nblk;
+ *             PWCLO_KNN_PRUNED: knn_pruned_kernel, one query per wave (nsample > 32, or use_rows = 0);
+ *   qpw       exhaustive search only, else 0;   L, R: rows search only, else 0;
+ *   build_r   the knn_build_kernel<R> that sorts the cloud, R = 1 / 2 / 4 / 8 / 16 points per thread (smallest with
+ *             1024 * R >= n): launched by this call (prebuilt = 0) or by knn_build_kernel_wrapper before it (prebuilt = 1);
+ *             0 for the exhaustive search, which builds nothing;
+ *   nslab     x-slabs of the structure (knn_point_slabs(n)), nblk = ceil(n / 64) + nslab blocks of 64 sorted rows (what
+ *             knn_point_workspace_sections lays out); both 0 for the exhaustive search;
+ *   grid_x    workgroups per cloud of the search kernel (grid y = b).
+ * Returns 0, or -1 for arguments the launchers refuse (a non-positive size, nsample outside [1, min(n, 64)], prebuilt with n
+ * outside [64, 16384]). */
+#define PWCLO_KNN_EXHAUSTIVE 0
+#define PWCLO_KNN_ROWS 1
+#define PWCLO_KNN_PRUNED 2
+int knn_point_plan_query(int b, int n, int s, int nsample, int prebuilt, int use_rows, int *out);
+
 /* ---- 4. hoisted variants of section 3 ----------------------------------------------------------
  * The first layer of every grouped MLP is linear in [geometry | feat_centre[s] | feat_nbr[n]]; the
  * feature parts depend on one point only, so W_feat . feat[point] (+ bias) is computed once per

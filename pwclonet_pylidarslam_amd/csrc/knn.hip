@@ -217,24 +217,27 @@ __global__ __launch_bounds__(KNN_WAVES * 64) void knn_kernel(int n, int s, int K
 
 using namespace pwclo;
 
+// 8 queries per wave amortise the candidate loads when there are enough queries to fill the
+// chip; small problems keep 4 (or 2) to expose more waves.  (The launcher below and knn_plan ask here.)
+static int knn_exhaustive_qpw(int b, int s) {
+  const long long queries = (long long)b * s;
+  return queries >= 65536 ? 8 : (queries >= 8192 ? 4 : 2);
+}
+
 extern "C" void knn_point_kernel_wrapper(int b, int n, int s, int nsample, const float *xyz,
                                          const float *new_xyz, int *idx, float *dist) {
   if (b <= 0 || s <= 0) return;
   PWCLO_REQUIRE(nsample >= 1 && nsample <= 64, "knn_point: nsample=%d outside [1,64]", nsample);
   PWCLO_REQUIRE(nsample <= n, "knn_point: nsample=%d exceeds the number of points n=%d", nsample, n);
   PWCLO_REQUIRE(b <= 65535, "knn_point: b=%d exceeds the grid limit", b);
-  // 8 queries per wave amortise the candidate loads when there are enough queries to fill the
-  // chip; small problems keep 4 (or 2) to expose more waves.
-  const long long queries = (long long)b * s;
-  if (queries >= 65536) {
-    hipLaunchKernelGGL(knn_kernel<8>, dim3(ceil_div(s, KNN_WAVES * 8), b), dim3(KNN_WAVES * 64), 0,
-                       current_stream(), n, s, nsample, xyz, new_xyz, idx, dist);
-  } else if (queries >= 8192) {
-    hipLaunchKernelGGL(knn_kernel<4>, dim3(ceil_div(s, KNN_WAVES * 4), b), dim3(KNN_WAVES * 64), 0,
-                       current_stream(), n, s, nsample, xyz, new_xyz, idx, dist);
+  const int qpw = knn_exhaustive_qpw(b, s);
+  const dim3 grid(ceil_div(s, KNN_WAVES * qpw), b), block(KNN_WAVES * 64);
+  if (qpw == 8) {
+    hipLaunchKernelGGL(knn_kernel<8>, grid, block, 0, current_stream(), n, s, nsample, xyz, new_xyz, idx, dist);
+  } else if (qpw == 4) {
+    hipLaunchKernelGGL(knn_kernel<4>, grid, block, 0, current_stream(), n, s, nsample, xyz, new_xyz, idx, dist);
   } else {
-    hipLaunchKernelGGL(knn_kernel<2>, dim3(ceil_div(s, KNN_WAVES * 2), b), dim3(KNN_WAVES * 64), 0,
-                       current_stream(), n, s, nsample, xyz, new_xyz, idx, dist);
+    hipLaunchKernelGGL(knn_kernel<2>, grid, block, 0, current_stream(), n, s, nsample, xyz, new_xyz, idx, dist);
   }
   check_launch("knn_point");
 }
@@ -782,6 +785,7 @@ static int knn_slabs(int n) {            // ~ sqrt(#blocks), power of two in [2,
   while (nslab < 16 && nslab * nslab * 4 <= (n + 63) / 64) nslab <<= 1;
   return nslab;
 }
+static int knn_blocks(int n) { return (n + 63) / 64 + knn_slabs(n); }   // blocks of 64 rows: the points + one padding block per slab
 
 static int knn_tune(const char *name, int dflt) {
   const char *e = getenv(name);
@@ -789,10 +793,12 @@ static int knn_tune(const char *name, int dflt) {
 }
 static int knn_min_n() { static const int v = knn_tune("PWCLO_KNN_MIN_N", 256); return v; }
 static int knn_min_s() { static const int v = knn_tune("PWCLO_KNN_MIN_S", 256); return v; }
+// K <= 32: several queries per wave (knn_rows_kernel); PWCLO_KNN_ROWS=0 keeps one query per wave (A/B switch)
+static int knn_use_rows() { static const int v = knn_tune("PWCLO_KNN_ROWS", 1); return v; }
 
 extern "C" long long knn_point_workspace_bytes(int b, int n) {
   if (n < knn_min_n() || n > pwclo::KNN_MAX_SORT) return 0;       // exhaustive kernel: no workspace
-  const long long nblk = (n + 63) / 64 + knn_slabs(n);
+  const long long nblk = knn_blocks(n);
   return (long long)b * nblk * (64 * 16 + 32);
 }
 
@@ -804,29 +810,79 @@ extern "C" int knn_point_workspace_sections(int b, int n, long long *out) {
   if (out == nullptr) return 0;
   out[0] = out[1] = out[2] = out[3] = 0;
   if (b <= 0 || knn_point_workspace_bytes(b, n) == 0) return 0;
-  const long long nblk = (n + 63) / 64 + knn_slabs(n);
+  const long long nblk = knn_blocks(n);
   out[1] = nblk * 64 * (long long)sizeof(float4);
   out[2] = (long long)b * out[1];
   out[3] = nblk * 2 * (long long)sizeof(float4);
   return 1;
 }
 
+// What a knn call launches: every launcher of this file and knn_point_plan_query ask here, so the kernels a shape
+// reaches are stated once.  search: PWCLO_KNN_EXHAUSTIVE (knn_kernel<qpw>), PWCLO_KNN_ROWS (knn_rows_kernel<L, R>) or
+// PWCLO_KNN_PRUNED; build_r: the knn_build_kernel<R> behind the structure the search reads (0: exhaustive, no structure).
+struct KnnPlan { int search, qpw, L, R, build_r, nslab, nblk, grid_x; };
+
+// `structure`: the search runs on sorted rows + block boxes (the prebuilt entry points always; knn_point_ws when the
+// workspace applies and there are enough queries to amortise the build).
+static KnnPlan knn_plan(int b, int n, int s, int nsample, bool structure, bool use_rows) {
+  KnnPlan pl = {PWCLO_KNN_EXHAUSTIVE, 0, 0, 0, 0, 0, 0, 0};
+  if (!structure) {
+    pl.qpw = knn_exhaustive_qpw(b, s);
+    pl.grid_x = ceil_div(s, KNN_WAVES * pl.qpw);
+    return pl;
+  }
+  pl.nslab = knn_slabs(n);
+  pl.nblk = knn_blocks(n);
+  const int regs = ceil_div(n, KB_THREADS);              // points per thread of the one-workgroup build
+  pl.build_r = regs <= 1 ? 1 : (regs <= 2 ? 2 : (regs <= 4 ? 4 : (regs <= 8 ? 8 : 16)));
+  pl.search = PWCLO_KNN_PRUNED;
+  pl.grid_x = ceil_div(s, KNN_WAVES);
+  if (use_rows && nsample <= 32) {                       // the smallest bound table (R blocks per lane) that holds nblk
+    static const int r16[] = {2, 3, 5, 9, 17}, r32[] = {1, 2, 3, 5, 9};
+    const int L = nsample <= 16 ? 16 : 32;
+    const int need = ceil_div(pl.nblk, L);
+    const int *rs = L == 16 ? r16 : r32;
+    for (int i = 0; i < 5; ++i)
+      if (need <= rs[i]) {
+        pl.search = PWCLO_KNN_ROWS;
+        pl.L = L;
+        pl.R = rs[i];
+        pl.grid_x = ceil_div(s, KNN_WAVES * (64 / L));
+        break;
+      }
+  }
+  return pl;
+}
+
+// knn_point_ws_kernel_wrapper's gate: a structure for 256 <= n <= 16384 (PWCLO_KNN_MIN_N) and >= 256 queries per cloud
+// (PWCLO_KNN_MIN_S: fewer do not amortise the build).
+static bool knn_ws_applies(int b, int n, int s) { return knn_point_workspace_bytes(b, n) != 0 && s >= knn_min_s(); }
+
+extern "C" int knn_point_plan_query(int b, int n, int s, int nsample, int prebuilt, int use_rows, int *out) {
+  if (b <= 0 || n <= 0 || s <= 0 || nsample < 1 || nsample > 64 || nsample > n || out == nullptr) return -1;
+  if (prebuilt && (n < 64 || n > pwclo::KNN_MAX_SORT)) return -1;
+  if (use_rows < 0) use_rows = knn_use_rows();
+  const KnnPlan pl = knn_plan(b, n, s, nsample, prebuilt ? true : knn_ws_applies(b, n, s), use_rows != 0);
+  out[0] = pl.search; out[1] = pl.qpw; out[2] = pl.L; out[3] = pl.R; out[4] = pl.build_r; out[5] = pl.nslab;
+  out[6] = pl.nblk; out[7] = pl.grid_x;
+  return 0;
+}
+
 // Build pass alone: sorted rows + block boxes into `workspace` (knn_point_workspace_bytes(b, n) bytes) and, when
 // slab_tab != NULL, 32 ints per cloud: (padded first row, row count) of up to 16 x-slabs.
 static bool knn_build_launch(int b, int n, const float *xyz, void *workspace, int *slab_tab) {
-  const int nslab = knn_slabs(n);
-  const int nblk = (n + 63) / 64 + nslab;
+  const KnnPlan pl = knn_plan(b, n, 1, 1, true, false);   // the build depends on n alone
+  const int nslab = pl.nslab, nblk = pl.nblk;
   float4 *rows = reinterpret_cast<float4 *>(workspace);
   float4 *boxes = rows + (size_t)b * nblk * 64;
-  const int regs = ceil_div(n, KB_THREADS);
 #define KB_CASE(RR)                                                                                   \
-  hipLaunchKernelGGL(knn_build_kernel<RR>, dim3(b), dim3(KB_THREADS), 0, current_stream(), n, nslab, nblk, \
-                     xyz, rows, boxes, slab_tab);
-  if (regs <= 1) { KB_CASE(1) }
-  else if (regs <= 2) { KB_CASE(2) }
-  else if (regs <= 4) { KB_CASE(4) }
-  else if (regs <= 8) { KB_CASE(8) }
-  else { KB_CASE(16) }
+  case RR:                                                                                            \
+    hipLaunchKernelGGL(knn_build_kernel<RR>, dim3(b), dim3(KB_THREADS), 0, current_stream(), n, nslab, nblk, \
+                       xyz, rows, boxes, slab_tab);                                                   \
+    break;
+  switch (pl.build_r) {
+    KB_CASE(1) KB_CASE(2) KB_CASE(4) KB_CASE(8) KB_CASE(16)
+  }
 #undef KB_CASE
   return check_launch("knn_point(build)");
 }
@@ -836,32 +892,29 @@ static bool knn_build_launch(int b, int n, const float *xyz, void *workspace, in
 // levels search one frame's half -- round 3).  The defaults describe a structure built for exactly these b clouds.
 static void knn_search_launch(int b, int n, int s, int nsample, const float *new_xyz, int *idx, float *dist,
                               void *workspace, int first_cloud = 0, int built_b = -1) {
-  const int nslab = knn_slabs(n);
-  const int nblk = (n + 63) / 64 + nslab;
+  const KnnPlan pl = knn_plan(b, n, s, nsample, true, knn_use_rows() != 0);
+  const int nblk = pl.nblk;
   if (built_b < 0) built_b = b;
   float4 *rows = reinterpret_cast<float4 *>(workspace) + (size_t)first_cloud * nblk * 64;
   float4 *boxes = reinterpret_cast<float4 *>(workspace) + (size_t)built_b * nblk * 64 + (size_t)first_cloud * nblk * 2;
-  // K <= 32: several queries per wave (knn_rows_kernel); PWCLO_KNN_ROWS=0 keeps one query per wave (A/B switch)
-  static int use_rows = -1;
-  if (use_rows < 0) { const char *e = getenv("PWCLO_KNN_ROWS"); use_rows = e ? atoi(e) : 1; }
-  const int L = nsample <= 16 ? 16 : 32;
-  const int need = ceil_div(nblk, L);
-  static const int settle16 = knn_tune_early("PWCLO_KNN_SETTLE16", 4), settle32 = knn_tune_early("PWCLO_KNN_SETTLE32", 16);
-  const int settle_min = L == 16 ? settle16 : settle32;
+  const dim3 grid(pl.grid_x, b), block(KNN_WAVES * 64);
+  if (pl.search == PWCLO_KNN_ROWS) {
+    static const int settle16 = knn_tune_early("PWCLO_KNN_SETTLE16", 4), settle32 = knn_tune_early("PWCLO_KNN_SETTLE32", 16);
+    const int settle_min = pl.L == 16 ? settle16 : settle32;
 #define KR_CASE(LL, RR)                                                                                        \
-  if (L == LL && need <= RR) {                                                                                 \
-    hipLaunchKernelGGL((knn_rows_kernel<LL, RR>), dim3(ceil_div(s, KNN_WAVES * (64 / LL)), b), dim3(KNN_WAVES * 64), \
-                       0, current_stream(), nblk, s, nsample, rows, boxes, new_xyz, idx, dist, settle_min);    \
+  if (pl.L == LL && pl.R == RR) {                                                                              \
+    hipLaunchKernelGGL((knn_rows_kernel<LL, RR>), grid, block, 0, current_stream(), nblk, s, nsample, rows,    \
+                       boxes, new_xyz, idx, dist, settle_min);                                                 \
     check_launch("knn_point(rows)");                                                                           \
     return;                                                                                                    \
   }
-  if (use_rows && nsample <= 32) {
     KR_CASE(16, 2) KR_CASE(16, 3) KR_CASE(16, 5) KR_CASE(16, 9) KR_CASE(16, 17)
     KR_CASE(32, 1) KR_CASE(32, 2) KR_CASE(32, 3) KR_CASE(32, 5) KR_CASE(32, 9)
-  }
 #undef KR_CASE
-  hipLaunchKernelGGL(knn_pruned_kernel, dim3(ceil_div(s, KNN_WAVES), b), dim3(KNN_WAVES * 64), 0,
-                     current_stream(), nblk, s, nsample, rows, boxes, new_xyz, idx, dist);
+    PWCLO_REQUIRE(false, "knn_point(rows): no knn_rows_kernel<%d, %d>", pl.L, pl.R);
+  }
+  hipLaunchKernelGGL(knn_pruned_kernel, grid, block, 0, current_stream(), nblk, s, nsample, rows, boxes, new_xyz, idx,
+                     dist);
   check_launch("knn_point(pruned)");
 }
 
@@ -869,7 +922,7 @@ extern "C" void knn_point_ws_kernel_wrapper(int b, int n, int s, int nsample, co
                                             const float *new_xyz, int *idx, float *dist,
                                             void *workspace) {
   if (b <= 0 || s <= 0) return;
-  if (workspace == nullptr || knn_point_workspace_bytes(b, n) == 0 || s < knn_min_s()) {
+  if (workspace == nullptr || !knn_ws_applies(b, n, s)) {
     knn_point_kernel_wrapper(b, n, s, nsample, xyz, new_xyz, idx, dist);   // too few queries to amortise the build
     return;
   }
@@ -915,6 +968,6 @@ extern "C" void knn_point_prebuilt_slice_kernel_wrapper(int b, int n, int s, int
 extern "C" int knn_point_slabs(int n) { return knn_slabs(n); }
 extern "C" long long knn_point_build_bytes(int b, int n) {        // workspace of the build for ANY 64 <= n <= 16384
   if (n < 64 || n > pwclo::KNN_MAX_SORT) return 0;
-  const long long nblk = (n + 63) / 64 + knn_slabs(n);
+  const long long nblk = knn_blocks(n);
   return (long long)b * nblk * (64 * 16 + 32);
 }

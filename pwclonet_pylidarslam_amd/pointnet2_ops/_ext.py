@@ -399,6 +399,25 @@ def knn_point(nsample, xyz, new_xyz, return_dist=False, exhaustive=None):
     return (dist, idx) if return_dist else idx
 
 
+_KNN_PLAN_FIELDS = ("kernel", "qpw", "L", "R", "build_r", "nslab", "nblk", "grid_x")
+_KNN_PLAN_KERNELS = ("exhaustive", "rows", "pruned")      # PWCLO_KNN_*
+
+
+def knn_point_plan(b, n, s, nsample, prebuilt=False, use_rows=None):
+    """knn_point_plan_query: what ``knn_point`` (``prebuilt``: ``knn_build`` + ``knn_point_prebuilt[_slice]``, which take
+    any 64 <= n <= 16384 and any s) launches for xyz (b, n, 3), new_xyz (b, s, 3) -> dict of the fields documented in
+    include/pwclo_ops.h, ``kernel`` as "exhaustive" / "rows" / "pruned".  ``use_rows``: None = the PWCLO_KNN_ROWS switch
+    as the launcher reads it.  Host only: works without a GPU."""
+    import ctypes
+    out = (ctypes.c_int * 8)()
+    args = (int(b), int(n), int(s), int(nsample), int(bool(prebuilt)), -1 if use_rows is None else int(bool(use_rows)))
+    if _lib.load().knn_point_plan_query(*args, out) != 0:
+        raise ValueError("knn_point_plan_query%r" % (args,))
+    plan = dict(zip(_KNN_PLAN_FIELDS, out[:len(_KNN_PLAN_FIELDS)]))
+    plan["kernel"] = _KNN_PLAN_KERNELS[plan["kernel"]]
+    return plan
+
+
 def quat_warp(xyz, q, t):
     """Native kernel behind ``PWCLO_utils.warp``.  xyz (B,3,N), q (B,4[,1]), t (B,3[,1])."""
     B, _, N = xyz.shape

@@ -390,11 +390,16 @@ def test_quat_warp(cuda):
     torch.testing.assert_close(got, torch.tensor([1.0, 3.0, 3.0]), rtol=0, atol=1e-6)
 
 
-@pytest.mark.parametrize("k,n,s", [(32, 8192, 2048), (6, 2048, 2048), (16, 1024, 256), (1, 513, 77),
-                                   (64, 16384, 100), (8, 700, 1500)])
+@pytest.mark.parametrize("k,n,s", [(32, 8192, 2048), (6, 2048, 2048), (16, 1024, 256), (1, 513, 277),
+                                   (64, 16384, 300), (8, 700, 1500)])
 def test_knn_pruned_equals_exhaustive(cuda, k, n, s):
-    """The Morton-block pruned search (512 <= n <= 16384) returns exactly what the exhaustive
-    kernel returns, on KITTI-shaped (strongly non-uniform) clouds and with duplicated points."""
+    """The spatially pruned search (256 <= n <= 16384, >= 256 queries) returns exactly what the exhaustive
+    kernel returns, on KITTI-shaped (strongly non-uniform) clouds and with duplicated points.  The plan query
+    confirms that the first call of every case searches a structure (K = 64: knn_pruned_kernel, the others a rows
+    kernel); tests/test_gpu_knn_variants.py pins every form."""
+    plan = E.knn_point_plan(2, n, s, k)
+    assert plan["kernel"] != "exhaustive" and plan["build_r"] > 0, plan
+    assert plan["kernel"] == ("pruned" if k > 32 else "rows"), plan
     pc1, _, _, _ = synthetic.kitti_like_pair(90 + k, 8192, 2)
     base = torch.from_numpy(np.ascontiguousarray(pc1[:, :, :3]))
     reps = (n + 8191) // 8192
@@ -408,13 +413,20 @@ def test_knn_pruned_equals_exhaustive(cuda, k, n, s):
     assert torch.equal(d1, d0)
 
 
-@pytest.mark.parametrize("k,n,s", [(4, 2000, 523), (6, 2000, 523), (16, 5000, 1201), (32, 5000, 1201), (8, 16384, 600),
-                                   (32, 16000, 513), (1, 600, 700), (12, 513, 512)])
+# the rows form every case reaches (knn_rows_kernel<L, R>, asserted through the plan query)
+KNN_ROWS_SHAPES = [(4, 2000, 523, (16, 3)), (6, 2000, 523, (16, 3)), (16, 5000, 1201, (16, 9)), (32, 5000, 1201, (32, 3)),
+                   (8, 16384, 600, (16, 17)), (32, 16000, 513, (32, 9)), (1, 600, 700, (16, 2)), (12, 513, 512, (16, 2))]
+
+
+@pytest.mark.parametrize("k,n,s", [c[:3] for c in KNN_ROWS_SHAPES])
 def test_knn_rows_kernel_ties_and_ragged_shapes(cuda, k, n, s):
-    """K <= 32 with >= 512 queries runs several queries per wave (csrc/knn.hip: knn_rows_kernel, L = 16 / 32 lanes per
+    """K <= 32 with >= 256 queries runs several queries per wave (csrc/knn.hip: knn_rows_kernel, L = 16 / 32 lanes per
     query): integer-lattice clouds (exact distance ties at every rank, duplicated points: lower index first), query
-    counts that are not a multiple of the queries per wave / workgroup, every block-register case (n up to 16384),
-    against the oracle -- indices AND keys bit for bit."""
+    counts that are not a multiple of the queries per wave / workgroup, n up to 16384, against the oracle -- indices
+    AND keys bit for bit.  Each case asserts the rows form it reaches; tests/knn_cases.py holds the table that covers
+    every form and both sides of every register-count boundary."""
+    plan = E.knn_point_plan(2, n, s, k)
+    assert (plan["kernel"], (plan["L"], plan["R"])) == ("rows", dict((c[:3], c[3]) for c in KNN_ROWS_SHAPES)[(k, n, s)]), plan
     gen = torch.Generator().manual_seed(k * 100 + n)
     xyz = torch.randint(-7, 8, (2, n, 3), generator=gen).float()
     xyz[1] = (torch.rand(n, 3, generator=gen) * 2 - 1) * 25            # one lattice cloud, one random cloud
