@@ -397,6 +397,25 @@ void compact_frames_scan_kernel_wrapper(int b, int n, int cap, const int *keep, 
 void sweep_filter_compact_kernel_wrapper(int S, int R, int cap, const int *lengths, const float *sweeps, int dataset,
                                          const double *tr, float ground_z, float near, float *packed, int *counts);
 
+/* Voxel grid sampling (preprocess.grid_sample): one row per occupied voxel, the lowest-index one.
+ * q_a = rint((double)p_a / voxel) (fp64 division, half to even), h = 73856093 q_x + 19349669 q_y + 83492791 q_z in 64 bits
+ * with wraparound; a row is a winner iff no lower-index candidate row of its cloud has its h.  Rows with a non-finite
+ * coordinate or |p_a / voxel| >= 2^31 are no candidates.  One workgroup per cloud and an open-addressing table in the
+ * caller's workspace, cleared by the launch itself (nothing persists between launches; graph-capturable).
+ * Bytes of workspace for b clouds of up to n rows (8-byte aligned; 0 when b or n is out of range, n <= 2^20). */
+long long grid_sample_workspace_bytes(int b, int n);
+/* points (b,n,stride) f32 with stride 3 or 4 floats per row; lengths (b) i32 in DEVICE memory or null (all n rows; clamped
+ * to [0, n]); keep_in (b,n) i32 or null: rows with 0 are no candidates.  keep_out (b,n) i32 = 1 for the winners, 0
+ * elsewhere (all n entries written); counts (b) i32 = winners per cloud. */
+void grid_sample_keep_kernel_wrapper(int b, int n, int stride, const float *points, const int *lengths, const int *keep_in,
+                                     double voxel, void *workspace, int *keep_out, int *counts);
+/* sweep_filter_compact_kernel_wrapper with the grid between the filter and the compaction: the candidates are the rows the
+ * filter keeps, keyed on the coordinates it outputs.  workspace: grid_sample_workspace_bytes(S, R).  packed (S,cap,3): the
+ * winners in row order, then zero rows; winners (S) i32 = the number of winners, counts (S) i32 = min(winners, cap). */
+void sweep_filter_grid_compact_kernel_wrapper(int S, int R, int cap, const int *lengths, const float *sweeps, int dataset,
+                                              const double *tr, float ground_z, float near, double voxel, void *workspace,
+                                              float *packed, int *counts, int *winners);
+
 /* Training batches from raw LiDAR pairs (batches.TrainBatchBuilder), two launches per batch.
  * state (3) i64 in DEVICE memory = {seed, next step, step of the batch in flight}; random words are Philox4x32-10 with
  * key = seed and counter = (index, cloud or pair, step mod 2^32, purpose: 0 selection keys, 1 draws with replacement,

@@ -70,6 +70,10 @@ SIGNATURES = {
     "pose_head_train_backward_kernel_wrapper": ([_i, _i] + [_F] * 24, None),
     "compact_frames_scan_kernel_wrapper": ([_i, _i, _i, _F, _F, _F, _F], None),
     "sweep_filter_compact_kernel_wrapper": ([_i, _i, _i, _F, _F, _i, _F, ctypes.c_float, ctypes.c_float, _F, _F], None),
+    "grid_sample_workspace_bytes": ([_i, _i], ctypes.c_longlong),
+    "grid_sample_keep_kernel_wrapper": ([_i, _i, _i, _F, _F, _F, ctypes.c_double, _F, _F, _F], None),
+    "sweep_filter_grid_compact_kernel_wrapper": ([_i, _i, _i, _F, _F, _i, _F, ctypes.c_float, ctypes.c_float, ctypes.c_double,
+                                                 _F, _F, _F, _F], None),
     "train_batch_pose_kernel_wrapper": ([_i, _i, _i, _F, _F, _F, _F, _F, _F], None),
     "train_batch_sample_kernel_wrapper": ([_i, _i, _i, _i, _F, _F, _F, ctypes.c_float, ctypes.c_float, _F, _F, _i, _F, _F, _F,
                                            _F], None),

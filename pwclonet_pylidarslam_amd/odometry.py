@@ -48,7 +48,10 @@ class StreamingOdometry:
     ``[:lengths[s]]``, and runs filter + compaction + exact sampling to ``num_points`` (default 8192) inside the same
     prime / step graphs: one capture of each serves every length.  The clouds are bit for bit
     those of ``preprocess.frames_to_clouds(sweep[None, :length], num_points, dataset, cap=capacity)``;
-    ``survivor_counts()`` tells a caller which streams kept fewer than ``num_points`` points.
+    ``survivor_counts()`` tells a caller which streams kept fewer than ``num_points`` points.  With ``voxel_size=0.3`` (and
+    optionally ``voxel_capacity=24576``) in the dict the kept rows are grid-sampled to one per voxel ahead of the sampler
+    (``preprocess.grid_sample``); the clouds are then those of ``frames_to_clouds(...,
+    voxel_size=, voxel_capacity=)`` and ``voxel_counts()`` gives the winners per stream before the clamp.
 
     Per-stream mode (``per_stream=True``): ``step(frames, active=None, restart=None)`` and ``step_sweeps(sweeps, lengths,
     active=None, restart=None)`` take two (S,) masks, bool or integer, host sequences or device tensors (device tensors
@@ -178,6 +181,12 @@ class StreamingOdometry:
         if self._front is None or self._front.bufs is None:
             return None
         return self._front.bufs["counts"]
+
+    def voxel_counts(self):
+        """Raw mode with ``sweeps=dict(..., voxel_size=...)``: (S,) int32 device view of the last sweep's voxel winners per
+        stream, not clamped (above ``voxel_capacity`` the later winners were dropped; ``survivor_counts()`` is the clamped
+        number).  None without a grid or before the first sweep."""
+        return None if self._front is None else self._front.voxel_counts()
 
     def step(self, frames, active=None, restart=None):
         if self.per_stream:

@@ -14,7 +14,13 @@ transform, ground = ``z < -(1.73 - 0.3)``, range test on x and y (``kitti360_fil
 a whole batch of equally long frames ``(b, n, 4)``; ``compact`` packs every frame's survivors to the front
 of a zero-padded ``(b, cap, 3)`` batch (zero rows are never selected by the sampler, sampling_gpu.cu:100-101)
 and ``frames_to_clouds`` chains filter -> compaction -> one batched furthest-point-sampling call.
+
+``grid_sample`` is the reference's voxel grid filter (``slam/common/pointcloud.py:105-130``): one row per
+occupied voxel, the lowest-index one.  It is opt-in (``voxel_size=``) in ``frames_to_clouds`` and the raw-sweep front end.
 """
+import math
+import numbers
+
 import numpy as np
 import torch
 
@@ -73,19 +79,96 @@ def compact(xyz, keep, cap=None):
     return out, counts
 
 
-def frames_to_clouds(points, npoints, dataset="kitti", tr=None, near_threshold=30.0, cap=None):
+def _voxel_args(voxel_size, voxel_capacity, capacity, what):
+    """Host check of the two grid arguments -> (voxel_size as a float or None, the width of the packed batch)."""
+    if voxel_size is None:
+        if voxel_capacity is not None:
+            raise ValueError("%s: voxel_capacity=%r needs a voxel_size" % (what, voxel_capacity))
+        return None, capacity
+    if isinstance(voxel_size, bool) or not isinstance(voxel_size, numbers.Real) or not math.isfinite(voxel_size) \
+            or not voxel_size > 0:
+        raise ValueError("%s: voxel_size=%r must be a finite positive number" % (what, voxel_size))
+    if voxel_capacity is None:
+        return float(voxel_size), capacity
+    if isinstance(voxel_capacity, bool) or not isinstance(voxel_capacity, numbers.Integral) \
+            or not 1 <= voxel_capacity <= capacity:
+        raise ValueError("%s: voxel_capacity=%r outside [1, capacity=%d]" % (what, voxel_capacity, capacity))
+    return float(voxel_size), int(voxel_capacity)
+
+
+def grid_sample_workspace(b, n, device):
+    """The open-addressing table ``grid_sample`` and the raw front end deduplicate through: b clouds of up to n rows."""
+    nbytes = _lib.load().grid_sample_workspace_bytes(b, n)
+    if nbytes <= 0:
+        raise ValueError("grid_sample: no workspace for %d clouds of %d rows (at most 2**20 rows per cloud)" % (b, n))
+    return torch.empty((nbytes // 8,), dtype=torch.int64, device=device)
+
+
+def grid_sample(points, voxel_size, lengths=None, keep=None, workspace=None):
+    """Voxel grid sampling (the reference's ``grid_sample`` filter): points (n, 3|4) or (b, n, 3|4)
+    f32 cuda -> (keep (b, n) i32: 1 for the lowest-index row of every occupied voxel, counts (b,) i32).  A voxel is the hash
+    73856093 qx + 19349669 qy + 83492791 qz (64 bits) of q = rint(double(p) / voxel_size); rows with a non-finite
+    coordinate or |p / voxel_size| >= 2^31 are dropped.  ``lengths`` (b,) device integers: only rows [:lengths[c]] of
+    cloud c take part; ``keep`` (b, n) i32: only rows with keep != 0 take part (the filters' masks).  The result composes
+    with ``compact``.  ``workspace``: a ``grid_sample_workspace(b, n, device)`` to reuse; allocated here otherwise."""
+    v, _ = _voxel_args(voxel_size, None, None, "grid_sample")
+    if v is None:
+        raise ValueError("grid_sample: voxel_size=None must be a finite positive number")
+    if not points.is_cuda:
+        raise RuntimeError("CPU not supported")
+    if points.dim() == 2:
+        points = points.unsqueeze(0)
+    if points.dim() != 3 or points.size(-1) not in (3, 4) or points.dtype != torch.float32:
+        raise ValueError("grid_sample: points must be float32 (n, 3|4) or (b, n, 3|4), got %s %s"
+                         % (points.dtype, tuple(points.shape)))
+    points = points.contiguous()
+    b, n, c = points.shape
+    dev = points.device
+    keep_out = torch.zeros((b, n), dtype=torch.int32, device=dev)
+    counts = torch.zeros((b,), dtype=torch.int32, device=dev)
+    if b == 0 or n == 0:
+        return keep_out, counts
+    if lengths is not None:
+        if lengths.shape != (b,) or not lengths.is_cuda or lengths.dtype.is_floating_point or lengths.dtype == torch.bool:
+            raise ValueError("grid_sample: lengths must be (%d,) integers on the device" % b)
+        lengths = lengths.to(torch.int32).contiguous()
+    if keep is not None:
+        if keep.dim() == 1:
+            keep = keep.unsqueeze(0)
+        if keep.shape != (b, n) or keep.dtype != torch.int32 or not keep.is_cuda:
+            raise ValueError("grid_sample: keep must be int32 (%d, %d) on the device" % (b, n))
+        keep = keep.contiguous()
+    if workspace is None:
+        workspace = grid_sample_workspace(b, n, dev)
+    elif workspace.numel() * workspace.element_size() < _lib.load().grid_sample_workspace_bytes(b, n):
+        raise ValueError("grid_sample: the workspace is smaller than grid_sample_workspace(%d, %d)" % (b, n))
+    _lib.call("grid_sample_keep_kernel_wrapper", dev, b, n, c, points.data_ptr(),
+              lengths.data_ptr() if lengths is not None else 0, keep.data_ptr() if keep is not None else 0, v,
+              workspace.data_ptr(), keep_out.data_ptr(), counts.data_ptr())
+    return keep_out, counts
+
+
+def frames_to_clouds(points, npoints, dataset="kitti", tr=None, near_threshold=30.0, cap=None, voxel_size=None,
+                     voxel_capacity=None):
     """A batch of raw frames (b,n,4) -> (clouds (b,npoints,3) f32, counts (b,) i32), deterministic
     (furthest point sampling of each frame's survivors; BASELINE.json configs[4]).  A frame with fewer
     than ``npoints`` survivors gets index-0 repeats past its count exactly as the reference's sampler
     returns them for m > #valid; check ``counts`` when that matters (the dataset's own rule for that case
-    is a random draw with replacement, see ``kitti_frame_to_cloud``)."""
+    is a random draw with replacement, see ``kitti_frame_to_cloud``).  ``voxel_size``: ``grid_sample`` of the filter's
+    survivors ahead of the sampler (one point per voxel, frame order); the packed batch is then ``voxel_capacity`` wide
+    (default ``cap``) and ``counts`` are the rows that reach the sampler."""
     assert points.dim() == 3
+    width = points.shape[1] if cap is None else int(cap)
+    voxel_size, width = _voxel_args(voxel_size, voxel_capacity, width, "frames_to_clouds")
     if dataset == "kitti":
         xyz, keep = transform_filter(points, tr)
     elif dataset == "kitti360":
         xyz, keep = kitti360_filter(points, near_threshold)
     else:
         raise ValueError(f"unknown dataset {dataset!r}")
+    if voxel_size is not None:
+        keep, _ = grid_sample(xyz, voxel_size, keep=keep)
+        cap = width
     packed, counts = compact(xyz, keep, cap)
     idx = _ext.furthest_point_sampling(packed, npoints)
     clouds = torch.gather(packed, 1, idx.long().unsqueeze(-1).expand(-1, -1, 3))
@@ -129,25 +212,33 @@ class SweepFrontEnd:
     ``sweep_filter_compact_kernel`` (filter + compaction of every stream's ``[:length]`` rows, zero rows up to
     ``capacity``, lengths read from the device), then the exact sampler over the (S, capacity, 3) batch writing the
     sampled coordinates itself (no gather).  A captured graph of ``run()`` therefore serves every length up to
-    ``capacity``; ``load()`` is the only per-frame host work (two copies).  Host-side checks only until ``load``."""
+    ``capacity``; ``load()`` is the only per-frame host work (two copies).  Host-side checks only until ``load``.
+
+    ``voxel_size``: the first launch becomes ``sweep_filter_grid_compact_kernel`` (filter, then one row per occupied voxel
+    of the kept rows as ``grid_sample`` chooses them, then the compaction), and the packed batch is ``voxel_capacity`` wide
+    (default ``capacity``; 1 <= voxel_capacity <= capacity): that width, not ``capacity``, decides the sampler kernel, its
+    buffers and ``sampler_max_clouds``.  Winners beyond it are dropped in row order; ``voxel_counts()`` is the unclamped
+    number per stream.  The clouds are those of ``frames_to_clouds(..., cap=capacity, voxel_size=, voxel_capacity=)``."""
 
     def __init__(self, streams, npoints, dataset="kitti360", capacity=131072, tr=None, near_threshold=30.0,
-                 ground_z=KITTI360_GROUND_Z):
+                 ground_z=KITTI360_GROUND_Z, voxel_size=None, voxel_capacity=None):
         if dataset not in ("kitti", "kitti360"):
             raise ValueError("sweeps: unknown dataset %r (\"kitti\" or \"kitti360\")" % (dataset,))
         capacity = int(capacity)
         if not 1 <= capacity < SWEEP_CAPACITY_LIMIT:
             raise ValueError("sweeps: capacity=%d outside [1, %d): at or above the sampler's index limit"
                              % (capacity, SWEEP_CAPACITY_LIMIT))
-        per = sampler_max_clouds(capacity)
+        voxel_size, width = _voxel_args(voxel_size, voxel_capacity, capacity, "sweeps")
+        per = sampler_max_clouds(width)
         if per is not None and streams > per:
             raise ValueError("sweeps: %d streams of capacity %d need %d sampler workgroups each; one plain launch keeps "
                              "only %d such clouds co-resident (fewer streams or a smaller capacity)"
-                             % (streams, capacity, -(-capacity // _COOP_POINTS), per))
+                             % (streams, width, -(-width // _COOP_POINTS), per))
         if dataset == "kitti" and tr is None:
             raise ValueError('sweeps: dataset="kitti" needs the calibration tr ((3,4) or (S,3,4))')
         self.streams, self.npoints, self.dataset, self.capacity = int(streams), int(npoints), dataset, capacity
         self.near_threshold, self.ground_z = float(near_threshold), float(ground_z)
+        self.voxel_size, self.width = voxel_size, width        # width of the packed batch: what the sampler sees
         self._tr_host = _calibration(tr, self.streams) if dataset == "kitti" else None
         self.bufs = None
 
@@ -214,14 +305,22 @@ class SweepFrontEnd:
         fused.masked_copy([(b["sweeps"].data_ptr(), src.data_ptr(), rows), (b["lengths"].data_ptr(), new_len.data_ptr(), 4)],
                           active, dst_strides=[cap * 16, 4], src_strides=[rows, 4])
 
+    def voxel_counts(self):
+        """(S,) int32 device view: every stream's voxel winners in the last sweep, not clamped to ``voxel_capacity``
+        (``bufs["counts"]`` is the clamped number, the rows that reach the sampler).  None without a grid or before ``load``."""
+        return None if self.bufs is None else self.bufs.get("winners")
+
     def _alloc(self, device):
-        S, cap, m = self.streams, self.capacity, self.npoints
+        S, rows, cap, m = self.streams, self.capacity, self.width, self.npoints
         e = lambda shape, dt: torch.empty(shape, dtype=dt, device=device)
-        b = dict(sweeps=torch.zeros((S, cap, 4), dtype=torch.float32, device=device), lengths=e((S,), torch.int32),
+        b = dict(sweeps=torch.zeros((S, rows, 4), dtype=torch.float32, device=device), lengths=e((S,), torch.int32),
                  packed=e((S, cap, 3), torch.float32), counts=torch.zeros((S,), dtype=torch.int32, device=device),
                  idx=e((S, m), torch.int32), tr=None)
         if self.dataset == "kitti":
             b["tr"] = self._tr_host.to(device)
+        if self.voxel_size is not None:
+            b["grid_ws"] = grid_sample_workspace(S, rows, device)
+            b["winners"] = torch.zeros((S,), dtype=torch.int32, device=device)
         if cap > _SMALL_CLOUD:
             b["tmp"] = e((S, cap), torch.float32)          # the cooperative sampler's exchange workspace
         if cap >= _SORTED_CLOUD:
@@ -233,12 +332,17 @@ class SweepFrontEnd:
 
     def run(self):
         """Filter + compaction + sampling of the loaded sweeps -> a fresh (S, npoints, 3) contiguous fp32 batch."""
-        b, S, cap, m = self.bufs, self.streams, self.capacity, self.npoints
+        b, S, cap, m = self.bufs, self.streams, self.width, self.npoints
         dev = b["packed"].device
         p = lambda t: t.data_ptr() if t is not None else 0
-        _lib.call("sweep_filter_compact_kernel_wrapper", dev, S, cap, cap, p(b["lengths"]), p(b["sweeps"]),
-                  0 if self.dataset == "kitti" else 1, p(b["tr"]), self.ground_z, self.near_threshold, p(b["packed"]),
-                  p(b["counts"]))
+        if self.voxel_size is None:
+            _lib.call("sweep_filter_compact_kernel_wrapper", dev, S, cap, cap, p(b["lengths"]), p(b["sweeps"]),
+                      0 if self.dataset == "kitti" else 1, p(b["tr"]), self.ground_z, self.near_threshold, p(b["packed"]),
+                      p(b["counts"]))
+        else:
+            _lib.call("sweep_filter_grid_compact_kernel_wrapper", dev, S, self.capacity, cap, p(b["lengths"]), p(b["sweeps"]),
+                      0 if self.dataset == "kitti" else 1, p(b["tr"]), self.ground_z, self.near_threshold, self.voxel_size,
+                      p(b["grid_ws"]), p(b["packed"]), p(b["counts"]), p(b["winners"]))
         clouds = torch.empty((S, m, 3), dtype=torch.float32, device=dev)
         if cap >= _SORTED_CLOUD:
             _lib.call("fps_spatial_order_kernel_wrapper", dev, S, cap, p(b["packed"]), p(b["sorted"]), p(b["perm"]),

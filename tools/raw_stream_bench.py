@@ -12,8 +12,13 @@ front end (near 30 m), capacity 131072, 8192 points.  A long stream plays one ge
 (c) ``sweep_filter_compact_kernel`` alone (HIP events around 50 back-to-back launches) at S = 1 and S = 8.
 Modes alternate repeat by repeat; medians over frames per repeat, then median / spread over repeats.
 Check: the streamed rows equal pair mode's bit for bit (the pair forward is the streaming contract's reference).
+(d) ``--voxel-size V [--voxel-capacity C]``: the grid-sampled front end against the plain one, in
+    this process and alternated repeat by repeat: kept rows and voxel winners per generated sweep (at V and at 0.1 .. 0.5 m),
+    ``sweep_filter_grid_compact_kernel`` against ``sweep_filter_compact_kernel`` alone, S = 1 ms per frame and S = 8
+    frames/s of ``step_sweeps`` without a grid, with the grid at ``voxel_capacity = capacity``, and with
+    ``voxel_capacity = C``.
 
-    python tools/raw_stream_bench.py [--frames F] [--repeats R] [--steps8 K]
+    python tools/raw_stream_bench.py [--frames F] [--repeats R] [--steps8 K] [--voxel-size V [--voxel-capacity C]]
 """
 import argparse
 import json
@@ -53,7 +58,11 @@ def main():
     ap.add_argument("--base", type=int, default=12, help="sweeps generated; the streams bounce through them")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--steps8", type=int, default=10, help="steps per timed region at S = 8")
+    ap.add_argument("--voxel-size", type=float, default=None, help="also measure the grid-sampled front end at this size")
+    ap.add_argument("--voxel-capacity", type=int, default=None, help="with --voxel-size: a packed width to measure as well")
     a = ap.parse_args()
+    if a.voxel_capacity is not None and a.voxel_size is None:
+        ap.error("--voxel-capacity needs --voxel-size")
     dev = torch.device("cuda:0")
     base = [torch.from_numpy(s).to(dev) for s in synthetic.raw_sweep_sequence(2024, a.base)[0]]
     period = 2 * (a.base - 1)
@@ -156,10 +165,88 @@ def main():
                           b["counts"].data_ptr())
         launches()
         res["sweep_filter_compact_ms_" + name] = _stats([_ms(launches)[0] / 50 for _ in range(5)])
+    if a.voxel_size is not None:
+        _grid_section(a, res, dev, net, base, order, batches, so, so8)
     res["sampler_workgroups_per_pose"] = {"stream": -(-CAP // 16384), "pair": 2 * -(-CAP // 16384)}
     torch.cuda.synchronize(dev)
     res["last_error"] = int(_lib.load().pwclo_last_error())
     print(json.dumps(res))
+
+
+def _grid_section(a, res, dev, net, base, order, batches, so, so8):
+    """Section (d): the plain front end (``so`` / ``so8``, already warm) against the grid-sampled one, alternated."""
+    V, S = a.voxel_size, 8
+    widths = [CAP] + ([a.voxel_capacity] if a.voxel_capacity is not None else [])
+    cfg = dict(dataset="kitti360", capacity=CAP, near_threshold=NEAR, voxel_size=V)
+    # kept rows and winners of every generated sweep (the synthetic scene: planes, not real LiDAR)
+    sizes = sorted({V, 0.1, 0.2, 0.3, 0.5})
+    winners = {"%g" % v: [] for v in sizes}
+    kept = []
+    for sw in base:
+        xyz, keep = preprocess.kitti360_filter(sw[None], NEAR)
+        kept.append(int(keep.sum()))
+        for v in sizes:
+            winners["%g" % v].append(int(preprocess.grid_sample(xyz, v, keep=keep)[1][0]))
+    res["voxel_size"], res["voxel_capacity"] = V, a.voxel_capacity
+    res["kept_rows_per_sweep"] = kept
+    res["voxel_winners_per_sweep"] = winners
+
+    def s1_pass(obj):
+        obj.reset()
+        obj.step_sweeps(base[order[0]][None], [base[order[0]].shape[0]])
+        ts = [_ms(lambda: obj.step_sweeps(base[order[k]][None], [base[order[k]].shape[0]]))[0] for k in range(1, a.frames)]
+        return sorted(ts)[len(ts) // 2]
+
+    def s8_pass(obj):
+        obj.reset()
+        obj.step_sweeps(*batches[0])
+        t = _ms(lambda: [obj.step_sweeps(*batches[k]) for k in range(1, a.steps8 + 1)])[0]
+        return S * a.steps8 / (t / 1e3)
+
+    one = {"none": so}
+    eight = {"none": so8}
+    for w in widths:
+        one["width_%d" % w] = StreamingOdometry(net, streams=1, max_frames=a.frames + 1, graph=True,
+                                                sweeps=dict(cfg, voxel_capacity=w))
+        eight["width_%d" % w] = StreamingOdometry(net, streams=S, max_frames=a.steps8 + 2, graph=True,
+                                                  sweeps=dict(cfg, voxel_capacity=w))
+    t1 = {k: [] for k in one}
+    t8 = {k: [] for k in eight}
+    for k in one:                                                             # warm-up and capture
+        s1_pass(one[k]), s8_pass(eight[k])
+    for _ in range(a.repeats):
+        for k in one:
+            t1[k].append(s1_pass(one[k]))
+        for k in eight:
+            t8[k].append(s8_pass(eight[k]))
+    res["grid_s1_ms_per_frame"] = {k: _stats(v) for k, v in t1.items()}
+    res["grid_s8_frames_per_s"] = {k: _stats(v) for k, v in t8.items()}
+    res["grid_s1_overflowed"] = {k: bool((one[k].voxel_counts() > one[k]._front.width).any()) for k in one if k != "none"}
+
+    # the first launch alone: filter + compaction against filter + grid + compaction, on the sweeps loaded last
+    tk = {}
+    for name, plain, grid in (("s1", so._front, one["width_%d" % CAP]._front), ("s8", so8._front, eight["width_%d" % CAP]._front)):
+        b, g = plain.bufs, grid.bufs
+
+        def old():
+            for _ in range(50):
+                _lib.call("sweep_filter_compact_kernel_wrapper", dev, plain.streams, CAP, CAP, b["lengths"].data_ptr(),
+                          b["sweeps"].data_ptr(), 1, 0, plain.ground_z, plain.near_threshold, b["packed"].data_ptr(),
+                          b["counts"].data_ptr())
+
+        def new():
+            for _ in range(50):
+                _lib.call("sweep_filter_grid_compact_kernel_wrapper", dev, grid.streams, CAP, CAP, g["lengths"].data_ptr(),
+                          g["sweeps"].data_ptr(), 1, 0, grid.ground_z, grid.near_threshold, V, g["grid_ws"].data_ptr(),
+                          g["packed"].data_ptr(), g["counts"].data_ptr(), g["winners"].data_ptr())
+        old(), new()
+        t_old, t_new = [], []
+        for _ in range(a.repeats):
+            t_old.append(_ms(old)[0] / 50)
+            t_new.append(_ms(new)[0] / 50)
+        tk[name] = {"sweep_filter_compact_ms": _stats(t_old), "sweep_filter_grid_compact_ms": _stats(t_new),
+                    "rows": g["lengths"].tolist(), "winners": g["winners"].tolist()}
+    res["grid_first_launch"] = tk
 
 
 if __name__ == "__main__":
