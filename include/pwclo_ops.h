@@ -416,6 +416,44 @@ void sweep_filter_grid_compact_kernel_wrapper(int S, int R, int cap, const int *
                                               const double *tr, float ground_z, float near, double voxel, void *workspace,
                                               float *packed, int *counts, int *winners);
 
+/* Motion compensation of raw sweeps (preprocess.deskew; the reference's `distortion` filter fed by its
+ * constant-velocity initialisation).  For one cloud with fp32 coordinates p_i as the filter outputs them, a time tau_i per
+ * row and a motion given as a pose row [tx ty tz qw qx qy qz] (fp32):
+ *   1. candidates are the rows the filter keeps; the keep decision is taken on the coordinates BEFORE de-skewing, so masks
+ *      and survivor counts are those without the step;
+ *   2. tau_min / tau_max = minimum / maximum over the candidates below the cloud's length whose time is finite;
+ *      alpha_i = (tau_i - tau_min) / (tau_max - tau_min) in fp64; alpha_i = 0 for every row if tau_max == tau_min or no
+ *      candidate has a finite time, and for a candidate whose own time is not finite; other rows have no influence;
+ *   3. q = (w, x, y, z) in fp64, nq = |q|^2; nq < 1e-8: the identity rotation; else q^ = q / sqrt(nq), negated if w < 0
+ *      (the shortest arc), theta = 2 atan2(|v|, w), axis k = v / |v| (any unit vector if |v| = 0); R(alpha) = the rotation
+ *      by alpha * theta about k (= SciPy's Slerp([0, 1], [I, R])(alpha) for R = quat2mat(q));
+ *   4. p'_i = R(alpha_i) p_i + alpha_i t, in fp64 from the fp32 inputs, rounded to fp32 once;
+ *   5. a row with alpha_i = 0, and every row of a cloud whose motion is the identity (theta = 0, t = 0), keeps p_i's bits;
+ *   6. in the front end: filter -> de-skew -> voxel grid (if any) -> compaction -> sampler.
+ * The op alone: points (b,n,stride) f32 with stride 3 or 4, times (b,n) f64, motion (b,7) f32, lengths (b) i32 in DEVICE
+ * memory or null (all n rows; clamped to [0, n]), keep_in (b,n) i32 or null (all rows).  xyz (b,n,3) f32, all n rows
+ * written; non-candidates pass through unchanged.  One workgroup per cloud; graph-capturable. */
+void deskew_rows_kernel_wrapper(int b, int n, int stride, const float *points, const double *times, const float *motion,
+                                const int *lengths, const int *keep_in, float *xyz);
+/* sweep_filter_compact_kernel_wrapper with the de-skew between the filter and the compaction: times (S,R) f64 with row
+ * stride R, motion (S,7) f32 in DEVICE memory (read by the launch: a captured graph follows it).  restart, have_prev (S)
+ * i32 or null (per-stream mode): stream s gets the identity motion when restart[s] != 0 or have_prev[s] == 0.  Same buffer
+ * contract: all of packed[s, :cap] is written, survivors then zeros; counts as there. */
+void sweep_filter_deskew_compact_kernel_wrapper(int S, int R, int cap, const int *lengths, const float *sweeps, int dataset,
+                                                const double *tr, float ground_z, float near, const double *times,
+                                                const float *motion, const int *restart, const int *have_prev,
+                                                float *packed, int *counts);
+/* sweep_filter_grid_compact_kernel_wrapper on the de-skewed coordinates (the grid sees what the network sees). */
+void sweep_filter_deskew_grid_compact_kernel_wrapper(int S, int R, int cap, const int *lengths, const float *sweeps,
+                                                     int dataset, const double *tr, float ground_z, float near,
+                                                     const double *times, const float *motion, const int *restart,
+                                                     const int *have_prev, double voxel, void *workspace, float *packed,
+                                                     int *counts, int *winners);
+/* After the append of a streaming step: motion[s] (S,7) f32 = the row at rows + s * row_stride floats (the level-1 pose row
+ * of the pair just registered), or the identity (0,0,0, 1,0,0,0) when rows is null (after a prime).  active (S) i32 or
+ * null (all): streams with active[s] == 0 keep their motion.  One workgroup, one thread per stream (S <= 1024). */
+void stream_motion_handover_kernel_wrapper(int S, const int *active, const float *rows, int row_stride, float *motion);
+
 /* Training batches from raw LiDAR pairs (batches.TrainBatchBuilder), two launches per batch.
  * state (3) i64 in DEVICE memory = {seed, next step, step of the batch in flight}; random words are Philox4x32-10 with
  * key = seed and counter = (index, cloud or pair, step mod 2^32, purpose: 0 selection keys, 1 draws with replacement,

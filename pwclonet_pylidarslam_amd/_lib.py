@@ -74,6 +74,12 @@ SIGNATURES = {
     "grid_sample_keep_kernel_wrapper": ([_i, _i, _i, _F, _F, _F, ctypes.c_double, _F, _F, _F], None),
     "sweep_filter_grid_compact_kernel_wrapper": ([_i, _i, _i, _F, _F, _i, _F, ctypes.c_float, ctypes.c_float, ctypes.c_double,
                                                  _F, _F, _F, _F], None),
+    "deskew_rows_kernel_wrapper": ([_i, _i, _i, _F, _F, _F, _F, _F, _F], None),
+    "sweep_filter_deskew_compact_kernel_wrapper": ([_i, _i, _i, _F, _F, _i, _F, ctypes.c_float, ctypes.c_float, _F, _F, _F,
+                                                   _F, _F, _F], None),
+    "sweep_filter_deskew_grid_compact_kernel_wrapper": ([_i, _i, _i, _F, _F, _i, _F, ctypes.c_float, ctypes.c_float, _F, _F,
+                                                        _F, _F, ctypes.c_double, _F, _F, _F, _F], None),
+    "stream_motion_handover_kernel_wrapper": ([_i, _F, _F, _i, _F], None),
     "train_batch_pose_kernel_wrapper": ([_i, _i, _i, _F, _F, _F, _F, _F, _F], None),
     "train_batch_sample_kernel_wrapper": ([_i, _i, _i, _i, _F, _F, _F, ctypes.c_float, ctypes.c_float, _F, _F, _i, _F, _F, _F,
                                            _F], None),

@@ -51,7 +51,14 @@ class StreamingOdometry:
     ``survivor_counts()`` tells a caller which streams kept fewer than ``num_points`` points.  With ``voxel_size=0.3`` (and
     optionally ``voxel_capacity=24576``) in the dict the kept rows are grid-sampled to one per voxel ahead of the sampler
     (``preprocess.grid_sample``); the clouds are then those of ``frames_to_clouds(...,
-    voxel_size=, voxel_capacity=)`` and ``voxel_counts()`` gives the winners per stream before the clamp.
+    voxel_size=, voxel_capacity=)`` and ``voxel_counts()`` gives the winners per stream before the clamp.  With
+    ``deskew=True`` in the dict every sweep is motion-compensated on the device (``preprocess.deskew``, DESIGN.md section
+    20) before grid, compaction and sampler: ``step_sweeps(sweeps, lengths, times=...)`` then needs the rows' times, (S, R)
+    floating on the sweeps' device (and refuses them otherwise), and the motion is the constant-velocity prior, the
+    level-1 pose row this stream registered last: the identity for the first two sweeps of a sequence, the row of pair
+    (k-2, k-1) for sweep k.  It lives in a device buffer written after the append, inside the graphs; ``motion()`` shows it.
+    Per-stream mode: a stream that primes (restart, or no previous frame) and its next sweep get the identity, an idle
+    stream keeps its motion, ``reset()`` / ``reset(streams=...)`` return the streams to the identity.
 
     Per-stream mode (``per_stream=True``): ``step(frames, active=None, restart=None)`` and ``step_sweeps(sweeps, lengths,
     active=None, restart=None)`` take two (S,) masks, bool or integer, host sequences or device tensors (device tensors
@@ -157,6 +164,7 @@ class StreamingOdometry:
                 self.set_calibration(tr)
             if self._have_prev is not None:
                 self._have_prev.mul_(1 - mask.to(self._have_prev.device))
+            self._reset_motion(mask)
             return
         if tr is not None:
             self.set_calibration(tr)
@@ -167,6 +175,26 @@ class StreamingOdometry:
         self._prev = None
         if self._overflow is not None:
             self._overflow.zero_()
+        self._reset_motion(None)
+
+    def _reset_motion(self, mask):
+        """The identity motion for the streams of ``mask`` ((S,) int32 0 / 1, anywhere; None: all).  No sync."""
+        motion = self.motion()
+        if motion is None:
+            return
+        ident = motion.new_tensor(preprocess.IDENTITY_MOTION).expand_as(motion)
+        if mask is None:
+            motion.copy_(ident)
+        else:
+            motion.copy_(torch.where(mask.to(motion.device).ne(0).unsqueeze(1), ident, motion))
+
+    def motion(self):
+        """Raw mode with ``deskew=True``: (S, 7) fp32 device view of the pose rows [tx ty tz qw qx qy qz] the streams' next
+        sweeps will be de-skewed with (a stream that primes on that sweep gets the identity whatever its row holds).  None
+        without ``deskew`` or before the first sweep."""
+        if self._front is None or self._front.bufs is None:
+            return None
+        return self._front.bufs.get("motion")
 
     def set_calibration(self, tr):
         """Raw KITTI mode: replace the calibration, (3,4) / (4,4) for all streams or (S,3,4) / (S,4,4) per stream.  It lives
@@ -211,24 +239,27 @@ class StreamingOdometry:
         self.frames_seen += 1
         return pose
 
-    def step_sweeps(self, sweeps, lengths, active=None, restart=None):
+    def step_sweeps(self, sweeps, lengths, times=None, active=None, restart=None):
         """Raw mode: sweeps (S, R <= capacity, 4) fp32 on the GPU, lengths (S,) host integers in [1, R] or a device
         integer tensor (read on the device; clamped to [0, R] there) -> pose as ``step``.  The host copies the rows
-        ``[:R]`` and the lengths into static buffers; filter, compaction and sampling run inside the captured graphs."""
+        ``[:R]`` and the lengths into static buffers; filter, compaction and sampling run inside the captured graphs.
+        ``times`` (S, R) floating, on the sweeps' device: the rows' timestamps, required iff the stream was built with
+        ``deskew=True`` (ValueError otherwise, before any launch)."""
         what = "StreamingOdometry"
         front = self._front
         if front is None:
             raise RuntimeError("%s: step_sweeps needs raw mode (StreamingOdometry(..., sweeps=dict(dataset=..., "
                                "capacity=...)))" % what)
+        front.check_times(times, sweeps, what)
         if self.per_stream:
-            return self._step_sweeps_masked(sweeps, lengths, active, restart)
+            return self._step_sweeps_masked(sweeps, lengths, times, active, restart)
         if active is not None or restart is not None:
             raise ValueError("%s: active / restart masks need per_stream=True" % what)
         self._check_room(what)
         host_lengths = front.check(sweeps, lengths, what)
         self._check_net(sweeps, what)
         fused = self._begin(sweeps.device)
-        front.load(sweeps, lengths, host_lengths)
+        front.load(sweeps, lengths, host_lengths, times)
         prime = self.frames_seen == 0
         if self.graph:
             entry = self._graphs.get("sweeps")
@@ -281,9 +312,11 @@ class StreamingOdometry:
         if prime:
             self._prev = fused.stream_prime(frames, self.num_points)
             self._append(None)
+            self._hand_motion(None)
             return None
         pose, self._prev = fused.stream_step(self._prev, frames, self.num_points)
         self._append(pose)
+        self._hand_motion(pose)
         return pose
 
     def _view(self, buf, stream=None):
@@ -320,6 +353,15 @@ class StreamingOdometry:
                   int(pose is None), _p(rows), int(rows.stride(0)) if rows is not None else 0, _p(self._rel),
                   _p(self._abs), _p(self._count), _p(self._overflow))
 
+    def _hand_motion(self, pose, active=None):
+        """Raw mode with ``deskew``, after the append, one launch: the motion of the streams' next sweeps = the level-1
+        rows of ``pose`` (S, 4, 7), or the identity after a prime (pose None); streams with ``active[s] == 0`` keep theirs."""
+        motion = self.motion()
+        if motion is None:
+            return
+        _lib.call("stream_motion_handover_kernel_wrapper", motion.device, self.streams, _p(active), _p(pose),
+                  int(pose.stride(0)) if pose is not None else 0, _p(motion))
+
     def _warm(self, fn):
         """Allocator warm-up and one-time kernel attributes on a side stream, as ``GraphedForward`` does."""
         dev = self._rel.device
@@ -355,6 +397,7 @@ class StreamingOdometry:
             def prime_body():
                 self._slot.copy_frame1_(fused.stream_prime(source(), n))
                 self._append(None)
+                self._hand_motion(None)
             entry["prime"] = self._capture(prime_body)[0]
         if not prime and entry["step"] is None:
             self._warm(lambda: fused.stream_step(self._slot, source(), n))
@@ -362,6 +405,7 @@ class StreamingOdometry:
             def step_body():
                 pose, new = fused.stream_step(self._slot, source(), n)
                 self._append(pose)
+                self._hand_motion(pose)
                 # The handover: every branch of the pair stage that reads the previous frame (the set-upconvs on side
                 # streams included) has been joined into this stream by now, so the copy is ordered after them.
                 self._slot.copy_frame1_(new)
@@ -442,6 +486,7 @@ class StreamingOdometry:
         stage has joined its side streams by the time it returns)."""
         pose, new = fused.stream_step(self._slot, source(), self.num_points)
         self._append_masked(pose)
+        self._hand_motion(pose, self._active)          # primed streams' rows are the identity by now
         self._slot.copy_frame1_masked_(new, self._active)
         return pose
 
@@ -492,7 +537,7 @@ class StreamingOdometry:
         self.frames_seen += 1
         return pose
 
-    def _step_sweeps_masked(self, sweeps, lengths, active, restart):
+    def _step_sweeps_masked(self, sweeps, lengths, times, active, restart):
         what = "StreamingOdometry"
         front = self._front
         self._check_room(what)
@@ -505,6 +550,9 @@ class StreamingOdometry:
                 idle = torch.from_numpy(~host).to(sweeps.device)
                 sweeps = sweeps.clone()
                 sweeps[idle] = sweeps[j]
+                if times is not None:
+                    times = times.clone()
+                    times[idle] = times[j]
                 if host_lengths is None:
                     lengths = lengths.clone()
                     lengths[idle] = lengths[j]
@@ -512,10 +560,12 @@ class StreamingOdometry:
                     host_lengths = [v if a else host_lengths[j] for v, a in zip(host_lengths, host)]
         fused = self._begin(sweeps.device)
         self._load_masks(act, rst)
+        if front.deskew:
+            front.stream_words = (self._restart, self._have_prev)      # read by the front end's launch, on the device
         if front.bufs is None:
-            front.load(sweeps, lengths, host_lengths)
+            front.load(sweeps, lengths, host_lengths, times)
         else:
-            front.load_masked(sweeps, lengths, host_lengths, self._active)
+            front.load_masked(sweeps, lengths, host_lengths, self._active, times)
         store = self._graphs if self.graph else self._static
         entry = store.get("sweeps")
         if entry is None:
@@ -534,7 +584,10 @@ class PWCLONetOdometry:
     (quat2mat of the level-1 row, not inverted).  Frames need at least ``num_points`` of the prediction config points;
     the first ``num_points`` are used.  With ``sweeps=dict(dataset=..., capacity=..., ...)`` (``StreamingOdometry``'s raw
     mode) ``data_dict["numpy_pc"]`` is instead a raw (n, 4) sweep of any n in [1, capacity], filtered and sampled to
-    ``num_points`` on the device."""
+    ``num_points`` on the device.  With ``deskew=True`` in that dict the rows' times come from
+    ``data_dict["numpy_pc_timestamps"]`` ((n,) array or tensor; the reference's ``DistortionConfig.timestamps_key``) and
+    the sweep is motion-compensated with the last relative pose; a frame without the key passes undistorted, as in the
+    reference."""
 
     def __init__(self, prediction_module_or_config, checkpoint_path=None, device="cuda:0", graph=True,
                  max_frames=4096, sweeps=None):
@@ -574,10 +627,24 @@ class PWCLONetOdometry:
         frame = pc.to(self.device, torch.float32)[None]
         with torch.no_grad():
             if self.stream._front is not None:
-                self.stream.step_sweeps(frame, [frame.shape[1]])
+                self.stream.step_sweeps(frame, [frame.shape[1]], times=self._times(data_dict, frame))
             else:
                 self.stream.step(frame)
         data_dict[self.relative_pose_key()] = self.stream.relative_poses()[-1, 0].float().cpu().numpy()
+
+    def _times(self, data_dict, frame):
+        """The (1, n) times of a raw frame when the stream de-skews, else None.  A frame without the key gets equal times:
+        every alpha is 0 and every row keeps its bits, the identity motion's result (the reference's "no distortion")."""
+        if not self.stream._front.deskew:
+            return None
+        ts = data_dict.get(self.timestamps_key())
+        if ts is None:
+            return torch.zeros(frame.shape[:2], dtype=torch.float64, device=self.device)
+        ts = torch.from_numpy(np.ascontiguousarray(ts)) if isinstance(ts, np.ndarray) else ts
+        if ts.numel() != frame.shape[1] or not ts.dtype.is_floating_point:
+            raise ValueError("PWCLONetOdometry: %s must hold one floating time per row (%d), got %s %s"
+                             % (self.timestamps_key(), frame.shape[1], ts.dtype, tuple(ts.shape)))
+        return ts.reshape(1, -1).to(self.device)
 
     def get_relative_poses(self):
         return self.stream.relative_poses()[:, 0].float().cpu().numpy()
@@ -588,6 +655,10 @@ class PWCLONetOdometry:
     @staticmethod
     def input_key():
         return "numpy_pc"
+
+    @staticmethod
+    def timestamps_key():
+        return "numpy_pc_timestamps"
 
     @staticmethod
     def pointcloud_key():

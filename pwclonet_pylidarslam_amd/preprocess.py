@@ -17,6 +17,10 @@ and ``frames_to_clouds`` chains filter -> compaction -> one batched furthest-poi
 
 ``grid_sample`` is the reference's voxel grid filter (``slam/common/pointcloud.py:105-130``): one row per
 occupied voxel, the lowest-index one.  It is opt-in (``voxel_size=``) in ``frames_to_clouds`` and the raw-sweep front end.
+
+``deskew`` is the reference's ``distortion`` filter (``slam/preprocessing.py:131-191``): every kept row
+moved by its share of a motion prior, the share being its timestamp normalised over the sweep.  Opt-in as well (``times=`` /
+``motion=`` in ``frames_to_clouds``, ``deskew=True`` in the raw-sweep front end); it sits between the filter and the grid.
 """
 import math
 import numbers
@@ -148,24 +152,89 @@ def grid_sample(points, voxel_size, lengths=None, keep=None, workspace=None):
     return keep_out, counts
 
 
+IDENTITY_MOTION = (0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0)      # a pose row [tx ty tz qw qx qy qz]
+
+
+def _times_arg(times, shape, device, what):
+    """A (b, n) tensor of row times, floating, where the points are -> fp64 contiguous (fp32 widens exactly)."""
+    if not isinstance(times, torch.Tensor) or not times.dtype.is_floating_point:
+        raise ValueError("%s: times must be a floating tensor %s, got %s" % (what, tuple(shape), getattr(times, "dtype",
+                                                                                                      type(times))))
+    if tuple(times.shape) != tuple(shape):
+        raise ValueError("%s: times must be %s (one per row), got %s" % (what, tuple(shape), tuple(times.shape)))
+    if times.device != device:
+        raise ValueError("%s: times live on %s, the rows on %s" % (what, times.device, device))
+    return times.to(torch.float64).contiguous()
+
+
+def deskew(points, times, motion, lengths=None, keep=None):
+    """Motion compensation of a sweep (the reference's ``distortion`` filter): points (n, 3|4) or
+    (b, n, 3|4) f32 cuda, times (n) or (b, n) fp32 / fp64 (widened exactly), motion (7) or (b, 7) f32 pose rows
+    [tx ty tz qw qx qy qz] -> xyz (b, n, 3) f32 with row i moved to R(a_i) p_i + a_i t: a_i = the row's time normalised
+    to [0, 1] over the candidates' finite times, R(a) the rotation by a * theta about the motion's axis (slerp from the
+    identity).  Candidates are the rows ``[:lengths[c]]`` (``lengths`` (b,) device integers) with ``keep != 0`` (``keep``
+    (b, n) i32, the filters' masks); every other row, every row with a_i = 0 and every row under the identity motion keeps
+    its bits."""
+    if points.dim() == 2:
+        points = points.unsqueeze(0)
+    if points.dim() != 3 or points.size(-1) not in (3, 4) or points.dtype != torch.float32:
+        raise ValueError("deskew: points must be float32 (n, 3|4) or (b, n, 3|4), got %s %s"
+                         % (points.dtype, tuple(points.shape)))
+    b, n, c = points.shape
+    dev = points.device
+    if isinstance(times, torch.Tensor) and times.dim() == 1:
+        times = times.unsqueeze(0)
+    times = _times_arg(times, (b, n), dev, "deskew")
+    if not isinstance(motion, torch.Tensor) or motion.dtype != torch.float32 or motion.device != dev:
+        raise ValueError("deskew: motion must be a float32 tensor of pose rows on the rows' device")
+    if motion.dim() == 1:
+        motion = motion.unsqueeze(0)
+    if tuple(motion.shape) != (b, 7):
+        raise ValueError("deskew: motion must be (%d, 7) pose rows [tx ty tz qw qx qy qz], got %s" % (b, tuple(motion.shape)))
+    if not points.is_cuda:
+        raise RuntimeError("CPU not supported")
+    points, motion = points.contiguous(), motion.contiguous()
+    if lengths is not None:
+        if lengths.shape != (b,) or not lengths.is_cuda or lengths.dtype.is_floating_point or lengths.dtype == torch.bool:
+            raise ValueError("deskew: lengths must be (%d,) integers on the device" % b)
+        lengths = lengths.to(torch.int32).contiguous()
+    if keep is not None:
+        if keep.dim() == 1:
+            keep = keep.unsqueeze(0)
+        if keep.shape != (b, n) or keep.dtype != torch.int32 or not keep.is_cuda:
+            raise ValueError("deskew: keep must be int32 (%d, %d) on the device" % (b, n))
+        keep = keep.contiguous()
+    xyz = torch.empty((b, n, 3), dtype=torch.float32, device=dev)
+    if b == 0 or n == 0:
+        return xyz
+    _lib.call("deskew_rows_kernel_wrapper", dev, b, n, c, points.data_ptr(), times.data_ptr(), motion.data_ptr(),
+              lengths.data_ptr() if lengths is not None else 0, keep.data_ptr() if keep is not None else 0, xyz.data_ptr())
+    return xyz
+
+
 def frames_to_clouds(points, npoints, dataset="kitti", tr=None, near_threshold=30.0, cap=None, voxel_size=None,
-                     voxel_capacity=None):
+                     voxel_capacity=None, times=None, motion=None):
     """A batch of raw frames (b,n,4) -> (clouds (b,npoints,3) f32, counts (b,) i32), deterministic
     (furthest point sampling of each frame's survivors; BASELINE.json configs[4]).  A frame with fewer
     than ``npoints`` survivors gets index-0 repeats past its count exactly as the reference's sampler
     returns them for m > #valid; check ``counts`` when that matters (the dataset's own rule for that case
     is a random draw with replacement, see ``kitti_frame_to_cloud``).  ``voxel_size``: ``grid_sample`` of the filter's
     survivors ahead of the sampler (one point per voxel, frame order); the packed batch is then ``voxel_capacity`` wide
-    (default ``cap``) and ``counts`` are the rows that reach the sampler."""
+    (default ``cap``) and ``counts`` are the rows that reach the sampler.  ``times`` (b, n) with ``motion`` (b, 7): ``deskew`` of the
+    kept rows between the filter and the grid (the keep decision is the filter's, on the coordinates before the step)."""
     assert points.dim() == 3
     width = points.shape[1] if cap is None else int(cap)
     voxel_size, width = _voxel_args(voxel_size, voxel_capacity, width, "frames_to_clouds")
+    if (times is None) != (motion is None):
+        raise ValueError("frames_to_clouds: times= and motion= come together (de-skewing needs both)")
     if dataset == "kitti":
         xyz, keep = transform_filter(points, tr)
     elif dataset == "kitti360":
         xyz, keep = kitti360_filter(points, near_threshold)
     else:
         raise ValueError(f"unknown dataset {dataset!r}")
+    if times is not None:
+        xyz = deskew(xyz, times, motion, keep=keep)
     if voxel_size is not None:
         keep, _ = grid_sample(xyz, voxel_size, keep=keep)
         cap = width
@@ -218,10 +287,18 @@ class SweepFrontEnd:
     of the kept rows as ``grid_sample`` chooses them, then the compaction), and the packed batch is ``voxel_capacity`` wide
     (default ``capacity``; 1 <= voxel_capacity <= capacity): that width, not ``capacity``, decides the sampler kernel, its
     buffers and ``sampler_max_clouds``.  Winners beyond it are dropped in row order; ``voxel_counts()`` is the unclamped
-    number per stream.  The clouds are those of ``frames_to_clouds(..., cap=capacity, voxel_size=, voxel_capacity=)``."""
+    number per stream.  The clouds are those of ``frames_to_clouds(..., cap=capacity, voxel_size=, voxel_capacity=)``.
+
+    ``deskew=True``: ``load`` / ``load_masked`` also take the rows' times (S, R) into a static
+    (S, capacity) fp64 buffer, and the first launch becomes ``sweep_filter_deskew_compact_kernel`` (or its grid form):
+    the kept rows are moved by ``deskew``'s rule with the motion in ``bufs["motion"]`` ((S, 7) pose rows on the device,
+    the identity to begin with; whoever owns the front end writes it between runs) before grid and compaction.
+    ``stream_words = (restart, have_prev)``: (S,) int32 device words of a per-stream state machine; a stream whose
+    restart word is set or whose have_prev word is clear gets the identity whatever the buffer holds.  The clouds are
+    those of ``frames_to_clouds(..., times=, motion=)``.  With ``deskew=False`` nothing of this exists."""
 
     def __init__(self, streams, npoints, dataset="kitti360", capacity=131072, tr=None, near_threshold=30.0,
-                 ground_z=KITTI360_GROUND_Z, voxel_size=None, voxel_capacity=None):
+                 ground_z=KITTI360_GROUND_Z, voxel_size=None, voxel_capacity=None, deskew=False):
         if dataset not in ("kitti", "kitti360"):
             raise ValueError("sweeps: unknown dataset %r (\"kitti\" or \"kitti360\")" % (dataset,))
         capacity = int(capacity)
@@ -239,6 +316,10 @@ class SweepFrontEnd:
         self.streams, self.npoints, self.dataset, self.capacity = int(streams), int(npoints), dataset, capacity
         self.near_threshold, self.ground_z = float(near_threshold), float(ground_z)
         self.voxel_size, self.width = voxel_size, width        # width of the packed batch: what the sampler sees
+        if not isinstance(deskew, (bool, np.bool_)):
+            raise ValueError("sweeps: deskew=%r must be True or False" % (deskew,))
+        self.deskew = bool(deskew)
+        self.stream_words = None                               # per-stream mode: (restart, have_prev) device words
         self._tr_host = _calibration(tr, self.streams) if dataset == "kitti" else None
         self.bufs = None
 
@@ -280,20 +361,36 @@ class SweepFrontEnd:
             raise RuntimeError("CPU not supported")
         return host
 
-    def load(self, sweeps, lengths, host_lengths):
-        """The per-frame host work: rows [:R] into the static sweep buffer, the lengths into the static device lengths."""
+    def check_times(self, times, sweeps, what):
+        """``times`` belongs to ``deskew=True`` and to nothing else: ValueError in both directions, and for a shape other
+        than the sweeps' (S, R), a dtype that is not floating or another device.  Before any launch."""
+        if not self.deskew:
+            if times is not None:
+                raise ValueError("%s: times= needs a front end built with deskew=True" % what)
+            return
+        if times is None:
+            raise ValueError("%s: built with deskew=True, so every call needs times= (S, R), one per row" % what)
+        if not isinstance(sweeps, torch.Tensor) or sweeps.dim() != 3:
+            return                                             # check() refuses the sweeps themselves
+        _times_arg(times, sweeps.shape[:2], sweeps.device, what)
+
+    def load(self, sweeps, lengths, host_lengths, times=None):
+        """The per-frame host work: rows [:R] into the static sweep buffer, the lengths into the static device lengths
+        (and with ``deskew`` the rows' times into the static times)."""
         if self.bufs is None:
             self._alloc(sweeps.device)
         b = self.bufs
         b["sweeps"][:, :sweeps.shape[1]].copy_(sweeps)
+        if self.deskew:
+            b["times"][:, :sweeps.shape[1]].copy_(times)       # fp32 widens exactly
         if host_lengths is None:
             b["lengths"].copy_(lengths)
         else:
             b["lengths"].copy_(torch.tensor(host_lengths, dtype=torch.int32), non_blocking=False)
 
-    def load_masked(self, sweeps, lengths, host_lengths, active):
+    def load_masked(self, sweeps, lengths, host_lengths, active, times=None):
         """``load`` for the streams s with ``active[s] != 0`` only ((S,) int32 on the device, read there; no sync): the
-        other streams' static rows and lengths keep the sweep they delivered last.  One launch."""
+        other streams' static rows and lengths (and times) keep the sweep they delivered last.  One launch."""
         from . import fused
         b, cap = self.bufs, self.capacity
         src = sweeps.contiguous()
@@ -302,8 +399,14 @@ class SweepFrontEnd:
             new_len = lengths.to(torch.int32).contiguous()
         else:
             new_len = torch.tensor(host_lengths, dtype=torch.int32).to(src.device)
-        fused.masked_copy([(b["sweeps"].data_ptr(), src.data_ptr(), rows), (b["lengths"].data_ptr(), new_len.data_ptr(), 4)],
-                          active, dst_strides=[cap * 16, 4], src_strides=[rows, 4])
+        segments = [(b["sweeps"].data_ptr(), src.data_ptr(), rows), (b["lengths"].data_ptr(), new_len.data_ptr(), 4)]
+        dst_strides, src_strides = [cap * 16, 4], [rows, 4]
+        if self.deskew:                                        # one more segment of the same copy
+            tsrc = times.to(torch.float64).contiguous()
+            segments.append((b["times"].data_ptr(), tsrc.data_ptr(), rows // 2))
+            dst_strides.append(cap * 8)
+            src_strides.append(rows // 2)
+        fused.masked_copy(segments, active, dst_strides=dst_strides, src_strides=src_strides)
 
     def voxel_counts(self):
         """(S,) int32 device view: every stream's voxel winners in the last sweep, not clamped to ``voxel_capacity``
@@ -321,6 +424,9 @@ class SweepFrontEnd:
         if self.voxel_size is not None:
             b["grid_ws"] = grid_sample_workspace(S, rows, device)
             b["winners"] = torch.zeros((S,), dtype=torch.int32, device=device)
+        if self.deskew:
+            b["times"] = torch.zeros((S, rows), dtype=torch.float64, device=device)
+            b["motion"] = torch.tensor(IDENTITY_MOTION, dtype=torch.float32).repeat(S, 1).to(device)
         if cap > _SMALL_CLOUD:
             b["tmp"] = e((S, cap), torch.float32)          # the cooperative sampler's exchange workspace
         if cap >= _SORTED_CLOUD:
@@ -335,7 +441,16 @@ class SweepFrontEnd:
         b, S, cap, m = self.bufs, self.streams, self.width, self.npoints
         dev = b["packed"].device
         p = lambda t: t.data_ptr() if t is not None else 0
-        if self.voxel_size is None:
+        if self.deskew:
+            restart, have_prev = self.stream_words if self.stream_words is not None else (None, None)
+            head = (dev, S, self.capacity, cap, p(b["lengths"]), p(b["sweeps"]), 0 if self.dataset == "kitti" else 1, p(b["tr"]),
+                    self.ground_z, self.near_threshold, p(b["times"]), p(b["motion"]), p(restart), p(have_prev))
+            if self.voxel_size is None:
+                _lib.call("sweep_filter_deskew_compact_kernel_wrapper", *head, p(b["packed"]), p(b["counts"]))
+            else:
+                _lib.call("sweep_filter_deskew_grid_compact_kernel_wrapper", *head, self.voxel_size, p(b["grid_ws"]),
+                          p(b["packed"]), p(b["counts"]), p(b["winners"]))
+        elif self.voxel_size is None:
             _lib.call("sweep_filter_compact_kernel_wrapper", dev, S, cap, cap, p(b["lengths"]), p(b["sweeps"]),
                       0 if self.dataset == "kitti" else 1, p(b["tr"]), self.ground_z, self.near_threshold, p(b["packed"]),
                       p(b["counts"]))

@@ -18,7 +18,12 @@ Check: the streamed rows equal pair mode's bit for bit (the pair forward is the 
     frames/s of ``step_sweeps`` without a grid, with the grid at ``voxel_capacity = capacity``, and with
     ``voxel_capacity = C``.
 
-    python tools/raw_stream_bench.py [--frames F] [--repeats R] [--steps8 K] [--voxel-size V [--voxel-capacity C]]
+(e) ``--deskew``: the de-skewing front end against the plain one, in this process and alternated
+    repeat by repeat, with synthetic times proportional to the row index: S = 1 ms per frame and S = 8 frames/s of
+    ``step_sweeps`` with ``deskew`` off and on, and ``sweep_filter_deskew_compact_kernel`` against
+    ``sweep_filter_compact_kernel`` alone under HIP events, on the sweeps and the motion loaded last.
+
+    python tools/raw_stream_bench.py [--frames F] [--repeats R] [--steps8 K] [--voxel-size V [--voxel-capacity C]] [--deskew]
 """
 import argparse
 import json
@@ -60,6 +65,7 @@ def main():
     ap.add_argument("--steps8", type=int, default=10, help="steps per timed region at S = 8")
     ap.add_argument("--voxel-size", type=float, default=None, help="also measure the grid-sampled front end at this size")
     ap.add_argument("--voxel-capacity", type=int, default=None, help="with --voxel-size: a packed width to measure as well")
+    ap.add_argument("--deskew", action="store_true", help="also measure the de-skewing front end against the plain one")
     a = ap.parse_args()
     if a.voxel_capacity is not None and a.voxel_size is None:
         ap.error("--voxel-capacity needs --voxel-size")
@@ -167,6 +173,8 @@ def main():
         res["sweep_filter_compact_ms_" + name] = _stats([_ms(launches)[0] / 50 for _ in range(5)])
     if a.voxel_size is not None:
         _grid_section(a, res, dev, net, base, order, batches, so, so8)
+    if a.deskew:
+        _deskew_section(a, res, dev, net, base, order, batches, so, so8)
     res["sampler_workgroups_per_pose"] = {"stream": -(-CAP // 16384), "pair": 2 * -(-CAP // 16384)}
     torch.cuda.synchronize(dev)
     res["last_error"] = int(_lib.load().pwclo_last_error())
@@ -247,6 +255,79 @@ def _grid_section(a, res, dev, net, base, order, batches, so, so8):
         tk[name] = {"sweep_filter_compact_ms": _stats(t_old), "sweep_filter_grid_compact_ms": _stats(t_new),
                     "rows": g["lengths"].tolist(), "winners": g["winners"].tolist()}
     res["grid_first_launch"] = tk
+
+
+def _deskew_section(a, res, dev, net, base, order, batches, so, so8):
+    """Section (e): the plain front end (``so`` / ``so8``, already warm) against the de-skewing one, alternated."""
+    S = 8
+    cfg = dict(dataset="kitti360", capacity=CAP, near_threshold=NEAR, deskew=True)
+
+    def times(shape):                                                         # 0.1 s per sweep, proportional to the row index
+        return (0.1 * torch.arange(shape[1], dtype=torch.float64, device=dev) / shape[1]).expand(shape[0], -1).contiguous()
+
+    t1 = [times((1, sw.shape[0])) for sw in base]
+    t8 = [times(b[0].shape[:2]) for b in batches]
+    one = {"off": so, "on": StreamingOdometry(net, streams=1, max_frames=a.frames + 1, graph=True, sweeps=cfg)}
+    eight = {"off": so8, "on": StreamingOdometry(net, streams=S, max_frames=a.steps8 + 2, graph=True, sweeps=cfg)}
+
+    def step1(key, k):
+        sw = base[order[k]]
+        kw = dict(times=t1[order[k]]) if key == "on" else {}
+        return one[key].step_sweeps(sw[None], [sw.shape[0]], **kw)
+
+    def step8(key, k):
+        kw = dict(times=t8[k]) if key == "on" else {}
+        return eight[key].step_sweeps(*batches[k], **kw)
+
+    def s1_pass(key):
+        one[key].reset()
+        step1(key, 0)
+        ts = [_ms(lambda: step1(key, k))[0] for k in range(1, a.frames)]
+        return sorted(ts)[len(ts) // 2]
+
+    def s8_pass(key):
+        eight[key].reset()
+        step8(key, 0)
+        t = _ms(lambda: [step8(key, k) for k in range(1, a.steps8 + 1)])[0]
+        return S * a.steps8 / (t / 1e3)
+
+    r1 = {k: [] for k in one}
+    r8 = {k: [] for k in eight}
+    for k in one:                                                             # warm-up and capture
+        s1_pass(k), s8_pass(k)
+    for _ in range(a.repeats):
+        for k in one:
+            r1[k].append(s1_pass(k))
+        for k in eight:
+            r8[k].append(s8_pass(k))
+    res["deskew_s1_ms_per_frame"] = {k: _stats(v) for k, v in r1.items()}
+    res["deskew_s8_frames_per_s"] = {k: _stats(v) for k, v in r8.items()}
+    res["deskew_motion_s1"] = one["on"].motion()[0].tolist()
+
+    # the first launch alone: filter + compaction against filter + de-skew + compaction, on the sweeps loaded last
+    tk = {}
+    for name, plain, desk in (("s1", so._front, one["on"]._front), ("s8", so8._front, eight["on"]._front)):
+        b, g = plain.bufs, desk.bufs
+
+        def old():
+            for _ in range(50):
+                _lib.call("sweep_filter_compact_kernel_wrapper", dev, plain.streams, CAP, CAP, b["lengths"].data_ptr(),
+                          b["sweeps"].data_ptr(), 1, 0, plain.ground_z, plain.near_threshold, b["packed"].data_ptr(),
+                          b["counts"].data_ptr())
+
+        def new():
+            for _ in range(50):
+                _lib.call("sweep_filter_deskew_compact_kernel_wrapper", dev, desk.streams, CAP, CAP, g["lengths"].data_ptr(),
+                          g["sweeps"].data_ptr(), 1, 0, desk.ground_z, desk.near_threshold, g["times"].data_ptr(),
+                          g["motion"].data_ptr(), 0, 0, g["packed"].data_ptr(), g["counts"].data_ptr())
+        old(), new()
+        t_old, t_new = [], []
+        for _ in range(a.repeats):
+            t_old.append(_ms(old)[0] / 50)
+            t_new.append(_ms(new)[0] / 50)
+        tk[name] = {"sweep_filter_compact_ms": _stats(t_old), "sweep_filter_deskew_compact_ms": _stats(t_new),
+                    "rows": g["lengths"].tolist(), "kept": g["counts"].tolist()}
+    res["deskew_first_launch"] = tk
 
 
 if __name__ == "__main__":
