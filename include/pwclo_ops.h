@@ -866,6 +866,48 @@ void odom_sequence_errors_kernel_wrapper(int nseq, int total_slots, const int *s
                                          const double *poses_gt, const double *poses_result, const double *dist,
                                          int step, int nlen, const double *lengths, double *err, int *valid);
 
+/* ---- 6. point-to-plane registration against a sliding local map ---------------------------
+ * Refines a frame's pose on the device: the reference's ICPFrameToModel (slam/odometry/icp_odometry.py:248-299,
+ * slam/odometry/local_map.py:254-427, slam/common/optimization.py:297-354, 391-443).  All pointers DEVICE memory; clouds
+ * (.., n, 3) fp32 point-major; poses (.., 4, 4) fp64 row-major.  The pose T of a frame maps its points into the previous
+ * frame.  A map holds M slots per stream, each with its cloud, normals and search structure (knn_build_kernel_wrapper) in
+ * the slot's own frame; A (S,M,4,4) maps the previous frame into slot m, R (S,M,3,3) rotates slot m into the previous
+ * frame, live (S,M) ints, cursor (S) ints: the slot the next frame goes to.  One iteration = icp_queries, the search
+ * knn_point_prebuilt_kernel_wrapper(S * M, n, n, 1, q, idx, dist, map_ws), icp_accumulate, icp_solve.  No atomics; every
+ * sum has a fixed order. */
+
+/* Normals as KdTreeLocalMap.__get_normals: idx (b,n,k+1) = the k+1 nearest of every point in its own cloud (column 0, the
+ * point itself, is dropped); covariance of (neighbour - point) and its eigen-decomposition in fp64 (8 cyclic Jacobi
+ * sweeps); normals (b,n,3) fp32 = the unit eigenvector of the smallest eigenvalue with n . point <= 0, or the zero vector
+ * when the covariance has rank < 2: !(l_mid > 1e-10 l_max); eig (b,n,3) fp64 ascending.  1 <= k <= min(63, n - 1). */
+void icp_normals_kernel_wrapper(int b, int n, int k, const float *xyz, const int *idx, float *normals, double *eig);
+/* q[s,m,i] = fp32(A[s,m] . T[s] . p[s,i]) (T NULL: the identity), products in fp64, one rounding.  q (S,M,n,3). */
+void icp_queries_kernel_wrapper(int S, int M, int n, const double *A, const double *T, const float *p, float *q);
+/* Rows per stream that icp_accumulate writes for clouds of n points (one per workgroup of 256 points). */
+int icp_accumulate_groups(int n);
+/* Point i of stream s: the live slot with the smallest fp32 dist (tie: lower slot); rejected when none is live, dist >
+ * max_dist, or the matched normal is zero.  r = n . (q - y), J = [p' x n', n'] with n' = R[s,m] n, p' = T[s] p; Huber
+ * w^2 = 1 below sigma, else (2 sigma |r| - sigma^2) / max(|r|, 1e-4)^2.  partial (S, groups, 32) fp64: 21 upper entries of
+ * sum w^2 J^T J, 6 of sum w^2 J r, sum w^2, sum w^2 r^2, pairs, 2 zeros.  idx / dist (S,M,n). */
+void icp_accumulate_kernel_wrapper(int S, int M, int n, const float *p, const float *q, const int *idx, const float *dist,
+                                   const float *map_xyz, const float *map_normals, const int *live, const double *R,
+                                   const double *T, double sigma, float max_dist, double *partial);
+/* One workgroup.  Per stream: the rows added in group order -> sum (S,32); it == 0 clears status and iters first.  A stream
+ * with status != 0 is frozen: T stays, delta = 0.  Otherwise iters = it + 1, pairs, cost = sum w^2 r^2 are recorded, and
+ * pairs < min_pairs sets status 2, a pivot that is not positive sets 4 (T untouched in both), else delta = -(H / sw +
+ * damping I)^-1 (g / sw) by Cholesky, T <- [Rodrigues(delta[0:3]) | delta[3:6]] T with the rotation re-orthonormalised,
+ * and |delta| < threshold sets status 1.  delta (S,6). */
+void icp_solve_kernel_wrapper(int S, int groups, int it, const double *partial, double damping, double threshold,
+                              int min_pairs, double *T, int *status, int *iters, int *pairs, double *cost, double *sum,
+                              double *delta);
+/* The handover after a registration.  Per stream: the staged frame (cloud (S,n,3), normals (S,n,3), stage_ws = the
+ * structure knn_build_kernel_wrapper built for these S clouds) is copied into slot cursor[s] of map_xyz / map_normals
+ * (S,M,n,3) and map_ws (a structure for S * M clouds); every other live slot gets A <- A T, R <- R_T^T R; the new slot gets
+ * A = I, R = I, live = 1; cursor <- (cursor + 1) mod M.  64 <= n <= 16384, M <= 64. */
+void icp_map_push_kernel_wrapper(int S, int M, int n, const double *T, const float *cloud, const float *normals,
+                                 const void *stage_ws, float *map_xyz, float *map_normals, void *map_ws, double *A,
+                                 double *R, int *live, int *cursor);
+
 #ifdef __cplusplus
 }
 #endif

@@ -155,6 +155,12 @@ SIGNATURES = {
     "stream_handover_masked_kernel_wrapper": ([_i] + [ctypes.POINTER(ctypes.c_void_p)] * 2
                                               + [ctypes.POINTER(ctypes.c_longlong)] * 3 + [_i, _F], None),
     "odom_sequence_errors_kernel_wrapper": ([_i, _i] + [_F] * 5 + [_i, _i] + [_F] * 3, None),
+    "icp_normals_kernel_wrapper": ([_i, _i, _i, _F, _F, _F, _F], None),
+    "icp_queries_kernel_wrapper": ([_i, _i, _i, _F, _F, _F, _F], None),
+    "icp_accumulate_groups": ([_i], _i),
+    "icp_accumulate_kernel_wrapper": ([_i, _i, _i] + [_F] * 9 + [ctypes.c_double, ctypes.c_float, _F], None),
+    "icp_solve_kernel_wrapper": ([_i, _i, _i, _F, ctypes.c_double, ctypes.c_double, _i] + [_F] * 7, None),
+    "icp_map_push_kernel_wrapper": ([_i, _i, _i] + [_F] * 11, None),
 }
 
 _lib = None

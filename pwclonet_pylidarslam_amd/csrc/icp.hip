@@ -1,0 +1,336 @@
+// Point-to-plane registration of a frame against a sliding local map of the last frames (gfx950).
+//
+// The reference's ICPFrameToModel (slam/odometry/icp_odometry.py:248-299) refines a learned initial pose by Gauss-Newton on
+// point-to-plane residuals against a kd-tree of the last frames, on the host.  Here every map slot keeps its cloud, its
+// normals and its neighbour-search structure (knn.hip) in the slot's own frame, built once when the frame arrives; only the
+// queries move.  icp.hpp holds the arithmetic; this file holds
+//   icp_normals_kernel      normals of a cloud from its own k nearest neighbours
+//   icp_queries_kernel      q[s, m, i] = fp32(A[s, m] (T[s]) p[s, i]): the frame's points in every slot's coordinates
+//   icp_accumulate_kernel   slot choice, rejection, Huber weights, the sums of the normal equations: one row per workgroup
+//   icp_solve_kernel        rows -> 6x6 Cholesky solve -> pose update, freeze flags, diagnostics
+//   icp_map_push_kernel     the handover: poses of the live slots re-based on the new frame, the oldest slot replaced
+// One iteration is queries, the existing search (nsample = 1 over S * M clouds), accumulate, solve.  Nothing is sized at run
+// time from the data, no kernel uses an atomic, and every sum is added in a fixed order: two runs give the same bits and a
+// captured graph serves every frame.
+#include <math.h>
+
+#include "common.hpp"
+#include "icp.hpp"
+
+extern "C" long long knn_point_build_bytes(int b, int n);
+
+namespace pwclo {
+
+constexpr int ICP_MAX_SLOTS = 64;
+constexpr int ICP_SOLVE_THREADS = 1024;     // 32 streams at a time, 32 lanes (one per column of a row) each
+
+// xyz (b, n, 3); idx (b, n, k + 1): the k + 1 nearest of every point in its own cloud, column 0 (the point itself, or a
+// duplicate of it) dropped.  normals (b, n, 3) fp32, eig (b, n, 3) fp64 ascending.
+__global__ __launch_bounds__(256) void icp_normals_kernel(int n, int k, const float *__restrict__ xyz,
+                                                          const int *__restrict__ idx, float *__restrict__ normals,
+                                                          double *__restrict__ eig) {
+  const int c = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float *xc = xyz + (size_t)c * n * 3;
+  const int *ic = idx + ((size_t)c * n + i) * (k + 1);
+  const float y[3] = {xc[(size_t)i * 3], xc[(size_t)i * 3 + 1], xc[(size_t)i * 3 + 2]};
+  double cov[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int j = 1; j <= k; ++j) {
+    const int nb = min(max(ic[j], 0), n - 1);
+    const double dx = (double)xc[(size_t)nb * 3] - (double)y[0], dy = (double)xc[(size_t)nb * 3 + 1] - (double)y[1],
+                 dz = (double)xc[(size_t)nb * 3 + 2] - (double)y[2];
+    cov[0] += dx * dx; cov[1] += dx * dy; cov[2] += dx * dz;
+    cov[3] += dy * dy; cov[4] += dy * dz; cov[5] += dz * dz;
+  }
+  float out[3];
+  double val[3];
+  icp_normal(cov, y, out, val);
+  float *nc = normals + ((size_t)c * n + i) * 3;
+  double *ec = eig + ((size_t)c * n + i) * 3;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    nc[a] = out[a];
+    ec[a] = val[a];
+  }
+}
+
+// A (S, M, 4, 4), T (S, 4, 4) or nullptr (the identity), p (S, n, 3) -> q (S, M, n, 3).  The matrix product and the
+// matrix-vector product are fp64; one rounding to fp32.
+__global__ __launch_bounds__(256) void icp_queries_kernel(int M, int n, const double *__restrict__ A,
+                                                          const double *__restrict__ T, const float *__restrict__ p,
+                                                          float *__restrict__ q) {
+  const int sm = blockIdx.y, s = sm / M, i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  double a[12];
+  const double *am = A + (size_t)sm * 16;
+  if (T != nullptr) {
+    icp_pose_mul(am, T + (size_t)s * 16, a);
+  } else {
+#pragma unroll
+    for (int e = 0; e < 12; ++e) a[e] = am[e];
+  }
+  const float *pi = p + ((size_t)s * n + i) * 3;
+  const float pt[3] = {pi[0], pi[1], pi[2]};
+  double o[3];
+  icp_pose_apply(a, pt, o);
+  float *qi = q + ((size_t)sm * n + i) * 3;
+  qi[0] = (float)o[0]; qi[1] = (float)o[1]; qi[2] = (float)o[2];
+}
+
+// p (S, n, 3), q / idx / dist (S, M, n[, 3]) from the search with nsample = 1, map_xyz / map_normals (S, M, n, 3), live
+// (S, M), Rm (S, M, 3, 3), T (S, 4, 4) -> partial (S, gridDim.x, ICP_ROW).  A dead slot's idx, dist and map rows are never
+// read.
+__global__ __launch_bounds__(ICP_ACC_THREADS) void icp_accumulate_kernel(
+    int M, int n, const float *__restrict__ p, const float *__restrict__ q, const int *__restrict__ idx,
+    const float *__restrict__ dist, const float *__restrict__ map_xyz, const float *__restrict__ map_normals,
+    const int *__restrict__ live, const double *__restrict__ Rm, const double *__restrict__ T, double sigma, float max_dist,
+    double *__restrict__ partial) {
+  __shared__ double wave_row[ICP_ACC_THREADS / 64][ICP_ROW];
+  const int s = blockIdx.y, i = blockIdx.x * ICP_ACC_THREADS + threadIdx.x;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  double acc[ICP_TERMS];
+#pragma unroll
+  for (int e = 0; e < ICP_TERMS; ++e) acc[e] = 0.0;
+  if (i < n) {
+    int best = -1;
+    float bd = 0.0f;
+    for (int m = 0; m < M; ++m) {
+      if (live[s * M + m] == 0) continue;
+      const float d = dist[((size_t)(s * M + m)) * n + i];
+      if (best < 0 || d < bd) {                           // strict: on a tie the lower slot stays
+        best = m;
+        bd = d;
+      }
+    }
+    if (best >= 0 && bd <= max_dist) {                    // NaN fails
+      const size_t sm = (size_t)(s * M + best);
+      const int j = idx[sm * n + i];
+      if (j >= 0 && j < n) {
+        const float *yr = map_xyz + (sm * n + j) * 3, *nr = map_normals + (sm * n + j) * 3, *qr = q + (sm * n + i) * 3,
+                    *pr = p + ((size_t)s * n + i) * 3;
+        const float y[3] = {yr[0], yr[1], yr[2]}, nn[3] = {nr[0], nr[1], nr[2]}, qq[3] = {qr[0], qr[1], qr[2]},
+                    pp[3] = {pr[0], pr[1], pr[2]};
+        if (nn[0] != 0.0f || nn[1] != 0.0f || nn[2] != 0.0f) {
+          double t[12], r9[9];
+#pragma unroll
+          for (int e = 0; e < 12; ++e) t[e] = T[(size_t)s * 16 + e];
+#pragma unroll
+          for (int e = 0; e < 9; ++e) r9[e] = Rm[sm * 9 + e];
+          icp_add_pair(pp, qq, y, nn, t, r9, sigma, acc);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < ICP_TERMS; ++e) {
+    double v = acc[e];
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    if (lane == 0) wave_row[wave][e] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < ICP_ROW) {
+    double v = 0.0;
+    if (threadIdx.x < ICP_TERMS) {
+      v = wave_row[0][threadIdx.x];
+#pragma unroll
+      for (int w = 1; w < ICP_ACC_THREADS / 64; ++w) v += wave_row[w][threadIdx.x];
+    }
+    partial[((size_t)s * gridDim.x + blockIdx.x) * ICP_ROW + threadIdx.x] = v;
+  }
+}
+
+// One workgroup.  32 lanes add the columns of a stream's rows in group order, then one thread per stream solves.
+__global__ __launch_bounds__(ICP_SOLVE_THREADS) void icp_solve_kernel(
+    int S, int groups, int it, const double *__restrict__ partial, double damping, double threshold, int min_pairs,
+    double *__restrict__ T, int *__restrict__ status, int *__restrict__ iters, int *__restrict__ pairs,
+    double *__restrict__ cost, double *__restrict__ sum_out, double *__restrict__ delta_out) {
+  __shared__ double rows[ICP_SOLVE_THREADS / 32][ICP_ROW];
+  const int col = threadIdx.x & 31, sl = threadIdx.x >> 5;
+  for (int base = 0; base < S; base += ICP_SOLVE_THREADS / 32) {
+    __syncthreads();                                       // the previous chunk's rows have been read
+    if (base + sl < S) {
+      const double *pr = partial + (size_t)(base + sl) * groups * ICP_ROW + col;
+      double v = 0.0;
+      for (int g = 0; g < groups; ++g) v += pr[(size_t)g * ICP_ROW];
+      rows[sl][col] = v;
+      sum_out[(size_t)(base + sl) * ICP_ROW + col] = v;
+    }
+    __syncthreads();
+    const int s = base + (int)threadIdx.x;
+    if (threadIdx.x < ICP_SOLVE_THREADS / 32 && s < S) {
+      double sum[ICP_ROW], delta[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int e = 0; e < ICP_ROW; ++e) sum[e] = rows[threadIdx.x][e];
+      int st = it == 0 ? 0 : status[s];
+      if (it == 0) iters[s] = 0;
+      if (st == 0) {
+        const int np = (int)sum[ICP_PAIRS];
+        iters[s] = it + 1;
+        pairs[s] = np;
+        cost[s] = sum[ICP_COST];
+        if (np < min_pairs) {
+          st = ICP_FEW_PAIRS;
+        } else if (!icp_solve6(sum, damping, delta)) {
+          st = ICP_BAD_PIVOT;
+#pragma unroll
+          for (int e = 0; e < 6; ++e) delta[e] = 0.0;
+        } else {
+          double t[12];
+#pragma unroll
+          for (int e = 0; e < 12; ++e) t[e] = T[(size_t)s * 16 + e];
+          icp_update_pose(delta, t);
+#pragma unroll
+          for (int e = 0; e < 12; ++e) T[(size_t)s * 16 + e] = t[e];
+          double nd = 0.0;
+#pragma unroll
+          for (int e = 0; e < 6; ++e) nd += delta[e] * delta[e];
+          if (sqrt(nd) < threshold) st = ICP_CONVERGED;
+        }
+      }
+      status[s] = st;
+#pragma unroll
+      for (int e = 0; e < 6; ++e) delta_out[(size_t)s * 6 + e] = delta[e];
+    }
+  }
+}
+
+// One workgroup per stream.  The staged frame (cloud, normals, the rows and boxes of its search structure, built for S
+// clouds) goes into slot cursor[s] of the stream's map (structures built for S * M clouds); the live slots' poses are
+// re-based on the new frame; the cursor moves on.
+__global__ __launch_bounds__(1024) void icp_map_push_kernel(int M, int n, int S, int nblk, const double *__restrict__ T,
+                                                            const float *__restrict__ cloud,
+                                                            const float *__restrict__ normals,
+                                                            const float4 *__restrict__ stage_ws, float *__restrict__ map_xyz,
+                                                            float *__restrict__ map_normals, float4 *__restrict__ map_ws,
+                                                            double *__restrict__ A, double *__restrict__ Rm,
+                                                            int *__restrict__ live, int *__restrict__ cursor) {
+  const int s = blockIdx.x;
+  const int slot = min(max(cursor[s], 0), M - 1);
+  const size_t sm = (size_t)s * M + slot;
+  const size_t n3 = (size_t)n * 3, nrow = (size_t)nblk * 64, nbox = (size_t)nblk * 2;
+  for (size_t j = threadIdx.x; j < n3; j += 1024) {
+    map_xyz[sm * n3 + j] = cloud[(size_t)s * n3 + j];
+    map_normals[sm * n3 + j] = normals[(size_t)s * n3 + j];
+  }
+  const float4 *srow = stage_ws + (size_t)s * nrow, *sbox = stage_ws + (size_t)S * nrow + (size_t)s * nbox;
+  float4 *drow = map_ws + sm * nrow, *dbox = map_ws + (size_t)S * M * nrow + sm * nbox;
+  for (size_t j = threadIdx.x; j < nrow; j += 1024) drow[j] = srow[j];
+  for (size_t j = threadIdx.x; j < nbox; j += 1024) dbox[j] = sbox[j];
+  const int m = threadIdx.x;
+  if (m < M) {
+    double *am = A + ((size_t)s * M + m) * 16, *rm = Rm + ((size_t)s * M + m) * 9;
+    if (m == slot) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) am[e] = (e % 5 == 0) ? 1.0 : 0.0;
+#pragma unroll
+      for (int e = 0; e < 9; ++e) rm[e] = (e % 4 == 0) ? 1.0 : 0.0;
+      live[s * M + m] = 1;
+    } else if (live[s * M + m] != 0) {
+      double a[12], t[12], c[12], r[9];
+#pragma unroll
+      for (int e = 0; e < 12; ++e) {
+        a[e] = am[e];
+        t[e] = T[(size_t)s * 16 + e];
+      }
+      icp_pose_mul(a, t, c);
+#pragma unroll
+      for (int e = 0; e < 12; ++e) am[e] = c[e];
+#pragma unroll
+      for (int e = 0; e < 9; ++e) r[e] = rm[e];
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) rm[3 * i + j] = (t[i] * r[j] + t[4 + i] * r[3 + j]) + t[8 + i] * r[6 + j];   // R_new^T R
+    }
+  }
+  __syncthreads();                                         // everyone has read the cursor
+  if (threadIdx.x == 0) cursor[s] = slot + 1 == M ? 0 : slot + 1;
+}
+
+}  // namespace pwclo
+
+using namespace pwclo;
+
+static bool icp_aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+extern "C" void icp_normals_kernel_wrapper(int b, int n, int k, const float *xyz, const int *idx, float *normals,
+                                           double *eig) {
+  if (b <= 0) return;
+  PWCLO_REQUIRE(n >= 2 && (long long)n * 3 < (1ll << 31) && b <= 65535, "icp_normals: b=%d n=%d out of range", b, n);
+  PWCLO_REQUIRE(k >= 1 && k <= 63 && k < n, "icp_normals: k=%d outside [1, min(63, n - 1)] for n=%d", k, n);
+  PWCLO_REQUIRE((long long)n * (k + 1) < (1ll << 31), "icp_normals: n=%d k=%d neighbour lists too long", n, k);
+  PWCLO_REQUIRE(xyz != nullptr && idx != nullptr && normals != nullptr && eig != nullptr && icp_aligned(eig, 8),
+                "icp_normals: xyz, idx, normals and eig (8-byte aligned) are required%s", "");
+  hipLaunchKernelGGL(icp_normals_kernel, dim3(ceil_div(n, 256), b), dim3(256), 0, current_stream(), n, k, xyz, idx, normals,
+                     eig);
+  check_launch("icp_normals");
+}
+
+extern "C" void icp_queries_kernel_wrapper(int S, int M, int n, const double *A, const double *T, const float *p, float *q) {
+  if (S <= 0) return;
+  PWCLO_REQUIRE(M >= 1 && M <= ICP_MAX_SLOTS && n >= 1 && (long long)n * 3 < (1ll << 31) && (long long)S * M <= 65535,
+                "icp_queries: S=%d M=%d n=%d out of range (M <= %d, S * M <= 65535)", S, M, n, ICP_MAX_SLOTS);
+  PWCLO_REQUIRE(A != nullptr && p != nullptr && q != nullptr && icp_aligned(A, 8) && icp_aligned(T, 8),
+                "icp_queries: A (8-byte aligned), p and q are required%s", "");
+  hipLaunchKernelGGL(icp_queries_kernel, dim3(ceil_div(n, 256), S * M), dim3(256), 0, current_stream(), M, n, A, T, p, q);
+  check_launch("icp_queries");
+}
+
+extern "C" int icp_accumulate_groups(int n) { return n >= 1 ? ceil_div(n, ICP_ACC_THREADS) : 0; }
+
+extern "C" void icp_accumulate_kernel_wrapper(int S, int M, int n, const float *p, const float *q, const int *idx,
+                                              const float *dist, const float *map_xyz, const float *map_normals,
+                                              const int *live, const double *R, const double *T, double sigma,
+                                              float max_dist, double *partial) {
+  if (S <= 0) return;
+  PWCLO_REQUIRE(M >= 1 && M <= ICP_MAX_SLOTS && n >= 1 && (long long)n * 3 < (1ll << 31) && S <= 65535 &&
+                (long long)S * M * n < (1ll << 31),
+                "icp_accumulate: S=%d M=%d n=%d out of range (M <= %d)", S, M, n, ICP_MAX_SLOTS);
+  PWCLO_REQUIRE(sigma > 0.0 && isfinite(sigma) && max_dist >= 0.0f, "icp_accumulate: sigma=%g must be > 0, max_dist=%g >= 0",
+                sigma, (double)max_dist);
+  PWCLO_REQUIRE(p != nullptr && q != nullptr && idx != nullptr && dist != nullptr && map_xyz != nullptr &&
+                map_normals != nullptr && live != nullptr && R != nullptr && T != nullptr && partial != nullptr,
+                "icp_accumulate: every pointer is required%s", "");
+  PWCLO_REQUIRE(icp_aligned(R, 8) && icp_aligned(T, 8) && icp_aligned(partial, 8),
+                "icp_accumulate: R, T and partial must be 8-byte aligned%s", "");
+  hipLaunchKernelGGL(icp_accumulate_kernel, dim3(icp_accumulate_groups(n), S), dim3(ICP_ACC_THREADS), 0, current_stream(), M,
+                     n, p, q, idx, dist, map_xyz, map_normals, live, R, T, sigma, max_dist, partial);
+  check_launch("icp_accumulate");
+}
+
+extern "C" void icp_solve_kernel_wrapper(int S, int groups, int it, const double *partial, double damping, double threshold,
+                                         int min_pairs, double *T, int *status, int *iters, int *pairs, double *cost,
+                                         double *sum, double *delta) {
+  if (S <= 0) return;
+  PWCLO_REQUIRE(S <= 65535 && groups >= 1 && it >= 0, "icp_solve: S=%d groups=%d it=%d out of range", S, groups, it);
+  PWCLO_REQUIRE(damping >= 0.0 && isfinite(damping) && threshold >= 0.0 && min_pairs >= 1,
+                "icp_solve: damping=%g and threshold=%g must be >= 0, min_pairs=%d >= 1", damping, threshold, min_pairs);
+  PWCLO_REQUIRE(partial != nullptr && T != nullptr && status != nullptr && iters != nullptr && pairs != nullptr &&
+                cost != nullptr && sum != nullptr && delta != nullptr, "icp_solve: every pointer is required%s", "");
+  PWCLO_REQUIRE(icp_aligned(partial, 8) && icp_aligned(T, 8) && icp_aligned(cost, 8) && icp_aligned(sum, 8) &&
+                icp_aligned(delta, 8), "icp_solve: fp64 arrays must be 8-byte aligned%s", "");
+  hipLaunchKernelGGL(icp_solve_kernel, dim3(1), dim3(ICP_SOLVE_THREADS), 0, current_stream(), S, groups, it, partial, damping,
+                     threshold, min_pairs, T, status, iters, pairs, cost, sum, delta);
+  check_launch("icp_solve");
+}
+
+extern "C" void icp_map_push_kernel_wrapper(int S, int M, int n, const double *T, const float *cloud, const float *normals,
+                                            const void *stage_ws, float *map_xyz, float *map_normals, void *map_ws, double *A,
+                                            double *R, int *live, int *cursor) {
+  if (S <= 0) return;
+  const long long per = knn_point_build_bytes(1, n);       // 0 outside the range the search structure supports
+  PWCLO_REQUIRE(per > 0 && M >= 1 && M <= ICP_MAX_SLOTS && (long long)S * M <= 65535,
+                "icp_map_push: S=%d M=%d n=%d out of range (64 <= n <= 16384, M <= %d, S * M <= 65535)", S, M, n,
+                ICP_MAX_SLOTS);
+  PWCLO_REQUIRE(T != nullptr && cloud != nullptr && normals != nullptr && stage_ws != nullptr && map_xyz != nullptr &&
+                map_normals != nullptr && map_ws != nullptr && A != nullptr && R != nullptr && live != nullptr &&
+                cursor != nullptr, "icp_map_push: every pointer is required%s", "");
+  PWCLO_REQUIRE(icp_aligned(stage_ws, 16) && icp_aligned(map_ws, 16) && icp_aligned(T, 8) && icp_aligned(A, 8) &&
+                icp_aligned(R, 8), "icp_map_push: structures must be 16-byte, fp64 arrays 8-byte aligned%s", "");
+  const int nblk = (int)(per / (64 * 16 + 32));
+  hipLaunchKernelGGL(icp_map_push_kernel, dim3(S), dim3(1024), 0, current_stream(), M, n, S, nblk, T, cloud, normals,
+                     static_cast<const float4 *>(stage_ws), map_xyz, map_normals, static_cast<float4 *>(map_ws), A, R, live,
+                     cursor);
+  check_launch("icp_map_push");
+}

@@ -60,6 +60,13 @@ class StreamingOdometry:
     Per-stream mode: a stream that primes (restart, or no previous frame) and its next sweep get the identity, an idle
     stream keeps its motion, ``reset()`` / ``reset(streams=...)`` return the streams to the identity.
 
+    Refinement (``refine=dict(map_size=4, iters=10, ...)``, ``registration.IcpRefiner``'s keywords):
+    after each step's own graph, which is unchanged, the cloud the step sampled from is registered by point-to-plane ICP
+    against a local map of the stream's last frames, with the level-1 row's transform as the initial guess (one more
+    captured graph).  ``refined_relative_poses()`` / ``refined_trajectory()`` sit beside ``relative_poses()`` /
+    ``trajectory()``, which stay the network's, as does the de-skew prior; ``refiner().status()`` tells why a stream's
+    registration stopped.  Lock step only: ``per_stream=True`` together with ``refine`` raises.
+
     Per-stream mode (``per_stream=True``): ``step(frames, active=None, restart=None)`` and ``step_sweeps(sweeps, lengths,
     active=None, restart=None)`` take two (S,) masks, bool or integer, host sequences or device tensors (device tensors
     are read on the device, without a sync); ``None`` = all active, none restarting.  ``active[s]``: stream s delivered a
@@ -79,7 +86,7 @@ class StreamingOdometry:
     start as copies of the first active stream's, so that no step ever reads an uninitialised buffer."""
 
     def __init__(self, net, streams=1, num_points=None, max_frames=4096, graph=True, warmup=1, sweeps=None,
-                 per_stream=False):
+                 per_stream=False, refine=None):
         if not 1 <= int(streams) <= MAX_STREAMS:
             raise ValueError("StreamingOdometry: streams=%d outside [1, %d]" % (int(streams), MAX_STREAMS))
         if int(max_frames) < 1:
@@ -101,6 +108,12 @@ class StreamingOdometry:
         self._static = {}           # per-stream eager mode: input shape -> static frames (graph mode: in _graphs)
         self._active = self._restart = self._have_prev = self._counts = self._valid = None    # (S,) int32, device
         self._front = None          # raw mode: preprocess.SweepFrontEnd (persistent sweep, lengths, tr, sampler buffers)
+        self._refine_cfg = None if refine is None else dict(refine)     # registration.IcpRefiner's keywords
+        self._refiner = self._ref_rel = None
+        self._tapped = None         # refine: the frame batch the last step's graph (or eager step) sampled from
+        if refine is not None and self.per_stream:
+            raise ValueError("StreamingOdometry: refine= registers all streams in lock step; per_stream=True with refine "
+                             "is not supported (masked registration is not implemented)")
         if sweeps is not None:
             if self.num_points is None:
                 self.num_points = RAW_NUM_POINTS
@@ -233,9 +246,10 @@ class StreamingOdometry:
                 entry = self._graphs[key] = dict(static=frames.clone(), prime=None, step=None)
             static = entry["static"]
             static.copy_(frames)
-            pose = self._replay(fused, entry, lambda: static, prime)
+            pose = self._replay(fused, entry, self._tap(lambda: static), prime)
         else:
-            pose = self._eager(fused, frames, prime)
+            pose = self._eager(fused, self._tap(lambda: frames)(), prime)
+        self._refine(pose)
         self.frames_seen += 1
         return pose
 
@@ -265,9 +279,10 @@ class StreamingOdometry:
             entry = self._graphs.get("sweeps")
             if entry is None:
                 entry = self._graphs["sweeps"] = dict(static=None, prime=None, step=None)
-            pose = self._replay(fused, entry, front.run, prime)
+            pose = self._replay(fused, entry, self._tap(front.run), prime)
         else:
-            pose = self._eager(fused, front.run(), prime)
+            pose = self._eager(fused, self._tap(front.run)(), prime)
+        self._refine(pose)
         self.frames_seen += 1
         return pose
 
@@ -280,6 +295,32 @@ class StreamingOdometry:
         """(frames_seen, S, 4, 4) fp64 device view: the absolute poses, products of ``relative_poses()``; ``stream=i``
         as there."""
         return self._view(self._abs, stream)
+
+    def refined_relative_poses(self):
+        """With ``refine=``: (frames_seen, S, 4, 4) fp64 device view beside ``relative_poses()``: row k is pair (k-1, k)'s
+        transform after point-to-plane registration against the local map, row 0 the identity."""
+        if self._refine_cfg is None:
+            raise RuntimeError("StreamingOdometry: refined poses need refine=dict(...)")
+        if self._ref_rel is None:
+            return torch.empty((0, self.streams, 4, 4), dtype=torch.float64)
+        return self._ref_rel[:self.frames_seen]
+
+    def refined_trajectory(self):
+        """With ``refine=``: (frames_seen, S, 4, 4) fp64, the products of ``refined_relative_poses()`` per stream
+        (``evaluation.accumulate``, the kernel behind ``compute_absolute_poses``)."""
+        from . import evaluation
+        rel = self.refined_relative_poses()
+        k = rel.shape[0]
+        if k == 0:
+            return rel
+        flat = rel.permute(1, 0, 2, 3).contiguous().view(-1, 4, 4)
+        out = evaluation.accumulate(flat, [k] * self.streams)
+        return out.view(self.streams, k, 4, 4).permute(1, 0, 2, 3).contiguous()
+
+    def refiner(self):
+        """The ``registration.IcpRefiner`` behind ``refine=`` (``status()``, ``diagnostics()``); None before the first
+        frame or without ``refine``."""
+        return self._refiner
 
     def valid(self):
         """Per-stream mode: (S,) int32 device view, 1 where the last call's pose row is a real pair.  None before the
@@ -307,6 +348,34 @@ class StreamingOdometry:
         if self._rel is None:
             self._alloc(device)
         return fused
+
+    def _tap(self, source):
+        """``source`` itself, or with ``refine=`` a wrapper that remembers the frame batch it returned: the refiner
+        registers the cloud the step sampled from.  The step's launches are the same either way."""
+        if self._refine_cfg is None:
+            return source
+
+        def tapped():
+            self._tapped = source()
+            return self._tapped
+        return tapped
+
+    def _refine(self, pose):
+        """After the step (outside its graph): register the step's cloud, initial guess = the level-1 row's transform
+        (the identity for a frame that primes), and record the refined relative pose."""
+        if self._refine_cfg is None:
+            return
+        from . import registration
+        cloud = self._tapped[:, :self.num_points, :3].contiguous()
+        if self._refiner is None:
+            self._refiner = registration.IcpRefiner(self.streams, self.num_points, graph=self.graph, **self._refine_cfg)
+            self._ref_rel = torch.zeros((self.max_frames, self.streams, 4, 4), dtype=torch.float64, device=cloud.device)
+        if pose is None:
+            self._refiner.reset()
+            init = torch.eye(4, dtype=torch.float64, device=cloud.device).expand(self.streams, 4, 4).contiguous()
+        else:
+            init = pose[:, 0, :]
+        self._ref_rel[self.frames_seen].copy_(self._refiner.register(cloud, init))
 
     def _eager(self, fused, frames, prime):
         if prime:
@@ -399,6 +468,7 @@ class StreamingOdometry:
                 self._append(None)
                 self._hand_motion(None)
             entry["prime"] = self._capture(prime_body)[0]
+            entry["prime_cloud"] = self._tapped
         if not prime and entry["step"] is None:
             self._warm(lambda: fused.stream_step(self._slot, source(), n))
 
@@ -411,6 +481,8 @@ class StreamingOdometry:
                 self._slot.copy_frame1_(new)
                 return pose
             entry["step"] = self._capture(step_body)
+            entry["step_cloud"] = self._tapped
+        self._tapped = entry.get("prime_cloud" if prime else "step_cloud")
         if prime:
             entry["prime"].replay()
             return None
@@ -590,7 +662,7 @@ class PWCLONetOdometry:
     reference."""
 
     def __init__(self, prediction_module_or_config, checkpoint_path=None, device="cuda:0", graph=True,
-                 max_frames=4096, sweeps=None):
+                 max_frames=4096, sweeps=None, refine=None):
         from .prediction import PWCLONetPredictionModule
         self.device = torch.device(device)
         mod = prediction_module_or_config
@@ -602,7 +674,8 @@ class PWCLONetOdometry:
         self.checkpoint_path = checkpoint_path
         self.elapsed = []
         self.stream = StreamingOdometry(mod.pwclonet, streams=1, num_points=mod.num_points, max_frames=max_frames,
-                                        graph=graph, sweeps=sweeps)
+                                        graph=graph, sweeps=sweeps, refine=refine)
+        self.refine = refine is not None
 
     def init(self):
         """Start of a sequence: clears the elapsed times and the trajectory, loads the checkpoint if one is given."""
@@ -630,7 +703,8 @@ class PWCLONetOdometry:
                 self.stream.step_sweeps(frame, [frame.shape[1]], times=self._times(data_dict, frame))
             else:
                 self.stream.step(frame)
-        data_dict[self.relative_pose_key()] = self.stream.relative_poses()[-1, 0].float().cpu().numpy()
+        poses = self.stream.refined_relative_poses() if self.refine else self.stream.relative_poses()
+        data_dict[self.relative_pose_key()] = poses[-1, 0].float().cpu().numpy()
 
     def _times(self, data_dict, frame):
         """The (1, n) times of a raw frame when the stream de-skews, else None.  A frame without the key gets equal times:

@@ -1,0 +1,357 @@
+"""Point-to-plane registration of incoming frames against a sliding local map, on the device.
+
+The reference's odometry is ``ICPFrameToModel`` (R/slam/odometry/icp_odometry.py:248-299, R = /root/reference): a learned
+model supplies the initial guess (R/slam/initialization.py:225-285) and point-to-plane Gauss-Newton refines it against a
+local map of the last frames (R/slam/odometry/local_map.py:254-427, R/slam/common/optimization.py:297-354, 391-443), on the
+host.  ``IcpRefiner`` does the refinement with the kernels of ``csrc/icp.hip`` and the existing neighbour search:
+
+    ref = IcpRefiner(streams=S, num_points=8192)
+    T = ref.register(cloud, init)          # cloud (S, n, 3) fp32, init (S, 4, 4) fp64 or (S, 7) pose rows
+
+``T`` maps the frame's points into the previous frame (``synthetic.kitti_like_sequence``'s ground truth, what
+``StreamingOdometry.trajectory()`` multiplies).  Every map slot keeps its cloud, normals and search structure in its own
+frame; only the frame's points move (``icp_queries``).  One iteration is four launches (queries, search, accumulate, solve);
+the iteration count is fixed and streams freeze on the device (``status()``), so a whole registration plus the map handover
+replays as one captured graph.  There is no CPU path.
+"""
+import numpy as np
+import torch
+
+from . import _lib, evaluation
+
+MAX_STREAMS = 1024
+MAX_SLOTS = 64                                   # csrc/icp.hip: ICP_MAX_SLOTS
+ROW = 32                                         # csrc/icp.hpp: ICP_ROW and the offsets inside a row of sums
+H0, G0, SW, COST, PAIRS = 0, 21, 27, 28, 29
+CONVERGED, FEW_PAIRS, BAD_PIVOT = 1, 2, 4        # status bits
+
+
+def _p(t):
+    return t.data_ptr() if t is not None else 0
+
+
+def _need(t, name, dtype, shape=None):
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise ValueError("%s must be a %s tensor%s, got %s %s" % (
+            name, str(dtype).replace("torch.", ""), "" if shape is None else " of shape %s" % (tuple(shape),),
+            getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ()))))
+    if not t.is_cuda:
+        raise RuntimeError("CPU not supported")
+    if not t.is_contiguous():
+        raise ValueError("%s must be contiguous" % name)
+
+
+def groups(n):
+    """Rows of partial sums per stream that ``accumulate`` writes for clouds of n points."""
+    return (int(n) + 255) // 256
+
+
+# ---- the ops alone -----------------------------------------------------------------------------------------------------
+
+def self_neighbours(xyz, k):
+    """xyz (b, n, 3) -> (idx (b, n, k + 1) int32 of every point's k + 1 nearest in its own cloud, the structure)."""
+    b, n, _ = xyz.shape
+    lib = _lib.load()
+    ws = torch.empty((lib.knn_point_build_bytes(b, n),), dtype=torch.uint8, device=xyz.device)
+    idx = torch.empty((b, n, k + 1), dtype=torch.int32, device=xyz.device)
+    _lib.call("knn_build_kernel_wrapper", xyz.device, b, n, _p(xyz), _p(ws), 0)
+    _lib.call("knn_point_prebuilt_kernel_wrapper", xyz.device, b, n, n, k + 1, _p(xyz), _p(idx), 0, _p(ws))
+    return idx, ws
+
+
+def normals(xyz, k=10):
+    """xyz (b, n, 3) fp32, 64 <= n <= 16384 -> (normals (b, n, 3) fp32, eig (b, n, 3) fp64 ascending): the unit eigenvector
+    of the smallest eigenvalue of the covariance of the k nearest neighbours about the point, turned towards the origin;
+    zero where that covariance has rank below 2."""
+    if not isinstance(xyz, torch.Tensor) or xyz.dim() != 3 or xyz.shape[-1] != 3:
+        raise ValueError("normals: xyz must be (b, n, 3), got %s" % (tuple(getattr(xyz, "shape", ())),))
+    b, n, _ = xyz.shape
+    k = int(k)
+    if not 64 <= n <= 16384:
+        raise ValueError("normals: n=%d outside [64, 16384] (the neighbour search's range)" % n)
+    if not 1 <= k <= min(63, n - 1):
+        raise ValueError("normals: k=%d outside [1, %d]" % (k, min(63, n - 1)))
+    _need(xyz, "normals: xyz", torch.float32)
+    idx, _ = self_neighbours(xyz, k)
+    out = torch.empty((b, n, 3), dtype=torch.float32, device=xyz.device)
+    eig = torch.empty((b, n, 3), dtype=torch.float64, device=xyz.device)
+    _lib.call("icp_normals_kernel_wrapper", xyz.device, b, n, k, _p(xyz), _p(idx), _p(out), _p(eig))
+    return out, eig
+
+
+def queries(A, p, T=None):
+    """A (S, M, 4, 4) fp64, p (S, n, 3) fp32, T (S, 4, 4) fp64 or None -> q (S, M, n, 3) = fp32(A[s, m] T[s] p[s, i])."""
+    if not isinstance(A, torch.Tensor) or A.dim() != 4:
+        raise ValueError("queries: A must be (S, M, 4, 4)")
+    S, M = A.shape[:2]
+    _need(A, "queries: A", torch.float64, (S, M, 4, 4))
+    if not isinstance(p, torch.Tensor) or p.dim() != 3:
+        raise ValueError("queries: p must be (S, n, 3)")
+    n = p.shape[1]
+    _need(p, "queries: p", torch.float32, (S, n, 3))
+    if T is not None:
+        _need(T, "queries: T", torch.float64, (S, 4, 4))
+    q = torch.empty((S, M, n, 3), dtype=torch.float32, device=p.device)
+    _lib.call("icp_queries_kernel_wrapper", p.device, S, M, n, _p(A), _p(T), _p(p), _p(q))
+    return q
+
+
+def accumulate(p, q, idx, dist, map_xyz, map_normals, live, R, T, sigma=0.5, max_dist=1.0):
+    """One launch of the normal equations' sums -> partial (S, groups(n), 32) fp64, one row per workgroup of 256 points.
+    p (S, n, 3), q (S, M, n, 3), idx / dist (S, M, n) from the search with nsample = 1, map_xyz / map_normals (S, M, n, 3),
+    live (S, M) int32, R (S, M, 3, 3) and T (S, 4, 4) fp64."""
+    if not isinstance(q, torch.Tensor) or q.dim() != 4:
+        raise ValueError("accumulate: q must be (S, M, n, 3)")
+    S, M, n, _ = q.shape
+    if not float(sigma) > 0.0 or not float(max_dist) >= 0.0:
+        raise ValueError("accumulate: sigma=%r must be > 0 and max_dist=%r >= 0" % (sigma, max_dist))
+    _need(p, "accumulate: p", torch.float32, (S, n, 3))
+    _need(q, "accumulate: q", torch.float32, (S, M, n, 3))
+    _need(idx, "accumulate: idx", torch.int32, (S, M, n))
+    _need(dist, "accumulate: dist", torch.float32, (S, M, n))
+    _need(map_xyz, "accumulate: map_xyz", torch.float32, (S, M, n, 3))
+    _need(map_normals, "accumulate: map_normals", torch.float32, (S, M, n, 3))
+    _need(live, "accumulate: live", torch.int32, (S, M))
+    _need(R, "accumulate: R", torch.float64, (S, M, 3, 3))
+    _need(T, "accumulate: T", torch.float64, (S, 4, 4))
+    partial = torch.empty((S, groups(n), ROW), dtype=torch.float64, device=p.device)
+    _lib.call("icp_accumulate_kernel_wrapper", p.device, S, M, n, _p(p), _p(q), _p(idx), _p(dist), _p(map_xyz),
+              _p(map_normals), _p(live), _p(R), _p(T), float(sigma), float(max_dist), _p(partial))
+    return partial
+
+
+def solve(partial, T, status, it=0, damping=1e-6, threshold_delta_pose=1e-4, min_pairs=64):
+    """One launch of the solver on partial (S, G, 32): updates T (S, 4, 4) fp64 and status (S,) int32 in place and returns
+    dict(sum (S, 32), delta (S, 6), iterations, pairs (S,) int32, cost (S,) fp64)."""
+    if not isinstance(partial, torch.Tensor) or partial.dim() != 3:
+        raise ValueError("solve: partial must be (S, G, 32)")
+    S, G, _ = partial.shape
+    if not float(damping) >= 0.0 or not float(threshold_delta_pose) >= 0.0 or int(min_pairs) < 1 or int(it) < 0:
+        raise ValueError("solve: damping, threshold_delta_pose >= 0, min_pairs >= 1 and it >= 0 are required")
+    _need(partial, "solve: partial", torch.float64, (S, G, ROW))
+    _need(T, "solve: T", torch.float64, (S, 4, 4))
+    _need(status, "solve: status", torch.int32, (S,))
+    dev = partial.device
+    out = dict(sum=torch.empty((S, ROW), dtype=torch.float64, device=dev),
+               delta=torch.empty((S, 6), dtype=torch.float64, device=dev),
+               iterations=torch.zeros((S,), dtype=torch.int32, device=dev),
+               pairs=torch.zeros((S,), dtype=torch.int32, device=dev),
+               cost=torch.zeros((S,), dtype=torch.float64, device=dev))
+    _lib.call("icp_solve_kernel_wrapper", dev, S, G, int(it), _p(partial), float(damping), float(threshold_delta_pose),
+              int(min_pairs), _p(T), _p(status), _p(out["iterations"]), _p(out["pairs"]), _p(out["cost"]), _p(out["sum"]),
+              _p(out["delta"]))
+    return out
+
+
+# ---- the refiner -------------------------------------------------------------------------------------------------------
+
+class IcpRefiner:
+    """Registers one frame per call for S streams in lock step against each stream's map of the last ``map_size`` frames.
+
+    ``register(cloud, init)``: cloud (S, n, 3) fp32, init (S, 4, 4) fp64 or (S, 7) fp32 pose rows [tx ty tz qw qx qy qz]
+    (``evaluation.rows_to_transforms``) -> the refined pose (S, 4, 4) fp64, a static buffer that the next call overwrites
+    (clone to keep it).  The first frame after a reset only fills the map and returns ``init`` unchanged (no slot is live,
+    so the stream freezes in iteration 0 with the few-pairs bit).  ``iters`` Gauss-Newton iterations always run; a stream
+    freezes on the device when its step falls below ``threshold_delta_pose`` (status bit 1), when fewer than ``min_pairs``
+    points found a partner within ``max_dist`` (bit 2) or when the damped 6x6 system has a pivot that is not positive (bit
+    4); a stream frozen by bit 2 or 4 in iteration 0 returns ``init`` bit for bit.  ``damping`` is added to the diagonal of
+    the system normalised by the sum of weights: a direction the scene does not constrain keeps the initial guess.
+    ``graph=True``: the first call runs eagerly (it loads every kernel), the second captures one graph that every later
+    call replays.  ``register(..., trace=True)`` (``graph=False`` only) also returns, per iteration, clones of the queries,
+    ``idx``, ``dist``, the summed row, ``delta`` and ``T``."""
+
+    def __init__(self, streams, num_points, map_size=4, iters=10, sigma=0.5, max_dist=1.0, k_normals=10, damping=1e-6,
+                 threshold_delta_pose=1e-4, min_pairs=64, graph=True):
+        S, n, M, k = int(streams), int(num_points), int(map_size), int(k_normals)
+        if not 1 <= S <= MAX_STREAMS:
+            raise ValueError("IcpRefiner: streams=%d outside [1, %d]" % (S, MAX_STREAMS))
+        if not 64 <= n <= 16384:
+            raise ValueError("IcpRefiner: num_points=%d outside [64, 16384] (the neighbour search's range)" % n)
+        if not 1 <= M <= MAX_SLOTS or S * M > 65535:
+            raise ValueError("IcpRefiner: map_size=%d outside [1, %d] (and streams * map_size <= 65535)" % (M, MAX_SLOTS))
+        if int(iters) < 1:
+            raise ValueError("IcpRefiner: iters=%d must be >= 1" % int(iters))
+        if not float(sigma) > 0.0 or not np.isfinite(float(sigma)):
+            raise ValueError("IcpRefiner: sigma=%r must be finite and > 0" % (sigma,))
+        if not float(max_dist) >= 0.0:
+            raise ValueError("IcpRefiner: max_dist=%r must be >= 0" % (max_dist,))
+        if not 1 <= k <= min(63, n - 1):
+            raise ValueError("IcpRefiner: k_normals=%d outside [1, %d]" % (k, min(63, n - 1)))
+        if not float(damping) >= 0.0 or not np.isfinite(float(damping)):
+            raise ValueError("IcpRefiner: damping=%r must be finite and >= 0" % (damping,))
+        if not float(threshold_delta_pose) >= 0.0:
+            raise ValueError("IcpRefiner: threshold_delta_pose=%r must be >= 0" % (threshold_delta_pose,))
+        if int(min_pairs) < 1:
+            raise ValueError("IcpRefiner: min_pairs=%d must be >= 1 (an empty map freezes a stream through it)"
+                             % int(min_pairs))
+        self.streams, self.num_points, self.map_size, self.iters, self.k_normals = S, n, M, int(iters), k
+        self.sigma, self.max_dist, self.damping = float(sigma), float(max_dist), float(damping)
+        self.threshold_delta_pose, self.min_pairs, self.graph = float(threshold_delta_pose), int(min_pairs), bool(graph)
+        self.bufs = None
+        self.calls = 0              # register() calls so far: call 0 is eager, call 1 captures
+        self._graph = None
+
+    # ---- state -------------------------------------------------------------------------------------------------------
+
+    def _alloc(self, device):
+        S, M, n, k = self.streams, self.map_size, self.num_points, self.k_normals
+        lib = _lib.load()
+        f32 = lambda *s: torch.zeros(s, dtype=torch.float32, device=device)
+        f64 = lambda *s: torch.zeros(s, dtype=torch.float64, device=device)
+        i32 = lambda *s: torch.zeros(s, dtype=torch.int32, device=device)
+        eye = lambda *s: torch.eye(s[-1], dtype=torch.float64, device=device).expand(*s).contiguous()
+        G = groups(n)
+        assert G == lib.icp_accumulate_groups(n)
+        self.bufs = dict(
+            cloud=f32(S, n, 3), T=eye(S, 4, 4),
+            stage_ws=torch.zeros((lib.knn_point_build_bytes(S, n),), dtype=torch.uint8, device=device),
+            self_idx=i32(S, n, k + 1), stage_normals=f32(S, n, 3), stage_eig=f64(S, n, 3),
+            map_xyz=f32(S, M, n, 3), map_normals=f32(S, M, n, 3),
+            map_ws=torch.zeros((lib.knn_point_build_bytes(S * M, n),), dtype=torch.uint8, device=device),
+            A=eye(S, M, 4, 4), R=eye(S, M, 3, 3), live=i32(S, M), cursor=i32(S),
+            q=f32(S, M, n, 3), idx=i32(S, M, n), dist=f32(S, M, n), partial=f64(S, G, ROW),
+            status=i32(S), iterations=i32(S), pairs=i32(S), cost=f64(S), sum=f64(S, ROW), delta=f64(S, 6))
+
+    def _seed_structures(self):
+        """Before the first registration: every slot's search structure becomes the first frame's (its live flag stays 0),
+        so that no search ever walks memory that no build has written."""
+        b, S, M = self.bufs, self.streams, self.map_size
+        rows = b["stage_ws"].numel() // S // 33 * 32            # bytes per cloud: 64 * 16 of rows for every 32 of boxes
+        boxes = rows // 32
+        b["map_ws"][:S * M * rows].view(S, M, rows).copy_(b["stage_ws"][:S * rows].view(S, 1, rows).expand(S, M, rows))
+        b["map_ws"][S * M * rows:].view(S, M, boxes).copy_(b["stage_ws"][S * rows:].view(S, 1, boxes).expand(S, M, boxes))
+
+    def status(self):
+        """(S,) int32 device view: 0 = the stream moved in every iteration of the last registration, else the bits of why
+        it froze (1 converged, 2 too few pairs, 4 pivot not positive).  None before the first call."""
+        return None if self.bufs is None else self.bufs["status"]
+
+    def diagnostics(self):
+        """Device views of the last registration: iterations used, pairs and the weighted cost sum w^2 r^2 of the last
+        iteration a stream took part in.  None before the first call."""
+        if self.bufs is None:
+            return None
+        return dict(iterations=self.bufs["iterations"], pairs=self.bufs["pairs"], cost=self.bufs["cost"])
+
+    def map_state(self):
+        """Device views of the maps' bookkeeping: A (S, M, 4, 4) previous frame -> slot, R (S, M, 3, 3) slot -> previous
+        frame, live (S, M), cursor (S,)."""
+        if self.bufs is None:
+            return None
+        return {k: self.bufs[k] for k in ("A", "R", "live", "cursor")}
+
+    def reset(self, streams=None):
+        """Empty the maps of all streams, or of ``streams`` (stream indices, or an (S,) bool mask): their next frame only
+        fills the map.  No sync and no new capture: the flags are device memory that the graph reads."""
+        S = self.streams
+        if streams is None:
+            mask = np.ones((S,), dtype=bool)
+        else:
+            arr = np.asarray(streams.cpu().numpy() if isinstance(streams, torch.Tensor) else streams)
+            if arr.dtype == bool:
+                if arr.shape != (S,):
+                    raise ValueError("IcpRefiner: a stream mask must have shape (%d,), got %s" % (S, arr.shape))
+                mask = arr
+            else:
+                if arr.ndim != 1 or (arr.size and arr.dtype.kind not in "iu"):
+                    raise ValueError("IcpRefiner: streams must be stream indices or an (S,) bool mask")
+                arr = arr.astype(np.int64)
+                if arr.size and (arr.min() < 0 or arr.max() >= S):
+                    raise ValueError("IcpRefiner: streams %s outside [0, %d)" % (arr.tolist(), S))
+                mask = np.zeros((S,), dtype=bool)
+                mask[arr] = True
+        if self.bufs is None:
+            return
+        b = self.bufs
+        m = torch.from_numpy(mask).to(b["live"].device)
+        b["live"][m] = 0
+        b["cursor"][m] = 0
+        b["A"][m] = torch.eye(4, dtype=torch.float64, device=m.device)
+        b["R"][m] = torch.eye(3, dtype=torch.float64, device=m.device)
+
+    # ---- one registration ----------------------------------------------------------------------------------------------
+
+    def _stage(self):
+        """The new frame's search structure, own neighbours and normals: what its slot will hold."""
+        b, S, n, k = self.bufs, self.streams, self.num_points, self.k_normals
+        dev = b["cloud"].device
+        _lib.call("knn_build_kernel_wrapper", dev, S, n, _p(b["cloud"]), _p(b["stage_ws"]), 0)
+        _lib.call("knn_point_prebuilt_kernel_wrapper", dev, S, n, n, k + 1, _p(b["cloud"]), _p(b["self_idx"]), 0,
+                  _p(b["stage_ws"]))
+        _lib.call("icp_normals_kernel_wrapper", dev, S, n, k, _p(b["cloud"]), _p(b["self_idx"]), _p(b["stage_normals"]),
+                  _p(b["stage_eig"]))
+
+    def _iterate(self, trace=None):
+        b, S, M, n = self.bufs, self.streams, self.map_size, self.num_points
+        dev = b["cloud"].device
+        G = b["partial"].shape[1]
+        for it in range(self.iters):
+            _lib.call("icp_queries_kernel_wrapper", dev, S, M, n, _p(b["A"]), _p(b["T"]), _p(b["cloud"]), _p(b["q"]))
+            _lib.call("knn_point_prebuilt_kernel_wrapper", dev, S * M, n, n, 1, _p(b["q"]), _p(b["idx"]), _p(b["dist"]),
+                      _p(b["map_ws"]))
+            _lib.call("icp_accumulate_kernel_wrapper", dev, S, M, n, _p(b["cloud"]), _p(b["q"]), _p(b["idx"]), _p(b["dist"]),
+                      _p(b["map_xyz"]), _p(b["map_normals"]), _p(b["live"]), _p(b["R"]), _p(b["T"]), self.sigma,
+                      self.max_dist, _p(b["partial"]))
+            if trace is not None:
+                before = b["T"].clone()
+            _lib.call("icp_solve_kernel_wrapper", dev, S, G, it, _p(b["partial"]), self.damping, self.threshold_delta_pose,
+                      self.min_pairs, _p(b["T"]), _p(b["status"]), _p(b["iterations"]), _p(b["pairs"]), _p(b["cost"]),
+                      _p(b["sum"]), _p(b["delta"]))
+            if trace is not None:
+                trace.append(dict(q=b["q"].clone(), idx=b["idx"].clone(), dist=b["dist"].clone(), sum=b["sum"].clone(),
+                                  delta=b["delta"].clone(), T_before=before, T=b["T"].clone(),
+                                  status=b["status"].clone()))
+
+    def _push(self):
+        b, S, M, n = self.bufs, self.streams, self.map_size, self.num_points
+        _lib.call("icp_map_push_kernel_wrapper", b["cloud"].device, S, M, n, _p(b["T"]), _p(b["cloud"]),
+                  _p(b["stage_normals"]), _p(b["stage_ws"]), _p(b["map_xyz"]), _p(b["map_normals"]), _p(b["map_ws"]),
+                  _p(b["A"]), _p(b["R"]), _p(b["live"]), _p(b["cursor"]))
+
+    def _body(self, trace=None):
+        self._stage()
+        self._iterate(trace)
+        self._push()
+
+    def _check(self, cloud, init):
+        S, n = self.streams, self.num_points
+        if not isinstance(cloud, torch.Tensor) or cloud.dtype != torch.float32 or tuple(cloud.shape) != (S, n, 3):
+            raise ValueError("IcpRefiner: cloud must be float32 (%d, %d, 3), got %s %s"
+                             % (S, n, getattr(cloud, "dtype", type(cloud)), tuple(getattr(cloud, "shape", ()))))
+        ok = isinstance(init, torch.Tensor) and (
+            (init.dtype == torch.float64 and tuple(init.shape) == (S, 4, 4)) or
+            (init.dtype == torch.float32 and tuple(init.shape) == (S, 7)))
+        if not ok:
+            raise ValueError("IcpRefiner: init must be float64 (%d, 4, 4) or float32 (%d, 7) pose rows, got %s %s"
+                             % (S, S, getattr(init, "dtype", type(init)), tuple(getattr(init, "shape", ()))))
+        if not cloud.is_cuda or not init.is_cuda:
+            raise RuntimeError("CPU not supported")
+
+    def register(self, cloud, init, trace=False):
+        if trace and self.graph:
+            raise ValueError("IcpRefiner: trace=True needs graph=False (a replayed graph cannot hand out its iterations)")
+        self._check(cloud, init)
+        if init.dim() == 2:
+            init = evaluation.rows_to_transforms(init)
+        first = self.bufs is None
+        if first:
+            self._alloc(cloud.device)
+        b = self.bufs
+        b["cloud"].copy_(cloud)
+        b["T"].copy_(init)
+        if first:
+            self._stage()
+            self._seed_structures()
+        steps = [] if trace else None
+        if not self.graph or self.calls == 0:
+            self._body(steps)
+        else:
+            if self._graph is None:
+                torch.cuda.synchronize(cloud.device)
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    self._body()
+                self._graph = g
+            self._graph.replay()
+        self.calls += 1
+        return (b["T"], steps) if trace else b["T"]
