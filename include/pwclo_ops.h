@@ -828,13 +828,6 @@ void pose_head_train_backward_kernel_wrapper(int B, int N, const float *emb, con
 void odom_rows_to_transforms_kernel_wrapper(int n, int row_stride, const float *rows, double *T, int invert);
 /* abs[f] = T[first] . ... . T[f] inside every sequence (kitti360_utils.py:422-426 applied to rel = T^-1). */
 void odom_accumulate_kernel_wrapper(int nseq, const int *seq_start, const double *T, double *abs_out);
-/* Streaming odometry: append one frame of S <= 1024 streams (one workgroup) to trajectories kept on the device.
- * rel / abs_out: (capacity, S, 4, 4) fp64; count: ONE int in DEVICE memory, the frames appended so far.  Step
- * (prime == 0): k = *count, rel[k, i] = the transform of pose row i (rows, row_stride as above; 28 for level 1 of a
- * (S,4,7) pose_params tensor), abs_out[k, i] = abs_out[k-1, i] . rel[k, i], then *count = k + 1.  Prime (prime != 0,
- * rows unused): rel[0, i] = abs_out[0, i] = I and *count = 1.  k >= capacity: nothing written, *overflow = 1. */
-void odom_stream_append_kernel_wrapper(int S, int capacity, int prime, const float *rows, int row_stride, double *rel,
-                                       double *abs_out, int *count, int *overflow);
 /* Streaming odometry with per-stream dropouts and restarts.  All pointers DEVICE memory.
  * One workgroup, one thread per stream (S <= 1024).  active / restart: S ints, this call's masks.  pose: (S,4,7) fp32
  * contiguous, rows [tx ty tz qw qx qy qz].  Persistent: have_prev / count / valid (S ints each), rel / abs_out

@@ -5,6 +5,7 @@ fails, the call raises.  ``load()`` never builds anything; run
 ``python -m pwclonet_pylidarslam_amd.build`` (or ``__graft_entry__.build()``) first.
 """
 import ctypes
+import gc
 import os
 
 import torch
@@ -149,7 +150,6 @@ SIGNATURES = {
     "odom_rows_to_transforms_kernel_wrapper": ([_i, _i, _F, _F, _i], None),
     "odom_accumulate_kernel_wrapper": ([_i, _F, _F, _F], None),
     "odom_cumulative_distance_kernel_wrapper": ([_i, _F, _F, _F], None),
-    "odom_stream_append_kernel_wrapper": ([_i, _i, _i, _F, _i, _F, _F, _F, _F], None),
     "stream_append_masked_kernel_wrapper": ([_i, _i] + [_F] * 9, None),
     "stream_handover_max_segments": ([], _i),
     "stream_handover_masked_kernel_wrapper": ([_i] + [ctypes.POINTER(ctypes.c_void_p)] * 2
@@ -191,6 +191,16 @@ def check(what):
         msg = lib.pwclo_last_error_message().decode("utf-8", "replace")
         lib.pwclo_clear_error()
         raise RuntimeError("%s failed (error %d): %s" % (what, code, msg))
+
+
+def capture(graph, **kw):
+    """``torch.cuda.graph(graph, **kw)`` after a full garbage collection.  torch (2.9 on) no longer collects before a
+    capture, so a dead Python cycle that holds captured graphs or device memory -- the traceback of a failed call keeps
+    its frame's locals in one -- would be freed by the automatic collector whenever it next runs, possibly in the middle
+    of this capture, where destroying another graph aborts the process.  Collected here, it is freed outside every
+    capture, like any object that goes out of scope."""
+    gc.collect()
+    return torch.cuda.graph(graph, **kw)
 
 
 def synchronize(device=None):

@@ -207,7 +207,7 @@ __global__ __launch_bounds__(1024) void sweep_filter_deskew_grid_compact_kernel(
 
 // After the append: the motion the next sweep of stream s is de-skewed with (ConstantVelocityInitialization: the relative
 // pose registered last).  One thread per stream.  active (nullable: every stream): an idle stream's motion stays as it is.
-// rows (nullable: the identity, after a prime): stream s's level-1 pose row at rows + s * row_stride; the masked append has
+// rows (nullable: the identity for every active stream): stream s's level-1 pose row at rows + s * row_stride; the masked append has
 // already turned the rows of streams that primed into the identity, so a primed stream hands over the identity too.
 __global__ __launch_bounds__(1024) void stream_motion_handover_kernel(int S, const int *__restrict__ active,
                                                                       const float *__restrict__ rows, int row_stride,

@@ -27,39 +27,6 @@ __global__ __launch_bounds__(256) void odom_rows_to_transforms_kernel(int n, int
   se3_store(T + (size_t)i * 16, a);
 }
 
-// Streaming odometry: append one frame of S streams to device-resident trajectories.
-// rel / abs: (capacity, S, 4, 4) fp64; *count = frames appended so far (device int, so a captured graph appends
-// without new arguments).  k = *count; rel[k, i] = quat2mat(row i), abs[k, i] = abs[k-1, i] . rel[k, i] (abs[-1] = I,
-// the recurrence of odom_accumulate_kernel).  prime != 0: k = 0 and rel[0, i] = abs[0, i] = I (the reference's
-// relative_poses[0] = eye).  k >= capacity: nothing is written but *overflow = 1.  One workgroup: every thread reads
-// *count before the barrier, thread 0 advances it after.
-__global__ __launch_bounds__(1024) void odom_stream_append_kernel(int S, int capacity, int prime,
-                                                                  const float *__restrict__ rows, int row_stride,
-                                                                  double *__restrict__ rel, double *__restrict__ abs_out,
-                                                                  int *__restrict__ count, int *__restrict__ overflow) {
-  const int i = threadIdx.x;
-  const int k = prime ? 0 : *count;
-  const bool fits = k >= 0 && k < capacity;
-  if (fits && i < S) {
-    const size_t at = ((size_t)k * S + i) * 16;
-    if (prime) {
-      const Se3 id = se3_identity();
-      se3_store(rel + at, id);
-      se3_store(abs_out + at, id);
-    } else {
-      const Se3 t = pose_row_to_se3(rows + (size_t)i * row_stride);
-      const Se3 a = k > 0 ? se3_mul(se3_load(abs_out + at - (size_t)S * 16), t) : t;
-      se3_store(rel + at, t);
-      se3_store(abs_out + at, a);
-    }
-  }
-  __syncthreads();
-  if (i == 0) {
-    if (fits) *count = k + 1;
-    else *overflow = 1;
-  }
-}
-
 // abs[f] = T[0] . T[1] ... T[f] within each sequence (kitti360_utils.py:422-426 with rel = T^-1:
 // abs[f] = inv(rel[f] @ inv(abs[f-1])) = abs[f-1] . T[f], abs[-1] = I).  One wave per sequence: every lane
 // multiplies a contiguous chunk, the 64 chunk products are scanned with 6 shuffle steps, then each lane
@@ -175,18 +142,6 @@ extern "C" void odom_rows_to_transforms_kernel_wrapper(int n, int row_stride, co
   hipLaunchKernelGGL(odom_rows_to_transforms_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, current_stream(), n,
                      row_stride, rows, T, invert);
   check_launch("odom_rows_to_transforms");
-}
-
-extern "C" void odom_stream_append_kernel_wrapper(int S, int capacity, int prime, const float *rows, int row_stride,
-                                                  double *rel, double *abs_out, int *count, int *overflow) {
-  if (S <= 0) return;
-  PWCLO_REQUIRE(S <= 1024, "odom_stream_append: S=%d streams exceed one workgroup (1024)", S);
-  PWCLO_REQUIRE(capacity >= 1, "odom_stream_append: capacity=%d must be >= 1", capacity);
-  PWCLO_REQUIRE(prime || (rows != nullptr && row_stride >= 7), "odom_stream_append: rows missing or row_stride=%d < 7",
-                row_stride);
-  hipLaunchKernelGGL(odom_stream_append_kernel, dim3(1), dim3(ceil_div(S, 64) * 64), 0, current_stream(), S, capacity,
-                     prime, rows, row_stride, rel, abs_out, count, overflow);
-  check_launch("odom_stream_append");
 }
 
 extern "C" void odom_accumulate_kernel_wrapper(int nseq, const int *seq_start, const double *T, double *abs_out) {

@@ -1,8 +1,8 @@
-// Streaming odometry with per-stream dropouts and restarts (gfx950).
+// The state machine of streaming odometry (gfx950).
 //
-// The lock-step stream (section 11) has one frame counter and copies the whole previous-frame state at the end of
-// every step.  Here every stream carries its own state on the device, driven by two masks the caller delivers with
-// every call -- active[s]: stream s delivered a frame; restart[s]: that frame starts a new sequence:
+// Every stream carries its own state on the device, driven by two masks loaded before every call -- active[s]: stream
+// s delivered a frame; restart[s]: that frame starts a new sequence (lock step, section 11, is the case active = 1,
+// restart = 0 for every stream):
 //   idle   (!active)                          nothing moves, valid = 0
 //   prime  (active && (restart || !have_prev))  rel[0,s] = abs[0,s] = I, count = 1, have_prev = 1, valid = 0
 //   pair   (otherwise)                        k = count: rel[k,s] = quat2mat(row), abs[k,s] = abs[k-1,s] . rel[k,s],

@@ -233,13 +233,13 @@ class FlatTrainStep:
             torch.cuda.synchronize(dev)
             self.opt.zero_grad(set_to_none=True)
             self.front = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.front, **self.capture_kw(process_group)):
+            with _lib.capture(self.front, **self.capture_kw(process_group)):
                 self.static_loss = self._front()
                 if process_group is None:
                     self.opt.step()
             if process_group is not None:
                 self.back = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.back, **self.capture_kw(process_group)):
+                with _lib.capture(self.back, **self.capture_kw(process_group)):
                     self.opt.step()
             torch.cuda.synchronize(dev)
 

@@ -7,6 +7,8 @@ allocate nothing and never synchronise, so they are capturable) and replays it p
 """
 import torch
 
+from . import _lib
+
 
 class GraphedForward:
     """``GraphedForward(net)(xyz_f1, xyz_f2) -> pose_params (B,4,7)`` for a ``PWCLONet`` in eval
@@ -46,7 +48,7 @@ class GraphedForward:
                 fused.branch = fused.branch and self.branch
             graph = torch.cuda.CUDAGraph()
             try:
-                with torch.cuda.graph(graph), torch.no_grad():
+                with _lib.capture(graph), torch.no_grad():
                     pose, log = self._run(*static)
             finally:
                 if fused is not None:
@@ -246,9 +248,9 @@ class StagedPipeline:
         fused = self.net._fused
         s1, s2 = xyz_f1.clone(), xyz_f2.clone()
         g_f, g_r = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g_f), torch.no_grad():
+        with _lib.capture(g_f), torch.no_grad():
             state = fused.sample(s1, s2)
-        with torch.cuda.graph(g_r, pool=g_f.pool()), torch.no_grad():   # same pool: `state` stays live
+        with _lib.capture(g_r, pool=g_f.pool()), torch.no_grad():   # same pool: `state` stays live
             pose, inter = fused.rest(state, return_intermediates=True)
         saved = self.net.log_mode
         self.net.log_mode = "device" if saved == "host" else saved      # no D2H inside a pipeline

@@ -6,13 +6,14 @@ it serves as frame 2 of pair (k-1, k) at once and as frame 1 of pair (k, k+1) on
 (``FusedPWCLONet.stream_step``).  Pair mode (``PWCLONet.forward``) computes every frame's pyramid twice; sequence mode
 (``forward_sequence``) needs the whole window first.  The rows are bit for bit the fused pair forward's at batch S.
 
-Every step appends its level-1 poses to trajectories kept on the device (``odom_stream_append_kernel``, fp64):
+Every step appends its level-1 poses to trajectories kept on the device (``stream_append_masked_kernel``, fp64):
 ``relative_poses()[k]`` = quat2mat of pair (k-1, k)'s row (``evaluation.rows_to_transforms``, not inverted),
 ``trajectory()[k]`` = their product (``evaluation.compute_absolute_poses``), row 0 the identity in both.
 
-``per_stream=True`` lifts the lock step: every call says which streams delivered a frame and which
-of those start a new sequence; a state machine on the device keeps one frame counter per stream and the handover moves
-only the streams that advanced, all inside one captured graph.
+One engine runs both modes: a state machine on the device keeps one frame counter per stream and
+the handover moves only the streams that advanced, all inside one captured graph per input shape.  ``per_stream=True``
+lets every call say which streams delivered a frame and which of those start a new sequence; lock step (the default) is
+the same machine with every stream active and none restarting, seen through a host-side view.
 
 ``PWCLONetOdometry`` mirrors the reference's ``PoseNetOdometry`` / ``OdometryAlgorithm`` interface for one stream
 (``init``, ``process_next_frame``, ``get_relative_poses``, ...); Hydra / OmegaConf configs stay out of scope.
@@ -24,7 +25,7 @@ import torch
 
 from . import _lib, preprocess
 
-MAX_STREAMS = 1024          # odom_stream_append_kernel: one workgroup, one thread per stream
+MAX_STREAMS = 1024          # stream_append_masked_kernel: one workgroup, one thread per stream
 RAW_NUM_POINTS = 8192       # raw mode: points sampled from every sweep's survivors (BASELINE configs[4])
 
 
@@ -38,15 +39,16 @@ class StreamingOdometry:
     -> pose_params (S, 4, 7) of the pair (previous frame, this frame), ``None`` for the first frame after ``reset()``.
 
     ``net``: a ``PWCLONet`` in eval mode with its fused weights packed (or packable: ``fused="auto"``); call ``step``
-    under ``torch.no_grad()``.  ``graph=True`` replays one captured prime graph and one captured step graph per input
-    shape; the returned pose is then a static buffer that the next step overwrites (clone to keep it), as with
+    under ``torch.no_grad()``.  ``graph=True`` replays one captured graph per input shape, which serves the frame
+    that primes after ``reset()`` as well (its row is computed against the stale previous frame and discarded); the
+    returned pose is then a static buffer that the next step overwrites (clone to keep it), as with
     ``graphed.GraphedForward``.  ``max_frames``: capacity of the device trajectories; ``step`` raises once that many
     frames have been recorded since ``reset()``.
 
     Raw mode (``sweeps=dict(dataset="kitti360" | "kitti", capacity=131072, near_threshold=30.0, tr=...)``):
     ``step_sweeps(sweeps, lengths)`` takes raw LiDAR sweeps (S, R <= capacity, 4) fp32 on the GPU, stream s using rows
     ``[:lengths[s]]``, and runs filter + compaction + exact sampling to ``num_points`` (default 8192) inside the same
-    prime / step graphs: one capture of each serves every length.  The clouds are bit for bit
+    graph: one capture serves every length.  The clouds are bit for bit
     those of ``preprocess.frames_to_clouds(sweep[None, :length], num_points, dataset, cap=capacity)``;
     ``survivor_counts()`` tells a caller which streams kept fewer than ``num_points`` points.  With ``voxel_size=0.3`` (and
     optionally ``voxel_capacity=24576``) in the dict the kept rows are grid-sampled to one per voxel ahead of the sampler
@@ -56,7 +58,7 @@ class StreamingOdometry:
     20) before grid, compaction and sampler: ``step_sweeps(sweeps, lengths, times=...)`` then needs the rows' times, (S, R)
     floating on the sweeps' device (and refuses them otherwise), and the motion is the constant-velocity prior, the
     level-1 pose row this stream registered last: the identity for the first two sweeps of a sequence, the row of pair
-    (k-2, k-1) for sweep k.  It lives in a device buffer written after the append, inside the graphs; ``motion()`` shows it.
+    (k-2, k-1) for sweep k.  It lives in a device buffer written after the append, inside the graph; ``motion()`` shows it.
     Per-stream mode: a stream that primes (restart, or no previous frame) and its next sweep get the identity, an idle
     stream keeps its motion, ``reset()`` / ``reset(streams=...)`` return the streams to the identity.
 
@@ -97,15 +99,14 @@ class StreamingOdometry:
         self.num_points = None if num_points is None else int(num_points)
         self.graph, self.warmup = bool(graph), int(warmup)
         self.frames_seen = 0
-        self._prev = None           # eager: the previous frame's FrameState
-        self._slot = None           # graph: persistent buffers of the previous frame (outside every graph pool)
-        self._graphs = {}           # input shape (or "sweeps") -> dict(static, prime, step)
+        self._slot = None           # persistent buffers of the previous frame (outside every graph pool)
+        self._graphs = {}           # input shape (or "sweeps") -> dict(static, step=(graph, pose), cloud)
         self._fused_id = None
-        self._rel = self._abs = self._count = self._overflow = None
-        self.handover_bytes = 0     # bytes the captured step copies into the persistent previous frame
+        self._rel = self._abs = self._overflow = None
+        self.handover_bytes = 0     # bytes the step hands over into the persistent previous frame
         self.per_stream = bool(per_stream)
-        self.captures = 0           # per-stream mode: graphs captured so far
-        self._static = {}           # per-stream eager mode: input shape -> static frames (graph mode: in _graphs)
+        self.captures = 0           # graphs captured so far
+        self._static = {}           # eager mode: input shape -> static frames (graph mode: in _graphs)
         self._active = self._restart = self._have_prev = self._counts = self._valid = None    # (S,) int32, device
         self._front = None          # raw mode: preprocess.SweepFrontEnd (persistent sweep, lengths, tr, sampler buffers)
         self._refine_cfg = None if refine is None else dict(refine)     # registration.IcpRefiner's keywords
@@ -185,7 +186,6 @@ class StreamingOdometry:
             for t in (self._have_prev, self._counts, self._valid):
                 t.zero_()
         self.frames_seen = 0
-        self._prev = None
         if self._overflow is not None:
             self._overflow.zero_()
         self._reset_motion(None)
@@ -209,6 +209,11 @@ class StreamingOdometry:
             return None
         return self._front.bufs.get("motion")
 
+    @property
+    def front(self):
+        """Raw mode: the ``preprocess.SweepFrontEnd`` behind ``step_sweeps``; None otherwise."""
+        return self._front
+
     def set_calibration(self, tr):
         """Raw KITTI mode: replace the calibration, (3,4) / (4,4) for all streams or (S,3,4) / (S,4,4) per stream.  It lives
         in a device buffer the captured graphs read, so no new capture follows."""
@@ -230,33 +235,38 @@ class StreamingOdometry:
         return None if self._front is None else self._front.voxel_counts()
 
     def step(self, frames, active=None, restart=None):
-        if self.per_stream:
-            return self._step_masked(frames, active, restart)
-        if active is not None or restart is not None:
-            raise ValueError("StreamingOdometry: active / restart masks need per_stream=True")
+        from . import fused as fused_mod
+        self._check_mode(active, restart)
         num_points = self._check(frames)
+        act, rst = self._masks(active, restart)
+        key = (tuple(frames.shape), frames.device)
+        store = self._graphs if self.graph else self._static
+        filled = None
+        if self._fused_id != id(self.net._fused) or key not in store:
+            host, j = self._first_active(act)               # new static rows: idle streams start from an active one
+            filled = frames.clone()
+            if not host.all():
+                filled[torch.from_numpy(~host).to(frames.device)] = frames[j]
         if self.num_points is None:
             self.num_points = num_points       # fixed from the first frame on: the persistent state has its shapes
         fused = self._begin(frames.device)
-        prime = self.frames_seen == 0
-        if self.graph:
-            key = (tuple(frames.shape), frames.device)
-            entry = self._graphs.get(key)
-            if entry is None:
-                entry = self._graphs[key] = dict(static=frames.clone(), prime=None, step=None)
-            static = entry["static"]
-            static.copy_(frames)
-            pose = self._replay(fused, entry, self._tap(lambda: static), prime)
+        self._load_masks(act, rst)
+        entry = store.get(key)
+        if entry is None:
+            entry = store[key] = dict(static=filled, step=None)
+        elif act is None:
+            entry["static"].copy_(frames)
         else:
-            pose = self._eager(fused, self._tap(lambda: frames)(), prime)
-        self._refine(pose)
-        self.frames_seen += 1
-        return pose
+            static, src = entry["static"], frames.contiguous()
+            per = static[0].numel() * static.element_size()
+            fused_mod.masked_copy([(static.data_ptr(), src.data_ptr(), per)], self._active)
+        static = entry["static"]
+        return self._finish(self._run(fused, entry, self._tap(lambda: static)))
 
     def step_sweeps(self, sweeps, lengths, times=None, active=None, restart=None):
         """Raw mode: sweeps (S, R <= capacity, 4) fp32 on the GPU, lengths (S,) host integers in [1, R] or a device
         integer tensor (read on the device; clamped to [0, R] there) -> pose as ``step``.  The host copies the rows
-        ``[:R]`` and the lengths into static buffers; filter, compaction and sampling run inside the captured graphs.
+        ``[:R]`` and the lengths into static buffers; filter, compaction and sampling run inside the captured graph.
         ``times`` (S, R) floating, on the sweeps' device: the rows' timestamps, required iff the stream was built with
         ``deskew=True`` (ValueError otherwise, before any launch)."""
         what = "StreamingOdometry"
@@ -265,26 +275,38 @@ class StreamingOdometry:
             raise RuntimeError("%s: step_sweeps needs raw mode (StreamingOdometry(..., sweeps=dict(dataset=..., "
                                "capacity=...)))" % what)
         front.check_times(times, sweeps, what)
-        if self.per_stream:
-            return self._step_sweeps_masked(sweeps, lengths, times, active, restart)
-        if active is not None or restart is not None:
-            raise ValueError("%s: active / restart masks need per_stream=True" % what)
+        self._check_mode(active, restart)
         self._check_room(what)
         host_lengths = front.check(sweeps, lengths, what)
         self._check_net(sweeps, what)
+        act, rst = self._masks(active, restart)
+        if front.bufs is None and act is not None:          # new static rows: idle streams start from an active one
+            host, j = self._first_active(act)
+            if not host.all():
+                idle = torch.from_numpy(~host).to(sweeps.device)
+                sweeps = sweeps.clone()
+                sweeps[idle] = sweeps[j]
+                if times is not None:
+                    times = times.clone()
+                    times[idle] = times[j]
+                if host_lengths is None:
+                    lengths = lengths.clone()
+                    lengths[idle] = lengths[j]
+                else:
+                    host_lengths = [v if a else host_lengths[j] for v, a in zip(host_lengths, host)]
         fused = self._begin(sweeps.device)
-        front.load(sweeps, lengths, host_lengths, times)
-        prime = self.frames_seen == 0
-        if self.graph:
-            entry = self._graphs.get("sweeps")
-            if entry is None:
-                entry = self._graphs["sweeps"] = dict(static=None, prime=None, step=None)
-            pose = self._replay(fused, entry, self._tap(front.run), prime)
+        self._load_masks(act, rst)
+        if front.deskew:
+            front.stream_words = (self._restart, self._have_prev)      # read by the front end's launch, on the device
+        if front.bufs is None or act is None:
+            front.load(sweeps, lengths, host_lengths, times)
         else:
-            pose = self._eager(fused, self._tap(front.run)(), prime)
-        self._refine(pose)
-        self.frames_seen += 1
-        return pose
+            front.load_masked(sweeps, lengths, host_lengths, self._active, times)
+        store = self._graphs if self.graph else self._static
+        entry = store.get("sweeps")
+        if entry is None:
+            entry = store["sweeps"] = dict(static=None, step=None)
+        return self._finish(self._run(fused, entry, self._tap(front.run)))
 
     def relative_poses(self, stream=None):
         """(frames_seen, S, 4, 4) fp64 device view: row 0 the identity, row k the transform of pair (k-1, k).
@@ -323,13 +345,13 @@ class StreamingOdometry:
         return self._refiner
 
     def valid(self):
-        """Per-stream mode: (S,) int32 device view, 1 where the last call's pose row is a real pair.  None before the
-        first call."""
+        """(S,) int32 device view, 1 where the last call's pose row is a real pair (lock step: all 0 on the call that
+        primes, all 1 otherwise).  None before the first call."""
         return self._valid
 
     def frame_counts(self):
-        """Per-stream mode: (S,) int32 device view of the frames recorded per stream since its last restart.  None
-        before the first call."""
+        """(S,) int32 device view of the frames recorded per stream since its last restart (lock step: ``frames_seen``
+        for every stream).  None before the first call."""
         return self._counts
 
     def overflowed(self):
@@ -377,17 +399,6 @@ class StreamingOdometry:
             init = pose[:, 0, :]
         self._ref_rel[self.frames_seen].copy_(self._refiner.register(cloud, init))
 
-    def _eager(self, fused, frames, prime):
-        if prime:
-            self._prev = fused.stream_prime(frames, self.num_points)
-            self._append(None)
-            self._hand_motion(None)
-            return None
-        pose, self._prev = fused.stream_step(self._prev, frames, self.num_points)
-        self._append(pose)
-        self._hand_motion(pose)
-        return pose
-
     def _view(self, buf, stream=None):
         if stream is None:
             if self.per_stream:
@@ -409,27 +420,18 @@ class StreamingOdometry:
         shape = (self.max_frames, self.streams, 4, 4)
         self._rel = torch.zeros(shape, dtype=torch.float64, device=device)
         self._abs = torch.zeros(shape, dtype=torch.float64, device=device)
-        self._count = torch.zeros((1,), dtype=torch.int32, device=device)
         self._overflow = torch.zeros((1,), dtype=torch.int32, device=device)
-        if self.per_stream:
-            z = lambda: torch.zeros((self.streams,), dtype=torch.int32, device=device)
-            self._active, self._restart, self._have_prev, self._counts, self._valid = z(), z(), z(), z(), z()
+        z = lambda: torch.zeros((self.streams,), dtype=torch.int32, device=device)
+        self._active, self._restart, self._have_prev, self._counts, self._valid = z(), z(), z(), z(), z()
 
-    def _append(self, pose):
-        """One launch: prime (pose None) or append the level-1 rows of pose (S,4,7) to the device trajectories."""
-        rows = pose[:, 0, :] if pose is not None else None
-        _lib.call("odom_stream_append_kernel_wrapper", self._rel.device, self.streams, self.max_frames,
-                  int(pose is None), _p(rows), int(rows.stride(0)) if rows is not None else 0, _p(self._rel),
-                  _p(self._abs), _p(self._count), _p(self._overflow))
-
-    def _hand_motion(self, pose, active=None):
+    def _hand_motion(self, pose):
         """Raw mode with ``deskew``, after the append, one launch: the motion of the streams' next sweeps = the level-1
-        rows of ``pose`` (S, 4, 7), or the identity after a prime (pose None); streams with ``active[s] == 0`` keep theirs."""
+        rows of ``pose`` (S, 4, 7), the identity for a stream that primed; streams with ``active[s] == 0`` keep theirs."""
         motion = self.motion()
         if motion is None:
             return
-        _lib.call("stream_motion_handover_kernel_wrapper", motion.device, self.streams, _p(active), _p(pose),
-                  int(pose.stride(0)) if pose is not None else 0, _p(motion))
+        _lib.call("stream_motion_handover_kernel_wrapper", motion.device, self.streams, _p(self._active), _p(pose),
+                  int(pose.stride(0)), _p(motion))
 
     def _warm(self, fn):
         """Allocator warm-up and one-time kernel attributes on a side stream, as ``GraphedForward`` does."""
@@ -446,51 +448,9 @@ class StreamingOdometry:
 
     def _capture(self, fn):
         graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph), torch.no_grad():
+        with _lib.capture(graph), torch.no_grad():
             out = fn()
         return graph, out
-
-    def _replay(self, fused, entry, source, prime):
-        """Replay (capturing first if needed) ``entry``'s prime or step graph.  ``source()`` launches whatever produces
-        the frame batch from the static inputs (the static frames themselves, or the raw front end) and returns it;
-        it is captured into both graphs."""
-        n = self.num_points
-        if prime and entry["prime"] is None:
-            first = self._warm(lambda: fused.stream_prime(source(), n))
-            if self._slot is None:
-                # persistent previous frame, allocated outside every graph pool and filled with a real state at once
-                # (a step must never read uninitialised search structures)
-                self._slot = first.frame1_buffers().copy_frame1_(first)
-                self.handover_bytes = self._slot.frame1_bytes()
-
-            def prime_body():
-                self._slot.copy_frame1_(fused.stream_prime(source(), n))
-                self._append(None)
-                self._hand_motion(None)
-            entry["prime"] = self._capture(prime_body)[0]
-            entry["prime_cloud"] = self._tapped
-        if not prime and entry["step"] is None:
-            self._warm(lambda: fused.stream_step(self._slot, source(), n))
-
-            def step_body():
-                pose, new = fused.stream_step(self._slot, source(), n)
-                self._append(pose)
-                self._hand_motion(pose)
-                # The handover: every branch of the pair stage that reads the previous frame (the set-upconvs on side
-                # streams included) has been joined into this stream by now, so the copy is ordered after them.
-                self._slot.copy_frame1_(new)
-                return pose
-            entry["step"] = self._capture(step_body)
-            entry["step_cloud"] = self._tapped
-        self._tapped = entry.get("prime_cloud" if prime else "step_cloud")
-        if prime:
-            entry["prime"].replay()
-            return None
-        graph, pose = entry["step"]
-        graph.replay()
-        return pose
-
-    # ---- per-stream mode (DESIGN.md section 18) ------------------------------------------------------------------------
 
     def _stream_mask(self, mask, what="streams"):
         """An (S,) bool or integer mask, host sequence or device tensor -> (S,) int32 0 / 1 tensor where the caller's
@@ -518,6 +478,10 @@ class StreamingOdometry:
                              % (what, S, arr.dtype, arr.shape))
         return torch.from_numpy((arr != 0).astype(np.int32))
 
+    def _check_mode(self, active, restart):
+        if not self.per_stream and (active is not None or restart is not None):
+            raise ValueError("StreamingOdometry: active / restart masks need per_stream=True")
+
     def _masks(self, active, restart):
         """The call's masks, checked (ValueError before any launch) -> ((S,) int32 tensors or None, None)."""
         act = None if active is None else self._stream_mask(active, "active")
@@ -534,7 +498,6 @@ class StreamingOdometry:
         return host, int(np.flatnonzero(host)[0])
 
     def _load_masks(self, act, rst):
-        dev = self._active.device
         if act is None:
             self._active.fill_(1)
         else:
@@ -543,28 +506,28 @@ class StreamingOdometry:
             self._restart.zero_()
         else:
             self._restart.copy_(rst)
-        return dev
 
-    def _append_masked(self, pose):
+    def _append(self, pose):
         """One launch: the per-stream state machine over this call's masks; non-pair rows of ``pose`` become identity."""
         assert pose.is_contiguous() and pose.shape == (self.streams, 4, 7)
         _lib.call("stream_append_masked_kernel_wrapper", pose.device, self.streams, self.max_frames, _p(self._active),
                   _p(self._restart), _p(pose), _p(self._rel), _p(self._abs), _p(self._have_prev), _p(self._counts),
                   _p(self._valid), _p(self._overflow))
 
-    def _masked_body(self, fused, source):
-        """The launches of one per-stream call, captured or eager: source, the step against the persistent previous
-        frame, the masked append, the masked handover (ordered after every reader of the previous frame: the pair
-        stage has joined its side streams by the time it returns)."""
+    def _body(self, fused, source):
+        """The launches of one call, captured or eager: source, the step against the persistent previous frame, the
+        masked append, the motion handover, the masked frame-1 handover (ordered after every reader of the previous
+        frame: the pair stage has joined its side streams by the time it returns)."""
         pose, new = fused.stream_step(self._slot, source(), self.num_points)
-        self._append_masked(pose)
-        self._hand_motion(pose, self._active)          # primed streams' rows are the identity by now
+        self._append(pose)
+        self._hand_motion(pose)                        # primed streams' rows are the identity by now
         self._slot.copy_frame1_masked_(new, self._active)
         return pose
 
-    def _run_masked(self, fused, entry, source):
+    def _run(self, fused, entry, source):
         """``entry``: dict(step=(graph, pose) | None) of this input shape.  Creates the persistent previous frame from a
-        real state on the very first call, captures once per entry, replays (or runs the same launches eagerly)."""
+        real state on the very first call (a step must never read uninitialised search structures), captures once per
+        entry, replays (or runs the same launches eagerly)."""
         n = self.num_points
         if self._slot is None:
             prime = lambda: fused.stream_prime(source(), n)
@@ -572,77 +535,23 @@ class StreamingOdometry:
             self._slot = first.frame1_buffers().copy_frame1_(first)
             self.handover_bytes = self._slot.frame1_bytes()
         if not self.graph:
-            return self._masked_body(fused, source)
+            return self._body(fused, source)
         if entry["step"] is None:
             self._warm(lambda: fused.stream_step(self._slot, source(), n))
-            entry["step"] = self._capture(lambda: self._masked_body(fused, source))
+            entry["step"] = self._capture(lambda: self._body(fused, source))
+            entry["cloud"] = self._tapped              # refine: the batch this graph samples from
             self.captures += 1
+        self._tapped = entry["cloud"]
         graph, pose = entry["step"]
         graph.replay()
         return pose
 
-    def _step_masked(self, frames, active, restart):
-        from . import fused as fused_mod
-        num_points = self._check(frames)
-        act, rst = self._masks(active, restart)
-        key = (tuple(frames.shape), frames.device)
-        store = self._graphs if self.graph else self._static
-        filled = None
-        if self._fused_id != id(self.net._fused) or key not in store:
-            host, j = self._first_active(act)               # new static rows: idle streams start from an active one
-            filled = frames.clone()
-            if not host.all():
-                filled[torch.from_numpy(~host).to(frames.device)] = frames[j]
-        if self.num_points is None:
-            self.num_points = num_points
-        fused = self._begin(frames.device)
-        self._load_masks(act, rst)
-        entry = store.get(key)
-        if entry is None:
-            entry = store[key] = dict(static=filled, step=None)
-        else:
-            static, src = entry["static"], frames.contiguous()
-            per = static[0].numel() * static.element_size()
-            fused_mod.masked_copy([(static.data_ptr(), src.data_ptr(), per)], self._active)
-        static = entry["static"]
-        pose = self._run_masked(fused, entry, lambda: static)
-        self.frames_seen += 1
-        return pose
-
-    def _step_sweeps_masked(self, sweeps, lengths, times, active, restart):
-        what = "StreamingOdometry"
-        front = self._front
-        self._check_room(what)
-        host_lengths = front.check(sweeps, lengths, what)
-        self._check_net(sweeps, what)
-        act, rst = self._masks(active, restart)
-        if front.bufs is None:
-            host, j = self._first_active(act)
-            if not host.all():
-                idle = torch.from_numpy(~host).to(sweeps.device)
-                sweeps = sweeps.clone()
-                sweeps[idle] = sweeps[j]
-                if times is not None:
-                    times = times.clone()
-                    times[idle] = times[j]
-                if host_lengths is None:
-                    lengths = lengths.clone()
-                    lengths[idle] = lengths[j]
-                else:
-                    host_lengths = [v if a else host_lengths[j] for v, a in zip(host_lengths, host)]
-        fused = self._begin(sweeps.device)
-        self._load_masks(act, rst)
-        if front.deskew:
-            front.stream_words = (self._restart, self._have_prev)      # read by the front end's launch, on the device
-        if front.bufs is None:
-            front.load(sweeps, lengths, host_lengths, times)
-        else:
-            front.load_masked(sweeps, lengths, host_lengths, self._active, times)
-        store = self._graphs if self.graph else self._static
-        entry = store.get("sweeps")
-        if entry is None:
-            entry = store["sweeps"] = dict(static=None, step=None)
-        pose = self._run_masked(fused, entry, front.run)
+    def _finish(self, pose):
+        """After the step: lock step knows on the host that this call primed every stream (the first since ``reset()``)
+        and returns None for it; the refinement; the call counter."""
+        if not self.per_stream and self.frames_seen == 0:
+            pose = None
+        self._refine(pose)
         self.frames_seen += 1
         return pose
 
@@ -699,7 +608,7 @@ class PWCLONetOdometry:
                              % (self.input_key(), tuple(pc.shape)))
         frame = pc.to(self.device, torch.float32)[None]
         with torch.no_grad():
-            if self.stream._front is not None:
+            if self.stream.front is not None:
                 self.stream.step_sweeps(frame, [frame.shape[1]], times=self._times(data_dict, frame))
             else:
                 self.stream.step(frame)
@@ -709,7 +618,7 @@ class PWCLONetOdometry:
     def _times(self, data_dict, frame):
         """The (1, n) times of a raw frame when the stream de-skews, else None.  A frame without the key gets equal times:
         every alpha is 0 and every row keeps its bits, the identity motion's result (the reference's "no distortion")."""
-        if not self.stream._front.deskew:
+        if not self.stream.front.deskew:
             return None
         ts = data_dict.get(self.timestamps_key())
         if ts is None:

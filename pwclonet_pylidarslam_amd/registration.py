@@ -349,7 +349,7 @@ class IcpRefiner:
             if self._graph is None:
                 torch.cuda.synchronize(cloud.device)
                 g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
+                with _lib.capture(g):
                     self._body()
                 self._graph = g
             self._graph.replay()

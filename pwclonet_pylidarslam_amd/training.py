@@ -11,6 +11,7 @@ drifts to its own loss weights and then to its own network.  ``PWCLONetWithLoss`
 import torch
 import torch.nn as nn
 
+from . import _lib
 from .flat_step import FlatAdam, FlatTrainStep  # noqa: F401  (the data-parallel step that replays as graphs)
 
 
@@ -108,13 +109,13 @@ class TrainStep:
             torch.cuda.synchronize(dev)
             self.graph = torch.cuda.CUDAGraph()
             self.opt.zero_grad(set_to_none=True)
-            with torch.cuda.graph(self.graph):
+            with _lib.capture(self.graph):
                 self.static_loss, _pose, _log = self._forward()
                 self.static_loss.backward()
                 self.opt.step()
             if sample_ahead:
                 self.sample_graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.sample_graph):
+                with _lib.capture(self.sample_graph):
                     self._sample_next()
                 torch.cuda.synchronize(dev)
 
@@ -306,7 +307,6 @@ class DropoutStream:
 
     def begin(self, device):
         """One launch: step in flight = next step, next step += 1."""
-        from . import _lib
         _lib.call("pose_head_train_begin_kernel_wrapper", device, self.state_on(device).data_ptr())
 
     # ---- the step counter ------------------------------------------------------------------------------------------------

@@ -332,9 +332,11 @@ def _lock_step(dev, graph):
         assert float((last - _ident(S, dev)).abs().max()) > 1e-4             # the net's motion is no identity
         raw.reset()
         assert torch.equal(raw.motion(), _ident(S, dev))
+        assert raw.step_sweeps(batch, lengths, times=times) is None          # the frame that primes replays the graph too
+        assert torch.equal(raw.motion(), _ident(S, dev))
+        assert torch.equal(raw._front.bufs["packed"], plain_p)               # de-skewed with the identity
     if graph:
-        entry = raw._graphs["sweeps"]
-        assert list(raw._graphs) == ["sweeps"] and entry["prime"] is not None and entry["step"] is not None
+        assert list(raw._graphs) == ["sweeps"] and raw.captures == 1
     _lib.synchronize(dev)
     return poses
 

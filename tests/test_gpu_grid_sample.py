@@ -339,8 +339,9 @@ def test_streaming_on_grid_sampled_sweeps_is_the_pair_forward(cuda):
             else:
                 assert torch.equal(got, fs(_cm(prev), _cm(clouds))), k
             prev = clouds
-    entry = raw._graphs["sweeps"]
-    assert list(raw._graphs) == ["sweeps"] and entry["prime"] is not None and entry["step"] is not None
+        raw.reset()
+        assert raw.step_sweeps(batch, lens) is None                          # the frame that primes replays it too
+    assert list(raw._graphs) == ["sweeps"] and raw.captures == 1
     _lib.synchronize(cuda)
 
 

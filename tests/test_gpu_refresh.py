@@ -182,14 +182,14 @@ def test_streaming_odometry_keeps_its_graphs(cuda):
             want, state = old.stream_step(state, seq[k], 4096)
             assert torch.equal(so.step(seq[k]), want)
         entry = next(iter(so._graphs.values()))
-        graphs = (entry["prime"], entry["step"][0])
+        graph = entry["step"][0]
         _refill(net, "second/")
         net.refresh_fused()
         got = so.step(seq[3]).clone()
         fresh = fused.FusedPWCLONet(net)
         want, _ = fresh.stream_step(state, seq[3], 4096)
         stale, _ = old.stream_step(state, seq[3], 4096)
-    assert len(so._graphs) == 1 and entry["prime"] is graphs[0] and entry["step"][0] is graphs[1]
+    assert len(so._graphs) == 1 and entry["step"][0] is graph and so.captures == 1
     assert torch.equal(got, want) and not torch.equal(got, stale)
 
 

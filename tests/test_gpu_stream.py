@@ -80,7 +80,7 @@ def test_stream_is_bitwise_the_pair_forward(cuda, monkeypatch, name, env, dtype,
 
 
 def test_graph_replay_and_reset(cuda):
-    """Captured prime + step graphs give the eager rows over 13 steps, then again on a second sequence after reset()."""
+    """The captured graph gives the eager rows over 13 steps, then again on a second sequence after reset()."""
     net = _net(cuda)
     S = 2
     a = _streams(21, 4096, 13, S, cuda)
@@ -98,7 +98,7 @@ def test_graph_replay_and_reset(cuda):
                 assert torch.equal(got, want), k
             assert torch.equal(graphed.relative_poses(), eager.relative_poses())
             assert torch.equal(graphed.trajectory(), eager.trajectory())
-    assert graphed.handover_bytes > 0 and len(graphed._graphs) == 1
+    assert graphed.handover_bytes > 0 and len(graphed._graphs) == 1 and graphed.captures == 1
     assert not graphed.overflowed()
 
 
@@ -131,11 +131,46 @@ def test_trajectory_matches_the_evaluation_kernels(cuda):
     with torch.no_grad(), pytest.raises(RuntimeError, match="max_frames=%d" % T):
         so.step(seq[0])
     assert so.frames_seen == T and not so.overflowed()
-    assert int(so._count.item()) == T
+    assert so.frame_counts().tolist() == [T] * S
     so.reset()
     with torch.no_grad():
         assert so.step(seq[0]) is None
     assert so.relative_poses().shape == (1, S, 4, 4)
+
+
+@pytest.mark.parametrize("graph", [True, False], ids=["graph", "eager"])
+def test_reset_and_reprime_run_through_the_one_step(cuda, graph):
+    """Lock step has no prime graph: the first frame and the first frame after reset() go through the same step (and in
+    graph mode the same captured graph) as every pair; the state machine on the device primes all streams there."""
+    S, T = 2, 3
+    net = _net(cuda)
+    fs = net._fused
+    so = StreamingOdometry(net, streams=S, graph=graph)
+    eye = torch.eye(4, dtype=torch.float64, device=cuda).expand(S, 4, 4)
+    with torch.no_grad():
+        for half, seed in enumerate((81, 85)):
+            seq = _streams(seed, 1024, T, S, cuda)
+            if half:
+                so.reset()
+            assert so.step(seq[0]) is None
+            rows = []
+            for k in range(1, T):
+                got = so.step(seq[k]).clone()
+                assert torch.equal(got, fs(_cm(seq[k - 1]), _cm(seq[k]))), (half, k)
+                rows.append(got)
+            pose = torch.stack(rows)                                 # (T-1, S, 4, 7)
+            rel, traj = so.relative_poses(), so.trajectory()
+            assert rel.shape == traj.shape == (T, S, 4, 4) and so.frames_seen == T
+            assert torch.equal(rel[0], eye) and torch.equal(traj[0], eye)
+            for i in range(S):
+                mats = evaluation.rows_to_transforms(pose[:, i, 0, :])
+                assert torch.equal(rel[1:, i], mats)
+                want = evaluation.compute_absolute_poses(torch.cat((eye[:1], mats)))
+                assert torch.allclose(traj[:, i], want, rtol=1e-12, atol=1e-12)
+            assert so.frame_counts().tolist() == [T] * S
+    if graph:
+        assert so.captures == 1 and len(so._graphs) == 1
+    assert not so.overflowed()
 
 
 def test_posenet_odometry_at_the_real_size(cuda, tmp_path):

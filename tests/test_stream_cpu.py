@@ -54,13 +54,38 @@ def test_stream_arguments_and_max_frames_bookkeeping():
 
 
 def test_stream_launcher_is_declared_with_the_header_arity():
-    args, res = _lib.SIGNATURES["odom_stream_append_kernel_wrapper"]
+    args, res = _lib.SIGNATURES["stream_append_masked_kernel_wrapper"]
     assert res is None
     with open(os.path.join(ROOT, "include", "pwclo_ops.h")) as f:
         header = f.read()
-    m = re.search(r"void\s+odom_stream_append_kernel_wrapper\s*\(([^)]*)\)\s*;", header)
-    assert m is not None, "odom_stream_append_kernel_wrapper is not declared in include/pwclo_ops.h"
+    m = re.search(r"void\s+stream_append_masked_kernel_wrapper\s*\(([^)]*)\)\s*;", header)
+    assert m is not None, "stream_append_masked_kernel_wrapper is not declared in include/pwclo_ops.h"
     params = [p.strip() for p in m.group(1).split(",")]
-    assert len(args) == len(params) == 9
+    assert len(args) == len(params) == 11
     for p, a in zip(params, args):                              # pointers travel as c_void_p, ints as c_int
         assert (a is _lib._F) == ("*" in p), (p, a)
+
+
+def test_the_lock_step_launcher_is_gone_and_lock_step_refuses_the_per_stream_arguments():
+    with open(os.path.join(ROOT, "include", "pwclo_ops.h")) as f:
+        assert "odom_stream_append_kernel_wrapper" not in f.read()
+    assert "odom_stream_append_kernel_wrapper" not in _lib.SIGNATURES
+    lock = StreamingOdometry(_cpu_net(), streams=2, graph=False)
+    frames = torch.zeros(2, 64, 3)
+    masks = "StreamingOdometry: active / restart masks need per_stream=True"
+    with torch.no_grad():                                        # refused before the frames are looked at
+        with pytest.raises(ValueError, match=re.escape(masks)):
+            lock.step(frames, active=[1, 0])
+        with pytest.raises(ValueError, match=re.escape(masks)):
+            lock.step(frames, restart=[0, 1])
+    raw = StreamingOdometry(_cpu_net(), streams=2, graph=False, sweeps=dict(dataset="kitti360", capacity=64))
+    for kw in (dict(active=[1, 0]), dict(restart=[0, 1])):
+        with torch.no_grad(), pytest.raises(ValueError, match=re.escape(masks)):
+            raw.step_sweeps(torch.zeros(2, 64, 4), [64, 64], **kw)
+    with pytest.raises(ValueError, match=re.escape("StreamingOdometry: reset(streams=...) needs per_stream=True")):
+        lock.reset(streams=[0])
+    for accessor in (lock.relative_poses, lock.trajectory):
+        with pytest.raises(ValueError, match=re.escape("StreamingOdometry: stream= needs per_stream=True (lock-step "
+                                                       "trajectories are (frames, S, 4, 4))")):
+            accessor(stream=0)
+    assert lock.frames_seen == 0 and lock.frame_counts() is None

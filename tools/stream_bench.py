@@ -10,7 +10,7 @@
 (b) S = 32: frames/s of ``StreamingOdometry(graph=True)`` against ``GraphedForward`` at batch 32 (the same 32 pairs per
     step), one in flight (HIP events around a region of back-to-back steps), alternated, repeated.
 (c) launches per step (eager, ``_lib`` launch sites; the pair forward's for comparison) and the handover: the bytes the
-    captured step copies into the persistent previous frame and the time of that copy alone (eager, HIP events).
+    captured step moves into the persistent previous frame and the time of that one launch alone (eager, HIP events).
 Check: the streamed rows equal the pair forward's at the same batch bit for bit.
 
     python tools/stream_bench.py [--frames F] [--repeats R] [--steps32 K] [--trace-only] [--per-stream]
@@ -18,11 +18,14 @@ Check: the streamed rows equal the pair forward's at the same batch bit for bit.
 ``--trace-only``: only the S = 1 graphed stream over the frames, for ``rocprofv3 --kernel-trace --stats -- python
 tools/stream_bench.py --trace-only`` (a run of its own).
 
-``--per-stream``: instead of (a)-(c), the masked step of ``StreamingOdometry(per_stream=True)``
-against the lock-step step, alternated repeat by repeat in this process: S = 1 per-frame time (all active), S = 32
-frames/s with all streams active and with every other stream active (steps x S per second in both: an idle stream costs
-what an active one does), and at S = 32 the masked handover launch alone against the lock-step copies (HIP events,
-bytes read + written per second).  ``--per-stream --trace-only``: only 30 masked handover launches at S = 32, all streams
+``--per-stream``: instead of (a)-(c), ``StreamingOdometry(per_stream=True)`` beside the lock-step
+object, alternated repeat by repeat in this process: S = 1 per-frame time (all active), S = 32 frames/s with all streams
+active and with every other stream active (steps x S per second in both: an idle stream costs what an active one does).
+With all streams active the two objects replay the SAME graph (the same launches) through two front doors, so the
+``lockstep`` / ``masked`` all-active pair measures the host front ends and the run's noise, not two kernels; the
+half-active series is the one only per-stream mode can run.  At S = 32 also the masked handover launch alone against one
+``copy_`` per tensor, which is what the step did before it had the launch (HIP events, bytes read + written per
+second).  ``--per-stream --trace-only``: only 30 masked handover launches at S = 32, all streams
 active, for ``rocprofv3 --kernel-trace --stats -- python tools/stream_bench.py --per-stream --trace-only`` (a run of its own):
 the kernel's device time without launch latency.
 """
@@ -103,7 +106,8 @@ def _region_ms(dev, fn, steps):
 
 
 def _per_stream(a, dev, net, clouds, res):
-    """``--per-stream``: masked step against lock-step step, same frames, alternated."""
+    """``--per-stream``: the per-stream front door against the lock-step one (all active: the same graph), same
+    frames, alternated; then the series with every other stream active."""
     F = a.frames
     if a.trace_only:
         S = 32
@@ -136,6 +140,8 @@ def _per_stream(a, dev, net, clouds, res):
         tm.append(run1(per))
     res["s1_lockstep_ms_per_frame"], res["s1_masked_ms_per_frame"] = _stats(tl), _stats(tm)
     res["s1_rows_bitwise_equal_lockstep"] = bool(same)
+    res["all_active_note"] = ("lockstep and masked all-active are the same captured launches entered through "
+                              "step(frames) and step(frames, active=None) of two objects")
 
     S, K = 32, a.steps32
     idx = [[(k + 5 * i) % F for i in range(S)] for k in range(K + 1)]
@@ -164,7 +170,7 @@ def _per_stream(a, dev, net, clouds, res):
     res["s32_masked_half_active_stream_steps_per_s"] = _stats(rh)
     res["s32_rows_bitwise_equal_lockstep"] = bool(same32)
 
-    # the handover alone at S = 32: one masked launch (all active, half active) against the lock-step copies
+    # the handover alone at S = 32: one masked launch (all active, half active) against one copy_ per tensor
     fs = net._fused
     prev = fs.stream_prime(batches[0], a.npoints)
     _, new = fs.stream_step(prev, batches[1], a.npoints)
@@ -203,7 +209,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--steps32", type=int, default=20, help="steps per timed region at S = 32")
     ap.add_argument("--trace-only", action="store_true")
-    ap.add_argument("--per-stream", action="store_true", help="masked step against lock-step step (section 18)")
+    ap.add_argument("--per-stream", action="store_true", help="the per-stream front door beside the lock-step one, and half-active streams (section 18)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     base = torch.from_numpy(synthetic.kitti_like_sequence(2024, a.npoints, a.base)[0]).to(dev)   # (base, N, 4)
@@ -261,18 +267,20 @@ def main():
     # ---- (c) launches and handover ----
     _, new = fs.stream_step(prev, clouds[1:2], a.npoints)
     slot = new.frame1_buffers()
+    one = torch.ones((1,), dtype=torch.int32, device=dev)
     s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     torch.cuda.synchronize(dev)
     times = []
     for _ in range(20):
         s.record()
-        slot.copy_frame1_(new)
+        slot.copy_frame1_masked_(new, one)
         e.record()
         e.synchronize()
         times.append(s.elapsed_time(e))
-    res["launches_per_step"] = {"stream_step_eager": n_stream, "append": 1, "handover_copies": len(slot.frame1_tensors()),
+    res["launches_per_step"] = {"stream_step_eager": n_stream, "append": 1, "handover_launches": 1,
+                                "handover_segments": len(new.frame1_segments(slot)),
                                 "pair_forward_eager": n_pair}
-    res["handover"] = {"bytes_s1": so.handover_bytes, "copy_ms_s1": _stats(times)}
+    res["handover"] = {"bytes_s1": so.handover_bytes, "launch_ms_s1": _stats(times)}
 
     # ---- (b) S = 32 ----
     S = 32
