@@ -697,6 +697,14 @@ int three_interpolate_grad_plan_query(int b, int c, int n, int m, int use_lds, i
 #define PWCLO_KNN_PRUNED 2
 int knn_point_plan_query(int b, int n, int s, int nsample, int prebuilt, int use_rows, int *out);
 
+/* Host only (no launch, no device needed): how the reduction passes of the batchnorm_train_* entry points cut a problem of
+ * c channels with M = b * l positions each in rows of L, answered by the launchers' own code: *nsplit position ranges of
+ * *per_split positions per channel (grid (nsplit, c); per_split % 4 == 0, nsplit <= 256, the workspace holds c * nsplit
+ * pairs of doubles), *vec = 1 when L % 4 == 0 selects the 16-byte loads (of the reduction and of the element-wise passes).
+ * The forward and the dense backward ask for (c, b * l, l), batchnorm_train_relu_maxk_forward for (c, b * s * k, s * k), the
+ * reduction of batchnorm_train_relu_maxk_backward for (c, b * s, s).  Returns 0, or -1 for a non-positive size. */
+int batchnorm_train_plan_query(int c, long long M, int L, int *nsplit, long long *per_split, int *vec);
+
 /* ---- 4. hoisted variants of section 3 ----------------------------------------------------------
  * The first layer of every grouped MLP is linear in [geometry | feat_centre[s] | feat_nbr[n]]; the
  * feature parts depend on one point only, so W_feat . feat[point] (+ bias) is computed once per

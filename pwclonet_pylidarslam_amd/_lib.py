@@ -120,6 +120,8 @@ SIGNATURES = {
     "group_points_grad_plan_query": ([_i] * 6 + [ctypes.POINTER(ctypes.c_int)], _i),
     "three_interpolate_grad_plan_query": ([_i] * 5 + [ctypes.POINTER(ctypes.c_int)], _i),
     "knn_point_plan_query": ([_i] * 6 + [ctypes.POINTER(ctypes.c_int)], _i),
+    "batchnorm_train_plan_query": ([_i, ctypes.c_longlong, _i, ctypes.POINTER(ctypes.c_int),
+                                    ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_int)], _i),
     "group_points_grad_sorted_kernel_wrapper": ([_i, _i, _i, _i, _i, _F, _F, _F, _F], None),
     "xyz_diff_kernel_wrapper": ([_i, _i, _i, _i, _F, _F, _F, _F, ctypes.c_longlong], None),
     "geometry_encode_kernel_wrapper": ([_i, _i, _i, _i, _F, _F, _F, _F, ctypes.c_longlong], None),

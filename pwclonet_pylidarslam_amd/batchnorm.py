@@ -128,6 +128,18 @@ def _workspace(c, device):
     return torch.empty((nbytes // 8,), dtype=torch.float64, device=device)
 
 
+def plan(c, M, L):
+    """batchnorm_train_plan_query: how the reduction passes cut ``c`` channels of ``M`` positions in rows of ``L`` -> dict
+    ``nsplit`` (position ranges per channel), ``per_split`` (positions of one range), ``vec`` (1: 16-byte loads, L % 4 == 0).
+    The launchers' own code answers; the max-K backward reduces (c, b * s, s).  Host only: works without a GPU."""
+    import ctypes
+    nsplit, per_split, vec = ctypes.c_int(), ctypes.c_longlong(), ctypes.c_int()
+    if _lib.load().batchnorm_train_plan_query(int(c), int(M), int(L), ctypes.byref(nsplit), ctypes.byref(per_split),
+                                              ctypes.byref(vec)) != 0:
+        raise ValueError("batchnorm_train_plan_query(%d, %d, %d)" % (c, M, L))
+    return dict(nsplit=nsplit.value, per_split=per_split.value, vec=vec.value)
+
+
 class _BatchNormTrain(Function):
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, momentum, eps, relu, given_mean=None, given_invstd=None):

@@ -323,6 +323,15 @@ extern "C" long long batchnorm_train_workspace_bytes(int c) {
   return (long long)(c > 0 ? c : 1) * BN_MAX_SPLITS * 2 * (long long)sizeof(double);
 }
 
+// Host only: how the reduction passes cut (c, M = b * l positions per channel, rows of L) -- bn_splits() as every launcher
+// above and below calls it -- and whether the 16-byte path runs (L % 4 == 0).  The max-K backward asks for (c, b * s, s).
+extern "C" int batchnorm_train_plan_query(int c, long long M, int L, int *nsplit, long long *per_split, int *vec) {
+  if (c <= 0 || M <= 0 || L <= 0 || nsplit == nullptr || per_split == nullptr || vec == nullptr) return -1;
+  *nsplit = bn_splits(c, M, per_split);
+  *vec = (L % 4 == 0) ? 1 : 0;
+  return 0;
+}
+
 template <int MODE, bool RELU>
 static void bn_launch_apply(bool vec, int b, int c, int l, float inv_m, const float *x, const float *dy,
                             const float *gamma, const float *beta, const float *mean, const float *invstd,

@@ -31,7 +31,7 @@ def test_library_exports_every_declared_symbol():
     lib_path = build.build()                      # hipcc cross-compiles without a GPU
     names = header_functions()
     assert len(names) >= 25 and "group_points_kernel_wrapper" in names and "knn_point_kernel_wrapper" in names
-    assert {"conv1x1_plan_query", "group_points_grad_plan_query", "knn_point_plan_query"} <= set(names)     # the host-only plan queries
+    assert {"conv1x1_plan_query", "group_points_grad_plan_query", "knn_point_plan_query", "batchnorm_train_plan_query"} <= set(names)     # the host-only plan queries
     lib = ctypes.CDLL(lib_path)
     for n in names:
         assert hasattr(lib, n), "libpwclo_hip.so does not export %s" % n
