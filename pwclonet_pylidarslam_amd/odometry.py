@@ -67,7 +67,14 @@ class StreamingOdometry:
     against a local map of the stream's last frames, with the level-1 row's transform as the initial guess (one more
     captured graph).  ``refined_relative_poses()`` / ``refined_trajectory()`` sit beside ``relative_poses()`` /
     ``trajectory()``, which stay the network's, as does the de-skew prior; ``refiner().status()`` tells why a stream's
-    registration stopped.  Lock step only: ``per_stream=True`` together with ``refine`` raises.
+    registration stopped.  Per-stream mode takes the masked refiner, opted into inside the dict: ``per_stream=True``
+    needs ``refine=dict(..., per_stream=True)`` (a different graph: two mask words, one more launch, status bit 8 for
+    idle streams) and raises without the key; lock step raises with it.  Then, after the step's graph, the call's
+    ``active`` mask and ``restart = active * (1 - valid)`` (a stream that primed in this call: a first frame, a ``restart``
+    mask or ``reset(streams=...)``) go to ``IcpRefiner.register`` as device words, and one launch records the refined pose at
+    the stream's own frame counter: ``refined_relative_poses(stream=i)`` / ``refined_trajectory(stream=i)`` give (count_i,
+    4, 4), row 0 the identity again after a restart.  No sync, no new capture; pose rows, ``relative_poses``,
+    ``trajectory``, ``valid``, ``frame_counts`` and the de-skew prior stay the network's.
 
     Per-stream mode (``per_stream=True``): ``step(frames, active=None, restart=None)`` and ``step_sweeps(sweeps, lengths,
     active=None, restart=None)`` take two (S,) masks, bool or integer, host sequences or device tensors (device tensors
@@ -110,11 +117,14 @@ class StreamingOdometry:
         self._active = self._restart = self._have_prev = self._counts = self._valid = None    # (S,) int32, device
         self._front = None          # raw mode: preprocess.SweepFrontEnd (persistent sweep, lengths, tr, sampler buffers)
         self._refine_cfg = None if refine is None else dict(refine)     # registration.IcpRefiner's keywords
-        self._refiner = self._ref_rel = None
+        self._refiner = self._ref_rel = self._ref_abs = self._ref_restart = None
         self._tapped = None         # refine: the frame batch the last step's graph (or eager step) sampled from
-        if refine is not None and self.per_stream:
-            raise ValueError("StreamingOdometry: refine= registers all streams in lock step; per_stream=True with refine "
-                             "is not supported (masked registration is not implemented)")
+        if refine is not None and self.per_stream != bool(self._refine_cfg.get("per_stream", False)):
+            if self.per_stream:
+                raise ValueError("StreamingOdometry: per_stream=True registers with the masked refiner, which the refine "
+                                 "dict opts into: refine=dict(..., per_stream=True)")
+            raise ValueError("StreamingOdometry: refine=dict(per_stream=True) is the masked refiner of per_stream=True; "
+                             "lock step registers all streams at once, leave the key out")
         if sweeps is not None:
             if self.num_points is None:
                 self.num_points = RAW_NUM_POINTS
@@ -188,6 +198,8 @@ class StreamingOdometry:
         self.frames_seen = 0
         if self._overflow is not None:
             self._overflow.zero_()
+        if self.per_stream and self._refiner is not None:
+            self._refiner.reset()                           # the maps too (lock step: the priming call does it)
         self._reset_motion(None)
 
     def _reset_motion(self, mask):
@@ -284,14 +296,14 @@ class StreamingOdometry:
             host, j = self._first_active(act)
             if not host.all():
                 idle = torch.from_numpy(~host).to(sweeps.device)
-                sweeps = sweeps.clone()
-                sweeps[idle] = sweeps[j]
+                first, sweeps = sweeps[j], sweeps.clone()   # the source row is the caller's: a write may not alias its source
+                sweeps[idle] = first
                 if times is not None:
-                    times = times.clone()
-                    times[idle] = times[j]
+                    first, times = times[j], times.clone()
+                    times[idle] = first
                 if host_lengths is None:
-                    lengths = lengths.clone()
-                    lengths[idle] = lengths[j]
+                    first, lengths = lengths[j], lengths.clone()
+                    lengths[idle] = first
                 else:
                     host_lengths = [v if a else host_lengths[j] for v, a in zip(host_lengths, host)]
         fused = self._begin(sweeps.device)
@@ -318,19 +330,27 @@ class StreamingOdometry:
         as there."""
         return self._view(self._abs, stream)
 
-    def refined_relative_poses(self):
+    def refined_relative_poses(self, stream=None):
         """With ``refine=``: (frames_seen, S, 4, 4) fp64 device view beside ``relative_poses()``: row k is pair (k-1, k)'s
-        transform after point-to-plane registration against the local map, row 0 the identity."""
+        transform after point-to-plane registration against the local map, row 0 the identity.
+        Per-stream mode: ``stream=i`` is required and gives that stream's (count_i, 4, 4), as ``relative_poses``."""
         if self._refine_cfg is None:
             raise RuntimeError("StreamingOdometry: refined poses need refine=dict(...)")
+        if self.per_stream or stream is not None:
+            return self._view(self._ref_rel, stream)
         if self._ref_rel is None:
             return torch.empty((0, self.streams, 4, 4), dtype=torch.float64)
         return self._ref_rel[:self.frames_seen]
 
-    def refined_trajectory(self):
+    def refined_trajectory(self, stream=None):
         """With ``refine=``: (frames_seen, S, 4, 4) fp64, the products of ``refined_relative_poses()`` per stream
-        (``evaluation.accumulate``, the kernel behind ``compute_absolute_poses``)."""
+        (``evaluation.accumulate``, the kernel behind ``compute_absolute_poses``).  Per-stream mode: ``stream=i`` is
+        required and gives (count_i, 4, 4), a view of the products kept on the device as the poses are recorded."""
         from . import evaluation
+        if self.per_stream or stream is not None:
+            if self._refine_cfg is None:
+                raise RuntimeError("StreamingOdometry: refined poses need refine=dict(...)")
+            return self._view(self._ref_abs, stream)
         rel = self.refined_relative_poses()
         k = rel.shape[0]
         if k == 0:
@@ -392,6 +412,17 @@ class StreamingOdometry:
         if self._refiner is None:
             self._refiner = registration.IcpRefiner(self.streams, self.num_points, graph=self.graph, **self._refine_cfg)
             self._ref_rel = torch.zeros((self.max_frames, self.streams, 4, 4), dtype=torch.float64, device=cloud.device)
+            if self.per_stream:
+                self._ref_abs = torch.zeros_like(self._ref_rel)
+                self._ref_restart = torch.zeros_like(self._active)
+        if self.per_stream:
+            # restart = active * (1 - valid), written as one launch: valid is set for active streams only, so the product
+            # is the difference.  A stream that primed in this call starts a new map.
+            torch.sub(self._active, self._valid, out=self._ref_restart)
+            T = self._refiner.register(cloud, pose[:, 0, :], active=self._active, restart=self._ref_restart)
+            _lib.call("stream_record_refined_kernel_wrapper", cloud.device, self.streams, self.max_frames, _p(self._active),
+                      _p(self._valid), _p(self._counts), _p(T), _p(self._ref_rel), _p(self._ref_abs))
+            return
         if pose is None:
             self._refiner.reset()
             init = torch.eye(4, dtype=torch.float64, device=cloud.device).expand(self.streams, 4, 4).contiguous()

@@ -13,6 +13,10 @@ host.  ``IcpRefiner`` does the refinement with the kernels of ``csrc/icp.hip`` a
 frame; only the frame's points move (``icp_queries``).  One iteration is four launches (queries, search, accumulate, solve);
 the iteration count is fixed and streams freeze on the device (``status()``), so a whole registration plus the map handover
 replays as one captured graph.  There is no CPU path.
+
+Masked registration (``IcpRefiner(..., per_stream=True)``): every call says which streams delivered a frame and which of
+those start a new sequence, in two (S,) masks that live in device memory; one graph serves idle, restarting and pairing
+streams alike.  An idle stream keeps its map and gets status ``IDLE``.
 """
 import numpy as np
 import torch
@@ -24,6 +28,7 @@ MAX_SLOTS = 64                                   # csrc/icp.hip: ICP_MAX_SLOTS
 ROW = 32                                         # csrc/icp.hpp: ICP_ROW and the offsets inside a row of sums
 H0, G0, SW, COST, PAIRS = 0, 21, 27, 28, 29
 CONVERGED, FEW_PAIRS, BAD_PIVOT = 1, 2, 4        # status bits
+IDLE = 8                                         # masked registration: the stream delivered no frame in this call
 
 
 def _p(t):
@@ -79,8 +84,13 @@ def normals(xyz, k=10):
     return out, eig
 
 
-def queries(A, p, T=None):
-    """A (S, M, 4, 4) fp64, p (S, n, 3) fp32, T (S, 4, 4) fp64 or None -> q (S, M, n, 3) = fp32(A[s, m] T[s] p[s, i])."""
+def _need_mask(active, what, S):
+    _need(active, "%s: active" % what, torch.int32, (S,))
+
+
+def queries(A, p, T=None, active=None, out=None):
+    """A (S, M, 4, 4) fp64, p (S, n, 3) fp32, T (S, 4, 4) fp64 or None -> q (S, M, n, 3) = fp32(A[s, m] T[s] p[s, i]).
+    ``active`` (S,) int32: the masked launch, which leaves the rows of ``out`` (S, M, n, 3) of idle streams as they are."""
     if not isinstance(A, torch.Tensor) or A.dim() != 4:
         raise ValueError("queries: A must be (S, M, 4, 4)")
     S, M = A.shape[:2]
@@ -91,15 +101,25 @@ def queries(A, p, T=None):
     _need(p, "queries: p", torch.float32, (S, n, 3))
     if T is not None:
         _need(T, "queries: T", torch.float64, (S, 4, 4))
-    q = torch.empty((S, M, n, 3), dtype=torch.float32, device=p.device)
-    _lib.call("icp_queries_kernel_wrapper", p.device, S, M, n, _p(A), _p(T), _p(p), _p(q))
+    if out is not None:
+        _need(out, "queries: out", torch.float32, (S, M, n, 3))
+    if out is not None:
+        q = out
+    else:                                            # masked: idle streams' rows are not written, so they start defined
+        q = (torch.empty if active is None else torch.zeros)((S, M, n, 3), dtype=torch.float32, device=p.device)
+    if active is None:
+        _lib.call("icp_queries_kernel_wrapper", p.device, S, M, n, _p(A), _p(T), _p(p), _p(q))
+    else:
+        _need_mask(active, "queries", S)
+        _lib.call("icp_queries_masked_kernel_wrapper", p.device, S, M, n, _p(A), _p(T), _p(p), _p(q), _p(active))
     return q
 
 
-def accumulate(p, q, idx, dist, map_xyz, map_normals, live, R, T, sigma=0.5, max_dist=1.0):
+def accumulate(p, q, idx, dist, map_xyz, map_normals, live, R, T, sigma=0.5, max_dist=1.0, active=None):
     """One launch of the normal equations' sums -> partial (S, groups(n), 32) fp64, one row per workgroup of 256 points.
     p (S, n, 3), q (S, M, n, 3), idx / dist (S, M, n) from the search with nsample = 1, map_xyz / map_normals (S, M, n, 3),
-    live (S, M) int32, R (S, M, 3, 3) and T (S, 4, 4) fp64."""
+    live (S, M) int32, R (S, M, 3, 3) and T (S, 4, 4) fp64.  ``active`` (S,) int32: the masked launch, zero rows for idle
+    streams."""
     if not isinstance(q, torch.Tensor) or q.dim() != 4:
         raise ValueError("accumulate: q must be (S, M, n, 3)")
     S, M, n, _ = q.shape
@@ -115,14 +135,20 @@ def accumulate(p, q, idx, dist, map_xyz, map_normals, live, R, T, sigma=0.5, max
     _need(R, "accumulate: R", torch.float64, (S, M, 3, 3))
     _need(T, "accumulate: T", torch.float64, (S, 4, 4))
     partial = torch.empty((S, groups(n), ROW), dtype=torch.float64, device=p.device)
-    _lib.call("icp_accumulate_kernel_wrapper", p.device, S, M, n, _p(p), _p(q), _p(idx), _p(dist), _p(map_xyz),
-              _p(map_normals), _p(live), _p(R), _p(T), float(sigma), float(max_dist), _p(partial))
+    args = (S, M, n, _p(p), _p(q), _p(idx), _p(dist), _p(map_xyz), _p(map_normals), _p(live), _p(R), _p(T), float(sigma),
+            float(max_dist), _p(partial))
+    if active is None:
+        _lib.call("icp_accumulate_kernel_wrapper", p.device, *args)
+    else:
+        _need_mask(active, "accumulate", S)
+        _lib.call("icp_accumulate_masked_kernel_wrapper", p.device, *args, _p(active))
     return partial
 
 
-def solve(partial, T, status, it=0, damping=1e-6, threshold_delta_pose=1e-4, min_pairs=64):
+def solve(partial, T, status, it=0, damping=1e-6, threshold_delta_pose=1e-4, min_pairs=64, active=None):
     """One launch of the solver on partial (S, G, 32): updates T (S, 4, 4) fp64 and status (S,) int32 in place and returns
-    dict(sum (S, 32), delta (S, 6), iterations, pairs (S,) int32, cost (S,) fp64)."""
+    dict(sum (S, 32), delta (S, 6), iterations, pairs (S,) int32, cost (S,) fp64).  ``active`` (S,) int32: the masked
+    launch, which in iteration 0 starts idle streams from status ``IDLE``."""
     if not isinstance(partial, torch.Tensor) or partial.dim() != 3:
         raise ValueError("solve: partial must be (S, G, 32)")
     S, G, _ = partial.shape
@@ -137,10 +163,62 @@ def solve(partial, T, status, it=0, damping=1e-6, threshold_delta_pose=1e-4, min
                iterations=torch.zeros((S,), dtype=torch.int32, device=dev),
                pairs=torch.zeros((S,), dtype=torch.int32, device=dev),
                cost=torch.zeros((S,), dtype=torch.float64, device=dev))
-    _lib.call("icp_solve_kernel_wrapper", dev, S, G, int(it), _p(partial), float(damping), float(threshold_delta_pose),
-              int(min_pairs), _p(T), _p(status), _p(out["iterations"]), _p(out["pairs"]), _p(out["cost"]), _p(out["sum"]),
-              _p(out["delta"]))
+    args = (S, G, int(it), _p(partial), float(damping), float(threshold_delta_pose), int(min_pairs), _p(T), _p(status),
+            _p(out["iterations"]), _p(out["pairs"]), _p(out["cost"]), _p(out["sum"]), _p(out["delta"]))
+    if active is None:
+        _lib.call("icp_solve_kernel_wrapper", dev, *args)
+    else:
+        _need_mask(active, "solve", S)
+        _lib.call("icp_solve_masked_kernel_wrapper", dev, *args, _p(active))
     return out
+
+
+def begin(active, restart, A, R, live, cursor, armed=None):
+    """First launch of a masked registration: the maps of the streams with ``active and (restart or armed)`` are emptied in
+    place (live = 0, cursor = 0, A = R = I; ``armed`` is cleared for them).  Masks (S,) int32; A (S, M, 4, 4), R (S, M, 3,
+    3) fp64; live (S, M), cursor (S,) int32."""
+    if not isinstance(A, torch.Tensor) or A.dim() != 4:
+        raise ValueError("begin: A must be (S, M, 4, 4)")
+    S, M = A.shape[:2]
+    _need_mask(active, "begin", S)
+    _need(restart, "begin: restart", torch.int32, (S,))
+    if armed is not None:
+        _need(armed, "begin: armed", torch.int32, (S,))
+    _need(A, "begin: A", torch.float64, (S, M, 4, 4))
+    _need(R, "begin: R", torch.float64, (S, M, 3, 3))
+    _need(live, "begin: live", torch.int32, (S, M))
+    _need(cursor, "begin: cursor", torch.int32, (S,))
+    _lib.call("icp_begin_kernel_wrapper", A.device, S, M, _p(active), _p(restart), _p(armed), _p(A), _p(R), _p(live),
+              _p(cursor))
+
+
+def map_push(T, cloud, normals_, stage_ws, map_xyz, map_normals, map_ws, A, R, live, cursor, active=None):
+    """The handover after a registration, in place: the staged frame (cloud, normals (S, n, 3), stage_ws: its structure,
+    built for S clouds) goes into slot cursor[s] of map_xyz / map_normals (S, M, n, 3) and map_ws (built for S * M clouds),
+    the live slots' A / R are re-based with T (S, 4, 4), the cursor moves on.  ``active`` (S,) int32: the masked launch,
+    which leaves idle streams alone."""
+    if not isinstance(map_xyz, torch.Tensor) or map_xyz.dim() != 4:
+        raise ValueError("map_push: map_xyz must be (S, M, n, 3)")
+    S, M, n, _ = map_xyz.shape
+    lib = _lib.load()
+    _need(T, "map_push: T", torch.float64, (S, 4, 4))
+    _need(cloud, "map_push: cloud", torch.float32, (S, n, 3))
+    _need(normals_, "map_push: normals", torch.float32, (S, n, 3))
+    _need(stage_ws, "map_push: stage_ws", torch.uint8, (lib.knn_point_build_bytes(S, n),))
+    _need(map_xyz, "map_push: map_xyz", torch.float32, (S, M, n, 3))
+    _need(map_normals, "map_push: map_normals", torch.float32, (S, M, n, 3))
+    _need(map_ws, "map_push: map_ws", torch.uint8, (lib.knn_point_build_bytes(S * M, n),))
+    _need(A, "map_push: A", torch.float64, (S, M, 4, 4))
+    _need(R, "map_push: R", torch.float64, (S, M, 3, 3))
+    _need(live, "map_push: live", torch.int32, (S, M))
+    _need(cursor, "map_push: cursor", torch.int32, (S,))
+    args = (S, M, n, _p(T), _p(cloud), _p(normals_), _p(stage_ws), _p(map_xyz), _p(map_normals), _p(map_ws), _p(A), _p(R),
+            _p(live), _p(cursor))
+    if active is None:
+        _lib.call("icp_map_push_kernel_wrapper", T.device, *args)
+    else:
+        _need_mask(active, "map_push", S)
+        _lib.call("icp_map_push_masked_kernel_wrapper", T.device, *args, _p(active))
 
 
 # ---- the refiner -------------------------------------------------------------------------------------------------------
@@ -158,10 +236,26 @@ class IcpRefiner:
     the system normalised by the sum of weights: a direction the scene does not constrain keeps the initial guess.
     ``graph=True``: the first call runs eagerly (it loads every kernel), the second captures one graph that every later
     call replays.  ``register(..., trace=True)`` (``graph=False`` only) also returns, per iteration, clones of the queries,
-    ``idx``, ``dist``, the summed row, ``delta`` and ``T``."""
+    ``idx``, ``dist``, the summed row, ``delta`` and ``T``.
+
+    ``per_stream=True`` (masked registration): ``register(cloud, init, active=None, restart=None)`` takes two (S,) masks,
+    bool or integer, host sequences or device tensors (device tensors are copied on the device, without a sync); ``None``
+    = all active, none restarting.  ``active[s]``: stream s delivered a frame in this call; ``restart[s]`` (looked at only
+    where active): that frame starts a new sequence.  Per stream:
+      idle (not active)     nothing of the stream changes (map slots, A, R, live, cursor); ``T[s]`` is ``init[s]`` bit for
+                            bit, status ``IDLE`` (8), iterations = pairs = 0, cost = 0; its row of ``cloud`` is ignored
+      restart               the map is emptied on the device, inside the graph, before the iterations; the frame finds no
+                            live slot, freezes in iteration 0 with the few-pairs bit, returns ``init`` and fills slot 0
+      pair (otherwise)      the registration and push of lock step, bit for bit those of a refiner of its own
+    One graph (begin, stage, ``iters`` x (queries, search, accumulate, solve), push) serves every combination: the masks
+    are device memory that it reads.  The search and the staging run for every stream, so an idle stream costs what an
+    active one does bar the gathers.  The first call needs an active stream: the idle streams' rows of the persistent
+    cloud start as copies of the first active stream's (the mask is read once, there), so that staging never sees data no
+    caller supplied.  ``reset(streams=...)`` arms a restart for those streams' next delivered frame, on the device and
+    without a sync (``map_state()`` shows the old map until then).  ``trace=True`` returns ``(T, steps, masks)``."""
 
     def __init__(self, streams, num_points, map_size=4, iters=10, sigma=0.5, max_dist=1.0, k_normals=10, damping=1e-6,
-                 threshold_delta_pose=1e-4, min_pairs=64, graph=True):
+                 threshold_delta_pose=1e-4, min_pairs=64, graph=True, per_stream=False):
         S, n, M, k = int(streams), int(num_points), int(map_size), int(k_normals)
         if not 1 <= S <= MAX_STREAMS:
             raise ValueError("IcpRefiner: streams=%d outside [1, %d]" % (S, MAX_STREAMS))
@@ -187,6 +281,7 @@ class IcpRefiner:
         self.streams, self.num_points, self.map_size, self.iters, self.k_normals = S, n, M, int(iters), k
         self.sigma, self.max_dist, self.damping = float(sigma), float(max_dist), float(damping)
         self.threshold_delta_pose, self.min_pairs, self.graph = float(threshold_delta_pose), int(min_pairs), bool(graph)
+        self.per_stream = bool(per_stream)
         self.bufs = None
         self.calls = 0              # register() calls so far: call 0 is eager, call 1 captures
         self._graph = None
@@ -211,6 +306,8 @@ class IcpRefiner:
             A=eye(S, M, 4, 4), R=eye(S, M, 3, 3), live=i32(S, M), cursor=i32(S),
             q=f32(S, M, n, 3), idx=i32(S, M, n), dist=f32(S, M, n), partial=f64(S, G, ROW),
             status=i32(S), iterations=i32(S), pairs=i32(S), cost=f64(S), sum=f64(S, ROW), delta=f64(S, 6))
+        if self.per_stream:                  # the masks the graph reads; armed: restarts asked for by reset(streams=...)
+            self.bufs.update(active=i32(S), restart=i32(S), armed=i32(S))
 
     def _seed_structures(self):
         """Before the first registration: every slot's search structure becomes the first frame's (its live flag stays 0),
@@ -223,12 +320,14 @@ class IcpRefiner:
 
     def status(self):
         """(S,) int32 device view: 0 = the stream moved in every iteration of the last registration, else the bits of why
-        it froze (1 converged, 2 too few pairs, 4 pivot not positive).  None before the first call."""
+        it froze (1 converged, 2 too few pairs, 4 pivot not positive; masked registration: 8 idle, the stream delivered no
+        frame in that call).  None before the first call."""
         return None if self.bufs is None else self.bufs["status"]
 
     def diagnostics(self):
         """Device views of the last registration: iterations used, pairs and the weighted cost sum w^2 r^2 of the last
-        iteration a stream took part in.  None before the first call."""
+        iteration a stream took part in (masked registration: all 0 for an idle stream; 1, 0, 0 for one that restarted).
+        None before the first call."""
         if self.bufs is None:
             return None
         return dict(iterations=self.bufs["iterations"], pairs=self.bufs["pairs"], cost=self.bufs["cost"])
@@ -242,7 +341,9 @@ class IcpRefiner:
 
     def reset(self, streams=None):
         """Empty the maps of all streams, or of ``streams`` (stream indices, or an (S,) bool mask): their next frame only
-        fills the map.  No sync and no new capture: the flags are device memory that the graph reads."""
+        fills the map.  No new capture: the flags are device memory that the graph reads.  Masked registration: the
+        streams are armed on the device, without a sync, and the first launch of their next delivered frame's registration
+        empties the map."""
         S = self.streams
         if streams is None:
             mask = np.ones((S,), dtype=bool)
@@ -263,6 +364,9 @@ class IcpRefiner:
         if self.bufs is None:
             return
         b = self.bufs
+        if self.per_stream:
+            b["armed"].copy_(torch.maximum(b["armed"], torch.from_numpy(mask.astype(np.int32)).to(b["armed"].device)))
+            return
         m = torch.from_numpy(mask).to(b["live"].device)
         b["live"][m] = 0
         b["cursor"][m] = 0
@@ -285,18 +389,20 @@ class IcpRefiner:
         b, S, M, n = self.bufs, self.streams, self.map_size, self.num_points
         dev = b["cloud"].device
         G = b["partial"].shape[1]
+        masked = ("_masked", (_p(b["active"]),)) if self.per_stream else ("", ())
         for it in range(self.iters):
-            _lib.call("icp_queries_kernel_wrapper", dev, S, M, n, _p(b["A"]), _p(b["T"]), _p(b["cloud"]), _p(b["q"]))
+            _lib.call("icp_queries%s_kernel_wrapper" % masked[0], dev, S, M, n, _p(b["A"]), _p(b["T"]), _p(b["cloud"]),
+                      _p(b["q"]), *masked[1])
             _lib.call("knn_point_prebuilt_kernel_wrapper", dev, S * M, n, n, 1, _p(b["q"]), _p(b["idx"]), _p(b["dist"]),
                       _p(b["map_ws"]))
-            _lib.call("icp_accumulate_kernel_wrapper", dev, S, M, n, _p(b["cloud"]), _p(b["q"]), _p(b["idx"]), _p(b["dist"]),
-                      _p(b["map_xyz"]), _p(b["map_normals"]), _p(b["live"]), _p(b["R"]), _p(b["T"]), self.sigma,
-                      self.max_dist, _p(b["partial"]))
+            _lib.call("icp_accumulate%s_kernel_wrapper" % masked[0], dev, S, M, n, _p(b["cloud"]), _p(b["q"]), _p(b["idx"]),
+                      _p(b["dist"]), _p(b["map_xyz"]), _p(b["map_normals"]), _p(b["live"]), _p(b["R"]), _p(b["T"]),
+                      self.sigma, self.max_dist, _p(b["partial"]), *masked[1])
             if trace is not None:
                 before = b["T"].clone()
-            _lib.call("icp_solve_kernel_wrapper", dev, S, G, it, _p(b["partial"]), self.damping, self.threshold_delta_pose,
-                      self.min_pairs, _p(b["T"]), _p(b["status"]), _p(b["iterations"]), _p(b["pairs"]), _p(b["cost"]),
-                      _p(b["sum"]), _p(b["delta"]))
+            _lib.call("icp_solve%s_kernel_wrapper" % masked[0], dev, S, G, it, _p(b["partial"]), self.damping,
+                      self.threshold_delta_pose, self.min_pairs, _p(b["T"]), _p(b["status"]), _p(b["iterations"]),
+                      _p(b["pairs"]), _p(b["cost"]), _p(b["sum"]), _p(b["delta"]), *masked[1])
             if trace is not None:
                 trace.append(dict(q=b["q"].clone(), idx=b["idx"].clone(), dist=b["dist"].clone(), sum=b["sum"].clone(),
                                   delta=b["delta"].clone(), T_before=before, T=b["T"].clone(),
@@ -304,11 +410,20 @@ class IcpRefiner:
 
     def _push(self):
         b, S, M, n = self.bufs, self.streams, self.map_size, self.num_points
-        _lib.call("icp_map_push_kernel_wrapper", b["cloud"].device, S, M, n, _p(b["T"]), _p(b["cloud"]),
+        masked = ("_masked", (_p(b["active"]),)) if self.per_stream else ("", ())
+        _lib.call("icp_map_push%s_kernel_wrapper" % masked[0], b["cloud"].device, S, M, n, _p(b["T"]), _p(b["cloud"]),
                   _p(b["stage_normals"]), _p(b["stage_ws"]), _p(b["map_xyz"]), _p(b["map_normals"]), _p(b["map_ws"]),
-                  _p(b["A"]), _p(b["R"]), _p(b["live"]), _p(b["cursor"]))
+                  _p(b["A"]), _p(b["R"]), _p(b["live"]), _p(b["cursor"]), *masked[1])
+
+    def _begin(self):
+        """Masked registration: empty the maps of the streams whose frame starts a new sequence."""
+        b = self.bufs
+        _lib.call("icp_begin_kernel_wrapper", b["cloud"].device, self.streams, self.map_size, _p(b["active"]),
+                  _p(b["restart"]), _p(b["armed"]), _p(b["A"]), _p(b["R"]), _p(b["live"]), _p(b["cursor"]))
 
     def _body(self, trace=None):
+        if self.per_stream:
+            self._begin()
         self._stage()
         self._iterate(trace)
         self._push()
@@ -327,17 +442,68 @@ class IcpRefiner:
         if not cloud.is_cuda or not init.is_cuda:
             raise RuntimeError("CPU not supported")
 
-    def register(self, cloud, init, trace=False):
+    def _mask(self, mask, what):
+        """An (S,) bool or integer mask, host sequence or device tensor -> (S,) int32 0 / 1 tensor where the caller's data
+        lives.  Raises ValueError before anything is launched."""
+        S = self.streams
+        if isinstance(mask, torch.Tensor) and mask.is_cuda:
+            if tuple(mask.shape) != (S,) or mask.dtype.is_floating_point or mask.dtype.is_complex:
+                raise ValueError("IcpRefiner: %s must be a (%d,) bool or integer mask, got %s %s"
+                                 % (what, S, mask.dtype, tuple(mask.shape)))
+            return mask.ne(0).to(torch.int32)
+        arr = np.asarray(mask.numpy() if isinstance(mask, torch.Tensor) else mask)
+        if arr.shape != (S,) or arr.dtype.kind not in "biu":
+            raise ValueError("IcpRefiner: %s must be a (%d,) bool or integer mask, got %s %s" % (what, S, arr.dtype, arr.shape))
+        return torch.from_numpy((arr != 0).astype(np.int32))
+
+    def _load(self, cloud, act, rst, host):
+        """Masked registration: the masks into the words the graph reads, the active streams' rows into the persistent
+        cloud (one masked-copy launch).  ``host``: on the very first call the host's copy of ``active``; that call copies
+        every row, the idle streams' from the first active stream."""
+        from . import fused
+        b = self.bufs
+        if act is None:
+            b["active"].fill_(1)
+        else:
+            b["active"].copy_(act)
+        if rst is None:
+            b["restart"].zero_()
+        else:
+            b["restart"].copy_(rst)
+        if host is not None:
+            b["cloud"].copy_(cloud)
+            if not host.all():
+                b["cloud"][torch.from_numpy(~host).to(cloud.device)] = cloud[int(np.flatnonzero(host)[0])]
+        elif act is None:
+            b["cloud"].copy_(cloud)
+        else:
+            src = cloud.contiguous()
+            fused.masked_copy([(b["cloud"].data_ptr(), src.data_ptr(), self.num_points * 12)], b["active"])
+
+    def register(self, cloud, init, active=None, restart=None, trace=False):
         if trace and self.graph:
             raise ValueError("IcpRefiner: trace=True needs graph=False (a replayed graph cannot hand out its iterations)")
+        if not self.per_stream and (active is not None or restart is not None):
+            raise ValueError("IcpRefiner: active / restart masks need per_stream=True")
+        act = None if active is None else self._mask(active, "active")
+        rst = None if restart is None else self._mask(restart, "restart")
         self._check(cloud, init)
+        first = self.bufs is None
+        host = None
+        if first and self.per_stream:                       # the one read of the mask: every row of the cloud starts defined
+            host = np.ones((self.streams,), dtype=bool) if act is None else act.cpu().numpy() != 0
+            if not host.any():
+                raise ValueError("IcpRefiner: the first call needs at least one active stream: idle streams' clouds "
+                                 "start as copies of the first active stream's")
         if init.dim() == 2:
             init = evaluation.rows_to_transforms(init)
-        first = self.bufs is None
         if first:
             self._alloc(cloud.device)
         b = self.bufs
-        b["cloud"].copy_(cloud)
+        if self.per_stream:
+            self._load(cloud, act, rst, host)
+        else:
+            b["cloud"].copy_(cloud)
         b["T"].copy_(init)
         if first:
             self._stage()
@@ -354,4 +520,6 @@ class IcpRefiner:
                 self._graph = g
             self._graph.replay()
         self.calls += 1
+        if trace and self.per_stream:
+            return b["T"], steps, dict(active=b["active"].clone(), restart=b["restart"].clone())
         return (b["T"], steps) if trace else b["T"]

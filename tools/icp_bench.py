@@ -10,6 +10,12 @@ its pose is no vehicle motion, and a registration that starts there finds no pai
 sequence is fixed either way; what a sensible guess adds is the accumulation over real pairs and the search near the map.
 
     python tools/icp_bench.py [--frames F] [--repeats R] [--npoints N] [--map-size M] [--iters I]
+
+``--per-stream``: instead, the masked refiner (``IcpRefiner(per_stream=True)``) beside the lock-step one, same process,
+alternated repeat by repeat: the time of one ``register`` call (its eager loads of cloud, guess and masks, then the replay)
+with all streams active and, where there is more than one stream, with every second stream idle; and the two eager
+launches ``StreamingOdometry`` adds per call in per-stream mode with ``refine=`` (the restart mask and
+``stream_record_refined``), timed as a pair over a loop that ends in a sync.
 """
 import argparse
 import json
@@ -44,6 +50,68 @@ def _per_frame_ms(fn, frames):
     return sorted(out)[len(out) // 2]
 
 
+def _per_stream(a, S, batches, dev):
+    """Lock-step and masked ``register`` on the same frames, alternated; the eager launches of the streaming path."""
+    from pwclonet_pylidarslam_amd import _lib
+    kw = dict(map_size=a.map_size, iters=a.iters, graph=True)
+    lock, msk = IcpRefiner(S, a.npoints, **kw), IcpRefiner(S, a.npoints, per_stream=True, **kw)
+    eye = torch.eye(4, dtype=torch.float64, device=dev).expand(S, 4, 4).contiguous()
+    ones = torch.ones((S,), dtype=torch.int32, device=dev)
+    half = torch.tensor([1 - i % 2 for i in range(S)], dtype=torch.int32, device=dev)
+    zeros = torch.zeros((S,), dtype=torch.int32, device=dev)
+
+    def lock_pass():
+        lock.reset()
+        lock.register(batches[0], eye)
+        return _per_frame_ms(lambda k: lock.register(batches[k], eye), a.frames)
+
+    def masked_pass(active):
+        msk.reset()
+        msk.register(batches[0], eye, active=ones, restart=zeros)
+        return _per_frame_ms(lambda k: msk.register(batches[k], eye, active=active, restart=zeros), a.frames)
+
+    lock_pass(), lock_pass(), masked_pass(ones), masked_pass(ones), masked_pass(half)      # warm-up and captures
+    tl, ta, th = [], [], []
+    for _ in range(a.repeats):
+        tl.append(lock_pass())
+        ta.append(masked_pass(ones))
+        if S > 1:
+            th.append(masked_pass(half))
+    out = {"lockstep_register_ms": _stats(tl), "masked_all_active_register_ms": _stats(ta),
+           "masked_over_lockstep": _stats(ta)["median"] / _stats(tl)["median"],
+           "launches_per_register": {"lockstep": 3 + 4 * a.iters + 1, "masked": 4 + 4 * a.iters + 1},
+           "masked_last_status": msk.status().tolist(), "masked_last_pairs": msk.diagnostics()["pairs"].tolist()}
+    if S > 1:
+        out["masked_every_second_idle_register_ms"] = _stats(th)
+        out["half_idle_over_all_active"] = _stats(th)["median"] / _stats(ta)["median"]
+    # the eager launches StreamingOdometry adds per call: restart = active - valid, then the record launch
+    cap = 8
+    valid, count, restart = ones.clone(), torch.full((S,), 2, dtype=torch.int32, device=dev), zeros.clone()
+    rel = torch.zeros((cap, S, 4, 4), dtype=torch.float64, device=dev)
+    ab = torch.eye(4, dtype=torch.float64, device=dev).expand(cap, S, 4, 4).contiguous()
+    T = msk.bufs["T"]
+
+    def extra():
+        torch.sub(ones, valid, out=restart)
+        _lib.call("stream_record_refined_kernel_wrapper", dev, S, cap, ones.data_ptr(), valid.data_ptr(), count.data_ptr(),
+                  T.data_ptr(), rel.data_ptr(), ab.data_ptr())
+
+    loops, te = 200, []
+    for _ in range(20):
+        extra()
+    for _ in range(a.repeats):
+        torch.cuda.synchronize(dev)
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        for _ in range(loops):
+            extra()
+        e.record()
+        e.synchronize()
+        te.append(1000.0 * s.elapsed_time(e) / loops)
+    out["streaming_extra_eager_us_per_call"] = _stats(te)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=41)
@@ -52,6 +120,7 @@ def main():
     ap.add_argument("--map-size", type=int, default=4)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--per-stream", action="store_true", help="the masked refiner beside the lock-step one")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.set_grad_enabled(False)
@@ -63,6 +132,13 @@ def main():
     net = net.to(dev).eval().prepare_fused()
     res = {"tool": "icp_bench", "npoints": a.npoints, "map_size": a.map_size, "iters": a.iters, "frames": a.frames,
            "repeats": a.repeats, "hw_queues": os.environ.get("GPU_MAX_HW_QUEUES")}
+    if a.per_stream:
+        res["mode"] = "per_stream"
+        for S in (1, 8):
+            batches = [base[torch.tensor([order[k + 5 * i] for i in range(S)], device=dev)] for k in range(a.frames)]
+            res["s%d" % S] = _per_stream(a, S, batches, dev)
+        print(json.dumps(res))
+        return
     for S in (1, 8):
         batches = [base[torch.tensor([order[k + 5 * i] for i in range(S)], device=dev)] for k in range(a.frames)]
         so = StreamingOdometry(net, streams=S, max_frames=a.frames + 1, graph=True)
