@@ -672,6 +672,33 @@ int conv1x1_plan_query(int kind, int b, int cin, int cout, int p, int cus, int *
 int group_points_grad_plan_query(int b, int c, int n, int p, int aligned, int use_lds, int *out);
 int three_interpolate_grad_plan_query(int b, int c, int n, int m, int use_lds, int *out);
 
+/* Host only (no launch, no device needed): which kernel group_points (dense and strided) selects for points (b, c, n) and
+ * p = npoints * nsample grouped positions, answered by the launcher's own planning code (csrc/group_points.hip:
+ * gp_forward_plan).  aligned: points, idx and out are 16-byte aligned (what the launcher reads off its pointers).  use_lds,
+ * threads, target, nt: the PWCLO_GROUP_LDS / PWCLO_GP_THREADS / PWCLO_GP_TARGET / PWCLO_GP_NT settings (threads 0: 1024
+ * threads; target 0: 512 workgroups while the staged rows stay below 64 KiB, else 256), or -1 for what the launcher
+ * currently uses: pwclo_group_points_tuning()'s value, else the environment's.
+ * out receives {form, T, nt, gx, per_wg, lds_bytes, staged_vec, tail}:
+ *   form        PWCLO_GROUP_DIRECT_SCALAR: group_points_kernel<false>, one position per thread (p % 4 != 0 or unaligned);
+ *               PWCLO_GROUP_DIRECT_VEC4: group_points_kernel<true>, four positions per thread, gathers from global memory
+ *               (LDS switched off, or min(c, 8) rows of n floats beyond 128 KiB);
+ *               PWCLO_GROUP_LDS: group_points_lds_kernel<T, nt>, the slice's rows staged in lds_bytes of LDS;
+ *   T           threads of a workgroup of the kernel that runs: 1024, 512 or 256 (any other request runs and is sized for
+ *               256; the direct kernels: 256);
+ *   nt          LDS form: non-temporal stores; else 0;
+ *   gx, per_wg  grid x and the positions one workgroup covers (a multiple of 4 T in the LDS form: ceil(per_wg / 4 T)
+ *               passes of the workgroup, the last workgroup and its last pass possibly short);
+ *   staged_vec  LDS form: the rows are staged with 16-byte copies (n % 4 == 0); else 0;
+ *   tail        c % 8: channels of a narrower last slice, 0 for none.
+ * Returns 0, or -1 for a non-positive size. */
+#define PWCLO_GROUP_DIRECT_SCALAR 0
+#define PWCLO_GROUP_DIRECT_VEC4 1
+#define PWCLO_GROUP_LDS 2
+int group_points_plan_query(int b, int c, int n, int p, int aligned, int use_lds, int threads, int target, int nt, int *out);
+/* Sets the four settings above for later group_points launches of this process; -1 puts a setting back to the
+ * environment's value (read once per process).  For tests and sweeps that visit several kernel forms in one process. */
+void pwclo_group_points_tuning(int use_lds, int threads, int target, int nt);
+
 /* Host only (no launch, no device needed): what a knn call launches for xyz (b,n,3), new_xyz (b,s,3) and nsample
  * neighbours, answered by the launchers' own selection code (csrc/knn.hip: knn_plan).  prebuilt = 0 describes
  * knn_point_ws_kernel_wrapper with a workspace (knn_point_kernel_wrapper, and a NULL workspace, always take the exhaustive

@@ -119,6 +119,8 @@ SIGNATURES = {
     "conv1x1_plan_query": ([_i] * 6 + [ctypes.POINTER(ctypes.c_int)], _i),
     "group_points_grad_plan_query": ([_i] * 6 + [ctypes.POINTER(ctypes.c_int)], _i),
     "three_interpolate_grad_plan_query": ([_i] * 5 + [ctypes.POINTER(ctypes.c_int)], _i),
+    "group_points_plan_query": ([_i] * 9 + [ctypes.POINTER(ctypes.c_int)], _i),
+    "pwclo_group_points_tuning": ([_i] * 4, None),
     "knn_point_plan_query": ([_i] * 6 + [ctypes.POINTER(ctypes.c_int)], _i),
     "batchnorm_train_plan_query": ([_i, ctypes.c_longlong, _i, ctypes.POINTER(ctypes.c_int),
                                     ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_int)], _i),

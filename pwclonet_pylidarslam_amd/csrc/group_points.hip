@@ -10,6 +10,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <atomic>
+
 #include "common.hpp"
 
 namespace pwclo {
@@ -417,6 +419,74 @@ extern "C" void group_points_kernel_wrapper(int b, int c, int n, int npoints, in
   gp_forward(b, c, n, npoints, nsample, points, idx, out, (long long)c * npoints * nsample);
 }
 
+// The four launch settings of gp_forward: the PWCLO_GROUP_LDS / PWCLO_GP_THREADS / PWCLO_GP_TARGET / PWCLO_GP_NT values, read
+// once per process, unless pwclo_group_points_tuning() has set one (-1: as the environment says).
+static std::atomic<int> g_gp_use_lds{-1}, g_gp_threads{-1}, g_gp_target{-1}, g_gp_nt{-1};
+
+struct GroupTuning { int use_lds, threads, target, nt; };   // threads 0: 1024; target 0: by the size of the staged rows
+
+static GroupTuning gp_tuning() {
+  static const int e_lds = tuning("PWCLO_GROUP_LDS", 1), e_threads = tuning("PWCLO_GP_THREADS", 0),
+                   e_target = tuning("PWCLO_GP_TARGET", 0), e_nt = tuning("PWCLO_GP_NT", 1);
+  const int lds = g_gp_use_lds.load(), threads = g_gp_threads.load(), target = g_gp_target.load(), nt = g_gp_nt.load();
+  return {lds < 0 ? e_lds : lds, threads < 0 ? e_threads : threads, target < 0 ? e_target : target, nt < 0 ? e_nt : nt};
+}
+
+extern "C" void pwclo_group_points_tuning(int use_lds, int threads, int target, int nt) {
+  g_gp_use_lds.store(use_lds < 0 ? -1 : use_lds);
+  g_gp_threads.store(threads < 0 ? -1 : threads);
+  g_gp_target.store(target < 0 ? -1 : target);
+  g_gp_nt.store(nt < 0 ? -1 : nt);
+}
+
+// Which kernel gp_forward launches and how it cuts the positions: the launcher and group_points_plan_query both ask here.
+// `vec_aligned`: out and idx are 16-byte aligned (with P % 4 == 0 that is the 16-byte path); `points_aligned`: so are the
+// source rows (the LDS kernel stages them with 16-byte loads).
+struct GroupPlan { int form, T, nt, gx, per_wg, lds_bytes, staged_vec, tail; };
+
+static GroupPlan gp_forward_plan(int b, int c, int n, int P, bool vec_aligned, bool points_aligned, const GroupTuning &tu) {
+  const int gy = ceil_div(c, GP_CH_PER_BLOCK);
+  const bool vec = (P % 4 == 0) && vec_aligned;
+  // rows of one channel slice in LDS: min(C, 8) x n floats, at most 128 KiB (8 x 4096, or e.g. the 3 coordinate rows of an
+  // 8192-point cloud)
+  const long long lds_need = (long long)min(c, GP_CH_PER_BLOCK) * n * 4;
+  if (!(vec && tu.use_lds && lds_need <= (long long)GP_CH_PER_BLOCK * GP_LDS_MAXN * 4 && points_aligned)) {
+    if (vec) return {PWCLO_GROUP_DIRECT_VEC4, GP_THREADS, 0, ceil_div(P / 4, GP_THREADS), GP_THREADS * 4, 0, 0, c % GP_CH_PER_BLOCK};
+    return {PWCLO_GROUP_DIRECT_SCALAR, GP_THREADS, 0, ceil_div(P, GP_THREADS), GP_THREADS, 0, 0, c % GP_CH_PER_BLOCK};
+  }
+  const int lds_bytes = (int)lds_need;
+  // Workgroup shape: 1024 threads (16 waves: one workgroup saturates a CU's store path) when the slices alone give every
+  // CU a workgroup, 256 threads otherwise; positions are split over just enough workgroups to put ~2 per CU (LDS
+  // permitting), so a channel slice's rows are staged once or twice, not once per 4096 positions (round 3: the
+  // 4096-position chunks re-staged the rows 4x at the largest shape and left the kernel at 0.60 of the HBM roof).
+  const long long slices = (long long)b * gy;
+  int T = tu.threads ? tu.threads : 1024;
+  if (T != 1024 && T != 512) T = 256;      // the kernel exists for 1024, 512 and 256 threads: any other request runs the last
+  // measured (profiles/r03: tools/gp_sweep.sh): two workgroups per CU pay while a slice's rows are <= 32 KiB; with 64 KiB
+  // rows a second staging per slice costs more than the overlap gives
+  const int target = tu.target ? tu.target : (lds_bytes < 64 * 1024 ? 512 : 256);
+  int gx = (int)max(1LL, (target + slices - 1) / slices);
+  const int max_gx = ceil_div(P, T * 4);
+  if (gx > max_gx) gx = max_gx;
+  const int per_wg = ceil_div(ceil_div(P, gx), T * 4) * T * 4;
+  gx = ceil_div(P, per_wg);
+  return {PWCLO_GROUP_LDS, T, tu.nt ? 1 : 0, gx, per_wg, lds_bytes, (n & 3) == 0 ? 1 : 0, c % GP_CH_PER_BLOCK};
+}
+
+extern "C" int group_points_plan_query(int b, int c, int n, int p, int aligned, int use_lds, int threads, int target, int nt,
+                                       int *out) {
+  if (b <= 0 || c <= 0 || n <= 0 || p <= 0 || out == nullptr) return -1;
+  GroupTuning tu = gp_tuning();
+  if (use_lds >= 0) tu.use_lds = use_lds;
+  if (threads >= 0) tu.threads = threads;
+  if (target >= 0) tu.target = target;
+  if (nt >= 0) tu.nt = nt;
+  const GroupPlan pl = gp_forward_plan(b, c, n, p, aligned != 0, aligned != 0, tu);
+  out[0] = pl.form; out[1] = pl.T; out[2] = pl.nt; out[3] = pl.gx; out[4] = pl.per_wg; out[5] = pl.lds_bytes;
+  out[6] = pl.staged_vec; out[7] = pl.tail;
+  return 0;
+}
+
 static void gp_forward(int b, int c, int n, int npoints, int nsample, const float *points, const int *idx, float *out,
                        long long out_bstride) {
   if (b <= 0 || c <= 0 || npoints <= 0 || nsample <= 0) return;
@@ -425,33 +495,10 @@ static void gp_forward(int b, int c, int n, int npoints, int nsample, const floa
                 P64, b);
   const int P = (int)P64;
   const int gy = ceil_div(c, GP_CH_PER_BLOCK);
-  const bool vec = (P % 4 == 0) && ((reinterpret_cast<uintptr_t>(out) & 15) == 0) &&
-                   ((reinterpret_cast<uintptr_t>(idx) & 15) == 0);
-  static int use_lds = -1;
-  if (use_lds < 0) { const char *e = getenv("PWCLO_GROUP_LDS"); use_lds = e ? atoi(e) : 1; }
-  // rows of one channel slice in LDS: min(C, 8) x n floats, at most 128 KiB (8 x 4096, or e.g. the 3 coordinate rows of an
-  // 8192-point cloud)
-  const long long lds_need = (long long)min(c, GP_CH_PER_BLOCK) * n * 4;
-  if (vec && use_lds && lds_need <= (long long)GP_CH_PER_BLOCK * GP_LDS_MAXN * 4 && (reinterpret_cast<uintptr_t>(points) & 15) == 0) {
-    const int lds_bytes = (int)lds_need;
-    // Workgroup shape: 1024 threads (16 waves: one workgroup saturates a CU's store path) when the slices alone give every
-    // CU a workgroup, 256 threads otherwise; positions are split over just enough workgroups to put ~2 per CU (LDS
-    // permitting), so a channel slice's rows are staged once or twice, not once per 4096 positions (round 3: the
-    // 4096-position chunks re-staged the rows 4x at the largest shape and left the kernel at 0.60 of the HBM roof).
-    static int t_env = -1, tgt_env = -1, nt_env = -1;
-    if (t_env < 0) { const char *e = getenv("PWCLO_GP_THREADS"); t_env = e ? atoi(e) : 0; }
-    if (tgt_env < 0) { const char *e = getenv("PWCLO_GP_TARGET"); tgt_env = e ? atoi(e) : 0; }
-    if (nt_env < 0) { const char *e = getenv("PWCLO_GP_NT"); nt_env = e ? atoi(e) : 1; }
-    const long long slices = (long long)b * gy;
-    int T = t_env ? t_env : 1024;
-    // measured (profiles/r03: tools/gp_sweep.sh): two workgroups per CU pay while a slice's rows are <= 32 KiB; with 64 KiB
-    // rows a second staging per slice costs more than the overlap gives
-    const int target = tgt_env ? tgt_env : (lds_bytes < 64 * 1024 ? 512 : 256);
-    int gx = (int)max(1LL, (target + slices - 1) / slices);
-    const int max_gx = ceil_div(P, T * 4);
-    if (gx > max_gx) gx = max_gx;
-    const int per_wg = ceil_div(ceil_div(P, gx), T * 4) * T * 4;
-    gx = ceil_div(P, per_wg);
+  const bool vec_aligned = ((reinterpret_cast<uintptr_t>(out) & 15) == 0) && ((reinterpret_cast<uintptr_t>(idx) & 15) == 0);
+  const GroupPlan pl = gp_forward_plan(b, c, n, P, vec_aligned, (reinterpret_cast<uintptr_t>(points) & 15) == 0, gp_tuning());
+  if (pl.form == PWCLO_GROUP_LDS) {
+    const int gx = pl.gx, per_wg = pl.per_wg, lds_bytes = pl.lds_bytes;
 #define GP_LAUNCH(TT, NTT)                                                                                      \
     {                                                                                                           \
       static bool attr_set = false;                                                                             \
@@ -463,21 +510,21 @@ static void gp_forward(int b, int c, int n, int npoints, int nsample, const floa
       hipLaunchKernelGGL((group_points_lds_kernel<TT, NTT>), dim3(gx, gy, b), dim3(TT), lds_bytes,              \
                          current_stream(), c, n, P, per_wg, points, idx, out, out_bstride);                     \
     }
-    if (T == 1024 && nt_env) GP_LAUNCH(1024, true)
-    else if (T == 1024) GP_LAUNCH(1024, false)
-    else if (T == 512 && nt_env) GP_LAUNCH(512, true)
-    else if (T == 512) GP_LAUNCH(512, false)
-    else if (nt_env) GP_LAUNCH(256, true)
+    if (pl.T == 1024 && pl.nt) GP_LAUNCH(1024, true)
+    else if (pl.T == 1024) GP_LAUNCH(1024, false)
+    else if (pl.T == 512 && pl.nt) GP_LAUNCH(512, true)
+    else if (pl.T == 512) GP_LAUNCH(512, false)
+    else if (pl.nt) GP_LAUNCH(256, true)
     else GP_LAUNCH(256, false)
 #undef GP_LAUNCH
     check_launch("group_points");
     return;
   }
-  if (vec)
-    hipLaunchKernelGGL(group_points_kernel<true>, dim3(ceil_div(P / 4, GP_THREADS), gy, b),
+  if (pl.form == PWCLO_GROUP_DIRECT_VEC4)
+    hipLaunchKernelGGL(group_points_kernel<true>, dim3(pl.gx, gy, b),
                        dim3(GP_THREADS), 0, current_stream(), c, n, P, points, idx, out, out_bstride);
   else
-    hipLaunchKernelGGL(group_points_kernel<false>, dim3(ceil_div(P, GP_THREADS), gy, b),
+    hipLaunchKernelGGL(group_points_kernel<false>, dim3(pl.gx, gy, b),
                        dim3(GP_THREADS), 0, current_stream(), c, n, P, points, idx, out, out_bstride);
   check_launch("group_points");
 }

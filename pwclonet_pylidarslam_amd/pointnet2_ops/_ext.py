@@ -270,6 +270,36 @@ def three_interpolate_grad_plan(b, c, n, m, use_lds=None):
     return _plan("three_interpolate_grad_plan_query", (b, c, n, m, -1 if use_lds is None else int(bool(use_lds))))
 
 
+_GROUP_PLAN_FIELDS = ("form", "T", "nt", "gx", "per_wg", "lds_bytes", "staged_vec", "tail")
+_GROUP_PLAN_FORMS = ("direct_scalar", "direct_vec4", "lds")      # PWCLO_GROUP_*
+
+
+def _setting(v):
+    return -1 if v is None else int(v)
+
+
+def group_points_plan(b, c, n, p, aligned=True, use_lds=None, threads=None, target=None, nt=None):
+    """group_points_plan_query: the kernel ``group_points`` / ``group_points_into`` selects for points (b, c, n) grouped to
+    p = npoints * nsample positions -> dict of the fields documented in include/pwclo_ops.h, ``form`` as "direct_scalar" /
+    "direct_vec4" / "lds".  ``aligned``: points, idx and out are 16-byte aligned; ``use_lds``, ``threads``, ``target``,
+    ``nt``: None = what the launcher currently uses (``group_points_tuning``, else the PWCLO_GROUP_LDS / PWCLO_GP_THREADS /
+    PWCLO_GP_TARGET / PWCLO_GP_NT environment).  Host only: works without a GPU."""
+    import ctypes
+    out = (ctypes.c_int * 8)()
+    args = (int(b), int(c), int(n), int(p), int(bool(aligned)), _setting(use_lds), _setting(threads), _setting(target), _setting(nt))
+    if _lib.load().group_points_plan_query(*args, out) != 0:
+        raise ValueError("group_points_plan_query%r" % (args,))
+    plan = dict(zip(_GROUP_PLAN_FIELDS, out[:len(_GROUP_PLAN_FIELDS)]))
+    plan["form"] = _GROUP_PLAN_FORMS[plan["form"]]
+    return plan
+
+
+def group_points_tuning(use_lds=None, threads=None, target=None, nt=None):
+    """pwclo_group_points_tuning: the four settings of later ``group_points`` launches in this process; None = back to the
+    environment's value."""
+    _lib.load().pwclo_group_points_tuning(_setting(use_lds), _setting(threads), _setting(target), _setting(nt))
+
+
 def _slice_ptr(stack, c_off, c):
     """Address of channel ``c_off`` of cloud 0 of a contiguous (B,Ctot,S,K) tensor + its batch stride in floats."""
     _float(stack, "stack")
