@@ -23,7 +23,7 @@ import time
 import numpy as np
 import torch
 
-from . import _lib, preprocess
+from . import _lib, preprocess, stream_masks
 
 MAX_STREAMS = 1024          # stream_append_masked_kernel: one workgroup, one thread per stream
 RAW_NUM_POINTS = 8192       # raw mode: points sampled from every sweep's survivors (BASELINE configs[4])
@@ -67,14 +67,14 @@ class StreamingOdometry:
     against a local map of the stream's last frames, with the level-1 row's transform as the initial guess (one more
     captured graph).  ``refined_relative_poses()`` / ``refined_trajectory()`` sit beside ``relative_poses()`` /
     ``trajectory()``, which stay the network's, as does the de-skew prior; ``refiner().status()`` tells why a stream's
-    registration stopped.  Per-stream mode takes the masked refiner, opted into inside the dict: ``per_stream=True``
-    needs ``refine=dict(..., per_stream=True)`` (a different graph: two mask words, one more launch, status bit 8 for
-    idle streams) and raises without the key; lock step raises with it.  Then, after the step's graph, the call's
-    ``active`` mask and ``restart = active * (1 - valid)`` (a stream that primed in this call: a first frame, a ``restart``
-    mask or ``reset(streams=...)``) go to ``IcpRefiner.register`` as device words, and one launch records the refined pose at
-    the stream's own frame counter: ``refined_relative_poses(stream=i)`` / ``refined_trajectory(stream=i)`` give (count_i,
-    4, 4), row 0 the identity again after a restart.  No sync, no new capture; pose rows, ``relative_poses``,
-    ``trajectory``, ``valid``, ``frame_counts`` and the de-skew prior stay the network's.
+    registration stopped.  One path serves both modes: after the step's graph the refiner's graph reads the call's
+    ``active`` word and ``restart = active * (1 - valid)`` (a stream that primed in this call: a first frame, a ``restart``
+    mask, ``reset()`` or ``reset(streams=...)``) in place, and one launch records the refined pose at the stream's own
+    frame counter, row 0 the identity again after a restart.  No sync, no new capture; pose rows, ``relative_poses``,
+    ``trajectory``, ``valid``, ``frame_counts`` and the de-skew prior stay the network's.  Per-stream mode opts into
+    the per-stream view inside the dict: ``per_stream=True`` needs ``refine=dict(..., per_stream=True)`` (status bit 8
+    for idle streams) and raises without the key; lock step raises with it.  ``refined_relative_poses(stream=i)`` /
+    ``refined_trajectory(stream=i)`` then give (count_i, 4, 4).
 
     Per-stream mode (``per_stream=True``): ``step(frames, active=None, restart=None)`` and ``step_sweeps(sweeps, lengths,
     active=None, restart=None)`` take two (S,) masks, bool or integer, host sequences or device tensors (device tensors
@@ -198,8 +198,8 @@ class StreamingOdometry:
         self.frames_seen = 0
         if self._overflow is not None:
             self._overflow.zero_()
-        if self.per_stream and self._refiner is not None:
-            self._refiner.reset()                           # the maps too (lock step: the priming call does it)
+        if self._refiner is not None:
+            self._refiner.reset()                           # the maps too
         self._reset_motion(None)
 
     def _reset_motion(self, mask):
@@ -255,14 +255,12 @@ class StreamingOdometry:
         store = self._graphs if self.graph else self._static
         filled = None
         if self._fused_id != id(self.net._fused) or key not in store:
-            host, j = self._first_active(act)               # new static rows: idle streams start from an active one
-            filled = frames.clone()
-            if not host.all():
-                filled[torch.from_numpy(~host).to(frames.device)] = frames[j]
+            _, filled = self._seed_idle_rows(act, frames)   # new static rows: idle streams start from an active one
+            filled = frames.clone() if filled is frames else filled
         if self.num_points is None:
             self.num_points = num_points       # fixed from the first frame on: the persistent state has its shapes
         fused = self._begin(frames.device)
-        self._load_masks(act, rst)
+        stream_masks.load_words(self._active, self._restart, act, rst)
         entry = store.get(key)
         if entry is None:
             entry = store[key] = dict(static=filled, step=None)
@@ -293,21 +291,14 @@ class StreamingOdometry:
         self._check_net(sweeps, what)
         act, rst = self._masks(active, restart)
         if front.bufs is None and act is not None:          # new static rows: idle streams start from an active one
-            host, j = self._first_active(act)
-            if not host.all():
-                idle = torch.from_numpy(~host).to(sweeps.device)
-                first, sweeps = sweeps[j], sweeps.clone()   # the source row is the caller's: a write may not alias its source
-                sweeps[idle] = first
-                if times is not None:
-                    first, times = times[j], times.clone()
-                    times[idle] = first
-                if host_lengths is None:
-                    first, lengths = lengths[j], lengths.clone()
-                    lengths[idle] = first
-                else:
-                    host_lengths = [v if a else host_lengths[j] for v, a in zip(host_lengths, host)]
+            if host_lengths is None:
+                host, sweeps, times, lengths = self._seed_idle_rows(act, sweeps, times, lengths)
+            else:
+                host, sweeps, times = self._seed_idle_rows(act, sweeps, times)
+                first = host_lengths[int(np.flatnonzero(host)[0])]
+                host_lengths = [v if a else first for v, a in zip(host_lengths, host)]
         fused = self._begin(sweeps.device)
-        self._load_masks(act, rst)
+        stream_masks.load_words(self._active, self._restart, act, rst)
         if front.deskew:
             front.stream_words = (self._restart, self._have_prev)      # read by the front end's launch, on the device
         if front.bufs is None or act is None:
@@ -334,30 +325,17 @@ class StreamingOdometry:
         """With ``refine=``: (frames_seen, S, 4, 4) fp64 device view beside ``relative_poses()``: row k is pair (k-1, k)'s
         transform after point-to-plane registration against the local map, row 0 the identity.
         Per-stream mode: ``stream=i`` is required and gives that stream's (count_i, 4, 4), as ``relative_poses``."""
-        if self._refine_cfg is None:
-            raise RuntimeError("StreamingOdometry: refined poses need refine=dict(...)")
-        if self.per_stream or stream is not None:
-            return self._view(self._ref_rel, stream)
-        if self._ref_rel is None:
-            return torch.empty((0, self.streams, 4, 4), dtype=torch.float64)
-        return self._ref_rel[:self.frames_seen]
+        return self._view(self._refined(self._ref_rel), stream)
 
     def refined_trajectory(self, stream=None):
-        """With ``refine=``: (frames_seen, S, 4, 4) fp64, the products of ``refined_relative_poses()`` per stream
-        (``evaluation.accumulate``, the kernel behind ``compute_absolute_poses``).  Per-stream mode: ``stream=i`` is
-        required and gives (count_i, 4, 4), a view of the products kept on the device as the poses are recorded."""
-        from . import evaluation
-        if self.per_stream or stream is not None:
-            if self._refine_cfg is None:
-                raise RuntimeError("StreamingOdometry: refined poses need refine=dict(...)")
-            return self._view(self._ref_abs, stream)
-        rel = self.refined_relative_poses()
-        k = rel.shape[0]
-        if k == 0:
-            return rel
-        flat = rel.permute(1, 0, 2, 3).contiguous().view(-1, 4, 4)
-        out = evaluation.accumulate(flat, [k] * self.streams)
-        return out.view(self.streams, k, 4, 4).permute(1, 0, 2, 3).contiguous()
+        """With ``refine=``: (frames_seen, S, 4, 4) fp64 device view, the products of ``refined_relative_poses()`` per
+        stream, kept on the device as the poses are recorded; ``stream=i`` as there."""
+        return self._view(self._refined(self._ref_abs), stream)
+
+    def _refined(self, buf):
+        if self._refine_cfg is None:
+            raise RuntimeError("StreamingOdometry: refined poses need refine=dict(...)")
+        return buf
 
     def refiner(self):
         """The ``registration.IcpRefiner`` behind ``refine=`` (``status()``, ``diagnostics()``); None before the first
@@ -404,7 +382,10 @@ class StreamingOdometry:
 
     def _refine(self, pose):
         """After the step (outside its graph): register the step's cloud, initial guess = the level-1 row's transform
-        (the identity for a frame that primes), and record the refined relative pose."""
+        (the identity for a frame that primes), and record the refined relative pose at the stream's own frame counter.
+        The refiner reads the step's words: ``active``, and ``restart = active * (1 - valid)`` (a stream that primed in
+        this call starts a new map), written as one launch: valid is set for active streams only, so the product is the
+        difference."""
         if self._refine_cfg is None:
             return
         from . import registration
@@ -412,23 +393,13 @@ class StreamingOdometry:
         if self._refiner is None:
             self._refiner = registration.IcpRefiner(self.streams, self.num_points, graph=self.graph, **self._refine_cfg)
             self._ref_rel = torch.zeros((self.max_frames, self.streams, 4, 4), dtype=torch.float64, device=cloud.device)
-            if self.per_stream:
-                self._ref_abs = torch.zeros_like(self._ref_rel)
-                self._ref_restart = torch.zeros_like(self._active)
-        if self.per_stream:
-            # restart = active * (1 - valid), written as one launch: valid is set for active streams only, so the product
-            # is the difference.  A stream that primed in this call starts a new map.
-            torch.sub(self._active, self._valid, out=self._ref_restart)
-            T = self._refiner.register(cloud, pose[:, 0, :], active=self._active, restart=self._ref_restart)
-            _lib.call("stream_record_refined_kernel_wrapper", cloud.device, self.streams, self.max_frames, _p(self._active),
-                      _p(self._valid), _p(self._counts), _p(T), _p(self._ref_rel), _p(self._ref_abs))
-            return
-        if pose is None:
-            self._refiner.reset()
-            init = torch.eye(4, dtype=torch.float64, device=cloud.device).expand(self.streams, 4, 4).contiguous()
-        else:
-            init = pose[:, 0, :]
-        self._ref_rel[self.frames_seen].copy_(self._refiner.register(cloud, init))
+            self._ref_abs = torch.zeros_like(self._ref_rel)
+            self._ref_restart = torch.zeros_like(self._active)
+            self._refiner.adopt_words(self._active, self._ref_restart)
+        torch.sub(self._active, self._valid, out=self._ref_restart)
+        T = self._refiner.register_adopted(cloud, pose[:, 0, :], all_active=not self.per_stream)
+        _lib.call("stream_record_refined_kernel_wrapper", cloud.device, self.streams, self.max_frames, _p(self._active),
+                  _p(self._valid), _p(self._counts), _p(T), _p(self._ref_rel), _p(self._ref_abs))
 
     def _view(self, buf, stream=None):
         if stream is None:
@@ -484,30 +455,8 @@ class StreamingOdometry:
         return graph, out
 
     def _stream_mask(self, mask, what="streams"):
-        """An (S,) bool or integer mask, host sequence or device tensor -> (S,) int32 0 / 1 tensor where the caller's
-        data lives.  ``what == "streams"`` (``reset``): integers are stream indices (host sequences only), booleans a mask.
-        Raises ValueError before anything is launched."""
-        S = self.streams
-        if isinstance(mask, torch.Tensor) and mask.is_cuda:
-            if what == "streams" and mask.dtype != torch.bool:
-                raise ValueError("StreamingOdometry: reset(streams=...) takes a device mask as bool (integers are stream "
-                                 "indices and belong in a host list), got %s" % mask.dtype)
-            if mask.shape != (S,) or mask.dtype.is_floating_point or mask.dtype.is_complex:
-                raise ValueError("StreamingOdometry: %s must be a (%d,) bool or integer mask, got %s %s"
-                                 % (what, S, mask.dtype, tuple(mask.shape)))
-            return mask.ne(0).to(torch.int32)
-        arr = np.asarray(mask.numpy() if isinstance(mask, torch.Tensor) else mask)
-        if what == "streams" and arr.ndim == 1 and (arr.dtype.kind in "iu" or arr.size == 0):
-            arr = arr.astype(np.int64)
-            if arr.size and (arr.min() < 0 or arr.max() >= S):
-                raise ValueError("StreamingOdometry: streams %s outside [0, %d)" % (arr.tolist(), S))
-            out = np.zeros((S,), dtype=np.int32)
-            out[arr] = 1
-            return torch.from_numpy(out)
-        if arr.shape != (S,) or arr.dtype.kind not in "biu":
-            raise ValueError("StreamingOdometry: %s must be a (%d,) bool or integer mask, got %s %s"
-                             % (what, S, arr.dtype, arr.shape))
-        return torch.from_numpy((arr != 0).astype(np.int32))
+        """``stream_masks.stream_mask`` for this object; ``what == "streams"`` (``reset``): integers are stream indices."""
+        return stream_masks.stream_mask(mask, self.streams, what, "StreamingOdometry", indices=what == "streams")
 
     def _check_mode(self, active, restart):
         if not self.per_stream and (active is not None or restart is not None):
@@ -519,24 +468,8 @@ class StreamingOdometry:
         rst = None if restart is None else self._stream_mask(restart, "restart")
         return act, rst
 
-    def _first_active(self, act):
-        """New static inputs need every row initialised: -> (host bool mask of the active streams, index of the first),
-        reading a device mask once.  ValueError when no stream is active."""
-        host = np.ones((self.streams,), dtype=bool) if act is None else act.cpu().numpy() != 0
-        if not host.any():
-            raise ValueError("StreamingOdometry: the first call (of an input shape) needs at least one active stream: "
-                             "idle streams' inputs start as copies of the first active stream's")
-        return host, int(np.flatnonzero(host)[0])
-
-    def _load_masks(self, act, rst):
-        if act is None:
-            self._active.fill_(1)
-        else:
-            self._active.copy_(act)
-        if rst is None:
-            self._restart.zero_()
-        else:
-            self._restart.copy_(rst)
+    def _seed_idle_rows(self, act, *tensors):
+        return stream_masks.seed_idle_rows(act, self.streams, "StreamingOdometry", *tensors)
 
     def _append(self, pose):
         """One launch: the per-stream state machine over this call's masks; non-pair rows of ``pose`` become identity."""
@@ -578,13 +511,12 @@ class StreamingOdometry:
         return pose
 
     def _finish(self, pose):
-        """After the step: lock step knows on the host that this call primed every stream (the first since ``reset()``)
-        and returns None for it; the refinement; the call counter."""
-        if not self.per_stream and self.frames_seen == 0:
-            pose = None
+        """After the step: the refinement (a primed stream's rows of ``pose`` are the identity by now); the call
+        counter; lock step knows on the host that this call primed every stream (the first since ``reset()``) and
+        returns None for it."""
         self._refine(pose)
         self.frames_seen += 1
-        return pose
+        return None if not self.per_stream and self.frames_seen == 1 else pose
 
 
 class PWCLONetOdometry:

@@ -14,14 +14,15 @@ frame; only the frame's points move (``icp_queries``).  One iteration is four la
 the iteration count is fixed and streams freeze on the device (``status()``), so a whole registration plus the map handover
 replays as one captured graph.  There is no CPU path.
 
-Masked registration (``IcpRefiner(..., per_stream=True)``): every call says which streams delivered a frame and which of
-those start a new sequence, in two (S,) masks that live in device memory; one graph serves idle, restarting and pairing
-streams alike.  An idle stream keeps its map and gets status ``IDLE``.
+The registration is masked: two (S,) words in device memory say which streams delivered a frame and which of those start
+a new sequence, and one graph serves idle, restarting and pairing streams alike.  An idle stream keeps its map and gets
+status ``IDLE``.  ``IcpRefiner(..., per_stream=True)`` lets every call set the words; lock step (the default) is the same
+engine with every stream active, seen through a host-side view.
 """
 import numpy as np
 import torch
 
-from . import _lib, evaluation
+from . import _lib, evaluation, stream_masks
 
 MAX_STREAMS = 1024
 MAX_SLOTS = 64                                   # csrc/icp.hip: ICP_MAX_SLOTS
@@ -224,7 +225,7 @@ def map_push(T, cloud, normals_, stage_ws, map_xyz, map_normals, map_ws, A, R, l
 # ---- the refiner -------------------------------------------------------------------------------------------------------
 
 class IcpRefiner:
-    """Registers one frame per call for S streams in lock step against each stream's map of the last ``map_size`` frames.
+    """Registers one frame per call and stream against each stream's map of the last ``map_size`` frames.
 
     ``register(cloud, init)``: cloud (S, n, 3) fp32, init (S, 4, 4) fp64 or (S, 7) fp32 pose rows [tx ty tz qw qx qy qz]
     (``evaluation.rows_to_transforms``) -> the refined pose (S, 4, 4) fp64, a static buffer that the next call overwrites
@@ -238,21 +239,28 @@ class IcpRefiner:
     call replays.  ``register(..., trace=True)`` (``graph=False`` only) also returns, per iteration, clones of the queries,
     ``idx``, ``dist``, the summed row, ``delta`` and ``T``.
 
-    ``per_stream=True`` (masked registration): ``register(cloud, init, active=None, restart=None)`` takes two (S,) masks,
-    bool or integer, host sequences or device tensors (device tensors are copied on the device, without a sync); ``None``
-    = all active, none restarting.  ``active[s]``: stream s delivered a frame in this call; ``restart[s]`` (looked at only
-    where active): that frame starts a new sequence.  Per stream:
+    One engine runs both modes: the graph (begin, stage, ``iters`` x (queries, search, accumulate, solve), push: ``4 + 4
+    iters + 1`` launches) reads two (S,) words from device memory.  ``active[s]``: stream s delivered a frame in this call;
+    ``restart[s]`` (looked at only where active): that frame starts a new sequence.  Per stream:
       idle (not active)     nothing of the stream changes (map slots, A, R, live, cursor); ``T[s]`` is ``init[s]`` bit for
                             bit, status ``IDLE`` (8), iterations = pairs = 0, cost = 0; its row of ``cloud`` is ignored
       restart               the map is emptied on the device, inside the graph, before the iterations; the frame finds no
                             live slot, freezes in iteration 0 with the few-pairs bit, returns ``init`` and fills slot 0
-      pair (otherwise)      the registration and push of lock step, bit for bit those of a refiner of its own
-    One graph (begin, stage, ``iters`` x (queries, search, accumulate, solve), push) serves every combination: the masks
-    are device memory that it reads.  The search and the staging run for every stream, so an idle stream costs what an
-    active one does bar the gathers.  The first call needs an active stream: the idle streams' rows of the persistent
-    cloud start as copies of the first active stream's (the mask is read once, there), so that staging never sees data no
-    caller supplied.  ``reset(streams=...)`` arms a restart for those streams' next delivered frame, on the device and
-    without a sync (``map_state()`` shows the old map until then).  ``trace=True`` returns ``(T, steps, masks)``."""
+      pair (otherwise)      the registration and push, bit for bit those of a refiner of the stream's own
+    The search and the staging run for every stream, so an idle stream costs what an active one does bar the gathers.
+    ``reset()`` / ``reset(streams=...)`` arm a restart for the streams' next delivered frame, on the device and without a
+    sync (``map_state()`` shows the old map until then).  Lock step is the view "all active, none restarting": its words
+    are written once and no later call touches them.
+
+    ``per_stream=True``: ``register(cloud, init, active=None, restart=None)`` takes the two masks, bool or integer, host
+    sequences or device tensors (device tensors are copied on the device, without a sync); ``None`` = all active, none
+    restarting.  The first call needs an active stream: the idle streams' rows of the persistent cloud start as copies of
+    the first active stream's (the mask is read once, there), so that staging never sees data no caller supplied.
+    ``trace=True`` returns ``(T, steps, masks)``.
+
+    ``adopt_words(active, restart)``, before the first call: the graph reads the caller's two (S,) int32 0 / 1 device words
+    instead (``StreamingOdometry``'s, which its step's graph has just written); ``register_adopted(cloud, init)`` then
+    loads no mask at all."""
 
     def __init__(self, streams, num_points, map_size=4, iters=10, sigma=0.5, max_dist=1.0, k_normals=10, damping=1e-6,
                  threshold_delta_pose=1e-4, min_pairs=64, graph=True, per_stream=False):
@@ -285,6 +293,8 @@ class IcpRefiner:
         self.bufs = None
         self.calls = 0              # register() calls so far: call 0 is eager, call 1 captures
         self._graph = None
+        self._words = None          # adopt_words: the caller's (active, restart) words
+        self._plain = False         # the refiner's own words are known to hold "all active, none restarting"
 
     # ---- state -------------------------------------------------------------------------------------------------------
 
@@ -305,9 +315,10 @@ class IcpRefiner:
             map_ws=torch.zeros((lib.knn_point_build_bytes(S * M, n),), dtype=torch.uint8, device=device),
             A=eye(S, M, 4, 4), R=eye(S, M, 3, 3), live=i32(S, M), cursor=i32(S),
             q=f32(S, M, n, 3), idx=i32(S, M, n), dist=f32(S, M, n), partial=f64(S, G, ROW),
-            status=i32(S), iterations=i32(S), pairs=i32(S), cost=f64(S), sum=f64(S, ROW), delta=f64(S, 6))
-        if self.per_stream:                  # the masks the graph reads; armed: restarts asked for by reset(streams=...)
-            self.bufs.update(active=i32(S), restart=i32(S), armed=i32(S))
+            status=i32(S), iterations=i32(S), pairs=i32(S), cost=f64(S), sum=f64(S, ROW), delta=f64(S, 6),
+            armed=i32(S))                    # restarts asked for by reset()
+        active, restart = self._words or (i32(S), i32(S))
+        self.bufs.update(active=active, restart=restart)            # the masks the graph reads
 
     def _seed_structures(self):
         """Before the first registration: every slot's search structure becomes the first frame's (its live flag stays 0),
@@ -340,38 +351,18 @@ class IcpRefiner:
         return {k: self.bufs[k] for k in ("A", "R", "live", "cursor")}
 
     def reset(self, streams=None):
-        """Empty the maps of all streams, or of ``streams`` (stream indices, or an (S,) bool mask): their next frame only
-        fills the map.  No new capture: the flags are device memory that the graph reads.  Masked registration: the
-        streams are armed on the device, without a sync, and the first launch of their next delivered frame's registration
-        empties the map."""
-        S = self.streams
-        if streams is None:
-            mask = np.ones((S,), dtype=bool)
-        else:
-            arr = np.asarray(streams.cpu().numpy() if isinstance(streams, torch.Tensor) else streams)
-            if arr.dtype == bool:
-                if arr.shape != (S,):
-                    raise ValueError("IcpRefiner: a stream mask must have shape (%d,), got %s" % (S, arr.shape))
-                mask = arr
-            else:
-                if arr.ndim != 1 or (arr.size and arr.dtype.kind not in "iu"):
-                    raise ValueError("IcpRefiner: streams must be stream indices or an (S,) bool mask")
-                arr = arr.astype(np.int64)
-                if arr.size and (arr.min() < 0 or arr.max() >= S):
-                    raise ValueError("IcpRefiner: streams %s outside [0, %d)" % (arr.tolist(), S))
-                mask = np.zeros((S,), dtype=bool)
-                mask[arr] = True
+        """Empty the maps of all streams, or of ``streams`` (host stream indices, or an (S,) bool mask, host or device):
+        their next delivered frame only fills the map.  The streams are armed on the device, without a sync, and the
+        first launch of that frame's registration empties the map.  No new capture: the word is device memory that the
+        graph reads."""
+        mask = None if streams is None else stream_masks.stream_mask(streams, self.streams, "streams", "IcpRefiner", True)
         if self.bufs is None:
             return
-        b = self.bufs
-        if self.per_stream:
-            b["armed"].copy_(torch.maximum(b["armed"], torch.from_numpy(mask.astype(np.int32)).to(b["armed"].device)))
-            return
-        m = torch.from_numpy(mask).to(b["live"].device)
-        b["live"][m] = 0
-        b["cursor"][m] = 0
-        b["A"][m] = torch.eye(4, dtype=torch.float64, device=m.device)
-        b["R"][m] = torch.eye(3, dtype=torch.float64, device=m.device)
+        armed = self.bufs["armed"]
+        if mask is None:
+            armed.fill_(1)
+        else:
+            armed.copy_(torch.maximum(armed, mask.to(armed.device)))
 
     # ---- one registration ----------------------------------------------------------------------------------------------
 
@@ -389,20 +380,20 @@ class IcpRefiner:
         b, S, M, n = self.bufs, self.streams, self.map_size, self.num_points
         dev = b["cloud"].device
         G = b["partial"].shape[1]
-        masked = ("_masked", (_p(b["active"]),)) if self.per_stream else ("", ())
+        active = _p(b["active"])
         for it in range(self.iters):
-            _lib.call("icp_queries%s_kernel_wrapper" % masked[0], dev, S, M, n, _p(b["A"]), _p(b["T"]), _p(b["cloud"]),
-                      _p(b["q"]), *masked[1])
+            _lib.call("icp_queries_masked_kernel_wrapper", dev, S, M, n, _p(b["A"]), _p(b["T"]), _p(b["cloud"]), _p(b["q"]),
+                      active)
             _lib.call("knn_point_prebuilt_kernel_wrapper", dev, S * M, n, n, 1, _p(b["q"]), _p(b["idx"]), _p(b["dist"]),
                       _p(b["map_ws"]))
-            _lib.call("icp_accumulate%s_kernel_wrapper" % masked[0], dev, S, M, n, _p(b["cloud"]), _p(b["q"]), _p(b["idx"]),
+            _lib.call("icp_accumulate_masked_kernel_wrapper", dev, S, M, n, _p(b["cloud"]), _p(b["q"]), _p(b["idx"]),
                       _p(b["dist"]), _p(b["map_xyz"]), _p(b["map_normals"]), _p(b["live"]), _p(b["R"]), _p(b["T"]),
-                      self.sigma, self.max_dist, _p(b["partial"]), *masked[1])
+                      self.sigma, self.max_dist, _p(b["partial"]), active)
             if trace is not None:
                 before = b["T"].clone()
-            _lib.call("icp_solve%s_kernel_wrapper" % masked[0], dev, S, G, it, _p(b["partial"]), self.damping,
+            _lib.call("icp_solve_masked_kernel_wrapper", dev, S, G, it, _p(b["partial"]), self.damping,
                       self.threshold_delta_pose, self.min_pairs, _p(b["T"]), _p(b["status"]), _p(b["iterations"]),
-                      _p(b["pairs"]), _p(b["cost"]), _p(b["sum"]), _p(b["delta"]), *masked[1])
+                      _p(b["pairs"]), _p(b["cost"]), _p(b["sum"]), _p(b["delta"]), active)
             if trace is not None:
                 trace.append(dict(q=b["q"].clone(), idx=b["idx"].clone(), dist=b["dist"].clone(), sum=b["sum"].clone(),
                                   delta=b["delta"].clone(), T_before=before, T=b["T"].clone(),
@@ -410,20 +401,18 @@ class IcpRefiner:
 
     def _push(self):
         b, S, M, n = self.bufs, self.streams, self.map_size, self.num_points
-        masked = ("_masked", (_p(b["active"]),)) if self.per_stream else ("", ())
-        _lib.call("icp_map_push%s_kernel_wrapper" % masked[0], b["cloud"].device, S, M, n, _p(b["T"]), _p(b["cloud"]),
+        _lib.call("icp_map_push_masked_kernel_wrapper", b["cloud"].device, S, M, n, _p(b["T"]), _p(b["cloud"]),
                   _p(b["stage_normals"]), _p(b["stage_ws"]), _p(b["map_xyz"]), _p(b["map_normals"]), _p(b["map_ws"]),
-                  _p(b["A"]), _p(b["R"]), _p(b["live"]), _p(b["cursor"]), *masked[1])
+                  _p(b["A"]), _p(b["R"]), _p(b["live"]), _p(b["cursor"]), _p(b["active"]))
 
     def _begin(self):
-        """Masked registration: empty the maps of the streams whose frame starts a new sequence."""
+        """Empty the maps of the streams whose frame starts a new sequence (``restart``, or armed by ``reset``)."""
         b = self.bufs
         _lib.call("icp_begin_kernel_wrapper", b["cloud"].device, self.streams, self.map_size, _p(b["active"]),
                   _p(b["restart"]), _p(b["armed"]), _p(b["A"]), _p(b["R"]), _p(b["live"]), _p(b["cursor"]))
 
     def _body(self, trace=None):
-        if self.per_stream:
-            self._begin()
+        self._begin()
         self._stage()
         self._iterate(trace)
         self._push()
@@ -443,67 +432,55 @@ class IcpRefiner:
             raise RuntimeError("CPU not supported")
 
     def _mask(self, mask, what):
-        """An (S,) bool or integer mask, host sequence or device tensor -> (S,) int32 0 / 1 tensor where the caller's data
-        lives.  Raises ValueError before anything is launched."""
-        S = self.streams
-        if isinstance(mask, torch.Tensor) and mask.is_cuda:
-            if tuple(mask.shape) != (S,) or mask.dtype.is_floating_point or mask.dtype.is_complex:
-                raise ValueError("IcpRefiner: %s must be a (%d,) bool or integer mask, got %s %s"
-                                 % (what, S, mask.dtype, tuple(mask.shape)))
-            return mask.ne(0).to(torch.int32)
-        arr = np.asarray(mask.numpy() if isinstance(mask, torch.Tensor) else mask)
-        if arr.shape != (S,) or arr.dtype.kind not in "biu":
-            raise ValueError("IcpRefiner: %s must be a (%d,) bool or integer mask, got %s %s" % (what, S, arr.dtype, arr.shape))
-        return torch.from_numpy((arr != 0).astype(np.int32))
+        return stream_masks.stream_mask(mask, self.streams, what, "IcpRefiner")
 
-    def _load(self, cloud, act, rst, host):
-        """Masked registration: the masks into the words the graph reads, the active streams' rows into the persistent
-        cloud (one masked-copy launch).  ``host``: on the very first call the host's copy of ``active``; that call copies
-        every row, the idle streams' from the first active stream."""
-        from . import fused
-        b = self.bufs
-        if act is None:
-            b["active"].fill_(1)
-        else:
-            b["active"].copy_(act)
-        if rst is None:
-            b["restart"].zero_()
-        else:
-            b["restart"].copy_(rst)
-        if host is not None:
-            b["cloud"].copy_(cloud)
-            if not host.all():
-                b["cloud"][torch.from_numpy(~host).to(cloud.device)] = cloud[int(np.flatnonzero(host)[0])]
-        elif act is None:
-            b["cloud"].copy_(cloud)
-        else:
-            src = cloud.contiguous()
-            fused.masked_copy([(b["cloud"].data_ptr(), src.data_ptr(), self.num_points * 12)], b["active"])
+    def adopt_words(self, active, restart):
+        """Before the first call: the graph reads the caller's (S,) int32 0 / 1 device words, which the caller writes
+        before every ``register_adopted`` (a lock-step view's ``active`` holds ones)."""
+        if self.bufs is not None:
+            raise RuntimeError("IcpRefiner: adopt_words comes before the first call (a captured graph keeps its words)")
+        _need_mask(active, "IcpRefiner", self.streams)
+        _need(restart, "IcpRefiner: restart", torch.int32, (self.streams,))
+        self._words = (active, restart)
+
+    def register_adopted(self, cloud, init, all_active=False):
+        """``register`` with this call's masks already in the adopted words: no mask is parsed, copied or loaded.
+        ``all_active``: the caller knows on the host that ``active`` holds ones (the cloud then goes in as a plain copy)."""
+        if self._words is None:
+            raise RuntimeError("IcpRefiner: register_adopted needs adopt_words(active, restart)")
+        return self._register(cloud, init, every=bool(all_active))
 
     def register(self, cloud, init, active=None, restart=None, trace=False):
         if trace and self.graph:
             raise ValueError("IcpRefiner: trace=True needs graph=False (a replayed graph cannot hand out its iterations)")
         if not self.per_stream and (active is not None or restart is not None):
             raise ValueError("IcpRefiner: active / restart masks need per_stream=True")
+        if self._words is not None:
+            raise RuntimeError("IcpRefiner: the words are the caller's (adopt_words): call register_adopted")
         act = None if active is None else self._mask(active, "active")
         rst = None if restart is None else self._mask(restart, "restart")
+        return self._register(cloud, init, act, rst, trace, every=act is None)
+
+    def _register(self, cloud, init, act=None, rst=None, trace=False, every=False):
+        from . import fused
         self._check(cloud, init)
-        first = self.bufs is None
-        host = None
-        if first and self.per_stream:                       # the one read of the mask: every row of the cloud starts defined
-            host = np.ones((self.streams,), dtype=bool) if act is None else act.cpu().numpy() != 0
-            if not host.any():
-                raise ValueError("IcpRefiner: the first call needs at least one active stream: idle streams' clouds "
-                                 "start as copies of the first active stream's")
+        first, own, plain = self.bufs is None, self._words is None, act is None and rst is None
+        if first:                                           # every row of the cloud starts defined; the per-stream view
+            seen = None if not self.per_stream else act if own else self._words[0]        # reads the mask once, here
+            _, cloud = stream_masks.seed_idle_rows(seen, self.streams, "IcpRefiner", cloud)
         if init.dim() == 2:
             init = evaluation.rows_to_transforms(init)
         if first:
             self._alloc(cloud.device)
         b = self.bufs
-        if self.per_stream:
-            self._load(cloud, act, rst, host)
-        else:
+        if own and not (plain and self._plain):             # words that hold "all active, none restarting" are left alone
+            stream_masks.load_words(b["active"], b["restart"], act, rst)
+            self._plain = plain
+        if first or every:                                  # every: all streams are active, as the host knows
             b["cloud"].copy_(cloud)
+        else:                                               # the active streams' rows only, one launch
+            src = cloud.contiguous()
+            fused.masked_copy([(b["cloud"].data_ptr(), src.data_ptr(), self.num_points * 12)], b["active"])
         b["T"].copy_(init)
         if first:
             self._stage()

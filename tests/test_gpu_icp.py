@@ -32,6 +32,12 @@ def _bits(a):
     return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
+def _same_bits(a, b):
+    """Two device tensors hold the same bits (floating tensors compared as integers)."""
+    raw = lambda t: t.contiguous().view({8: torch.int64, 4: torch.int32}[t.element_size()]) if t.dtype.is_floating_point else t
+    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(raw(a), raw(b))
+
+
 def _ulps(a, b):
     """Distance in fp32 steps between finite arrays a and b (b fp64: first rounded to fp32)."""
     key = lambda x: np.where(_bits(x).view(np.int32) < 0, np.int64(-(2 ** 31)) - _bits(x).view(np.int32), _bits(x).view(np.int32)).astype(np.int64)
@@ -277,8 +283,10 @@ def test_map_bookkeeping_and_partial_reset(cuda):
     frames = M + 2
     clouds, gt = _rooms(S, frames, n)
     ref = registration.IcpRefiner(S, n, map_size=M, iters=2, graph=False)
+    twin = registration.IcpRefiner(S, n, map_size=M, iters=2, graph=False)      # the same frames, never reset
     maps = [model.Map(M, n, 10) for _ in range(S)]
     for k in range(frames):
+        twin.register(_dev(clouds[k], cuda), _dev(gt[k], cuda))
         T = ref.register(_dev(clouds[k], cuda), _dev(gt[k], cuda)).cpu().numpy().copy()
         state = {key: v.cpu().numpy() for key, v in ref.map_state().items()}
         nrm = ref.bufs["stage_normals"].cpu().numpy()
@@ -292,14 +300,49 @@ def test_map_bookkeeping_and_partial_reset(cuda):
     keep = {key: v.clone() for key, v in ref.map_state().items()}
     ref.reset(streams=[1])
     now = ref.map_state()
-    for key in keep:
-        assert torch.equal(now[key][0], keep[key][0])                           # stream 0 untouched
-    assert not now["live"][1].any() and int(now["cursor"][1]) == 0
-    assert torch.equal(now["A"][1], torch.eye(4, dtype=torch.float64, device=cuda).expand(M, 4, 4))
+    for key in keep:                                                            # armed only: the old maps until a frame comes
+        assert _same_bits(now[key], keep[key]), key
+    assert ref.bufs["armed"].tolist() == [0, 1]
     init = np.stack([gt[1, 0], model.perturbed(gt[1, 1])])
+    twin.register(_dev(clouds[1], cuda), _dev(init, cuda))
     T = ref.register(_dev(clouds[1], cuda), _dev(init, cuda)).cpu().numpy()
     assert np.array_equal(T[1], init[1]) and ref.status().tolist()[1] == model.FEW_PAIRS    # stream 1 only fills its map
-    assert ref.map_state()["live"].tolist() == [[1, 1], [1, 0]]
+    now = ref.map_state()
+    assert now["live"].tolist() == [[1, 1], [1, 0]] and int(now["cursor"][1]) == 1 and ref.bufs["armed"].tolist() == [0, 0]
+    assert torch.equal(now["A"][1, 0], torch.eye(4, dtype=torch.float64, device=cuda))
+    for key in ("T", "status", "iterations", "pairs", "cost", "A", "R", "live", "cursor", "map_xyz", "map_normals"):
+        assert _same_bits(ref.bufs[key][0], twin.bufs[key][0]), key             # stream 0: as if nothing had been reset
+    _lib.synchronize(cuda)
+
+
+# ---- 6b. lock step is a view of the masked engine --------------------------------------------------------------------------
+
+@pytest.mark.parametrize("graph", [False, True])
+def test_lock_step_and_per_stream_views_run_one_engine(cuda, graph):
+    """A lock-step refiner and a per-stream refiner called without masks hold the same bits after every call, allocate the
+    same buffers, and from the second call on no launch writes the mask words (their version counters stand still)."""
+    S, M, n, frames = 2, 2, 256, 4
+    clouds, gt = _rooms(S, frames, n)
+    lock = registration.IcpRefiner(S, n, map_size=M, iters=2, graph=graph)
+    per = registration.IcpRefiner(S, n, map_size=M, iters=2, graph=graph, per_stream=True)
+    # not map_ws: the build orders the points of a cell by an atomic counter, so a structure's bytes vary from run to run
+    keys = ("T", "status", "iterations", "pairs", "cost", "A", "R", "live", "cursor", "map_xyz", "map_normals")
+    versions = None
+    for k in range(frames):
+        init = _dev(np.stack([model.perturbed(gt[k, s]) if k else np.eye(4) for s in range(S)]), cuda)
+        Tl = lock.register(_dev(clouds[k], cuda), init)
+        Tp = per.register(_dev(clouds[k], cuda), init, active=None, restart=None)
+        assert _same_bits(Tl, Tp), k
+        assert sorted(lock.bufs) == sorted(per.bufs)
+        for key in keys:
+            assert _same_bits(lock.bufs[key], per.bufs[key]), (k, key)
+        for ref in (lock, per):
+            assert ref.bufs["active"].tolist() == [1] * S and ref.bufs["restart"].tolist() == [0] * S
+        now = [ref.bufs[w]._version for ref in (lock, per) for w in ("active", "restart")]
+        assert versions is None or now == versions, k
+        versions = now
+    assert lock.status().tolist() == per.status().tolist() and not (lock.status().cpu().numpy() & model.FEW_PAIRS).any()
+    assert (lock._graph is not None) == (per._graph is not None) == graph
     _lib.synchronize(cuda)
 
 
@@ -365,4 +408,15 @@ def test_streaming_odometry_with_refine(cuda):
                 assert np.linalg.norm(ref[k, s, :3, 3]) > 0.3                   # and the registration found the motion
     with pytest.raises(ValueError, match="per_stream"):
         StreamingOdometry(net, streams=S, per_stream=True, refine=cfg)
+    graph = refined.refiner()._graph
+    refined.reset()                                                             # a new sequence: the maps start over too
+    assert refined.refiner().bufs["armed"].tolist() == [1] * S
+    with torch.no_grad():
+        assert refined.step(seq[2]) is None and refined.refiner().status().tolist() == [model.FEW_PAIRS] * S
+        assert refined.step(seq[3]) is not None
+    again = refined.refined_relative_poses()
+    assert again.shape == (2, S, 4, 4) and _same_bits(again[0], torch.eye(4, dtype=torch.float64, device=cuda).expand(S, 4, 4))
+    assert np.linalg.norm(again[1, :, :3, 3].cpu().numpy(), axis=1).min() > 0.3
+    assert refined.captures == 1 and graph is not None and refined.refiner()._graph is graph    # one graph each, all along
+    assert refined.refiner().calls == frames + 2
     _lib.synchronize(cuda)

@@ -11,7 +11,7 @@ import torch
 
 import icp_mask_model as masked
 import icp_model as model
-from pwclonet_pylidarslam_amd import _lib, registration
+from pwclonet_pylidarslam_amd import _lib, registration, stream_masks
 from pwclonet_pylidarslam_amd.odometry import StreamingOdometry
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -93,6 +93,42 @@ def test_mask_argument_rules():
         registration.begin(None, None, None, None, None, None)
     with pytest.raises(ValueError, match="map_xyz"):
         registration.map_push(*[None] * 11)
+
+
+def test_the_shared_mask_helper_accepts_and_refuses_each_form_once():
+    f = stream_masks.stream_mask
+    for good in ([1, 0, 2], [True, False, True], np.array([1, 0, 1], dtype=np.uint8), torch.tensor([True, False, True]),
+                 torch.tensor([3, 0, 1])):
+        got = f(good, 3, "active", "Owner")
+        assert got.dtype == torch.int32 and got.tolist() == [1, 0, 1] and not got.is_cuda
+    assert f([2, 0], 3, "streams", "Owner", indices=True).tolist() == [1, 0, 1]             # integers: stream indices
+    assert f([], 3, "streams", "Owner", indices=True).tolist() == [0, 0, 0]
+    assert f([False, True, False], 3, "streams", "Owner", indices=True).tolist() == [0, 1, 0]
+    assert f(torch.tensor([0, 0]), 3, "streams", "Owner", indices=True).tolist() == [1, 0, 0]
+    for bad in ([1, 0], [[1, 0, 1]], [1.0, 0.0, 1.0], torch.ones(3), np.ones((4,), dtype=bool), "101"):
+        with pytest.raises(ValueError, match=r"^Owner: active must be a \(3,\) bool or integer mask"):
+            f(bad, 3, "active", "Owner")
+    for bad in ([3], [-1], np.array([0, 5])):
+        with pytest.raises(ValueError, match=r"^Owner: streams .* outside \[0, 3\)"):
+            f(bad, 3, "streams", "Owner", indices=True)
+    for bad in ([True, False], [0.0], [[0]]):
+        with pytest.raises(ValueError, match=r"^Owner: streams must be a \(3,\) bool or integer mask"):
+            f(bad, 3, "streams", "Owner", indices=True)
+    # idle rows start as copies of the first active row; the caller's tensors stay as they are
+    x = torch.arange(12.0).view(3, 4)
+    host, y, none = stream_masks.seed_idle_rows(torch.tensor([0, 1, 0], dtype=torch.int32), 3, "Owner", x, None)
+    assert host.tolist() == [False, True, False] and none is None and y is not x
+    assert y.tolist() == [x[1].tolist()] * 3 and x[0].tolist() == [0.0, 1.0, 2.0, 3.0]
+    host, y = stream_masks.seed_idle_rows(None, 3, "Owner", x)
+    assert host.all() and y is x
+    with pytest.raises(ValueError, match="^Owner: .*at least one active stream"):
+        stream_masks.seed_idle_rows(torch.zeros(3, dtype=torch.int32), 3, "Owner", x)
+    # the two words
+    a, r = torch.zeros(3, dtype=torch.int32), torch.ones(3, dtype=torch.int32)
+    stream_masks.load_words(a, r, None, None)
+    assert a.tolist() == [1, 1, 1] and r.tolist() == [0, 0, 0]
+    stream_masks.load_words(a, r, torch.tensor([0, 1, 0], dtype=torch.int32), torch.tensor([0, 1, 1], dtype=torch.int32))
+    assert a.tolist() == [0, 1, 0] and r.tolist() == [0, 1, 1]
 
 
 def test_streaming_constructor_rules():

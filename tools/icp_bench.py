@@ -11,11 +11,12 @@ sequence is fixed either way; what a sensible guess adds is the accumulation ove
 
     python tools/icp_bench.py [--frames F] [--repeats R] [--npoints N] [--map-size M] [--iters I]
 
-``--per-stream``: instead, the masked refiner (``IcpRefiner(per_stream=True)``) beside the lock-step one, same process,
-alternated repeat by repeat: the time of one ``register`` call (its eager loads of cloud, guess and masks, then the replay)
-with all streams active and, where there is more than one stream, with every second stream idle; and the two eager
-launches ``StreamingOdometry`` adds per call in per-stream mode with ``refine=`` (the restart mask and
-``stream_record_refined``), timed as a pair over a loop that ends in a sync.
+``--per-stream``: instead, the refiner's two views (one engine, one graph) in the same process,
+alternated repeat by repeat: the time of one ``register`` call (its eager loads of cloud, guess and, where given, masks, then
+the replay) through the lock-step view, through the per-stream view (``IcpRefiner(per_stream=True)``) with device masks
+that say all streams are active and, where there is more than one stream, with every second stream idle; and the two
+eager launches ``StreamingOdometry`` adds per call with ``refine=`` (the restart word and ``stream_record_refined``),
+timed as a pair over a loop that ends in a sync.
 """
 import argparse
 import json
@@ -51,7 +52,8 @@ def _per_frame_ms(fn, frames):
 
 
 def _per_stream(a, S, batches, dev):
-    """Lock-step and masked ``register`` on the same frames, alternated; the eager launches of the streaming path."""
+    """``register`` through the lock-step and the per-stream view on the same frames, alternated; the eager launches of
+    the streaming path."""
     from pwclonet_pylidarslam_amd import _lib
     kw = dict(map_size=a.map_size, iters=a.iters, graph=True)
     lock, msk = IcpRefiner(S, a.npoints, **kw), IcpRefiner(S, a.npoints, per_stream=True, **kw)
@@ -79,7 +81,7 @@ def _per_stream(a, S, batches, dev):
             th.append(masked_pass(half))
     out = {"lockstep_register_ms": _stats(tl), "masked_all_active_register_ms": _stats(ta),
            "masked_over_lockstep": _stats(ta)["median"] / _stats(tl)["median"],
-           "launches_per_register": {"lockstep": 3 + 4 * a.iters + 1, "masked": 4 + 4 * a.iters + 1},
+           "launches_per_register": 4 + 4 * a.iters + 1,
            "masked_last_status": msk.status().tolist(), "masked_last_pairs": msk.diagnostics()["pairs"].tolist()}
     if S > 1:
         out["masked_every_second_idle_register_ms"] = _stats(th)
@@ -163,7 +165,7 @@ def main():
         d = ref.diagnostics()
         res["s%d" % S] = {"register_ms": _stats(ti), "stream_step_ms": _stats(ts),
                           "register_over_step": _stats(ti)["median"] / _stats(ts)["median"],
-                          "launches_per_register": 3 + 4 * a.iters + 1,
+                          "launches_per_register": 4 + 4 * a.iters + 1,
                           "last_status": ref.status().tolist(), "last_pairs": d["pairs"].tolist(),
                           "last_iterations": d["iterations"].tolist()}
     print(json.dumps(res))
