@@ -266,6 +266,8 @@ def test_knn_search_on_a_slice_of_a_kept_structure(cuda, n, s, k):
 
 
 def test_fused_pointwise_and_pose_head(cuda):
+    # the pose head's and the warp's edges (N around 64 and 256, +-80 logits, non-unit coarse pose, composition with the
+    # in-launch warp, warps of more than 1024 points, float64 criterion): tests/test_gpu_pose_path.py
     g = torch.Generator().manual_seed(9)
     for chans in ((64, 64, 64), (32, 64, 64), (16, 64, 64), (64, 64, 32), (128, 64)):
         fp, osd = filled(FlowPredictor(in_channel=sum(chans), mlp=[128, 64]), "l4_flow_predictor")
