@@ -47,6 +47,21 @@ int pwclo_last_error(void);
 const char *pwclo_last_error_message(void);
 void pwclo_clear_error(void);
 
+/* Launch record.  The launch layer of the fused stack kernels, the linear jobs and the register / slab samplers
+ * (csrc/common.hpp: launch_grid) notes, per host thread, the kernel it launched last.  pwclo_take_launch() hands that
+ * record out and clears it: 1 with name = the instantiation as rocprofv3 prints it, e.g. "cv_a2_kernel<32, 2, 8, 0,
+ * false>" (the runtime's symbol of the launched kernel, demangled, without "void pwclo::" and the parameter list;
+ * truncated to name_cap - 1 characters) and geometry = {waves per workgroup, grid x, grid y, dynamic LDS bytes};
+ * 0, outputs untouched, when the thread has launched nothing through that layer since the last take, or when a call
+ * has failed since (a failed call leaves no record).  Either pointer may be NULL.  To learn what ONE call launched,
+ * take (and discard) before it and take after it.  Launches that bypass launch_grid are not recorded.
+ * pwclo_set_dry_run(1): until switched off, this thread's launch_grid launches are recorded but NOT made, and the
+ * launch check that follows them does not ask the runtime -- a wrapper's whole dispatch, argument guards included,
+ * runs on a machine without a GPU.  It covers ONLY launches through launch_grid: every other entry point still
+ * launches, so switch it on around calls of the recorded kernels alone. */
+int pwclo_take_launch(char *name, int name_cap, int *geometry);
+void pwclo_set_dry_run(int on);
+
 /* Developer tool: per-workgroup trace of the kernels on the fused forward path.  records: device buffer of
  * `capacity` 32-byte records {u64 t0, t1 (100 MHz constant clock); u32 kernel id, block, blocks in grid, hw id};
  * count: device u32 the kernels bump (zero it first).  records == NULL switches the trace off (the default).

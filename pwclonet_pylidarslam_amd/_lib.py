@@ -4,6 +4,7 @@ There is deliberately no CPU or pure-PyTorch fallback: if the library is missing
 fails, the call raises.  ``load()`` never builds anything; run
 ``python -m pwclonet_pylidarslam_amd.build`` (or ``__graft_entry__.build()``) first.
 """
+import contextlib
 import ctypes
 import gc
 import os
@@ -26,6 +27,8 @@ SIGNATURES = {
     "pwclo_last_error": ([], _i),
     "pwclo_last_error_message": ([], ctypes.c_char_p),
     "pwclo_clear_error": ([], None),
+    "pwclo_take_launch": ([ctypes.c_char_p, _i, ctypes.POINTER(ctypes.c_int)], _i),
+    "pwclo_set_dry_run": ([_i], None),
     "pwclo_fps_large_cloud_launch": ([_i], None),
     "pwclo_fps_large_cloud_exchange": ([_i], None),
     "pwclo_trace_enable": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint], None),
@@ -223,7 +226,8 @@ def synchronize(device=None):
 
 
 # Optional launch profiler (bench.py / tools): an object with .add(name, meta, start_evt, end_evt).
-# Wrappers describe the next launch's algorithmic work with annotate(); both are no-ops otherwise.
+# Wrappers describe the next launch's algorithmic work with annotate(); both are no-ops otherwise.  When the wrapper
+# launched through the library's launch layer, the profiler's meta also carries kernel=<the instantiation launched>.
 profiler = None
 _meta = None
 
@@ -236,41 +240,78 @@ def annotate(**meta):
 
 _fn_cache = {}
 
+# Inside ``launches()``: the list its caller reads, and whether the library is in dry-run mode.
+_recording = None
+_dry = False
+
+
+@contextlib.contextmanager
+def launches(dry=False):
+    """Yields a list to which every ``call()`` inside appends ``(wrapper name, kernel name, waves, (grid x, grid y), lds
+    bytes)`` when the wrapper launched through the library's launch layer (include/pwclo_ops.h: pwclo_take_launch) --
+    what the library DID launch, named as rocprofv3 names it.  ``dry=True`` sets the library's dry-run flag and skips
+    the stream lookups: the wrappers' whole dispatch runs, nothing is launched, and the tensors may live on the CPU
+    (outputs stay uninitialised).  Only for calls of the recorded kernels: other entry points ignore the flag."""
+    global _recording, _dry
+    lib = load()
+    saved = _recording, _dry
+    _recording, _dry = [], bool(dry)
+    lib.pwclo_set_dry_run(int(_dry))
+    try:
+        yield _recording
+    finally:
+        _recording, _dry = saved
+        lib.pwclo_set_dry_run(int(_dry))
+
+
+def _observed(name, device, launch, set_stream, args):
+    """``call()`` under a profiler or inside ``launches()``: the launch between two takes of the launch record."""
+    take = _lib.pwclo_take_launch
+    take(None, 0, None)                                  # whatever an earlier call left behind
+    timed = profiler is not None and not _dry
+    if _dry:
+        launch(*args)
+    else:
+        with torch.cuda.device(device):
+            stream = torch.cuda.current_stream(device)
+            set_stream(stream.cuda_stream)
+            if timed:   # HIP events on the very stream the kernel is launched on
+                s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                s.record(stream)
+            launch(*args)
+            if timed:
+                e.record(stream)
+    buf, geo = ctypes.create_string_buffer(256), (ctypes.c_int * 4)()
+    took = take(buf, len(buf), geo)
+    kernel = buf.value.decode() if took else None
+    if timed:
+        profiler.add(name, dict(_meta or {}, kernel=kernel) if took else _meta, s, e)
+    if took and _recording is not None:
+        _recording.append((name, kernel, geo[0], (geo[1], geo[2]), geo[3]))
+
 
 def call(name, device, *args):
     """Launch `name` on torch's current stream of `device` and check the sticky error.
     (The host cost of this function is the floor of every eager launch: function pointers are looked up once, the device
-    guard is skipped when `device` already is the current one.)"""
+    guard is skipped when `device` already is the current one, and the launch record is taken only under a profiler or
+    inside ``launches()``.)"""
     global _meta
     fn = _fn_cache.get(name)
     if fn is None:
         lib = load()
         fn = _fn_cache[name] = (getattr(lib, name), lib.pwclo_set_stream, lib.pwclo_last_error)
     launch, set_stream, last_error = fn
-    idx = device.index if isinstance(device, torch.device) and device.index is not None else None
-    if idx is None or idx == torch.cuda.current_device():
-        stream = torch.cuda.current_stream()
-        set_stream(stream.cuda_stream)
-        if profiler is None:
-            launch(*args)
-        else:   # HIP events on the very stream the kernel is launched on
-            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            s.record(stream)
-            launch(*args)
-            e.record(stream)
-            profiler.add(name, _meta, s, e)
+    if profiler is not None or _recording is not None:
+        _observed(name, device, launch, set_stream, args)
     else:
-        with torch.cuda.device(device):
-            stream = torch.cuda.current_stream(device)
-            set_stream(stream.cuda_stream)
-            if profiler is None:
+        idx = device.index if isinstance(device, torch.device) and device.index is not None else None
+        if idx is None or idx == torch.cuda.current_device():
+            set_stream(torch.cuda.current_stream().cuda_stream)
+            launch(*args)
+        else:
+            with torch.cuda.device(device):
+                set_stream(torch.cuda.current_stream(device).cuda_stream)
                 launch(*args)
-            else:
-                s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                s.record(stream)
-                launch(*args)
-                e.record(stream)
-                profiler.add(name, _meta, s, e)
     _meta = None
     if last_error() != 0:
         check(name)

@@ -14,7 +14,12 @@ constexpr int WAVE = 64;
 // ---- per-thread library state (stream + sticky error), defined in state.hip ----------------
 hipStream_t current_stream();
 void set_error(int code, const char *fmt, ...);
-bool check_launch(const char *what);  // hipGetLastError() -> sticky error; true when OK
+bool check_launch(const char *what);  // hipGetLastError() -> sticky error; true when OK (always, in a dry run)
+// What launch_grid launched last on this thread; kernel == nullptr: nothing since pwclo_take_launch() or a failure.
+struct LaunchRecord { const void *kernel; int waves; unsigned grid_x, grid_y; int lds_bytes; };
+// Stores the record (plain stores: the kernel's name is formed only when the record is taken) and says whether the
+// launch goes ahead: false in a dry run (pwclo_set_dry_run()).
+bool record_launch(const LaunchRecord &r);
 // batchnorm.hip: save_mean / save_invstd / running statistics of c channels from fp64 partial sums
 // partial[(ch * nsplit + s) * 2 + {sum, sum of squares}] over M elements per channel (conv1x1.hip's statistics epilogue)
 // momentum_dev (nullable): the momentum read from device memory instead of the argument
@@ -89,9 +94,10 @@ static void raise_lds_limit(int bytes) {
   attr_set = true;
 }
 
-// Launches Kern (workgroups of W waves) with lds_bytes of dynamic LDS on the library's stream.
+// Launches Kern (workgroups of W waves) with lds_bytes of dynamic LDS on the library's stream, and records the launch.
 template <auto Kern, int W, typename... Args>
 static void launch_grid(dim3 grid, int lds_bytes, const Args &...a) {
+  if (!record_launch({(const void *)Kern, W, grid.x, grid.y, lds_bytes})) return;
   if (lds_bytes > 64 * 1024) raise_lds_limit<Kern>(160 * 1024);   // the largest any configuration can ask for
   hipLaunchKernelGGL(Kern, grid, dim3(W * 64), lds_bytes, current_stream(), a...);
 }

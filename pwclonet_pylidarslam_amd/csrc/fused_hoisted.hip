@@ -705,7 +705,7 @@ extern "C" void linear_jobs_kernel_wrapper(int njobs, const int *npts, const int
   int gx = ceil_div(max_tiles, LIN_WAVES);
   const int cap = max(1, 512 / njobs);
   if (gx > cap) gx = cap;
-  hipLaunchKernelGGL(linear_jobs_kernel, dim3(gx, njobs), dim3(LIN_WAVES * 64), max_lds, current_stream(), a);
+  launch_grid<linear_jobs_kernel, LIN_WAVES>(dim3(gx, njobs), max_lds, a);
   check_launch("linear_jobs");
 }
 

@@ -1,4 +1,6 @@
-// Per-host-thread library state: launch stream and sticky error (see include/pwclo_ops.h, section 0).
+// Per-host-thread library state: launch stream, sticky error, launch record and dry-run flag (see include/pwclo_ops.h,
+// section 0).
+#include <cxxabi.h>
 #include <stdarg.h>
 #include <string.h>
 
@@ -9,8 +11,15 @@ namespace pwclo {
 static thread_local hipStream_t t_stream = nullptr;
 static thread_local int t_err = 0;
 static thread_local char t_msg[512] = "";
+static thread_local LaunchRecord t_launch = {};
+static thread_local bool t_dry = false;
 
 hipStream_t current_stream() { return t_stream; }
+
+bool record_launch(const LaunchRecord &r) {
+  t_launch = r;
+  return !t_dry;
+}
 
 void set_error(int code, const char *fmt, ...) {
   va_list ap;
@@ -18,6 +27,7 @@ void set_error(int code, const char *fmt, ...) {
   char buf[448];
   vsnprintf(buf, sizeof(buf), fmt, ap);
   va_end(ap);
+  t_launch.kernel = nullptr;  // a call that failed has launched nothing: no earlier call's record stands in for it
   if (t_err == 0) {  // sticky: keep the first failure
     t_err = code;
     snprintf(t_msg, sizeof(t_msg), "%s", buf);
@@ -68,6 +78,7 @@ static void poll_device_error() {
 }
 
 bool check_launch(const char *what) {
+  if (t_dry) return true;
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     set_error((int)e, "HIP kernel launch failed in %s: %s", what, hipGetErrorString(e));
@@ -101,6 +112,28 @@ void pwclo_trace_enable(void *records, void *count, unsigned capacity) {
   pwclo::trace_set_knn(b);
   pwclo::trace_set_sampling(b);
   pwclo::trace_set_warp(b);
+}
+void pwclo_set_dry_run(int on) { pwclo::t_dry = on != 0; }
+int pwclo_take_launch(char *name, int name_cap, int *geometry) {
+  const pwclo::LaunchRecord r = pwclo::t_launch;
+  pwclo::t_launch.kernel = nullptr;
+  if (r.kernel == nullptr) return 0;
+  if (geometry != nullptr) {
+    geometry[0] = r.waves, geometry[1] = (int)r.grid_x, geometry[2] = (int)r.grid_y, geometry[3] = r.lds_bytes;
+  }
+  if (name != nullptr && name_cap > 0) {
+    // the runtime's symbol of the host-side kernel handle (a table lookup: no device needed), demangled
+    const char *sym = hipKernelNameRefByPtr(r.kernel, pwclo::t_stream);
+    char *full = sym ? abi::__cxa_demangle(sym, nullptr, nullptr, nullptr) : nullptr;
+    const char *s = full ? full : (sym ? sym : "?");
+    if (strncmp(s, "void ", 5) == 0) s += 5;
+    if (strncmp(s, "pwclo::", 7) == 0) s += 7;
+    int len = 0, depth = 0;                       // up to the parameter list: the first '(' outside <...>
+    for (; s[len] != 0 && !(s[len] == '(' && depth == 0); ++len) depth += (s[len] == '<') - (s[len] == '>');
+    snprintf(name, (size_t)name_cap, "%.*s", len, s);
+    free(full);
+  }
+  return 1;
 }
 void pwclo_clear_error(void) {
   pwclo::t_err = 0;

@@ -148,56 +148,6 @@ def pack_layer(w, b, phys_map, nbo=None, wfmt=WFMT_F32, kmajor_out=False):
     return out
 
 
-# ---- kernel names for _lib.annotate(kernel=...) ----------------------------------------------------------
-# bench.py keys the committed PMC files (profiles/pmc_*.json) by the kernel name as rocprofv3 prints it, so Python has
-# to name the kernel a wrapper is about to pick.  Each function mirrors the dispatch of ONE wrapper of csrc/ (named
-# beside it) for the cases the fused forward reaches; a change to a wrapper's `if` chain is a change here.
-
-def _kname(name, wfmt, split_capable=True):
-    """The stack kernels carry a trailing `int FMT` template argument."""
-    return name[:-1] + (", %d>" % (wfmt if split_capable else 0))
-
-
-def _switch(name):                                           # csrc/launch.hpp: fl_wide() / coarse_w4(), default on
-    return os.environ.get(name, "1") != "0"
-
-
-def _a2_kernel_name(kp, B, S, wfmt):                         # fused_layers.hip: cv_fused_a2_kernel_wrapper
-    if kp == 6 and wfmt == WFMT_F32 and os.environ.get("PWCLO_LANE6", "1") != "0" and B * ((S + 15) // 16) > 1024:
-        return "cv_a2_lane6_kernel<8>"
-    if kp == 6:
-        w4 = B * ((S + 7) // 8) <= 2048 and (wfmt != WFMT_F32 or _switch("PWCLO_COARSE_W4"))
-        return _kname("cv_a2_dense6_kernel<%d>" % (4 if w4 else 8), wfmt)
-    if kp == 32:
-        return _kname("cv_a2_kernel<32, 2, 8>", wfmt)
-    return _kname("cv_a2_kernel<%d, %s>" % (kp, "1, 16" if _switch("PWCLO_FL_WIDE") else "2, 8"), wfmt, split_capable=False)
-
-
-def _upconv_h_kernel_name(B, S, wfmt):                       # fused_hoisted.hip: upconv_fused_h_kernel_wrapper
-    if wfmt == WFMT_F32 and os.environ.get("PWCLO_LANE_UP", "1") != "0" and B * ((S + 15) // 16) > 2048:
-        return "upconv_lane_kernel<16>"
-    return _kname("upconv_h_kernel<8, 1, 16>", wfmt)
-
-
-def _upconv_post_kernel_name(njobs, B, S, c2):               # fused_hoisted.hip: upconv_post_fused_h_kernel_wrapper
-    tiles = njobs * B * ((S + 15) // 16)
-    return "upconv_lane_post_kernel<%d, %d>" % (c2 // 16, 16 if tiles >= 4096 else 8 if tiles >= 2048 else 4)
-
-
-def _a1_h_kernel_name(kp, wfmt):                             # fused_hoisted.hip: cv_fused_a1_h_kernel_wrapper
-    return _kname("cv_a1_h_kernel<%d, 1, 16>" % kp, wfmt)
-
-
-def _a_lane6_kernel_name(B, S, fold_v2):                     # fused_hoisted.hip: cv_fused_a_lane6_kernel_wrapper
-    return "cv_a_lane6_kernel<%d, %s>" % (4 if fold_v2 and B * ((S + 15) // 16) <= 1024 else 8,
-                                          "true" if fold_v2 else "false")
-
-
-def _b_h_kernel_name(B, S, wfmt):                            # fused_hoisted.hip: cv_fused_b_h_kernel_wrapper
-    small = _switch("PWCLO_COARSE_W4") and B * ((S * 4 + 15) // 16) <= int(os.environ.get("PWCLO_COARSE_W4_TILES", "2047"))
-    return _kname("cv_b_h_kernel<4, 1, %d>" % (4 if small else 16), wfmt)
-
-
 def chain_map(cout_prev, nb):
     """Physical->original map of a layer fed by the previous layer's (padded) output."""
     return [c if c < cout_prev else -1 for c in range(16 * nb)]
@@ -504,8 +454,7 @@ class FusedCostVolume:
         _lib.call("cv_fused_a1_kernel_wrapper", dev, B, N, S, kq, self.c, _p(xyz1), _p(feat1), _p(xyz2),
                   _p(feat2), _p(idx_q), _p(self.w_a1), _p(pix), kp)
         first = torch.empty((B, S, 64), dtype=torch.float32, device=dev)
-        _lib.annotate(family="mlp", kernel=_a2_kernel_name(kp, B, S, self.wfmt_a2),
-                      flops=2.0 * B * S * kq * self.macs_a2,
+        _lib.annotate(family="mlp", flops=2.0 * B * S * kq * self.macs_a2,
                       bytes=4.0 * B * (S * kq * (1 + 3 + 64) + S * (3 + 64)))
         _lib.call("cv_fused_a2_kernel_wrapper", dev, B, N, S, kq, _p(xyz1), _p(xyz2), _p(idx_q),
                   _p(self.w_a2), _p(pix), _p(first), kp, self.wfmt_a2, self.w_a2.numel())
@@ -709,8 +658,7 @@ class FusedUpconvHoisted:
         B, S, _ = xyz2.shape
         N, K = xyz1.shape[1], idx.shape[2]
         pooled = torch.empty((B, S, 64), dtype=torch.float32, device=xyz2.device)
-        _lib.annotate(family="mlp", kernel=_upconv_h_kernel_name(B, S, self.wfmt),
-                      flops=2.0 * B * S * K * (self.macs - 64 * 128),
+        _lib.annotate(family="mlp", flops=2.0 * B * S * K * (self.macs - 64 * 128),
                       bytes=4.0 * B * (S * K * (1 + 3 + 128) + 3 * S + 64 * S))
         _lib.call("upconv_fused_h_kernel_wrapper", xyz2.device, B, N, S, K, _p(xyz2), _p(xyz1), _p(pre),
                   _p(idx), _p(self.packed), _p(pooled), self.wfmt, self.packed.numel())
@@ -734,8 +682,7 @@ def run_upconv_post(ups, xyz2, xyz1, feat2, pres, idx):
     c2 = feat2.shape[2]
     outs = [torch.empty((B, S, 64), dtype=torch.float32, device=xyz2.device) for _ in ups]
     pa = lambda v: (ctypes.c_void_p * n)(*v)
-    _lib.annotate(family="mlp", kernel=_upconv_post_kernel_name(n, B, S, c2),
-                  flops=sum(2.0 * B * S * (K * (u.macs - 64 * 128) + u.post.macs) for u in ups),
+    _lib.annotate(family="mlp", flops=sum(2.0 * B * S * (K * (u.macs - 64 * 128) + u.post.macs) for u in ups),
                   bytes=4.0 * n * B * (S * K * (1 + 3 + 128) + 3 * S + S * c2 + 64 * S))
     _lib.call("upconv_post_fused_h_kernel_wrapper", xyz2.device, n, B, N, S, K, c2, _p(xyz2), _p(xyz1), _p(idx), _p(feat2),
               pa([_p(t) for t in pres]), pa([_p(u.packed) for u in ups]), pa([_p(u.post.packed) for u in ups]),
@@ -799,14 +746,12 @@ class FusedCostVolumeHoisted:
         if merged:
             return self._merged(xyz1, xyz2, u, v, u2, idx_q, idx, taps, tap)
         pix = torch.empty((B, S * kp, 64), dtype=torch.bfloat16 if self.wfmt == WFMT_BF16 else torch.float32, device=dev)
-        _lib.annotate(family="mlp", kernel=_a1_h_kernel_name(kp, self.wfmt),
-                      flops=2.0 * B * S * kq * (self.macs_a1 - 2 * c * 128),
+        _lib.annotate(family="mlp", flops=2.0 * B * S * kq * (self.macs_a1 - 2 * c * 128),
                       bytes=4.0 * B * (S * kq * (1 + 3 + 128 + 64) + S * (3 + 128)))
         _lib.call("cv_fused_a1_h_kernel_wrapper", dev, B, N, S, kq, _p(xyz1), _p(u), _p(xyz2), _p(v), _p(idx_q),
                   _p(self.w_a1), _p(pix), kp, self.wfmt, self.w_a1.numel())
         first = torch.empty((B, S, 64), dtype=torch.float32, device=dev)
-        _lib.annotate(family="mlp", kernel=_a2_kernel_name(kp, B, S, self.wfmt_a2),
-                      flops=2.0 * B * S * kq * self.macs_a2,
+        _lib.annotate(family="mlp", flops=2.0 * B * S * kq * self.macs_a2,
                       bytes=4.0 * B * (S * kq * (1 + 3 + 64) + S * (3 + 64)))
         _lib.call("cv_fused_a2_kernel_wrapper", dev, B, N, S, kq, _p(xyz1), _p(xyz2), _p(idx_q),
                   _p(self.w_a2), _p(pix), _p(first), kp, self.wfmt_a2, self.w_a2.numel())
@@ -825,7 +770,7 @@ class FusedCostVolumeHoisted:
         fold_v2 = os.environ.get("PWCLO_CV_V2", "1") != "0" and not self.job_v2.out_bf16
         first = torch.empty((B, S, 64), dtype=torch.float32, device=dev)
         v2 = torch.empty((B, S, 128), dtype=torch.float32, device=dev) if fold_v2 else None
-        _lib.annotate(family="mlp", kernel=_a_lane6_kernel_name(B, S, fold_v2),
+        _lib.annotate(family="mlp",
                       flops=2.0 * B * S * (6 * (self.macs_a1 - 2 * self.c * 128 + self.macs_a2) + (64 * 128 if fold_v2 else 0)),
                       bytes=4.0 * B * (S * 6 * (1 + 3 + 128) + S * (3 + 3 * 128 + 64 + (128 if fold_v2 else 0))))
         _lib.call("cv_fused_a_lane6_kernel_wrapper", dev, B, N, S, _p(xyz1), _p(u), _p(xyz2), _p(v), _p(idx_q),
@@ -843,8 +788,7 @@ class FusedCostVolumeHoisted:
         B, S, _ = xyz1.shape
         dev, k, c = xyz1.device, self.nsample, self.c
         out = torch.empty((B, S, 64), dtype=torch.float32, device=dev)
-        _lib.annotate(family="mlp", kernel=_b_h_kernel_name(B, S, self.wfmt),
-                      flops=2.0 * B * S * k * (self.macs_b - (c + 64) * 128),
+        _lib.annotate(family="mlp", flops=2.0 * B * S * k * (self.macs_b - (c + 64) * 128),
                       bytes=4.0 * B * (S * k * (1 + 3 + 128 + 64) + S * (3 + 128 + 64)))
         _lib.call("cv_fused_b_h_kernel_wrapper", dev, B, S, k, _p(xyz1), _p(u2), _p(v2), _p(first), _p(idx),
                   _p(self.w_b), _p(out), self.wfmt, self.w_b.numel())

@@ -9,7 +9,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import stack_reference as SR                                                     # noqa: E402
-import test_gpu_stack_variants as V                                              # noqa: E402
+import stack_cases as V                                                          # noqa: E402
 from oracle import model as M                                                    # noqa: E402
 from oracle import ops as O                                                      # noqa: E402
 
