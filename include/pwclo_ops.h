@@ -988,6 +988,53 @@ void icp_map_push_masked_kernel_wrapper /**/ (int S, int M, int n, const double 
 void stream_record_refined_kernel_wrapper(int S, int capacity, const int *active, const int *valid, const int *count,
                                           const double *T, double *ref_rel, double *ref_abs);
 
+/* ---- 7. projective frame-to-model registration on spherical vertex maps ------------------------
+ * The reference's ICPFrameToModel over a ProjectiveLocalMap (slam/odometry/local_map.py:84-240, slam/common/projection.py:
+ * 20-82, 340-436, slam/common/geometry.py:248-303, 405-447).  All pointers DEVICE memory; vertex and normal maps
+ * (.., H, W, 3) fp32 point-major, an empty pixel is the zero vector; poses (.., 4, 4) fp64 row-major; fovs in degrees.
+ * The pixel of a point p, every operation in fp32: r = |p|, col = 0.5 (-atan2(y, x) / pi + 1) W, row = (1 - (asin(z / r) +
+ * |down_fov|) / (|up_fov| + |down_fov|)) H, both rounded half to even; p has a pixel when r > 0 (and finite), 0 <= row <=
+ * H - 1 and 0 <= col <= W - 1.  A z-buffer keeps the smallest r per pixel, the lowest index among equal r: one 64-bit
+ * atomicMin of (bits of r << 32 | index) per point on a key image preset to all ones, which is the only atomic here and
+ * gives the same bits whatever the order of arrival.  A map holds M slots per stream, each the vertex and normal map of a
+ * frame in that frame's own coordinates; A (S,M,4,4) maps the newest frame of the map into slot m, live (S,M) ints, cursor
+ * (S) ints.  One iteration = proj_accumulate, then section 6's solver on its rows. */
+
+/* Bytes of the key image that proj_vertex_map needs (8 per pixel and stream); 0 for arguments out of range. */
+long long proj_vertex_map_workspace_bytes(int S, int H, int W);
+/* points (S,R,C) fp32, C = 3 or 4 (xyz first); stream s offers the rows [0, min(lengths[s], R)) (lengths NULL: all R) with
+ * keep[s,i] != 0 (keep (S,R) ints or NULL: all).  vmap (S,H,W,3) = the winner's xyz, rows (S,H,W) ints = its row, -1 for an
+ * empty pixel.  A memset of the workspace and two launches. */
+void proj_vertex_map_kernel_wrapper(int S, int R, int C, int H, int W, double up_fov, double down_fov, const float *points,
+                                    const int *lengths, const int *keep, void *workspace, float *vmap, int *rows);
+/* compute_normal_map: over the k x k window (zero padding) m = sum p and C = sum p p^T in fp64, n = C^-1 m by the adjugate
+ * over the determinant, normalised, one rounding; zero where |fp32(det C)| <= 1e-6, |n| = 0 or the centre pixel is empty.
+ * n points away from the sensor.  kernel_size 3 or 5; vmap, nmap (B,H,W,3). */
+void proj_normal_map_kernel_wrapper(int B, int H, int W, int kernel_size, const float *vmap, float *nmap);
+/* Bytes of the key images that proj_model_build needs (8 per pixel, slot and stream); 0 for arguments out of range. */
+long long proj_model_build_workspace_bytes(int S, int M, int H, int W);
+/* Per (stream, live slot): every non-empty pixel of map_v[s,m] is moved into the newest frame by the rigid inverse of
+ * A[s,m] (fp64, one rounding), projected and z-buffered into model_v[s,m]; model_n gets the winner's normal rotated the
+ * same way; src (S,M,H,W) ints = the slot's pixel index that won, -1 for an empty pixel.  A slot that is not live gives an
+ * empty image.  map_v, map_n, model_v, model_n (S,M,H,W,3).  A memset of the workspace and two launches. */
+void proj_model_build_kernel_wrapper(int S, int M, int H, int W, double up_fov, double down_fov, const float *map_v,
+                                     const float *map_n, const double *A, const int *live, void *workspace, float *model_v,
+                                     float *model_n, int *src);
+/* One thread per pixel of the new frame's own vertex map vmap (S,H,W,3): q = fp32(T[s] p); among the M model images the
+ * non-empty candidate at q's pixel with the smallest fp32 |q - y| (tie: lower slot).  No pair when p is empty, q has no
+ * pixel, no candidate is there, the distance exceeds max_dist or the winner's normal is zero.  Then section 6's row: r =
+ * n . (q - y), J = [T p x n, n], the Huber weight, the same 30 sums in the same order.  partial (S, groups(H * W), 32) fp64
+ * with groups = icp_accumulate_groups.  slot / pixel (S,H,W) ints or NULL: the chosen slot (-1: no pair) and q's pixel
+ * index (-1: none). */
+void proj_accumulate_kernel_wrapper(int S, int M, int H, int W, double up_fov, double down_fov, const float *vmap,
+                                    const float *model_v, const float *model_n, const double *T, double sigma,
+                                    float max_dist, double *partial, int *slot, int *pixel);
+/* The handover: vmap / nmap (S,H,W,3) go into slot cursor[s] of map_v / map_n; every other live slot gets A <- A T; the
+ * new slot gets A = I, live = 1; cursor <- (cursor + 1) mod M.  Two launches (the copy reads the cursor, the bookkeeping
+ * moves it).  M <= 64. */
+void proj_map_push_kernel_wrapper(int S, int M, int H, int W, const double *T, const float *vmap, const float *nmap,
+                                  float *map_v, float *map_n, double *A, int *live, int *cursor);
+
 #ifdef __cplusplus
 }
 #endif

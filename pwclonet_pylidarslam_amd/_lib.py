@@ -174,6 +174,14 @@ SIGNATURES = {
     "icp_solve_masked_kernel_wrapper": ([_i, _i, _i, _F, ctypes.c_double, ctypes.c_double, _i] + [_F] * 8, None),
     "icp_map_push_masked_kernel_wrapper": ([_i, _i, _i] + [_F] * 12, None),
     "stream_record_refined_kernel_wrapper": ([_i, _i] + [_F] * 6, None),
+    "proj_vertex_map_workspace_bytes": ([_i, _i, _i], ctypes.c_longlong),
+    "proj_vertex_map_kernel_wrapper": ([_i] * 5 + [ctypes.c_double] * 2 + [_F] * 6, None),
+    "proj_normal_map_kernel_wrapper": ([_i, _i, _i, _i, _F, _F], None),
+    "proj_model_build_workspace_bytes": ([_i, _i, _i, _i], ctypes.c_longlong),
+    "proj_model_build_kernel_wrapper": ([_i] * 4 + [ctypes.c_double] * 2 + [_F] * 8, None),
+    "proj_accumulate_kernel_wrapper": ([_i] * 4 + [ctypes.c_double] * 2 + [_F] * 4 + [ctypes.c_double, ctypes.c_float]
+                                       + [_F] * 3, None),
+    "proj_map_push_kernel_wrapper": ([_i] * 4 + [_F] * 8, None),
 }
 
 _lib = None

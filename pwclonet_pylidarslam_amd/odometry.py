@@ -62,7 +62,10 @@ class StreamingOdometry:
     Per-stream mode: a stream that primes (restart, or no previous frame) and its next sweep get the identity, an idle
     stream keeps its motion, ``reset()`` / ``reset(streams=...)`` return the streams to the identity.
 
-    Refinement (``refine=dict(map_size=4, iters=10, ...)``, ``registration.IcpRefiner``'s keywords):
+    Refinement (``refine=dict(map_size=4, iters=10, ...)``, ``registration.IcpRefiner``'s keywords; DESIGN.md section 21;
+    ``refine=dict(kind="projective", height=64, width=1800, up_fov=3.0, down_fov=-24.8, ...)``: raw mode and lock step only,
+    ``projective.ProjectiveIcpRefiner``'s keywords, the dense search-free registration of section 22 on the rows the front
+    end keeps; ``kind`` defaults to ``"knn"``):
     after each step's own graph, which is unchanged, the cloud the step sampled from is registered by point-to-plane ICP
     against a local map of the stream's last frames, with the level-1 row's transform as the initial guess (one more
     captured graph).  ``refined_relative_poses()`` / ``refined_trajectory()`` sit beside ``relative_poses()`` /
@@ -116,7 +119,22 @@ class StreamingOdometry:
         self._static = {}           # eager mode: input shape -> static frames (graph mode: in _graphs)
         self._active = self._restart = self._have_prev = self._counts = self._valid = None    # (S,) int32, device
         self._front = None          # raw mode: preprocess.SweepFrontEnd (persistent sweep, lengths, tr, sampler buffers)
-        self._refine_cfg = None if refine is None else dict(refine)     # registration.IcpRefiner's keywords
+        self._refine_cfg = None if refine is None else dict(refine)     # the refiner's keywords
+        self._refine_kind = "knn" if refine is None else self._refine_cfg.pop("kind", "knn")
+        if self._refine_kind not in ("knn", "projective"):
+            raise ValueError("StreamingOdometry: refine=dict(kind=%r): \"knn\" (registration.IcpRefiner, the default) or "
+                             "\"projective\" (projective.ProjectiveIcpRefiner)" % (self._refine_kind,))
+        if self._refine_kind == "projective":
+            if self.per_stream or self._refine_cfg.get("per_stream", False):
+                raise ValueError("StreamingOdometry: refine=dict(kind=\"projective\") is lock step only: per-stream masks, "
+                                 "idle streams and restarts inside the graph are out of scope (per_stream=True registers "
+                                 "with kind=\"knn\")")
+            if sweeps is None:
+                raise ValueError("StreamingOdometry: refine=dict(kind=\"projective\") registers the rows the sweep front end "
+                                 "keeps and needs raw mode: sweeps=dict(...)")
+            if dict(sweeps).get("voxel_size") is not None:
+                raise ValueError("StreamingOdometry: refine=dict(kind=\"projective\") registers the rows before the grid, "
+                                 "which the front end does not keep when voxel_size is set: leave voxel_size out")
         self._refiner = self._ref_rel = self._ref_abs = self._ref_restart = None
         self._tapped = None         # refine: the frame batch the last step's graph (or eager step) sampled from
         if refine is not None and self.per_stream != bool(self._refine_cfg.get("per_stream", False)):
@@ -388,6 +406,8 @@ class StreamingOdometry:
         difference."""
         if self._refine_cfg is None:
             return
+        if self._refine_kind == "projective":
+            return self._refine_projective(pose)
         from . import registration
         cloud = self._tapped[:, :self.num_points, :3].contiguous()
         if self._refiner is None:
@@ -399,6 +419,21 @@ class StreamingOdometry:
         torch.sub(self._active, self._valid, out=self._ref_restart)
         T = self._refiner.register_adopted(cloud, pose[:, 0, :], all_active=not self.per_stream)
         _lib.call("stream_record_refined_kernel_wrapper", cloud.device, self.streams, self.max_frames, _p(self._active),
+                  _p(self._valid), _p(self._counts), _p(T), _p(self._ref_rel), _p(self._ref_abs))
+
+    def _refine_projective(self, pose):
+        """``kind="projective"`` (lock step): the rows the front end kept -- after the filter and the
+        de-skew, packed, before the sampler -- are registered as spherical vertex maps, the level-1 row's transform the
+        guess; the refined pose is recorded by the launch that serves ``kind="knn"``."""
+        from . import projective
+        front = self._front.bufs
+        if self._refiner is None:
+            self._refiner = projective.ProjectiveIcpRefiner(self.streams, self._front.width, graph=self.graph,
+                                                            **self._refine_cfg)
+            self._ref_rel = torch.zeros((self.max_frames, self.streams, 4, 4), dtype=torch.float64, device=pose.device)
+            self._ref_abs = torch.zeros_like(self._ref_rel)
+        T = self._refiner.register(front["packed"], front["counts"], pose[:, 0, :])
+        _lib.call("stream_record_refined_kernel_wrapper", pose.device, self.streams, self.max_frames, _p(self._active),
                   _p(self._valid), _p(self._counts), _p(T), _p(self._ref_rel), _p(self._ref_abs))
 
     def _view(self, buf, stream=None):
