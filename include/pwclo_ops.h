@@ -89,6 +89,43 @@ void pwclo_fps_large_cloud_exchange(int xcd_local);
  * host calls pwclo_last_error() after synchronising the stream.  The outputs of that call are invalid. */
 #define PWCLO_ECOOP_TIMEOUT 10002
 
+/* ---- 0b. the pipelines' stream set (csrc/pipeline.hip) ------------------------------------ */
+
+/* A set of n HIP streams for a pipeline that keeps several captured forwards in flight (graphed.PipelinedForward), plus
+ * one completion event per slot.  The runtime serialises streams that share a hardware queue, and which queue a stream gets
+ * follows from the order in which the process's streams are created / first used.  pwclo_stream_set_create makes all n
+ * streams back to back (hipStreamNonBlocking, one priority), then one empty launch on each, in order, and waits for those:
+ * the set's streams are bound to consecutive hardware queues with no other stream of the process in between.  No CU mask,
+ * no change of the queue count.
+ *
+ * Handles are positive ids that are never reused.  Every function returns 0 on success, PWCLO_EINVAL for an argument it
+ * refuses (n outside [1, PWCLO_STREAM_SET_MAX], a stream or slot index out of range, a handle that was never issued or is
+ * destroyed, a NULL result pointer, more than PWCLO_STREAM_SET_LIVE_MAX live sets) -- decided before any HIP call, so a
+ * refusal never touches the device -- or the hipError_t of the HIP call that failed.  The per-thread sticky status of
+ * pwclo_last_error() is not used here.  Streams travel as void* (hipStream_t), like pwclo_set_stream's.  None of these
+ * calls may be made while the calling thread captures a graph, except _stream and _size. */
+#define PWCLO_STREAM_SET_MAX 8        /* streams per set, and completion slots per set */
+#define PWCLO_STREAM_SET_LIVE_MAX 64  /* sets alive at once in a process */
+int pwclo_stream_set_create(int n, long long *handle);
+/* n of the set; -PWCLO_EINVAL for a handle that is not live. */
+int pwclo_stream_set_size(long long handle);
+int pwclo_stream_set_stream(long long handle, int i, void **hip_stream);
+/* Work queued on stream i after this call starts after everything queued on other_stream before it (NULL = the null
+ * stream; stream i itself: nothing to do). */
+int pwclo_stream_set_wait_stream(long long handle, int i, void *other_stream);
+/* Slot completion, slot in [0, PWCLO_STREAM_SET_MAX): _record marks the current end of stream i as the completion of
+ * `slot`; _query returns 1 when that point has been reached (or the slot was never recorded), 0 when not yet, a negative
+ * error code otherwise; _wait_slot makes waiting_stream (any stream) wait for it; _synchronize_slot makes the host wait. */
+int pwclo_stream_set_record(long long handle, int slot, int i);
+int pwclo_stream_set_query(long long handle, int slot);
+int pwclo_stream_set_wait_slot(long long handle, int slot, void *waiting_stream);
+int pwclo_stream_set_synchronize_slot(long long handle, int slot);
+/* The host waits for all n streams. */
+int pwclo_stream_set_synchronize(long long handle);
+/* Waits for the DEVICE (work on the set's streams, and work elsewhere that waits for the set's events), then destroys the
+ * events and streams.  The handle is refused from then on. */
+int pwclo_stream_set_destroy(long long handle);
+
 /* ---- 1. the nine reference launchers ------------------------------------------------------ */
 
 /* sampling.cpp:4-6 / sampling_gpu.cu:22-30.  out[b,c,j] = points[b,c,idx[b,j]].

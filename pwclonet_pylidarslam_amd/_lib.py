@@ -32,6 +32,16 @@ SIGNATURES = {
     "pwclo_fps_large_cloud_launch": ([_i], None),
     "pwclo_fps_large_cloud_exchange": ([_i], None),
     "pwclo_trace_enable": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint], None),
+    "pwclo_stream_set_create": ([_i, ctypes.POINTER(ctypes.c_longlong)], _i),
+    "pwclo_stream_set_size": ([ctypes.c_longlong], _i),
+    "pwclo_stream_set_stream": ([ctypes.c_longlong, _i, ctypes.POINTER(ctypes.c_void_p)], _i),
+    "pwclo_stream_set_wait_stream": ([ctypes.c_longlong, _i, ctypes.c_void_p], _i),
+    "pwclo_stream_set_record": ([ctypes.c_longlong, _i, _i], _i),
+    "pwclo_stream_set_query": ([ctypes.c_longlong, _i], _i),
+    "pwclo_stream_set_wait_slot": ([ctypes.c_longlong, _i, ctypes.c_void_p], _i),
+    "pwclo_stream_set_synchronize_slot": ([ctypes.c_longlong, _i], _i),
+    "pwclo_stream_set_synchronize": ([ctypes.c_longlong], _i),
+    "pwclo_stream_set_destroy": ([ctypes.c_longlong], _i),
     "gather_points_kernel_wrapper": ([_i, _i, _i, _i, _F, _F, _F], None),
     "gather_points_grad_kernel_wrapper": ([_i, _i, _i, _i, _F, _F, _F], None),
     "furthest_point_sampling_kernel_wrapper": ([_i, _i, _i, _F, _F, _F], None),

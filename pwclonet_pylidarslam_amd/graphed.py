@@ -99,7 +99,8 @@ class GraphedSequence(GraphedForward):
 
 
 class PipelinedForward:
-    """Keeps `depth` forwards in flight: one captured graph + stream per slot, used round-robin.
+    """Keeps `depth` forwards in flight: one captured graph per slot, used round-robin, on the streams of the native
+    stream set (one per slot where the process has hardware queues to spare, see ``_submit``).
 
     Within one forward the furthest-point-sampling chain is a long dependent sequence that
     occupies one CU per cloud (64 of 256 CUs at batch 32) while the rest of the chip waits; with
@@ -117,29 +118,72 @@ class PipelinedForward:
         # hardware queue round-robin, so a second set of streams in one process can collide with itself
         self.streams = list(streams) if streams is not None else None
         assert self.streams is None or len(self.streams) == depth
+        # without `streams`: the native library's stream set (pipe_streams.StreamSet: made and first used back to back), or
+        # torch's pool streams with PWCLO_PIPE_STREAMS=torch; either is made at the first call, when the device is known
+        self._set = None
         self.events = [None] * depth
+        self._where = [None] * depth      # the stream each slot's last replay went to
+        self._lanes = None                # how many of the streams the calls rotate over (pipe_streams.lanes)
         self._next = 0
+        self._calls = 0
 
     def _make_slot(self, net, branch):
         return GraphedForward(net, branch=branch)
 
+    def _make_streams(self, dev):
+        from . import pipe_streams
+        if pipe_streams.mode() == "torch":
+            return [torch.cuda.Stream(device=dev) for _ in self.slots]
+        n = min(len(self.slots), pipe_streams.MAX_STREAMS)   # deeper pipelines share streams round-robin
+        self._set = pipe_streams.StreamSet(n, dev)
+        wrapped = [self._set.wrap(i) for i in range(n)]
+        return [wrapped[i % n] for i in range(len(self.slots))]
+
     def _submit(self, *inputs, after=None):
-        """Replay the next slot on its stream; ``after(out)``, if given, is queued on that stream behind the replay."""
+        """Replay the next slot; ``after(out)``, if given, is queued behind the replay on the same stream.
+
+        Call c uses slot c % depth and stream c % lanes.  With lanes == depth that is one stream per slot.  With fewer
+        lanes (native streams in a process with no more hardware queues than slots: ``pipe_streams.lanes``) the slots
+        rotate over the first `lanes` streams -- as many replays in flight as run side by side, instead of `depth` of which
+        two share a hardware queue -- and a slot's replay first waits for the slot's previous one, which ran on
+        another stream."""
         dev = inputs[0].device
         if self.streams is None:
-            self.streams = [torch.cuda.Stream(device=dev) for _ in self.slots]
+            self.streams = self._make_streams(dev)
+        if self._lanes is None:
+            from . import pipe_streams
+            native = all(hasattr(s, "_pwclo_index") for s in self.streams)
+            self._lanes = pipe_streams.lanes(len(self.slots)) if native else len(self.slots)
         i = self._next
         self._next = (i + 1) % len(self.slots)
-        st = self.streams[i]
-        st.wait_stream(torch.cuda.current_stream(dev))   # inputs produced on the caller's stream
+        st, own = self.streams[self._calls % self._lanes], self._set
+        self._calls += 1
+        # inputs produced on the caller's stream
+        if own is not None:
+            own.wait_stream(st._pwclo_index, torch.cuda.current_stream(dev))
+        else:
+            st.wait_stream(torch.cuda.current_stream(dev))
+        if self._where[i] is not None and self._where[i] is not st:
+            self._stream_wait_slot(st, i)
         with torch.cuda.stream(st):
             out = self.slots[i](*inputs)
             if after is not None:
                 after(out)
-            ev = torch.cuda.Event()
-            ev.record(st)
-        self.events[i] = ev
+            if own is not None and i < own.max_slots:
+                ev = own.record(i, st._pwclo_index)
+            else:                       # torch's pool streams, someone else's streams, or more slots than the set has events for
+                ev = torch.cuda.Event()
+                ev.record(st)
+        self.events[i], self._where[i] = ev, st
         return out, i
+
+    def _stream_wait_slot(self, stream, slot):
+        """``stream`` waits for the last replay of ``slot`` (and what was queued behind it)."""
+        ev = self.events[slot]
+        if isinstance(ev, torch.cuda.Event):
+            stream.wait_event(ev)
+        elif ev is not None:
+            self._set.wait_slot(slot, stream)
 
     def __call__(self, xyz_f1, xyz_f2):
         return self._submit(xyz_f1, xyz_f2)
@@ -155,8 +199,11 @@ class PipelinedForward:
             self.events[slot].synchronize()
 
     def wait_all(self):
-        for s in self.streams or []:
-            s.synchronize()
+        if self._set is not None:
+            self._set.synchronize()
+        else:
+            for s in self.streams or []:
+                s.synchronize()
 
 
 def sequence_windows(n, window):
@@ -217,7 +264,7 @@ class PipelinedSequence(PipelinedForward):
             used.add(self._submit(frames[start:start + length], after=copy)[1])
         main = torch.cuda.current_stream(frames.device)
         for i in used:
-            main.wait_event(self.events[i])
+            self._stream_wait_slot(main, i)
         return rows
 
 

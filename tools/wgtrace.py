@@ -156,7 +156,7 @@ def main():
                         if e_ <= w0 or s_ >= w1:
                             continue
                         b0, b1 = max(s_, w0) - w0, min(e_, w1) - w0
-                        i0, i1 = int(b0 / a.bin_us), min(int(b1 / a.bin_us), nb - 1)
+                        i0, i1 = min(int(b0 / a.bin_us), nb - 1), min(int(b1 / a.bin_us), nb - 1)
                         if i0 == i1:
                             acc[i0] += rate * (b1 - b0) / a.bin_us
                         else:
