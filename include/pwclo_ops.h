@@ -94,9 +94,9 @@ void pwclo_fps_large_cloud_exchange(int xcd_local);
 /* A set of n HIP streams for a pipeline that keeps several captured forwards in flight (graphed.PipelinedForward), plus
  * one completion event per slot.  The runtime serialises streams that share a hardware queue, and which queue a stream gets
  * follows from the order in which the process's streams are created / first used.  pwclo_stream_set_create makes all n
- * streams back to back (hipStreamNonBlocking, one priority), then one empty launch on each, in order, and waits for those:
- * the set's streams are bound to consecutive hardware queues with no other stream of the process in between.  No CU mask,
- * no change of the queue count.
+ * streams back to back (hipStreamNonBlocking, normal priority), then one empty launch on each, in order, and waits for
+ * those: the set's streams are bound to consecutive hardware queues with no other stream of the process in between.  Then
+ * it measures how many of them run side by side (the probe, below).  No CU mask, no change of the queue count.
  *
  * Handles are positive ids that are never reused.  Every function returns 0 on success, PWCLO_EINVAL for an argument it
  * refuses (n outside [1, PWCLO_STREAM_SET_MAX], a stream or slot index out of range, a handle that was never issued or is
@@ -107,6 +107,30 @@ void pwclo_fps_large_cloud_exchange(int xcd_local);
 #define PWCLO_STREAM_SET_MAX 8        /* streams per set, and completion slots per set */
 #define PWCLO_STREAM_SET_LIVE_MAX 64  /* sets alive at once in a process */
 int pwclo_stream_set_create(int n, long long *handle);
+/* The same with a choice of the streams' priority class (pwclo_stream_set_create is _NORMAL).  The runtime keeps its
+ * hardware queues per priority class, so a stream of another class does not share a queue with the process's normal
+ * streams.  _HIGH / _LOW: every stream at the greatest / least priority of hipDeviceGetStreamPriorityRange; _MIXED:
+ * streams 0 .. k-1 normal and the rest high, k = GPU_MAX_HW_QUEUES - 1 (4 - 1 when unset; the variable is only read);
+ * _AUTO: tries _NORMAL, _MIXED, _HIGH, _LOW in that order and keeps the first set whose probe (below) finds all n
+ * streams side by side, a _NORMAL set if none does; a set that loses is destroyed as pwclo_stream_set_destroy does it.
+ * Only the create call of a stream differs between layouts.  On a device with one priority level every layout is
+ * _NORMAL, and so is _MIXED with n <= k; pwclo_stream_set_probe reports it so.  Any other layout value: PWCLO_EINVAL. */
+#define PWCLO_STREAM_LAYOUT_AUTO (-1)
+#define PWCLO_STREAM_LAYOUT_NORMAL 0
+#define PWCLO_STREAM_LAYOUT_HIGH 1
+#define PWCLO_STREAM_LAYOUT_LOW 2
+#define PWCLO_STREAM_LAYOUT_MIXED 3
+int pwclo_stream_set_create_ex(int n, int layout, long long *handle);
+/* The probe.  Every create call measures once how many of the set's streams run side by side and the set keeps the
+ * answer; these two only read it.  The measurement: one workgroup of 64 threads per stream, launched back to back, each
+ * running a fixed number of rounds of a dependent integer chain -- no memory traffic, nothing it waits for, so it ends by
+ * itself -- sized to about 0.5 ms by one calibration launch on stream 0, and stamping its start and end on the constant
+ * 100 MHz clock into a small device buffer of the set.  After one hipStreamSynchronize per stream the host takes the
+ * largest group of launches whose intervals overlap pairwise by more than half the longer one's length (of equal groups
+ * the one with the lowest stream indices).  side_by_side: that group's size, 1 .. n.  layout: the PWCLO_STREAM_LAYOUT_*
+ * in effect (never _AUTO); together: bit i set = stream i belongs to the group; probe_ns: the longest probe launch. */
+int pwclo_stream_set_concurrency(long long handle, int *side_by_side);
+int pwclo_stream_set_probe(long long handle, int *layout, unsigned *together, long long *probe_ns);
 /* n of the set; -PWCLO_EINVAL for a handle that is not live. */
 int pwclo_stream_set_size(long long handle);
 int pwclo_stream_set_stream(long long handle, int i, void **hip_stream);

@@ -10,11 +10,19 @@ EXPLICITLY, before its first HIP call -- the runtime reads the variable once, wh
 """
 import os as _os
 
+_requested = None         # what the program asked configure_hw_queues() for, granted or not
+
 
 def configure_hw_queues(n=8):
     """Ask the HIP runtime for ``n`` hardware queues (``GPU_MAX_HW_QUEUES``) unless the environment already
     says otherwise.  Must run before the process initialises HIP: raises ``RuntimeError`` if torch has already
-    initialised the device (the setting would silently not apply).  Returns the value in effect."""
+    initialised the device (the setting would silently not apply).  Returns the value in effect.
+
+    The call is also how a program says that it wants its pipelines as deep as they go: where the environment keeps
+    the queue count down, the pipelines' stream set may then take its queues from another stream priority class
+    (``pipe_streams.priority``).  A process that never calls it gets normal-priority streams only."""
+    global _requested
+    _requested = int(n)
     if "GPU_MAX_HW_QUEUES" in _os.environ:
         return int(_os.environ["GPU_MAX_HW_QUEUES"])
     import torch
@@ -23,6 +31,11 @@ def configure_hw_queues(n=8):
                            "(GPU_MAX_HW_QUEUES is read when the runtime initialises)")
     _os.environ["GPU_MAX_HW_QUEUES"] = str(int(n))
     return int(n)
+
+
+def requested_hw_queues():
+    """What the program passed to ``configure_hw_queues()`` (None: it never called it), whatever was granted."""
+    return _requested
 
 
 def hw_queues():

@@ -33,6 +33,10 @@ SIGNATURES = {
     "pwclo_fps_large_cloud_exchange": ([_i], None),
     "pwclo_trace_enable": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint], None),
     "pwclo_stream_set_create": ([_i, ctypes.POINTER(ctypes.c_longlong)], _i),
+    "pwclo_stream_set_create_ex": ([_i, _i, ctypes.POINTER(ctypes.c_longlong)], _i),
+    "pwclo_stream_set_concurrency": ([ctypes.c_longlong, ctypes.POINTER(ctypes.c_int)], _i),
+    "pwclo_stream_set_probe": ([ctypes.c_longlong, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint),
+                                ctypes.POINTER(ctypes.c_longlong)], _i),
     "pwclo_stream_set_size": ([ctypes.c_longlong], _i),
     "pwclo_stream_set_stream": ([ctypes.c_longlong, _i, ctypes.POINTER(ctypes.c_void_p)], _i),
     "pwclo_stream_set_wait_stream": ([ctypes.c_longlong, _i, ctypes.c_void_p], _i),

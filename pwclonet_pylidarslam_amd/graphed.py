@@ -100,7 +100,8 @@ class GraphedSequence(GraphedForward):
 
 class PipelinedForward:
     """Keeps `depth` forwards in flight: one captured graph per slot, used round-robin, on the streams of the native
-    stream set (one per slot where the process has hardware queues to spare, see ``_submit``).
+    stream set (one per slot where the set's probe finds them all running side by side, see ``_submit``; ``describe()``
+    says which layout and how many lanes a run got).
 
     Within one forward the furthest-point-sampling chain is a long dependent sequence that
     occupies one CU per cloud (64 of 256 CUs at batch 32) while the rest of the chip waits; with
@@ -123,7 +124,8 @@ class PipelinedForward:
         self._set = None
         self.events = [None] * depth
         self._where = [None] * depth      # the stream each slot's last replay went to
-        self._lanes = None                # how many of the streams the calls rotate over (pipe_streams.lanes)
+        self._lanes = None                # how many of the streams the calls rotate over (pipe_streams.rotation) ...
+        self._order = None                # ... and which: call c goes to streams[_order[c % _lanes]]
         self._next = 0
         self._calls = 0
 
@@ -142,21 +144,20 @@ class PipelinedForward:
     def _submit(self, *inputs, after=None):
         """Replay the next slot; ``after(out)``, if given, is queued behind the replay on the same stream.
 
-        Call c uses slot c % depth and stream c % lanes.  With lanes == depth that is one stream per slot.  With fewer
-        lanes (native streams in a process with no more hardware queues than slots: ``pipe_streams.lanes``) the slots
-        rotate over the first `lanes` streams -- as many replays in flight as run side by side, instead of `depth` of which
-        two share a hardware queue -- and a slot's replay first waits for the slot's previous one, which ran on
-        another stream."""
+        Call c uses slot c % depth and stream order[c % lanes].  With lanes == depth that is one stream per slot.  With
+        fewer lanes (the native set's probe found fewer streams running side by side than there are slots:
+        ``pipe_streams.rotation``; or, in a process that chose no layout, no more hardware queues than slots:
+        ``pipe_streams.lanes``) the slots rotate over the streams the probe saw together -- as many replays in flight
+        as run side by side, instead of `depth` of which two share a hardware queue -- and a slot's replay first waits for
+        the slot's previous one, which ran on another stream."""
         dev = inputs[0].device
         if self.streams is None:
             self.streams = self._make_streams(dev)
         if self._lanes is None:
-            from . import pipe_streams
-            native = all(hasattr(s, "_pwclo_index") for s in self.streams)
-            self._lanes = pipe_streams.lanes(len(self.slots)) if native else len(self.slots)
+            self._lanes, self._order = self._rotation()
         i = self._next
         self._next = (i + 1) % len(self.slots)
-        st, own = self.streams[self._calls % self._lanes], self._set
+        st, own = self.streams[self._order[self._calls % self._lanes]], self._set
         self._calls += 1
         # inputs produced on the caller's stream
         if own is not None:
@@ -176,6 +177,37 @@ class PipelinedForward:
                 ev.record(st)
         self.events[i], self._where[i] = ev, st
         return out, i
+
+    def _probed_set(self):
+        """The native set behind ``self.streams`` (this pipeline's own, or the one whose wrappers were passed in)."""
+        sets = {id(getattr(s, "_pwclo_set", None)) for s in self.streams}
+        return getattr(self.streams[0], "_pwclo_set", None) if len(sets) == 1 else None
+
+    def _rotation(self):
+        """(lanes, indices into ``self.streams``): what the set's probe measured (``pipe_streams.rotation``) where the
+        process chose a layout; the first ``pipe_streams.lanes(depth)`` streams of a set made for a process that chose
+        none; one stream per slot for streams that are not a native set's."""
+        from . import pipe_streams
+        s = self._probed_set()
+        if s is None:
+            return len(self.slots), tuple(range(len(self.slots)))
+        if not s.follows_probe:
+            n = pipe_streams.lanes(len(self.slots))
+            return n, tuple(range(n))
+        return pipe_streams.rotation(len(self.slots), s.side_by_side, s.together)
+
+    def describe(self):
+        """What labels a run: the kind of streams, the set's layout and probe result, the lanes in use (None before the
+        first call) and, for comparison, what the queue-count formula ``pipe_streams.lanes`` would have said."""
+        from . import pipe_streams
+        s = self._probed_set() if self.streams is not None else None
+        return dict(streams="unset" if self.streams is None else "torch" if s is None else "native",
+                    layout=s.layout if s is not None else None,
+                    side_by_side=s.side_by_side if s is not None else None,
+                    together=s.together if s is not None else None,
+                    follows_probe=s.follows_probe if s is not None else None,
+                    lanes=self._lanes, stream_indices=self._order,
+                    formula_lanes=pipe_streams.lanes(len(self.slots)))
 
     def _stream_wait_slot(self, stream, slot):
         """``stream`` waits for the last replay of ``slot`` (and what was queued behind it)."""
