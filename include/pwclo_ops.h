@@ -1096,6 +1096,32 @@ void proj_accumulate_kernel_wrapper(int S, int M, int H, int W, double up_fov, d
 void proj_map_push_kernel_wrapper(int S, int M, int H, int W, const double *T, const float *vmap, const float *nmap,
                                   float *map_v, float *map_n, double *A, int *live, int *cursor);
 
+/* ---- 8. keyframe local maps and the refined de-skew prior --------------------------------------
+ * The reference inserts a frame into its local map only when the motion accumulated since the last inserted frame exceeds
+ * a translation or a rotation threshold (slam/odometry/icp_odometry.py:361-381); otherwise the map is only moved into the
+ * new frame.  The decision is taken on the device, between the last solve and the push.  State per stream, DEVICE memory:
+ * kf_delta (S,4,4) fp64 row-major, the motion since the stream's last inserted frame; kf_insert (S) ints, this call's
+ * decision; kf_count (S) ints, frames inserted since the map was emptied.  The names of this section start with keyframe_:
+ * sections 6 and 7 pin the sets of names that carry their own prefixes. */
+
+/* One workgroup, one thread per stream (S <= 1024, M <= 64).  T (S,4,4) fp64 the registered poses, live (S,M) ints, active
+ * (S) ints or NULL (every stream delivered a frame); trans in metres, rot in degrees, both finite and >= 0.  In this order:
+ * active[s] == 0: kf_insert[s] = 0, nothing else changes.  No live slot: kf_insert = 1, kf_delta = I, kf_count = 1.
+ * Otherwise D = kf_delta . T[s], t = |D[:3,3]|, angle = atan2(s, c) 180 / pi with c = (trace - 1) / 2 and s = half the norm of
+ * (R32 - R23, R13 - R31, R21 - R12); insert iff t > trans or angle > rot (both strict); insert: kf_delta = I, kf_count += 1;
+ * no insert: kf_delta = D.  All arithmetic fp64. */
+void keyframe_gate_kernel_wrapper(int S, int M, const double *T, const int *live, const int *active, double trans, double rot,
+                                  double *kf_delta, int *kf_insert, int *kf_count);
+/* Section 6's masked push behind the gate (active (S) ints or NULL).  insert[s] != 0: the bits of that push.  insert[s] == 0:
+ * every live slot, the cursor's included, gets A <- A T and R <- R_T^T R; nothing is copied, live and cursor stay. */
+void keyframe_icp_push_kernel_wrapper(int S, int M, int n, const double *T, const float *cloud, const float *normals,
+                                      const void *stage_ws, float *map_xyz, float *map_normals, void *map_ws, double *A,
+                                      double *R, int *live, int *cursor, const int *active, const int *insert);
+/* The refined pose as the de-skew prior: a stream with active[s] and valid[s] (this call's words) gets motion[s] (S,7) fp32 =
+ * the pose row [tx ty tz qw qx qy qz] of T[s] (S,4,4) fp64: the translation rounded once; the quaternion from the rotation
+ * by Shepperd's branch selection in fp64, normalised, w >= 0, rounded once.  Every other row keeps its bits.  S <= 1024. */
+void stream_motion_from_refined_kernel_wrapper(int S, const int *active, const int *valid, const double *T, float *motion);
+
 #ifdef __cplusplus
 }
 #endif

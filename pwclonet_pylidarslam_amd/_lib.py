@@ -196,6 +196,9 @@ SIGNATURES = {
     "proj_accumulate_kernel_wrapper": ([_i] * 4 + [ctypes.c_double] * 2 + [_F] * 4 + [ctypes.c_double, ctypes.c_float]
                                        + [_F] * 3, None),
     "proj_map_push_kernel_wrapper": ([_i] * 4 + [_F] * 8, None),
+    "keyframe_gate_kernel_wrapper": ([_i, _i, _F, _F, _F, ctypes.c_double, ctypes.c_double, _F, _F, _F], None),
+    "keyframe_icp_push_kernel_wrapper": ([_i, _i, _i] + [_F] * 13, None),
+    "stream_motion_from_refined_kernel_wrapper": ([_i, _F, _F, _F, _F], None),
 }
 
 _lib = None

@@ -215,7 +215,10 @@ __global__ __launch_bounds__(ICP_SOLVE_THREADS) void icp_solve_kernel(
 
 // One workgroup per stream.  The staged frame (cloud, normals, the rows and boxes of its search structure, built for S
 // clouds) goes into slot cursor[s] of the stream's map (structures built for S * M clouds); the live slots' poses are
-// re-based on the new frame; the cursor moves on.
+// re-based on the new frame; the cursor moves on.  insert (S) or nullptr: the keyframe gate's decision (keyframe.hip,
+// DESIGN.md section 23).  nullptr is the ungated push.  A stream with insert[s] == 0 keeps its slots, live flags and cursor:
+// nothing is copied and every live slot, the cursor's included, is only re-based.  The word is the same for the whole
+// workgroup, so the exit is uniform.
 __global__ __launch_bounds__(1024) void icp_map_push_kernel(int M, int n, int S, int nblk, const double *__restrict__ T,
                                                             const float *__restrict__ cloud,
                                                             const float *__restrict__ normals,
@@ -223,24 +226,28 @@ __global__ __launch_bounds__(1024) void icp_map_push_kernel(int M, int n, int S,
                                                             float *__restrict__ map_normals, float4 *__restrict__ map_ws,
                                                             double *__restrict__ A, double *__restrict__ Rm,
                                                             int *__restrict__ live, int *__restrict__ cursor,
-                                                            const int *__restrict__ active) {
+                                                            const int *__restrict__ active,
+                                                            const int *__restrict__ insert) {
   const int s = blockIdx.x;
   if (active != nullptr && active[s] == 0) return;        // idle: before anything is read
+  const bool ins = insert == nullptr || insert[s] != 0;
   const int slot = min(max(cursor[s], 0), M - 1);
   const size_t sm = (size_t)s * M + slot;
   const size_t n3 = (size_t)n * 3, nrow = (size_t)nblk * 64, nbox = (size_t)nblk * 2;
-  for (size_t j = threadIdx.x; j < n3; j += 1024) {
-    map_xyz[sm * n3 + j] = cloud[(size_t)s * n3 + j];
-    map_normals[sm * n3 + j] = normals[(size_t)s * n3 + j];
+  if (ins) {
+    for (size_t j = threadIdx.x; j < n3; j += 1024) {
+      map_xyz[sm * n3 + j] = cloud[(size_t)s * n3 + j];
+      map_normals[sm * n3 + j] = normals[(size_t)s * n3 + j];
+    }
+    const float4 *srow = stage_ws + (size_t)s * nrow, *sbox = stage_ws + (size_t)S * nrow + (size_t)s * nbox;
+    float4 *drow = map_ws + sm * nrow, *dbox = map_ws + (size_t)S * M * nrow + sm * nbox;
+    for (size_t j = threadIdx.x; j < nrow; j += 1024) drow[j] = srow[j];
+    for (size_t j = threadIdx.x; j < nbox; j += 1024) dbox[j] = sbox[j];
   }
-  const float4 *srow = stage_ws + (size_t)s * nrow, *sbox = stage_ws + (size_t)S * nrow + (size_t)s * nbox;
-  float4 *drow = map_ws + sm * nrow, *dbox = map_ws + (size_t)S * M * nrow + sm * nbox;
-  for (size_t j = threadIdx.x; j < nrow; j += 1024) drow[j] = srow[j];
-  for (size_t j = threadIdx.x; j < nbox; j += 1024) dbox[j] = sbox[j];
   const int m = threadIdx.x;
   if (m < M) {
     double *am = A + ((size_t)s * M + m) * 16, *rm = Rm + ((size_t)s * M + m) * 9;
-    if (m == slot) {
+    if (ins && m == slot) {
 #pragma unroll
       for (int e = 0; e < 16; ++e) am[e] = (e % 5 == 0) ? 1.0 : 0.0;
 #pragma unroll
@@ -265,7 +272,7 @@ __global__ __launch_bounds__(1024) void icp_map_push_kernel(int M, int n, int S,
     }
   }
   __syncthreads();                                         // everyone has read the cursor
-  if (threadIdx.x == 0) cursor[s] = slot + 1 == M ? 0 : slot + 1;
+  if (ins && threadIdx.x == 0) cursor[s] = slot + 1 == M ? 0 : slot + 1;
 }
 
 // Masked registration, first launch of the body.  One workgroup per stream, one thread per slot: a stream that delivered a
@@ -411,7 +418,8 @@ extern "C" void icp_solve_masked_kernel_wrapper(int S, int groups, int it, const
 
 static void icp_map_push_launch(const char *what, int S, int M, int n, const double *T, const float *cloud,
                                 const float *normals, const void *stage_ws, float *map_xyz, float *map_normals, void *map_ws,
-                                double *A, double *R, int *live, int *cursor, const int *active) {
+                                double *A, double *R, int *live, int *cursor, const int *active,
+                                const int *insert = nullptr) {
   if (S <= 0) return;
   const long long per = knn_point_build_bytes(1, n);       // 0 outside the range the search structure supports
   PWCLO_REQUIRE(per > 0 && M >= 1 && M <= ICP_MAX_SLOTS && (long long)S * M <= 65535,
@@ -425,7 +433,7 @@ static void icp_map_push_launch(const char *what, int S, int M, int n, const dou
   const int nblk = (int)(per / (64 * 16 + 32));
   hipLaunchKernelGGL(icp_map_push_kernel, dim3(S), dim3(1024), 0, current_stream(), M, n, S, nblk, T, cloud, normals,
                      static_cast<const float4 *>(stage_ws), map_xyz, map_normals, static_cast<float4 *>(map_ws), A, R, live,
-                     cursor, active);
+                     cursor, active, insert);
   check_launch(what);
 }
 
@@ -443,6 +451,18 @@ extern "C" void icp_map_push_masked_kernel_wrapper(int S, int M, int n, const do
   PWCLO_REQUIRE(S <= 0 || (active != nullptr && icp_aligned(active, 4)), "icp_map_push_masked: active is required%s", "");
   icp_map_push_launch("icp_map_push_masked", S, M, n, T, cloud, normals, stage_ws, map_xyz, map_normals, map_ws, A, R, live,
                       cursor, active);
+}
+
+// The push behind the keyframe gate: icp_map_push_masked's launch with the gate's decision word.
+// active: (S) or nullptr, as there.
+extern "C" void keyframe_icp_push_kernel_wrapper(int S, int M, int n, const double *T, const float *cloud,
+                                                 const float *normals, const void *stage_ws, float *map_xyz,
+                                                 float *map_normals, void *map_ws, double *A, double *R, int *live,
+                                                 int *cursor, const int *active, const int *insert) {
+  PWCLO_REQUIRE(S <= 0 || (insert != nullptr && icp_aligned(insert, 4) && icp_aligned(active, 4)),
+                "keyframe_icp_push: insert is required, and insert and active must be 4-byte aligned%s", "");
+  icp_map_push_launch("keyframe_icp_push", S, M, n, T, cloud, normals, stage_ws, map_xyz, map_normals, map_ws, A, R, live,
+                      cursor, active, insert);
 }
 
 extern "C" void icp_begin_kernel_wrapper(int S, int M, const int *active, const int *restart, int *armed, double *A,

@@ -85,4 +85,32 @@ __device__ __forceinline__ Se3 pose_row_to_se3(const float *r) {
   return a;
 }
 
+// The other way: the pose row [tx ty tz qw qx qy qz] of a rigid transform.  The quaternion comes from the rotation by
+// Shepperd's branch selection (the largest of the trace and the three diagonal entries decides which component is taken
+// from a square root, so no branch divides by a small number), is normalised, gets w >= 0, and every component is rounded
+// to fp32 once.
+__device__ __forceinline__ void se3_to_pose_row(const Se3 &a, float *r) {
+  const double r00 = a.m[0], r01 = a.m[1], r02 = a.m[2], r10 = a.m[4], r11 = a.m[5], r12 = a.m[6], r20 = a.m[8],
+               r21 = a.m[9], r22 = a.m[10];
+  const double tr = (r00 + r11) + r22;
+  double w, x, y, z;
+  if (tr >= r00 && tr >= r11 && tr >= r22) {
+    const double u = sqrt(1.0 + tr), k = 0.5 / u;
+    w = 0.5 * u; x = (r21 - r12) * k; y = (r02 - r20) * k; z = (r10 - r01) * k;
+  } else if (r00 >= r11 && r00 >= r22) {
+    const double u = sqrt(((1.0 + r00) - r11) - r22), k = 0.5 / u;
+    x = 0.5 * u; w = (r21 - r12) * k; y = (r01 + r10) * k; z = (r02 + r20) * k;
+  } else if (r11 >= r22) {
+    const double u = sqrt(((1.0 - r00) + r11) - r22), k = 0.5 / u;
+    y = 0.5 * u; w = (r02 - r20) * k; x = (r01 + r10) * k; z = (r12 + r21) * k;
+  } else {
+    const double u = sqrt(((1.0 - r00) - r11) + r22), k = 0.5 / u;
+    z = 0.5 * u; w = (r10 - r01) * k; x = (r02 + r20) * k; y = (r12 + r21) * k;
+  }
+  double inv = 1.0 / sqrt(((w * w + x * x) + y * y) + z * z);
+  if (w < 0.0) inv = -inv;
+  r[0] = (float)a.m[3]; r[1] = (float)a.m[7]; r[2] = (float)a.m[11];
+  r[3] = (float)(w * inv); r[4] = (float)(x * inv); r[5] = (float)(y * inv); r[6] = (float)(z * inv);
+}
+
 }  // namespace pwclo

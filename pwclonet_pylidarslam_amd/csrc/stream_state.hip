@@ -10,8 +10,8 @@
 // stream_append_masked_kernel runs that machine, one thread per stream; stream_handover_masked_kernel then moves the
 // new frame's state into the persistent previous frame for the active streams only, in ONE launch over a table of
 // segments (it replaces one copy node per tensor); stream_record_refined_kernel keeps the refined trajectories of a
-// masked registration beside the network's.  Both read the masks from device memory, so one captured graph
-// serves priming, pairs and idling alike.
+// masked registration beside the network's; stream_motion_from_refined_kernel hands a refined pose to the de-skew
+// prior.  All four read their masks from device memory, so one captured graph serves priming, pairs and idling alike.
 #include "common.hpp"
 #include "se3.hpp"
 
@@ -88,6 +88,19 @@ __global__ __launch_bounds__(1024) void stream_record_refined_kernel(int S, int 
   const Se3 id = se3_identity();
   se3_store(ref_rel + (size_t)i * 16, id);
   se3_store(ref_abs + (size_t)i * 16, id);
+}
+
+// With refine=dict(..., feedback=True): the refined pose becomes the de-skew prior.  After the
+// registration and before the record above, a pair (active && valid) overwrites its row of motion (S, 7) fp32 -- the rows
+// stream_motion_handover_kernel (deskew.hip) writes, [tx ty tz qw qx qy qz] -- with the pose row of T[s]; every other stream's
+// row (primed, idle, or written by the step's own handover) keeps its bits.  One thread per stream.
+__global__ __launch_bounds__(1024) void stream_motion_from_refined_kernel(int S, const int *__restrict__ active,
+                                                                          const int *__restrict__ valid,
+                                                                          const double *__restrict__ T,
+                                                                          float *__restrict__ motion) {
+  const int i = threadIdx.x;
+  if (i >= S || active[i] == 0 || valid[i] == 0) return;
+  se3_to_pose_row(se3_load(T + (size_t)i * 16), motion + (size_t)i * 7);
 }
 
 // ---- masked handover -------------------------------------------------------------------------------------------------
@@ -191,6 +204,16 @@ extern "C" void stream_record_refined_kernel_wrapper(int S, int capacity, const 
   hipLaunchKernelGGL(stream_record_refined_kernel, dim3(1), dim3(ceil_div(S, 64) * 64), 0, current_stream(), S, capacity,
                      active, valid, count, T, ref_rel, ref_abs);
   check_launch("stream_record_refined");
+}
+
+extern "C" void stream_motion_from_refined_kernel_wrapper(int S, const int *active, const int *valid, const double *T,
+                                                          float *motion) {
+  PWCLO_REQUIRE(S >= 1 && S <= 1024, "stream_motion_from_refined: S=%d streams outside one workgroup [1, 1024]", S);
+  PWCLO_REQUIRE(active && valid && T && motion, "stream_motion_from_refined: a null argument");
+  PWCLO_REQUIRE((reinterpret_cast<uintptr_t>(T) & 7) == 0, "stream_motion_from_refined: T must be 8-byte aligned");
+  hipLaunchKernelGGL(stream_motion_from_refined_kernel, dim3(1), dim3(ceil_div(S, 64) * 64), 0, current_stream(), S, active,
+                     valid, T, motion);
+  check_launch("stream_motion_from_refined");
 }
 
 extern "C" int stream_handover_max_segments(void) { return HANDOVER_MAX_SEGMENTS; }

@@ -69,15 +69,24 @@ class StreamingOdometry:
     after each step's own graph, which is unchanged, the cloud the step sampled from is registered by point-to-plane ICP
     against a local map of the stream's last frames, with the level-1 row's transform as the initial guess (one more
     captured graph).  ``refined_relative_poses()`` / ``refined_trajectory()`` sit beside ``relative_poses()`` /
-    ``trajectory()``, which stay the network's, as does the de-skew prior; ``refiner().status()`` tells why a stream's
-    registration stopped.  One path serves both modes: after the step's graph the refiner's graph reads the call's
-    ``active`` word and ``restart = active * (1 - valid)`` (a stream that primed in this call: a first frame, a ``restart``
-    mask, ``reset()`` or ``reset(streams=...)``) in place, and one launch records the refined pose at the stream's own
-    frame counter, row 0 the identity again after a restart.  No sync, no new capture; pose rows, ``relative_poses``,
-    ``trajectory``, ``valid``, ``frame_counts`` and the de-skew prior stay the network's.  Per-stream mode opts into
-    the per-stream view inside the dict: ``per_stream=True`` needs ``refine=dict(..., per_stream=True)`` (status bit 8
-    for idle streams) and raises without the key; lock step raises with it.  ``refined_relative_poses(stream=i)`` /
-    ``refined_trajectory(stream=i)`` then give (count_i, 4, 4).
+    ``trajectory()``, which stay the network's, as does the de-skew prior (unless ``feedback=True``, below);
+    ``refiner().status()`` tells why a stream's registration stopped.  One path serves both modes: after the step's graph
+    the refiner's graph reads the call's ``active`` word and ``restart = active * (1 - valid)`` (a stream that primed in
+    this call: a first frame, a ``restart`` mask, ``reset()`` or ``reset(streams=...)``) in place, and one launch records
+    the refined pose at the stream's own frame counter, row 0 the identity again after a restart.  No sync, no new
+    capture; pose rows, ``relative_poses``, ``trajectory``, ``valid``, ``frame_counts`` and the de-skew prior stay the
+    network's.  Per-stream mode opts into the per-stream view inside the dict: ``per_stream=True`` needs
+    ``refine=dict(..., per_stream=True)`` (status bit 8 for idle streams) and raises without the key; lock step raises
+    with it.  ``refined_relative_poses(stream=i)`` / ``refined_trajectory(stream=i)`` then give (count_i, 4, 4).
+    Keyframes: ``refine=dict(..., keyframe=dict(trans=0.1, rot=0.3))`` (metres, degrees) reaches the
+    ``"knn"`` refiner in both modes: a frame goes into the local map only when the motion since the stream's last inserted
+    frame exceeds a threshold, decided on the device inside the refiner's graph (``refiner().keyframe_state()``).  The
+    projective refiner has no keyframe gate yet.
+    ``refine=dict(..., feedback=True)`` (raw mode with ``deskew=True`` only, ``ValueError`` otherwise): after the
+    registration one launch writes the refined pose's row into ``motion()`` for the streams that registered a pair in this
+    call, so the next sweep is de-skewed with the refined motion instead of the network's; primed and idle streams keep
+    their rows.  Pose rows, ``relative_poses()`` and ``trajectory()`` stay the network's in both settings, and without the
+    key ``motion()`` holds the bits it always held.
 
     Per-stream mode (``per_stream=True``): ``step(frames, active=None, restart=None)`` and ``step_sweeps(sweeps, lengths,
     active=None, restart=None)`` take two (S,) masks, bool or integer, host sequences or device tensors (device tensors
@@ -121,10 +130,19 @@ class StreamingOdometry:
         self._front = None          # raw mode: preprocess.SweepFrontEnd (persistent sweep, lengths, tr, sampler buffers)
         self._refine_cfg = None if refine is None else dict(refine)     # the refiner's keywords
         self._refine_kind = "knn" if refine is None else self._refine_cfg.pop("kind", "knn")
+        self._feedback = False if refine is None else self._refine_cfg.pop("feedback", False)
+        if not isinstance(self._feedback, (bool, np.bool_)):
+            raise ValueError("StreamingOdometry: refine=dict(feedback=%r) must be a bool" % (self._feedback,))
+        if self._feedback and not (sweeps is not None and dict(sweeps).get("deskew", False)):
+            raise ValueError("StreamingOdometry: refine=dict(feedback=True) hands the refined pose to the de-skew prior and "
+                             "needs raw mode with sweeps=dict(..., deskew=True)")
         if self._refine_kind not in ("knn", "projective"):
             raise ValueError("StreamingOdometry: refine=dict(kind=%r): \"knn\" (registration.IcpRefiner, the default) or "
                              "\"projective\" (projective.ProjectiveIcpRefiner)" % (self._refine_kind,))
         if self._refine_kind == "projective":
+            if "keyframe" in self._refine_cfg:
+                raise ValueError("StreamingOdometry: refine=dict(kind=\"projective\", keyframe=...): the projective refiner "
+                                 "has no keyframe gate; keyframe= is registration.IcpRefiner's (kind=\"knn\")")
             if self.per_stream or self._refine_cfg.get("per_stream", False):
                 raise ValueError("StreamingOdometry: refine=dict(kind=\"projective\") is lock step only: per-stream masks, "
                                  "idle streams and restarts inside the graph are out of scope (per_stream=True registers "
@@ -418,6 +436,7 @@ class StreamingOdometry:
             self._refiner.adopt_words(self._active, self._ref_restart)
         torch.sub(self._active, self._valid, out=self._ref_restart)
         T = self._refiner.register_adopted(cloud, pose[:, 0, :], all_active=not self.per_stream)
+        self._feed_motion(T)
         _lib.call("stream_record_refined_kernel_wrapper", cloud.device, self.streams, self.max_frames, _p(self._active),
                   _p(self._valid), _p(self._counts), _p(T), _p(self._ref_rel), _p(self._ref_abs))
 
@@ -433,8 +452,19 @@ class StreamingOdometry:
             self._ref_rel = torch.zeros((self.max_frames, self.streams, 4, 4), dtype=torch.float64, device=pose.device)
             self._ref_abs = torch.zeros_like(self._ref_rel)
         T = self._refiner.register(front["packed"], front["counts"], pose[:, 0, :])
+        self._feed_motion(T)
         _lib.call("stream_record_refined_kernel_wrapper", pose.device, self.streams, self.max_frames, _p(self._active),
                   _p(self._valid), _p(self._counts), _p(T), _p(self._ref_rel), _p(self._ref_abs))
+
+    def _feed_motion(self, T):
+        """``refine=dict(..., feedback=True)``, one launch after the registration: the streams that registered a pair in
+        this call (active and valid) get the pose row of the refined ``T`` as the motion of their next sweep; every other
+        row (primed or idle streams) keeps what the step's own handover left."""
+        if not self._feedback:
+            return
+        motion = self.motion()
+        _lib.call("stream_motion_from_refined_kernel_wrapper", motion.device, self.streams, _p(self._active),
+                  _p(self._valid), _p(T), _p(motion))
 
     def _view(self, buf, stream=None):
         if stream is None:

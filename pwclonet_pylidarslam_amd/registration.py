@@ -222,6 +222,78 @@ def map_push(T, cloud, normals_, stage_ws, map_xyz, map_normals, map_ws, A, R, l
         _lib.call("icp_map_push_masked_kernel_wrapper", T.device, *args, _p(active))
 
 
+def map_push_keyframe(T, cloud, normals_, stage_ws, map_xyz, map_normals, map_ws, A, R, live, cursor, insert, active=None):
+    """``map_push`` behind the keyframe gate: ``insert`` (S,) int32, the gate's decision.  A stream
+    with insert != 0 gets the bits of ``map_push``; one with insert == 0 keeps its slots, ``live`` and ``cursor``, and every
+    live slot's A / R is re-based with T.  ``active`` (S,) int32 or None, as there."""
+    if not isinstance(map_xyz, torch.Tensor) or map_xyz.dim() != 4:
+        raise ValueError("map_push_keyframe: map_xyz must be (S, M, n, 3)")
+    S, M, n, _ = map_xyz.shape
+    lib = _lib.load()
+    what = "map_push_keyframe"
+    _need(T, "%s: T" % what, torch.float64, (S, 4, 4))
+    _need(cloud, "%s: cloud" % what, torch.float32, (S, n, 3))
+    _need(normals_, "%s: normals" % what, torch.float32, (S, n, 3))
+    _need(stage_ws, "%s: stage_ws" % what, torch.uint8, (lib.knn_point_build_bytes(S, n),))
+    _need(map_xyz, "%s: map_xyz" % what, torch.float32, (S, M, n, 3))
+    _need(map_normals, "%s: map_normals" % what, torch.float32, (S, M, n, 3))
+    _need(map_ws, "%s: map_ws" % what, torch.uint8, (lib.knn_point_build_bytes(S * M, n),))
+    _need(A, "%s: A" % what, torch.float64, (S, M, 4, 4))
+    _need(R, "%s: R" % what, torch.float64, (S, M, 3, 3))
+    _need(live, "%s: live" % what, torch.int32, (S, M))
+    _need(cursor, "%s: cursor" % what, torch.int32, (S,))
+    _need(insert, "%s: insert" % what, torch.int32, (S,))
+    if active is not None:
+        _need_mask(active, what, S)
+    _lib.call("keyframe_icp_push_kernel_wrapper", T.device, S, M, n, _p(T), _p(cloud), _p(normals_), _p(stage_ws),
+              _p(map_xyz), _p(map_normals), _p(map_ws), _p(A), _p(R), _p(live), _p(cursor), _p(active), _p(insert))
+
+
+def keyframe_args(what, keyframe):
+    """``keyframe=None`` or ``dict(trans=metres, rot=degrees)`` -> None or (trans, rot), both finite and >= 0; ValueError
+    naming the argument otherwise."""
+    if keyframe is None:
+        return None
+    if not isinstance(keyframe, dict) or set(keyframe) - {"trans", "rot"}:
+        raise ValueError("%s: keyframe=%r must be None or dict(trans=metres, rot=degrees)" % (what, keyframe))
+    out = []
+    for key, default in (("trans", 0.1), ("rot", 0.3)):             # the reference's threshold_trans / threshold_rot
+        v = keyframe.get(key, default)
+        ok = isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool)
+        if not ok or not np.isfinite(float(v)) or float(v) < 0.0:
+            raise ValueError("%s: keyframe[%r]=%r must be finite and >= 0" % (what, key, v))
+        out.append(float(v))
+    return tuple(out)
+
+
+def keyframe_gate(T, delta, live, trans, rot, active=None, count=None, insert=None):
+    """One launch of the keyframe gate, in place on ``delta`` (S, 4, 4) fp64 (the motion since the
+    stream's last inserted frame) and ``count`` (S,) int32 (frames inserted since the map was emptied; zeros when None) ->
+    (insert (S,) int32, count).  T (S, 4, 4) fp64, live (S, M) int32, ``trans`` metres and ``rot`` degrees, ``active`` (S,)
+    int32 or None.  Idle: insert = 0, nothing else changes.  No live slot: insert = 1, delta = I, count = 1.  Otherwise D =
+    delta T; insert iff |D[:3, 3]| > trans or the rotation angle of D > rot; insert: delta = I, count += 1; else delta = D."""
+    if not isinstance(live, torch.Tensor) or live.dim() != 2:
+        raise ValueError("keyframe_gate: live must be (S, M)")
+    S, M = live.shape
+    trans, rot = keyframe_args("keyframe_gate", dict(trans=trans, rot=rot))
+    if not 1 <= S <= MAX_STREAMS or not 1 <= M <= MAX_SLOTS:
+        raise ValueError("keyframe_gate: S=%d M=%d out of range (S <= %d, M <= %d)" % (S, M, MAX_STREAMS, MAX_SLOTS))
+    _need(T, "keyframe_gate: T", torch.float64, (S, 4, 4))
+    _need(delta, "keyframe_gate: delta", torch.float64, (S, 4, 4))
+    _need(live, "keyframe_gate: live", torch.int32, (S, M))
+    if active is not None:
+        _need_mask(active, "keyframe_gate", S)
+    if count is None:
+        count = torch.zeros((S,), dtype=torch.int32, device=T.device)
+    if insert is None:
+        insert = torch.zeros((S,), dtype=torch.int32, device=T.device)
+    _need(count, "keyframe_gate: count", torch.int32, (S,))
+    _need(insert, "keyframe_gate: insert", torch.int32, (S,))
+    _lib.call("keyframe_gate_kernel_wrapper", T.device, S, M, _p(T), _p(live), _p(active), trans, rot, _p(delta),
+              _p(insert), _p(count))
+    return insert, count
+
+
 # ---- the refiner -------------------------------------------------------------------------------------------------------
 
 class IcpRefiner:
@@ -258,13 +330,21 @@ class IcpRefiner:
     the first active stream's (the mask is read once, there), so that staging never sees data no caller supplied.
     ``trace=True`` returns ``(T, steps, masks)``.
 
+    ``keyframe=dict(trans=0.1, rot=0.3)`` (metres, degrees): a frame goes into the map only when
+    the motion accumulated since the stream's last inserted frame exceeds one of the thresholds (the reference's
+    ``__update_map``); otherwise the map is only moved into the new frame.  One launch more per ``register``, between the
+    last solve and the push, decides on the device; the graph's node sequence is the same for every decision.  A stream
+    whose map is empty (first frame, restart, ``reset``) always inserts.  ``keyframe_state()`` shows the gate's words.
+    ``None`` (the default) inserts every frame with the launches and bits of a refiner without the keyword.
+
     ``adopt_words(active, restart)``, before the first call: the graph reads the caller's two (S,) int32 0 / 1 device words
     instead (``StreamingOdometry``'s, which its step's graph has just written); ``register_adopted(cloud, init)`` then
     loads no mask at all."""
 
     def __init__(self, streams, num_points, map_size=4, iters=10, sigma=0.5, max_dist=1.0, k_normals=10, damping=1e-6,
-                 threshold_delta_pose=1e-4, min_pairs=64, graph=True, per_stream=False):
+                 threshold_delta_pose=1e-4, min_pairs=64, graph=True, per_stream=False, keyframe=None):
         S, n, M, k = int(streams), int(num_points), int(map_size), int(k_normals)
+        self.keyframe = keyframe_args("IcpRefiner", keyframe)      # None or (trans, rot)
         if not 1 <= S <= MAX_STREAMS:
             raise ValueError("IcpRefiner: streams=%d outside [1, %d]" % (S, MAX_STREAMS))
         if not 64 <= n <= 16384:
@@ -319,6 +399,8 @@ class IcpRefiner:
             armed=i32(S))                    # restarts asked for by reset()
         active, restart = self._words or (i32(S), i32(S))
         self.bufs.update(active=active, restart=restart)            # the masks the graph reads
+        if self.keyframe is not None:                               # the gate's words
+            self.bufs.update(kf_delta=eye(S, 4, 4), kf_insert=i32(S), kf_count=i32(S))
 
     def _seed_structures(self):
         """Before the first registration: every slot's search structure becomes the first frame's (its live flag stays 0),
@@ -349,6 +431,14 @@ class IcpRefiner:
         if self.bufs is None:
             return None
         return {k: self.bufs[k] for k in ("A", "R", "live", "cursor")}
+
+    def keyframe_state(self):
+        """With ``keyframe=``: device views of the gate's words: delta (S, 4, 4) fp64 the motion since the stream's last
+        inserted frame, insert (S,) int32 the last call's decision, count (S,) int32 the frames inserted since the map was
+        emptied.  None before the first call or without ``keyframe``."""
+        if self.bufs is None or self.keyframe is None:
+            return None
+        return dict(delta=self.bufs["kf_delta"], insert=self.bufs["kf_insert"], count=self.bufs["kf_count"])
 
     def reset(self, streams=None):
         """Empty the maps of all streams, or of ``streams`` (host stream indices, or an (S,) bool mask, host or device):
@@ -401,6 +491,14 @@ class IcpRefiner:
 
     def _push(self):
         b, S, M, n = self.bufs, self.streams, self.map_size, self.num_points
+        if self.keyframe is not None:                       # the gate, then the push that reads its decision
+            dev = b["cloud"].device
+            _lib.call("keyframe_gate_kernel_wrapper", dev, S, M, _p(b["T"]), _p(b["live"]), _p(b["active"]),
+                      self.keyframe[0], self.keyframe[1], _p(b["kf_delta"]), _p(b["kf_insert"]), _p(b["kf_count"]))
+            _lib.call("keyframe_icp_push_kernel_wrapper", dev, S, M, n, _p(b["T"]), _p(b["cloud"]), _p(b["stage_normals"]),
+                      _p(b["stage_ws"]), _p(b["map_xyz"]), _p(b["map_normals"]), _p(b["map_ws"]), _p(b["A"]), _p(b["R"]),
+                      _p(b["live"]), _p(b["cursor"]), _p(b["active"]), _p(b["kf_insert"]))
+            return
         _lib.call("icp_map_push_masked_kernel_wrapper", b["cloud"].device, S, M, n, _p(b["T"]), _p(b["cloud"]),
                   _p(b["stage_normals"]), _p(b["stage_ws"]), _p(b["map_xyz"]), _p(b["map_normals"]), _p(b["map_ws"]),
                   _p(b["A"]), _p(b["R"]), _p(b["live"]), _p(b["cursor"]), _p(b["active"]))
