@@ -800,6 +800,50 @@ void pwclo_group_points_tuning(int use_lds, int threads, int target, int nt);
 #define PWCLO_KNN_PRUNED 2
 int knn_point_plan_query(int b, int n, int s, int nsample, int prebuilt, int use_rows, int *out);
 
+/* Host only (no launch, no device needed): what a furthest-point-sampling call launches for a cloud batch (b,n,3) and m
+ * samples, answered by the code every sampler launcher asks (csrc/sampling.hip: fps_plan).
+ *   entry      PWCLO_FPS_ENTRY_PLAIN: furthest_point_sampling[_xyz|_chain]_kernel_wrapper; _SORTED and _SLAB: the wrappers of
+ *              those names; _AUTO: what pointnet2_ops._ext.furthest_point_sampling does -- the plain entry, except that a
+ *              cooperative plan of n >= 32768 asks for the spatial order first (sorted = 1: the caller builds it and calls
+ *              the sorted entry);
+ *   temp       0: no temp buffer (sorted / slab entries: a required buffer is NULL), 1: given and 8-byte aligned, 2: given,
+ *              not 8-byte aligned;
+ *   tie_iters, tie_out, prefix_in: the chain arguments (the two pointers as 0 / 1);
+ *   capturing  the stream is under graph capture (the cooperative-launch API cannot be captured);
+ *   use_table, use_coop, coop_launch, xcd_local: PWCLO_FPS_TABLE, PWCLO_FPS_COOP, PWCLO_FPS_COOP_LAUNCH (or
+ *              pwclo_fps_large_cloud_launch), PWCLO_FPS_COOP_XCD_LOCAL (or pwclo_fps_large_cloud_exchange) as 0 / 1, or -1
+ *              for what the launchers use now; use_sorted: PWCLO_FPS_SORTED (read by the Python front end; AUTO only), -1 = 1.
+ * out receives 16 ints {kernel, T, E, I, table, G, sorted, per_launch, grid, launch, launches, xcd_local, lds_bytes, bs,
+ * log2bs, 0}:
+ *   kernel     PWCLO_FPS_REG: fps_reg_kernel<T, E, I, table>, one workgroup per cloud (n <= 24576), table = the cloud's copy
+ *              in LDS (it and the chain log of tie_out fit 160 KiB; 64 KiB with use_table = 0);
+ *              PWCLO_FPS_SLAB: fps_slab_kernel<512, I>, I = 16 / 18 sorted rows per lane (n <= 8192 / more);
+ *              PWCLO_FPS_COOP: fps_coop_kernel<16, sorted>, G = ceil(n / 16384) <= 32 workgroups per cloud, per_launch
+ *              clouds per launch (224 / G, whole groups of 8 from 8 on), `launches` launches, the first of `grid`
+ *              workgroups, launch = PWCLO_FPS_LAUNCH_COOPERATIVE (hipLaunchCooperativeKernel) or _PLAIN, xcd_local = the
+ *              exchange mode handed to the kernel;
+ *              PWCLO_FPS_STREAM: fps_stream_kernel<1024>, one workgroup per cloud of any n < 2^23 (more than 32 workgroups
+ *              per cloud, use_coop = 0, or a temp that is not 8-byte aligned);
+ *              PWCLO_FPS_REFUSED: the launcher records PWCLO_EINVAL and launches nothing; msg receives its message;
+ *   lds_bytes  dynamic LDS of the launch; bs, log2bs: the reference's block size for n, which the tie rule is written in.
+ * Fields that do not apply are 0.  msg (msg_len bytes, may be NULL) receives the refusal's message, else "".
+ * Returns 0, 1 for a refused call (out is filled all the same), -1 for an unknown entry or b <= 0 or m <= 0 (the launchers
+ * return at once, without an error). */
+#define PWCLO_FPS_ENTRY_PLAIN 0
+#define PWCLO_FPS_ENTRY_SORTED 1
+#define PWCLO_FPS_ENTRY_SLAB 2
+#define PWCLO_FPS_ENTRY_AUTO 3
+#define PWCLO_FPS_REG 0
+#define PWCLO_FPS_COOP 1
+#define PWCLO_FPS_STREAM 2
+#define PWCLO_FPS_SLAB 3
+#define PWCLO_FPS_REFUSED 4
+#define PWCLO_FPS_LAUNCH_PLAIN 0
+#define PWCLO_FPS_LAUNCH_COOPERATIVE 1
+int furthest_point_sampling_plan_query(int entry, int b, int n, int m, int temp, int tie_iters, int tie_out, int prefix_in,
+                                       int capturing, int use_table, int use_coop, int coop_launch, int xcd_local,
+                                       int use_sorted, int *out, char *msg, int msg_len);
+
 /* Host only (no launch, no device needed): how the reduction passes of the batchnorm_train_* entry points cut a problem of
  * c channels with M = b * l positions each in rows of L, answered by the launchers' own code: *nsplit position ranges of
  * *per_split positions per channel (grid (nsplit, c); per_split % 4 == 0, nsplit <= 256, the workspace holds c * nsplit

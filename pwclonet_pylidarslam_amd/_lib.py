@@ -139,6 +139,7 @@ SIGNATURES = {
     "group_points_plan_query": ([_i] * 9 + [ctypes.POINTER(ctypes.c_int)], _i),
     "pwclo_group_points_tuning": ([_i] * 4, None),
     "knn_point_plan_query": ([_i] * 6 + [ctypes.POINTER(ctypes.c_int)], _i),
+    "furthest_point_sampling_plan_query": ([_i] * 14 + [ctypes.POINTER(ctypes.c_int), ctypes.c_char_p, _i], _i),
     "batchnorm_train_plan_query": ([_i, ctypes.c_longlong, _i, ctypes.POINTER(ctypes.c_int),
                                     ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_int)], _i),
     "group_points_grad_sorted_kernel_wrapper": ([_i, _i, _i, _i, _i, _F, _F, _F, _F], None),

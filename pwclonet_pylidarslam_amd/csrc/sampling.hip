@@ -866,17 +866,15 @@ static int fps_coop_poll_delay() { static const int v = tuning("PWCLO_FPS_COOP_P
 static int fps_coop_xcd_local_default() { static const int v = tuning("PWCLO_FPS_COOP_XCD_LOCAL", 1); return v; }
 static int fps_coop_launch_default() { static const int v = tuning("PWCLO_FPS_COOP_LAUNCH", 1); return v; }
 
+// One row's launch; `table` and `lds_bytes` are fps_plan's (the point table in LDS, or the slots + chain log alone).
 template <int T, int E, int I>
 static void launch_fps_reg(int b, int n, int m, int bs, int log2bs, const float *dataset, int *idxs,
-                           float *new_xyz, int *tie_out, int tie_iters, const int *prefix_in) {
-  const size_t chain_bytes = tie_out ? (size_t)(tie_iters + 2) * 8 : 0;
-  const size_t table_bytes = FPS_SLOT_BYTES + (size_t)n * sizeof(float4) + chain_bytes;
-  const int use_table = fps_use_table();
-  if (table_bytes <= 160 * 1024 && (use_table || table_bytes <= 64 * 1024)) {
-    launch_grid<fps_reg_kernel<T, E, I, true>, T / 64>(dim3(b), (int)table_bytes, n, m, bs, log2bs, dataset, idxs, new_xyz,
+                           float *new_xyz, int *tie_out, int tie_iters, const int *prefix_in, bool table, int lds_bytes) {
+  if (table) {
+    launch_grid<fps_reg_kernel<T, E, I, true>, T / 64>(dim3(b), lds_bytes, n, m, bs, log2bs, dataset, idxs, new_xyz,
                                                        tie_out, tie_iters, prefix_in);
   } else {
-    launch_grid<fps_reg_kernel<T, E, I, false>, T / 64>(dim3(b), (int)(FPS_SLOT_BYTES + chain_bytes), n, m, bs, log2bs, dataset,
+    launch_grid<fps_reg_kernel<T, E, I, false>, T / 64>(dim3(b), lds_bytes, n, m, bs, log2bs, dataset,
                                                         idxs, new_xyz, tie_out, tie_iters, prefix_in);
   }
   check_launch("furthest_point_sampling");
@@ -894,13 +892,137 @@ static int fps_pick_threads(int n) {
 // Rows of one (T, E) stand in ascending order of I: fps_dispatch takes the first that fits.
 struct FpsRow {
   int T, E, I;
-  void (*launch)(int, int, int, int, int, const float *, int *, float *, int *, int, const int *);
+  void (*launch)(int, int, int, int, int, const float *, int *, float *, int *, int, const int *, bool, int);
 };
 template <int T, int E, int I> constexpr FpsRow fps_row() { return {T, E, I, launch_fps_reg<T, E, I>}; }
 static const FpsRow FPS_ROWS[] = {
     fps_row<64, 0, 1>(),  fps_row<64, 0, 2>(),  fps_row<64, 1, 1>(),  fps_row<64, 1, 2>(),  fps_row<64, 2, 1>(),
     fps_row<256, 0, 2>(), fps_row<256, 1, 1>(), fps_row<256, 1, 2>(), fps_row<256, 1, 4>(), fps_row<256, 1, 8>(),
     fps_row<512, 0, 16>(), fps_row<512, 0, 48>()};
+
+}  // namespace pwclo
+
+extern "C" int knn_point_slabs(int n);
+
+namespace pwclo {
+
+// What a sampler call launches: every launcher of this file and furthest_point_sampling_plan_query ask here, so the
+// kernel a call reaches, its launch geometry and the calls that are refused are stated once.  Pure host code.
+constexpr int FPS_SMALL_CLOUD = 24576;                  // the largest cloud of one workgroup (fps_row<512, 0, 48>)
+constexpr int FPS_COOP_POINTS = COOP_T * 16;            // points of one workgroup of the cooperative sampler
+constexpr int FPS_SORTED_CLOUD = 2 * FPS_COOP_POINTS;   // from here on the spatial order pays for itself (ENTRY_AUTO)
+constexpr int FPS_COOP_PLAIN_WGS = 224 * (1024 / COOP_T);   // workgroups that are certainly co-resident on an idle device
+constexpr int FPS_LDS_LIMIT = 160 * 1024;
+
+// entry: PWCLO_FPS_ENTRY_*.  temp: the (b,n) scratch is given / 8-byte aligned; buffers: the entry's other required
+// pointers are all non-NULL (sorted: dataset, sorted copy, permutation; slab: workspace, slab table, status).
+struct FpsCall {
+  int entry, b, n, m;
+  bool temp, temp_aligned, buffers;
+  bool tie_out;
+  int tie_iters;
+  bool prefix_in, capturing;
+};
+// The PWCLO_FPS_* switches a plan depends on; sorted: PWCLO_FPS_SORTED as pointnet2_ops/_ext.py reads it (ENTRY_AUTO only).
+struct FpsSwitches { int table, coop, coop_launch, xcd_local, sorted; };
+struct FpsPlan {
+  int kernel;                         // PWCLO_FPS_REG / COOP / STREAM / SLAB / REFUSED
+  int T, E, I, table;                 // reg: fps_reg_kernel<T, E, I, table>; slab: fps_slab_kernel<T, I>
+  int G, sorted, per_launch, grid, launch, launches, xcd_local;   // coop: fps_coop_kernel<16, sorted>
+  int lds, bs, log2bs;
+  const FpsRow *row;
+  char msg[224];                      // refused: the launcher's message
+};
+
+#define FPS_PLAN_REQUIRE(cond, ...)                       \
+  do {                                                    \
+    if (!(cond)) {                                        \
+      snprintf(pl.msg, sizeof(pl.msg), __VA_ARGS__);      \
+      return pl;                                          \
+    }                                                     \
+  } while (0)
+
+static FpsPlan fps_plan(const FpsCall &c, const FpsSwitches &sw) {
+  FpsPlan pl = {};
+  pl.kernel = PWCLO_FPS_REFUSED;
+  const int n = c.n;
+  const size_t chain_bytes = c.tie_out ? (size_t)(c.tie_iters + 2) * 8 : 0;
+  const int G = n > 0 ? ceil_div(n, FPS_COOP_POINTS) : 0;   // workgroups per cloud, <= 16 points per thread
+  // (8 points per thread on twice the workgroups was measured slower: 3.2 vs 2.9 us per iteration at n = 120k)
+  const bool coop_fits = G <= COOP_MAX_G && c.temp_aligned && (size_t)COOP_WS_WORDS * 2 <= (size_t)n;
+  bool coop = false;
+  if (c.entry == PWCLO_FPS_ENTRY_SLAB) {
+    FPS_PLAN_REQUIRE(c.buffers, "furthest_point_sampling(slab): workspace, slab table and status buffer are required");
+    const size_t lds = FPS_SLOT_BYTES + (size_t)(n > 0 ? n : 0) * sizeof(float4) + chain_bytes;
+    FPS_PLAN_REQUIRE(n >= 4096 && n <= 8 * 18 * 64 && knn_point_slabs(n) == 8 && lds <= (size_t)FPS_LDS_LIMIT,
+                     "furthest_point_sampling(slab): n=%d is outside the slab sampler's range (8 slabs, LDS table)", n);
+    const FpsGeometry g = fps_geometry(n);
+    pl.bs = g.bs; pl.log2bs = g.log2bs;
+    pl.kernel = PWCLO_FPS_SLAB;
+    pl.T = 512;
+    pl.I = (n + 7) / 8 <= 16 * 64 ? 16 : 18;            // rows of one of the 8 waves, 64 per register
+    pl.table = 1;
+    pl.lds = (int)lds;
+    pl.grid = c.b;
+    return pl;
+  }
+  if (c.entry == PWCLO_FPS_ENTRY_SORTED) {
+    FPS_PLAN_REQUIRE(n > FPS_SMALL_CLOUD && (long long)n < (1ll << PRI_SHIFT),
+                     "furthest_point_sampling(sorted): n=%d outside (24576, 2^23)", n);
+    FPS_PLAN_REQUIRE(c.buffers && c.temp,
+                     "furthest_point_sampling(sorted): dataset, sorted copy, permutation and temp are required");
+    FPS_PLAN_REQUIRE(coop_fits, "furthest_point_sampling(sorted): n=%d needs %d workgroups per cloud (max %d) / an 8-byte aligned temp",
+                     n, G, COOP_MAX_G);
+    coop = true;
+    pl.sorted = 1;
+  } else {
+    FPS_PLAN_REQUIRE(n >= 1, "furthest_point_sampling: n=%d must be >= 1", n);
+    FPS_PLAN_REQUIRE((long long)n < (1ll << PRI_SHIFT) * 1ll, "furthest_point_sampling: n=%d too large", n);
+  }
+  const FpsGeometry g = fps_geometry(n);
+  pl.bs = g.bs; pl.log2bs = g.log2bs;
+  if (!coop && n <= FPS_SMALL_CLOUD) {               // one workgroup per cloud, every point in a register
+    const int T = fps_pick_threads(n);
+    int E = 0;
+    while ((T << E) < g.bs) ++E;                    // T < bs: a thread owns 2^E residues
+    const int I = ceil_div(n, E == 0 ? T : g.bs);   // points per residue per thread
+    for (const FpsRow &r : FPS_ROWS)   // the first fit is the smallest: rows of one (T, E) are listed by ascending I
+      if (r.T == T && r.E == E && I <= r.I) { pl.row = &r; break; }
+    FPS_PLAN_REQUIRE(pl.row != nullptr, "furthest_point_sampling: n=%d needs (T, E, I) = (%d, %d, %d), which has no kernel", n, T, E, I);
+    const size_t table_bytes = FPS_SLOT_BYTES + (size_t)n * sizeof(float4) + chain_bytes;
+    pl.kernel = PWCLO_FPS_REG;
+    pl.T = pl.row->T; pl.E = pl.row->E; pl.I = pl.row->I;
+    pl.table = (table_bytes <= (size_t)FPS_LDS_LIMIT && (sw.table || table_bytes <= 64 * 1024)) ? 1 : 0;
+    pl.lds = (int)(pl.table ? table_bytes : FPS_SLOT_BYTES + chain_bytes);
+    pl.grid = c.b;
+    return pl;
+  }
+  if (!coop) {
+    FPS_PLAN_REQUIRE(c.temp, "furthest_point_sampling: n=%d needs the (b,n) temp buffer pre-filled with 1e10", n);
+    coop = sw.coop && coop_fits;
+    if (!coop) {                                     // one workgroup streams the cloud from global memory
+      pl.kernel = PWCLO_FPS_STREAM;
+      pl.T = 1024;
+      pl.grid = c.b;
+      return pl;
+    }
+    pl.sorted = (c.entry == PWCLO_FPS_ENTRY_AUTO && sw.sorted && n >= FPS_SORTED_CLOUD) ? 1 : 0;
+  }
+  // cooperative multi-workgroup sampler; `temp` doubles as its (re-zeroed) exchange workspace
+  pl.kernel = PWCLO_FPS_COOP;
+  pl.T = COOP_T;
+  pl.I = 16;
+  pl.G = G;
+  pl.per_launch = FPS_COOP_PLAIN_WGS / G;
+  if (pl.per_launch >= 8) pl.per_launch &= ~7;          // whole groups of 8 clouds: the grid is padded to 8 * G * ceil(clouds / 8)
+  pl.launches = ceil_div(c.b, pl.per_launch);
+  pl.grid = 8 * G * ceil_div(min(pl.per_launch, c.b), 8);   // of the first launch (the last may be smaller)
+  pl.launch = (sw.coop_launch && !c.capturing) ? PWCLO_FPS_LAUNCH_COOPERATIVE : PWCLO_FPS_LAUNCH_PLAIN;
+  pl.xcd_local = sw.xcd_local ? 1 : 0;
+  pl.lds = pl.sorted ? (int)((size_t)16 * COOP_T * sizeof(unsigned)) : 0;
+  return pl;
+}
+#undef FPS_PLAN_REQUIRE
 
 // out[b,c,j] = points[b,c,idx[b,j]]; grid (ceil(m/256), c, b) so that small m still fills CUs.
 __global__ __launch_bounds__(256) void gather_points_kernel(int c, int n, int m,
@@ -944,32 +1066,51 @@ extern "C" void group_points_grad_kernel_wrapper(int b, int c, int n, int npoint
 static std::atomic<int> g_xcd_local{-1};    // -1: as PWCLO_FPS_COOP_XCD_LOCAL says (default 1); set by pwclo_fps_large_cloud_exchange
 static std::atomic<int> g_coop_api{-1};     // -1: as PWCLO_FPS_COOP_LAUNCH says (default 1); set by pwclo_fps_large_cloud_launch
 
-static void coop_launch(int b, int n, int m, int bs, int log2bs, int G, const float *dataset,
+// The switches as the launchers take them now: the environment's values (read once per process) and the two setters.
+static FpsSwitches fps_switches() {
+  FpsSwitches sw = {fps_use_table(), fps_use_coop(), g_coop_api.load(), g_xcd_local.load(), 1};
+  if (sw.coop_launch < 0) sw.coop_launch = fps_coop_launch_default();
+  if (sw.xcd_local < 0) sw.xcd_local = fps_coop_xcd_local_default();
+  return sw;
+}
+
+// fps_plan for a launcher: a plan that asks for the cooperative-launch API is made again when the stream is capturing
+// (only these plans pay for the query).
+static FpsPlan fps_plan_for_launch(FpsCall c) {
+  const FpsSwitches sw = fps_switches();
+  FpsPlan pl = fps_plan(c, sw);
+  if (pl.kernel == PWCLO_FPS_COOP && pl.launch == PWCLO_FPS_LAUNCH_COOPERATIVE) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(current_stream(), &cap);
+    if (cap != hipStreamCaptureStatusNone) {
+      c.capturing = true;
+      pl = fps_plan(c, sw);
+    }
+  }
+  return pl;
+}
+
+static void coop_launch(const FpsPlan &pl, int b, int n, int m, const float *dataset,
                         unsigned long long *ws, int *idxs, float *new_xyz, const int *perm,
                         const float *orig_dataset) {
+  const int bs = pl.bs, log2bs = pl.log2bs, G = pl.G;
   hipStream_t st = current_stream();
   unsigned *host_err = device_error_word();            // a timeout inside the kernel reaches pwclo_last_error()
   if (host_err == nullptr) return;
   const char *dbg = getenv("PWCLO_FPS_COOP_DEBUG_TIMEOUT");   // test hook of the failure path (read per call)
   int holdback = (dbg && atoi(dbg) == 1) ? 1 : 0;
   int spin_limit = holdback == 1 ? 256 : (1 << 21);
-  int xcd_local = g_xcd_local.load();
-  if (xcd_local < 0) xcd_local = fps_coop_xcd_local_default();
+  int xcd_local = pl.xcd_local;
   int poll_delay = fps_coop_poll_delay();
   hipLaunchKernelGGL(fps_coop_init_kernel, dim3(ceil_div(b * COOP_WS_WORDS, 256)), dim3(256), 0, st, ws,
                      b * COOP_WS_WORDS);
-  int coop_api = g_coop_api.load();
-  if (coop_api < 0) coop_api = fps_coop_launch_default();
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  (void)hipStreamIsCapturing(st, &cap);
-  const bool use_coop_api = coop_api && cap == hipStreamCaptureStatusNone;
-  const bool sorted = perm != nullptr;
-  const size_t lds = sorted ? (size_t)16 * COOP_T * sizeof(unsigned) : 0;
+  const bool use_coop_api = pl.launch == PWCLO_FPS_LAUNCH_COOPERATIVE;
+  const bool sorted = pl.sorted != 0;
+  const size_t lds = (size_t)pl.lds;
   const void *kern = sorted ? reinterpret_cast<const void *>(fps_coop_kernel<16, true>)
                             : reinterpret_cast<const void *>(fps_coop_kernel<16, false>);
   if (sorted) raise_lds_limit<fps_coop_kernel<16, true>>((int)lds);
-  int per_launch = (224 * (1024 / COOP_T)) / G;         // plain launch: workgroups that are certainly co-resident on an idle device
-  if (per_launch >= 8) per_launch &= ~7;                // whole groups of 8 clouds: the grid is padded to 8 * G * ceil(clouds / 8)
+  const int per_launch = pl.per_launch;
   for (int c0 = 0; c0 < b; c0 += per_launch) {
     const int nb = min(per_launch, b - c0);
     const float *d0 = dataset + (size_t)c0 * n * 3;
@@ -1004,35 +1145,22 @@ static void fps_dispatch(int b, int n, int m, const float *dataset, float *temp,
                          float *new_xyz, int *tie_out = nullptr, int tie_iters = 0,
                          const int *prefix_in = nullptr) {
   if (b <= 0 || m <= 0) return;
-  PWCLO_REQUIRE(n >= 1, "furthest_point_sampling: n=%d must be >= 1", n);
-  PWCLO_REQUIRE((long long)n < (1ll << PRI_SHIFT) * 1ll, "furthest_point_sampling: n=%d too large", n);
-  const auto [bs, log2bs] = fps_geometry(n);
-  if (n <= 24576) {                               // one workgroup per cloud, every point in a register
-    const int T = fps_pick_threads(n);
-    int E = 0;
-    while ((T << E) < bs) ++E;                  // T < bs: a thread owns 2^E residues
-    const int I = ceil_div(n, E == 0 ? T : bs);   // points per residue per thread
-    const FpsRow *row = nullptr;
-    for (const FpsRow &r : FPS_ROWS)   // the first fit is the smallest: rows of one (T, E) are listed by ascending I
-      if (r.T == T && r.E == E && I <= r.I) { row = &r; break; }
-    PWCLO_REQUIRE(row != nullptr, "furthest_point_sampling: n=%d needs (T, E, I) = (%d, %d, %d), which has no kernel", n, T, E, I);
-    row->launch(b, n, m, bs, log2bs, dataset, idxs, new_xyz, tie_out, tie_iters, prefix_in);
+  const FpsPlan pl = fps_plan_for_launch({PWCLO_FPS_ENTRY_PLAIN, b, n, m, temp != nullptr,
+                                          (reinterpret_cast<uintptr_t>(temp) & 7) == 0, true, tie_out != nullptr, tie_iters,
+                                          prefix_in != nullptr, false});
+  PWCLO_REQUIRE(pl.kernel != PWCLO_FPS_REFUSED, "%s", pl.msg);
+  if (pl.kernel == PWCLO_FPS_REG) {
+    pl.row->launch(b, n, m, pl.bs, pl.log2bs, dataset, idxs, new_xyz, tie_out, tie_iters, prefix_in, pl.table != 0, pl.lds);
     return;
   }
-  PWCLO_REQUIRE(temp != nullptr,
-                "furthest_point_sampling: n=%d needs the (b,n) temp buffer pre-filled with 1e10", n);
   if (tie_out != nullptr)   // the large-cloud samplers keep no tie record: later levels run in full
     hipLaunchKernelGGL(fps_fill_flag_kernel, dim3(ceil_div(b, 256)), dim3(256), 0, current_stream(), tie_out, b, 1);
-  const int G = ceil_div(n, COOP_T * 16);                // workgroups per cloud, <= 16 points per thread
-  // (8 points per thread on twice the workgroups was measured slower: 3.2 vs 2.9 us per iteration at n = 120k)
-  if (fps_use_coop() && G <= COOP_MAX_G && (reinterpret_cast<uintptr_t>(temp) & 7) == 0 && (size_t)COOP_WS_WORDS * 2 <= (size_t)n) {
-    // cooperative multi-workgroup sampler; `temp` doubles as its (re-zeroed) exchange workspace
-    coop_launch(b, n, m, bs, log2bs, G, dataset, reinterpret_cast<unsigned long long *>(temp), idxs, new_xyz,
-                nullptr, nullptr);
+  if (pl.kernel == PWCLO_FPS_COOP) {
+    coop_launch(pl, b, n, m, dataset, reinterpret_cast<unsigned long long *>(temp), idxs, new_xyz, nullptr, nullptr);
     return;
   }
-  hipLaunchKernelGGL((fps_stream_kernel<1024>), dim3(b), dim3(1024), 0, current_stream(), n, m, bs,
-                     log2bs, dataset, temp, idxs, new_xyz);
+  hipLaunchKernelGGL((fps_stream_kernel<1024>), dim3(pl.grid), dim3(pl.T), 0, current_stream(), n, m, pl.bs,
+                     pl.log2bs, dataset, temp, idxs, new_xyz);
   check_launch("furthest_point_sampling(stream)");
 }
 
@@ -1061,15 +1189,11 @@ extern "C" void furthest_point_sampling_sorted_kernel_wrapper(int b, int n, int 
                                                               const float *sorted, const int *perm, float *temp,
                                                               int *idxs, float *new_xyz) {
   if (b <= 0 || m <= 0) return;
-  PWCLO_REQUIRE(n > 24576 && (long long)n < (1ll << PRI_SHIFT), "furthest_point_sampling(sorted): n=%d outside (24576, 2^23)", n);
-  PWCLO_REQUIRE(dataset != nullptr && sorted != nullptr && perm != nullptr && temp != nullptr,
-                "furthest_point_sampling(sorted): dataset, sorted copy, permutation and temp are required");
-  const auto [bs, log2bs] = fps_geometry(n);
-  const int G = ceil_div(n, COOP_T * 16);
-  PWCLO_REQUIRE(G <= COOP_MAX_G && (reinterpret_cast<uintptr_t>(temp) & 7) == 0 && (size_t)COOP_WS_WORDS * 2 <= (size_t)n,
-                "furthest_point_sampling(sorted): n=%d needs %d workgroups per cloud (max %d) / an 8-byte aligned temp", n, G,
-                COOP_MAX_G);
-  coop_launch(b, n, m, bs, log2bs, G, sorted, reinterpret_cast<unsigned long long *>(temp), idxs, new_xyz, perm, dataset);
+  const FpsPlan pl = fps_plan_for_launch({PWCLO_FPS_ENTRY_SORTED, b, n, m, temp != nullptr,
+                                          (reinterpret_cast<uintptr_t>(temp) & 7) == 0,
+                                          dataset != nullptr && sorted != nullptr && perm != nullptr, false, 0, false, false});
+  PWCLO_REQUIRE(pl.kernel != PWCLO_FPS_REFUSED, "%s", pl.msg);
+  coop_launch(pl, b, n, m, sorted, reinterpret_cast<unsigned long long *>(temp), idxs, new_xyz, perm, dataset);
 }
 
 // ---- spatial order for the large-cloud sampler, on the device (round 3) -----------------------------------------------
@@ -1275,24 +1399,40 @@ extern "C" void furthest_point_sampling_slab_kernel_wrapper(int b, int n, int m,
                                                             const void *knn_workspace, const int *slab_tab,
                                                             int *status) {
   if (b <= 0 || m <= 0) return;
-  PWCLO_REQUIRE(knn_workspace != nullptr && slab_tab != nullptr && status != nullptr,
-                "furthest_point_sampling(slab): workspace, slab table and status buffer are required");
-  const auto [bs, log2bs] = fps_geometry(n);
-  const size_t chain_bytes = tie_out ? (size_t)(tie_iters + 2) * 8 : 0;
-  const size_t lds = FPS_SLOT_BYTES + (size_t)n * sizeof(float4) + chain_bytes;
-  PWCLO_REQUIRE(knn_point_slabs(n) == 8 && n >= 4096 && n <= 8 * 18 * 64 && lds <= 160 * 1024,
-                "furthest_point_sampling(slab): n=%d is outside the slab sampler's range (8 slabs, LDS table)", n);
+  const FpsPlan pl = fps_plan({PWCLO_FPS_ENTRY_SLAB, b, n, m, false, false,
+                               knn_workspace != nullptr && slab_tab != nullptr && status != nullptr, tie_out != nullptr,
+                               tie_iters, false, false}, fps_switches());
+  PWCLO_REQUIRE(pl.kernel != PWCLO_FPS_REFUSED, "%s", pl.msg);
+  const int bs = pl.bs, log2bs = pl.log2bs, lds = pl.lds;
   const int nblk = (n + 63) / 64 + 8;
-  const int per = (n + 7) / 8;
   (void)dataset;
   const auto rows = reinterpret_cast<const float4 *>(knn_workspace);
-  if (per <= 16 * 64)
-    launch_grid<fps_slab_kernel<512, 16>, 8>(dim3(b), (int)lds, n, m, bs, log2bs, nblk, rows, slab_tab, idxs, new_xyz, tie_out,
+  if (pl.I == 16)
+    launch_grid<fps_slab_kernel<512, 16>, 8>(dim3(b), lds, n, m, bs, log2bs, nblk, rows, slab_tab, idxs, new_xyz, tie_out,
                                              tie_iters, status);
   else
-    launch_grid<fps_slab_kernel<512, 18>, 8>(dim3(b), (int)lds, n, m, bs, log2bs, nblk, rows, slab_tab, idxs, new_xyz, tie_out,
+    launch_grid<fps_slab_kernel<512, 18>, 8>(dim3(b), lds, n, m, bs, log2bs, nblk, rows, slab_tab, idxs, new_xyz, tie_out,
                                              tie_iters, status);
   check_launch("furthest_point_sampling(slab)");
+}
+
+extern "C" int furthest_point_sampling_plan_query(int entry, int b, int n, int m, int temp, int tie_iters, int tie_out,
+                                                  int prefix_in, int capturing, int use_table, int use_coop, int coop_launch,
+                                                  int xcd_local, int use_sorted, int *out, char *msg, int msg_len) {
+  if (entry < PWCLO_FPS_ENTRY_PLAIN || entry > PWCLO_FPS_ENTRY_AUTO || b <= 0 || m <= 0 || tie_iters < 0 || out == nullptr) return -1;
+  FpsSwitches sw = fps_switches();
+  if (use_table >= 0) sw.table = use_table;
+  if (use_coop >= 0) sw.coop = use_coop;
+  if (coop_launch >= 0) sw.coop_launch = coop_launch;
+  if (xcd_local >= 0) sw.xcd_local = xcd_local;
+  if (use_sorted >= 0) sw.sorted = use_sorted;
+  const FpsPlan pl = fps_plan({entry, b, n, m, temp != 0, temp == 1, temp != 0, tie_out != 0, tie_iters, prefix_in != 0,
+                               capturing != 0}, sw);
+  const int fields[16] = {pl.kernel, pl.T, pl.E, pl.I, pl.table, pl.G, pl.sorted, pl.per_launch, pl.grid, pl.launch, pl.launches,
+                          pl.xcd_local, pl.lds, pl.bs, pl.log2bs, 0};
+  for (int i = 0; i < 16; ++i) out[i] = fields[i];
+  if (msg != nullptr && msg_len > 0) snprintf(msg, (size_t)msg_len, "%s", pl.msg);
+  return pl.kernel == PWCLO_FPS_REFUSED ? 1 : 0;
 }
 
 extern "C" void gather_points_kernel_wrapper(int b, int c, int n, int npoints, const float *points,

@@ -131,17 +131,75 @@ def _fps_sorted_order(points):
     return sorted_pts, perm.to(torch.int32).contiguous()
 
 
+_FPS_PLAN_FIELDS = ("kernel", "T", "E", "I", "table", "G", "sorted", "per_launch", "grid", "launch", "launches", "xcd_local",
+                    "lds_bytes", "bs", "log2bs")
+_FPS_PLAN_KERNELS = ("reg", "coop", "stream", "slab", "refused")     # PWCLO_FPS_*
+_FPS_PLAN_ENTRIES = {"plain": 0, "sorted": 1, "slab": 2, "auto": 3}  # PWCLO_FPS_ENTRY_*
+_FPS_PLAN_LAUNCHES = ("plain", "cooperative")                        # PWCLO_FPS_LAUNCH_*
+
+
+def furthest_point_sampling_plan(b, n, m, entry="auto", temp=True, temp_aligned=True, tie_iters=0, tie_out=False,
+                                 prefix_in=False, capturing=False, use_table=None, use_coop=None, coop_launch=None,
+                                 xcd_local=None, use_sorted=None, order=None):
+    """furthest_point_sampling_plan_query: what a sampler call launches for a (b, n, 3) batch and m samples -> dict of the
+    fields documented in include/pwclo_ops.h, ``kernel`` as "reg" / "coop" / "stream" / "slab" / "refused" (then with
+    ``message``, the launcher's), ``launch`` as "plain" / "cooperative".  ``entry``: "plain" (``fused.fps_with_xyz`` and the
+    xyz / chain wrappers), "sorted", "slab" (``fused.fps_slab_with_xyz``) or "auto" (``furthest_point_sampling`` below).
+    ``temp`` / ``temp_aligned``: the (b, n) scratch is given / 8-byte aligned ("sorted" and "slab": temp=False stands for a
+    missing buffer).  The switches: None = as the launchers read them (PWCLO_FPS_TABLE, PWCLO_FPS_COOP,
+    PWCLO_FPS_COOP_LAUNCH, PWCLO_FPS_COOP_XCD_LOCAL, PWCLO_FPS_SORTED); ``order``: None = ``LARGE_CLOUD_ORDER``
+    (PWCLO_FPS_ORDER_TORCH), reported for sorted plans as who builds the spatial order.  Host only: works without a GPU."""
+    import ctypes
+    out = (ctypes.c_int * 16)()
+    msg = ctypes.create_string_buffer(256)
+    if use_sorted is None:
+        use_sorted = _os.environ.get("PWCLO_FPS_SORTED", "1") != "0"
+    args = (_FPS_PLAN_ENTRIES[entry], int(b), int(n), int(m), (1 if temp_aligned else 2) if temp else 0, int(tie_iters),
+            int(bool(tie_out)), int(bool(prefix_in)), int(bool(capturing)), _setting(use_table), _setting(use_coop),
+            _setting(coop_launch), _setting(xcd_local), int(bool(use_sorted)))
+    if _lib.load().furthest_point_sampling_plan_query(*args, out, msg, len(msg)) < 0:
+        raise ValueError("furthest_point_sampling_plan_query%r" % (args,))
+    plan = dict(zip(_FPS_PLAN_FIELDS, out[:len(_FPS_PLAN_FIELDS)]))
+    plan["kernel"] = _FPS_PLAN_KERNELS[plan["kernel"]]
+    plan["launch"] = _FPS_PLAN_LAUNCHES[plan["launch"]] if plan["kernel"] == "coop" else None
+    plan["order"] = (order or LARGE_CLOUD_ORDER) if plan["sorted"] else None
+    if plan["kernel"] == "refused":
+        plan["message"] = msg.value.decode()
+    return plan
+
+
+_FPS_ROUTES = {}
+
+
+def _fps_route(n, use_sorted):
+    """(kernel, spatial order first) of ``furthest_point_sampling`` for clouds of n points: the plan's answer, kept per n
+    (neither depends on the batch, the sample count or the settings that can change inside a process)."""
+    key = (n, use_sorted)
+    route = _FPS_ROUTES.get(key)
+    if route is None:
+        plan = furthest_point_sampling_plan(1, n, 1, use_sorted=use_sorted)
+        if len(_FPS_ROUTES) >= 64:
+            _FPS_ROUTES.clear()
+        route = _FPS_ROUTES[key] = (plan["kernel"], bool(plan["sorted"]))
+    return route
+
+
 def furthest_point_sampling(points, nsamples):
     """sampling.cpp:66-87.  (B,N,3) f32 -> (B,nsamples) i32.  The reference's (B,N) `tmp` scratch
     is only allocated when the cloud is too large for the register-resident kernel; those clouds (N > 24576) are
     also brought into a spatially coherent order first, which lets the cooperative sampler skip -- exactly -- the
-    distance update of every wave whose cell the new sample cannot reach (PWCLO_FPS_SORTED=0: plain order)."""
+    distance update of every wave whose cell the new sample cannot reach (PWCLO_FPS_SORTED=0: plain order).  Which of
+    the three it is comes from the launchers' own plan (``furthest_point_sampling_plan``): clouds the cooperative
+    sampler cannot take (more than 32 workgroups, PWCLO_FPS_COOP=0) go to the streaming kernel in plain order."""
     _float(points, "points"); _gpu(points)
     B, N, _ = points.shape
     out = torch.zeros((B, nsamples), dtype=torch.int32, device=points.device)
-    if N > 24576:
+    if B <= 0 or nsamples <= 0:
+        return out
+    kernel, in_order = _fps_route(N, _os.environ.get("PWCLO_FPS_SORTED", "1") != "0")
+    if kernel in ("coop", "stream"):     # the cooperative sampler, or (clouds it cannot take) the streaming kernel
         tmp_t = torch.full((B, N), 1e10, dtype=torch.float32, device=points.device)
-        if _os.environ.get("PWCLO_FPS_SORTED", "1") != "0" and N >= 2 * 1024 * 16:
+        if in_order:
             sorted_pts, perm = _fps_sorted_order(points)
             _lib.call("furthest_point_sampling_sorted_kernel_wrapper", points.device, B, N, nsamples, _p(points),
                       _p(sorted_pts), _p(perm), _p(tmp_t), _p(out), 0)
