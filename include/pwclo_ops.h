@@ -457,12 +457,10 @@ void kitti_transform_filter_kernel_wrapper(int n, const double *tr, const float 
  * |y| < near, compared in fp32.  n may span several frames laid end to end (b*n rows). */
 void kitti360_filter_kernel_wrapper(int n, float ground_z, float near, const float *points, float *xyz, int *keep);
 
-/* Stable per-frame compaction after either filter: keep, pos (b,n) i32 with pos = inclusive prefix sum of
- * keep along each frame; kept row i of frame f is copied to out[f, pos-1] (out (b,cap,3) f32, zero-filled by
- * the caller: zero rows are never selected by furthest_point_sampling), counts (b) i32 = min(kept, cap). */
-void compact_frames_kernel_wrapper(int b, int n, int cap, const int *keep, const int *pos, const float *xyz,
-                                   float *out, int *counts);
-/* The same compaction with the scan inside (no `pos` input): one workgroup per frame, ballot / popcount slots, stable. */
+/* Stable per-frame compaction after either filter: keep (b,n) i32, any non-zero word keeps the row; the kept rows of
+ * frame f are copied in frame order to out[f, 0 .. count-1] (out (b,cap,3) f32, zero-filled by the caller: zero rows are
+ * never selected by furthest_point_sampling; kept rows beyond cap are dropped), counts (b) i32 = min(kept, cap).  The
+ * scan is inside the kernel: one workgroup per frame, ballot / popcount slots. */
 void compact_frames_scan_kernel_wrapper(int b, int n, int cap, const int *keep, const float *xyz, float *out, int *counts);
 /* Filter + compaction of S raw sweeps of different lengths in one launch (one workgroup per stream): sweeps (S,R,4) f32
  * with row stride R (16-byte aligned), lengths (S) i32 in DEVICE memory (clamped to [0, R]; only rows [0, lengths[s])

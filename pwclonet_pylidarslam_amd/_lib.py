@@ -77,7 +77,6 @@ SIGNATURES = {
     "ingest_sequence_kernel_wrapper": ([_i, _i, _i, _i, _F, _F], None),
     "kitti_transform_filter_kernel_wrapper": ([_i, _F, _F, _F, _F], None),
     "kitti360_filter_kernel_wrapper": ([_i, ctypes.c_float, ctypes.c_float, _F, _F, _F], None),
-    "compact_frames_kernel_wrapper": ([_i, _i, _i, _F, _F, _F, _F, _F], None),
     "fps_spatial_order_workspace_bytes": ([_i, _i], ctypes.c_longlong),
     "fps_spatial_order_kernel_wrapper": ([_i, _i, _F, _F, _F, _F], None),
     "softmax_wsum_supported_k": ([_i], _i),

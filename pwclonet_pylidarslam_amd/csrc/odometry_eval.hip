@@ -87,8 +87,11 @@ __global__ __launch_bounds__(64) void odom_cumdist_kernel(const int *__restrict_
 }
 
 // evaluation.py:236-271 (= eval_odometry.py:316-361): for every first frame f = 0, step, 2*step, ... and every
-// segment length L: last = first i >= f with dist[i] > dist[f] + L (dist is non-decreasing, so the reference's
-// linear search is this upper-bound search); pose_error = inv(inv(R[f]) R[last]) . (inv(G[f]) G[last]);
+// segment length L: last = first i >= f with dist[i] > dist[f] + L.  The reference searches linearly; this is an
+// upper-bound search, the same frame wherever dist is non-decreasing.  odom_cumdist_kernel's dist is that only up to an
+// ulp: over a stationary stretch a lane's prefix may sit one ulp below the previous lane's last value, so the two
+// searches can part only if dist[f] + L falls inside such an ulp, and then by frames of one pose (DESIGN.md section 8,
+// f4).  pose_error = inv(inv(R[f]) R[last]) . (inv(G[f]) G[last]);
 // row = [f, r_err / L, t_err / L, L, speed], speed = L / (0.1 * (last - f + 1)).
 __global__ __launch_bounds__(256) void odom_sequence_errors_kernel(int nseq, const int *__restrict__ seq_start,
                                                                    const int *__restrict__ slot_start,

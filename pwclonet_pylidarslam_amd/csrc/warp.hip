@@ -131,30 +131,13 @@ __global__ __launch_bounds__(256) void kitti360_filter_kernel(int n, float groun
   keep[i] = k ? 1 : 0;
 }
 
-// Stable per-frame compaction of the kept rows: pos = inclusive scan of keep along the frame, row i of
-// frame f goes to out[f, pos-1]; rows >= count stay as the caller zero-filled them (the sampler never
-// selects zero rows).  Rows beyond `cap` are dropped (the caller sizes cap >= max count).
-__global__ __launch_bounds__(256) void compact_frames_kernel(int n, int cap, const int *__restrict__ keep,
-                                                             const int *__restrict__ pos,
-                                                             const float *__restrict__ xyz,
-                                                             float *__restrict__ out, int *__restrict__ counts) {
-  const int f = blockIdx.y;
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const size_t row = (size_t)f * n + i;
-  const int p = pos[row];
-  if (keep[row] != 0 && p <= cap) {
-    float *d = out + ((size_t)f * cap + (p - 1)) * 3;
-    d[0] = xyz[row * 3 + 0]; d[1] = xyz[row * 3 + 1]; d[2] = xyz[row * 3 + 2];
-  }
-  if (i == n - 1) counts[f] = p < cap ? p : cap;
-}
-
-// The same compaction WITHOUT a precomputed scan (round 3: the scan used to be torch.cumsum, a library kernel on the product
-// path of BASELINE configs[4]): one 1024-thread workgroup per frame; wave w owns a contiguous range of rows and walks it
-// 64 rows at a time (coalesced), a ballot + popcount gives every kept row its slot inside the step, the running sum of
-// popcounts its slot inside the wave's range; the 16 waves' totals are scanned through LDS between a counting pass and
-// the writing pass.  Stable (frame order), same output as the scan + scatter pair.
+// Stable per-frame compaction of the kept rows (keep != 0): kept row number p (frame order, from 0) of frame f goes to
+// out[f, p]; rows >= count stay as the caller zero-filled them (the sampler never selects zero rows).  Rows beyond `cap`
+// are dropped (the caller sizes cap >= max count).  The scan is inside the kernel (it used to be torch.cumsum, a library
+// kernel on the product path of BASELINE configs[4]): one 1024-thread workgroup per frame; wave w owns a contiguous range
+// of rows and walks it 64 rows at a time (coalesced), a ballot + popcount gives every kept row its slot inside the step,
+// the running sum of popcounts its slot inside the wave's range; the 16 waves' totals are scanned through LDS between a
+// counting pass and the writing pass.  Stable (frame order).
 __global__ __launch_bounds__(1024) void compact_frames_scan_kernel(int n, int cap, const int *__restrict__ keep,
                                                                    const float *__restrict__ xyz,
                                                                    float *__restrict__ out, int *__restrict__ counts) {
@@ -264,15 +247,6 @@ extern "C" void kitti360_filter_kernel_wrapper(int n, float ground_z, float near
   hipLaunchKernelGGL(kitti360_filter_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, current_stream(), n, ground_z,
                      near, points, xyz, keep);
   check_launch("kitti360_filter");
-}
-
-extern "C" void compact_frames_kernel_wrapper(int b, int n, int cap, const int *keep, const int *pos,
-                                              const float *xyz, float *out, int *counts) {
-  if (b <= 0 || n <= 0) return;
-  PWCLO_REQUIRE(b <= 65535 && cap > 0, "compact_frames: b=%d cap=%d out of range", b, cap);
-  hipLaunchKernelGGL(compact_frames_kernel, dim3(ceil_div(n, 256), b), dim3(256), 0, current_stream(), n, cap,
-                     keep, pos, xyz, out, counts);
-  check_launch("compact_frames");
 }
 
 extern "C" void compact_frames_scan_kernel_wrapper(int b, int n, int cap, const int *keep, const float *xyz, float *out,

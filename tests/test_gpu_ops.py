@@ -440,9 +440,11 @@ def test_knn_rows_kernel_ties_and_ragged_shapes(cuda, k, n, s):
 
 
 def test_kitti_transform_filter_and_sampling(cuda):
-    """the on-device transform + filter equals the NumPy restatement of the dataset code
-    (fp64 arithmetic, coordinates rounded to fp32: identical up to one fp32 ulp of BLAS-vs-fma ordering;
-    same mask), and both sampling modes return npoints survivors."""
+    """the on-device transform + filter is the source-order host model (tests/frontend_model.py) bit
+    for bit, coordinates and mask, with no row excused; against the NumPy restatement of the dataset code (a BLAS matmul,
+    another summation order) it is identical up to one fp32 ulp with the same mask away from the thresholds; and both
+    sampling modes return npoints survivors."""
+    import frontend_model
     from oracle.preprocess import transform_filter as ref_tf
     from pwclonet_pylidarslam_amd import preprocess
     rng = np.random.default_rng(12)
@@ -454,6 +456,9 @@ def test_kitti_transform_filter_and_sampling(cuda):
     q, keep = ref_tf(pts, tr)
     xyz, k = preprocess.transform_filter(torch.from_numpy(pts).to(cuda), tr)
     got = xyz.cpu().numpy()
+    model_words, model_keep = frontend_model.kitti_row(pts, tr)
+    assert np.array_equal(got.view(np.int32), model_words)
+    assert np.array_equal(k.cpu().numpy(), model_keep.astype(np.int32))
     ref32 = q.astype(np.float32)
     ulp = np.abs(got.view(np.int32).astype(np.int64) - ref32.view(np.int32).astype(np.int64))
     assert ulp.max() <= 1 and (ulp > 0).mean() < 1e-3
