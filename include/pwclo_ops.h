@@ -1164,6 +1164,47 @@ void keyframe_icp_push_kernel_wrapper(int S, int M, int n, const double *T, cons
  * by Shepperd's branch selection in fp64, normalised, w >= 0, rounded once.  Every other row keeps its bits.  S <= 1024. */
 void stream_motion_from_refined_kernel_wrapper(int S, const int *active, const int *valid, const double *T, float *motion);
 
+/* ---- 9. point-to-plane registration against a persistent voxel map per stream -------------------
+ * A stream's map is a toroidal grid of Nx x Ny x Nz voxels of edge voxel_size -- every N even, 4 <= N <= 1024, Nx Ny Nz <
+ * 2^28, S <= 1024 --: voxel c lives in cell ((cz mod Nz) Ny + (cy mod Ny)) Nx + (cx mod Nx), floor-mod.  With h_a =
+ * floor((double)w_a / (voxel_size / 2)): voxel c_a = h_a >> 1, octant = (h_z & 1) << 2 | (h_y & 1) << 1 | (h_x & 1); a
+ * coordinate is storable where -2^21 <= h_a < 2^21 on every axis.  The grid buffer (DEVICE memory, 8-byte aligned) has four
+ * sections: coordinate words (S, cells) u64 = (cz + 2^20) << 42 | (cy + 2^20) << 21 | (cx + 2^20), all ones = empty; keys
+ * (S, cells, 8) u64 = seq << 32 | row, all ones = empty; points and normals (S, cells, 8, 3) fp32 in the stream's map frame.
+ * P (S,4,4) fp64: the pose of the last registered frame in the map frame; nonempty (S) ints; seq (S) ints, frames inserted
+ * since the map was emptied.  active (S) ints or NULL in every call: a stream with active[s] == 0 keeps every bit. */
+
+/* 264 bytes per voxel and stream; 0 for arguments out of range. */
+long long voxel_map_bytes(int S, int nx, int ny, int nz);
+/* Streams with active && (restart || armed) (restart, armed: S ints or NULL) get an empty map: every coordinate word all
+ * ones, P = I, nonempty = 0, seq = 0.  armed is only read here; voxel_pose clears it. */
+void voxel_begin_kernel_wrapper(int S, int nx, int ny, int nz, const int *active, const int *restart, const int *armed,
+                                void *grid, double *P, int *nonempty, int *seq);
+/* Inserts cloud / normals (S,n,3) with the pose W = I where nonempty (S ints or NULL) is given and zero, else P T (T (S,4,4)
+ * or NULL: P), for the streams with active and insert[s] != 0 (insert: S ints or NULL = all).  w = fp32(W p) (fp64, one
+ * rounding), n_w = fp32(R_W n).  A point is inserted where w is finite, storable and |w_a - t_a| < (N_a / 2 - 1) voxel_size
+ * on every axis (t the translation of W; fp64, strict).  A cell whose word differs from the point's voxel is stale: the word
+ * is replaced, its keys emptied.  The octant keeps the smallest key seq[s] << 32 | row (64-bit atomicMin, the only atomic
+ * read-modify-write), and the row whose key stands writes w and n_w.  slot (S,n) ints: cell * 8 + octant a row asked for, -1
+ * where it is not inserted.  Three launches; nothing here writes P, nonempty or seq. */
+void voxel_insert_kernel_wrapper(int S, int n, int nx, int ny, int nz, double voxel_size, const float *cloud,
+                                 const float *normals, const double *P, const double *T, const int *nonempty, const int *seq,
+                                 void *grid, int *slot, const int *active, const int *insert);
+/* After the insertion, one thread per stream: P <- I where nonempty was zero, else P T (T NULL: P stays); a stream with
+ * insert[s] != 0 (NULL: all) gets seq += 1 and nonempty = 1; armed[s] = 0 (armed: S ints or NULL). */
+void voxel_pose_kernel_wrapper(int S, const double *T, double *P, int *nonempty, int *seq, int *armed, const int *active,
+                               const int *insert);
+/* One thread per point of p (S,n,3): q = fp32(P T p) (T NULL: the identity).  Candidates: the stored entries of the 27
+ * voxels around q's voxel, in the order dz, dy, dx ascending, then octants ascending, where the cell's word equals the wanted
+ * voxel and the key is not empty; fp32 d = sqrtf((dx dx + dy dy) + dz dz), strict <, so the first candidate stays on a tie.
+ * No pair when q is not storable, there is no candidate, !(d <= max_dist) or the winner's normal is zero; max_dist <=
+ * voxel_size.  Then section 6's row with Rm = R_P^T, the same 30 sums in the same order: partial (S, groups(n), 32) fp64 in
+ * the layout of section 6's solver, zero rows for an idle stream.  cell / octant (S,n) ints and dist (S,n) fp32, all three
+ * or all NULL: the nearest candidate whatever became of the pair (-1, -1, +Inf: none). */
+void voxel_accumulate_kernel_wrapper(int S, int n, int nx, int ny, int nz, double voxel_size, const float *p, const double *P,
+                                     const double *T, const void *grid, double sigma, float max_dist, double *partial,
+                                     int *cell, int *octant, float *dist, const int *active);
+
 #ifdef __cplusplus
 }
 #endif

@@ -199,6 +199,12 @@ SIGNATURES = {
     "keyframe_gate_kernel_wrapper": ([_i, _i, _F, _F, _F, ctypes.c_double, ctypes.c_double, _F, _F, _F], None),
     "keyframe_icp_push_kernel_wrapper": ([_i, _i, _i] + [_F] * 13, None),
     "stream_motion_from_refined_kernel_wrapper": ([_i, _F, _F, _F, _F], None),
+    "voxel_map_bytes": ([_i, _i, _i, _i], ctypes.c_longlong),
+    "voxel_begin_kernel_wrapper": ([_i] * 4 + [_F] * 7, None),
+    "voxel_insert_kernel_wrapper": ([_i] * 5 + [ctypes.c_double] + [_F] * 10, None),
+    "voxel_pose_kernel_wrapper": ([_i] + [_F] * 7, None),
+    "voxel_accumulate_kernel_wrapper": ([_i] * 5 + [ctypes.c_double] + [_F] * 4 + [ctypes.c_double, ctypes.c_float] + [_F] * 5,
+                                        None),
 }
 
 _lib = None

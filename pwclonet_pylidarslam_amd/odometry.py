@@ -82,6 +82,9 @@ class StreamingOdometry:
     ``"knn"`` refiner in both modes: a frame goes into the local map only when the motion since the stream's last inserted
     frame exceeds a threshold, decided on the device inside the refiner's graph (``refiner().keyframe_state()``).  The
     projective refiner has no keyframe gate yet.
+    ``refine=dict(kind="voxel_map", voxel_size=1.0, extent=(128, 128, 32), ...)`` (``voxel_map.VoxelMapRefiner``'s keywords;
+    DESIGN.md section 24) registers the same cloud against a persistent voxel map per stream instead of the ring of frames,
+    in both modes, with ``keyframe=`` and ``feedback=``.
     ``refine=dict(..., feedback=True)`` (raw mode with ``deskew=True`` only, ``ValueError`` otherwise): after the
     registration one launch writes the refined pose's row into ``motion()`` for the streams that registered a pair in this
     call, so the next sweep is de-skewed with the refined motion instead of the network's; primed and idle streams keep
@@ -136,9 +139,10 @@ class StreamingOdometry:
         if self._feedback and not (sweeps is not None and dict(sweeps).get("deskew", False)):
             raise ValueError("StreamingOdometry: refine=dict(feedback=True) hands the refined pose to the de-skew prior and "
                              "needs raw mode with sweeps=dict(..., deskew=True)")
-        if self._refine_kind not in ("knn", "projective"):
-            raise ValueError("StreamingOdometry: refine=dict(kind=%r): \"knn\" (registration.IcpRefiner, the default) or "
-                             "\"projective\" (projective.ProjectiveIcpRefiner)" % (self._refine_kind,))
+        if self._refine_kind not in ("knn", "projective", "voxel_map"):
+            raise ValueError("StreamingOdometry: refine=dict(kind=%r): \"knn\" (registration.IcpRefiner, the default), "
+                             "\"projective\" (projective.ProjectiveIcpRefiner) or \"voxel_map\" "
+                             "(voxel_map.VoxelMapRefiner)" % (self._refine_kind,))
         if self._refine_kind == "projective":
             if "keyframe" in self._refine_cfg:
                 raise ValueError("StreamingOdometry: refine=dict(kind=\"projective\", keyframe=...): the projective refiner "
@@ -426,10 +430,11 @@ class StreamingOdometry:
             return
         if self._refine_kind == "projective":
             return self._refine_projective(pose)
-        from . import registration
+        from . import registration, voxel_map
         cloud = self._tapped[:, :self.num_points, :3].contiguous()
         if self._refiner is None:
-            self._refiner = registration.IcpRefiner(self.streams, self.num_points, graph=self.graph, **self._refine_cfg)
+            make = voxel_map.VoxelMapRefiner if self._refine_kind == "voxel_map" else registration.IcpRefiner
+            self._refiner = make(self.streams, self.num_points, graph=self.graph, **self._refine_cfg)
             self._ref_rel = torch.zeros((self.max_frames, self.streams, 4, 4), dtype=torch.float64, device=cloud.device)
             self._ref_abs = torch.zeros_like(self._ref_rel)
             self._ref_restart = torch.zeros_like(self._active)

@@ -341,6 +341,8 @@ class IcpRefiner:
     instead (``StreamingOdometry``'s, which its step's graph has just written); ``register_adopted(cloud, init)`` then
     loads no mask at all."""
 
+    _name = "IcpRefiner"        # in front of the messages of the methods a subclass shares
+
     def __init__(self, streams, num_points, map_size=4, iters=10, sigma=0.5, max_dist=1.0, k_normals=10, damping=1e-6,
                  threshold_delta_pose=1e-4, min_pairs=64, graph=True, per_stream=False, keyframe=None):
         S, n, M, k = int(streams), int(num_points), int(map_size), int(k_normals)
@@ -445,7 +447,7 @@ class IcpRefiner:
         their next delivered frame only fills the map.  The streams are armed on the device, without a sync, and the
         first launch of that frame's registration empties the map.  No new capture: the word is device memory that the
         graph reads."""
-        mask = None if streams is None else stream_masks.stream_mask(streams, self.streams, "streams", "IcpRefiner", True)
+        mask = None if streams is None else stream_masks.stream_mask(streams, self.streams, "streams", self._name, True)
         if self.bufs is None:
             return
         armed = self.bufs["armed"]
@@ -518,43 +520,43 @@ class IcpRefiner:
     def _check(self, cloud, init):
         S, n = self.streams, self.num_points
         if not isinstance(cloud, torch.Tensor) or cloud.dtype != torch.float32 or tuple(cloud.shape) != (S, n, 3):
-            raise ValueError("IcpRefiner: cloud must be float32 (%d, %d, 3), got %s %s"
-                             % (S, n, getattr(cloud, "dtype", type(cloud)), tuple(getattr(cloud, "shape", ()))))
+            raise ValueError("%s: cloud must be float32 (%d, %d, 3), got %s %s"
+                             % (self._name, S, n, getattr(cloud, "dtype", type(cloud)), tuple(getattr(cloud, "shape", ()))))
         ok = isinstance(init, torch.Tensor) and (
             (init.dtype == torch.float64 and tuple(init.shape) == (S, 4, 4)) or
             (init.dtype == torch.float32 and tuple(init.shape) == (S, 7)))
         if not ok:
-            raise ValueError("IcpRefiner: init must be float64 (%d, 4, 4) or float32 (%d, 7) pose rows, got %s %s"
-                             % (S, S, getattr(init, "dtype", type(init)), tuple(getattr(init, "shape", ()))))
+            raise ValueError("%s: init must be float64 (%d, 4, 4) or float32 (%d, 7) pose rows, got %s %s"
+                             % (self._name, S, S, getattr(init, "dtype", type(init)), tuple(getattr(init, "shape", ()))))
         if not cloud.is_cuda or not init.is_cuda:
             raise RuntimeError("CPU not supported")
 
     def _mask(self, mask, what):
-        return stream_masks.stream_mask(mask, self.streams, what, "IcpRefiner")
+        return stream_masks.stream_mask(mask, self.streams, what, self._name)
 
     def adopt_words(self, active, restart):
         """Before the first call: the graph reads the caller's (S,) int32 0 / 1 device words, which the caller writes
         before every ``register_adopted`` (a lock-step view's ``active`` holds ones)."""
         if self.bufs is not None:
-            raise RuntimeError("IcpRefiner: adopt_words comes before the first call (a captured graph keeps its words)")
-        _need_mask(active, "IcpRefiner", self.streams)
-        _need(restart, "IcpRefiner: restart", torch.int32, (self.streams,))
+            raise RuntimeError("%s: adopt_words comes before the first call (a captured graph keeps its words)" % self._name)
+        _need_mask(active, self._name, self.streams)
+        _need(restart, "%s: restart" % self._name, torch.int32, (self.streams,))
         self._words = (active, restart)
 
     def register_adopted(self, cloud, init, all_active=False):
         """``register`` with this call's masks already in the adopted words: no mask is parsed, copied or loaded.
         ``all_active``: the caller knows on the host that ``active`` holds ones (the cloud then goes in as a plain copy)."""
         if self._words is None:
-            raise RuntimeError("IcpRefiner: register_adopted needs adopt_words(active, restart)")
+            raise RuntimeError("%s: register_adopted needs adopt_words(active, restart)" % self._name)
         return self._register(cloud, init, every=bool(all_active))
 
     def register(self, cloud, init, active=None, restart=None, trace=False):
         if trace and self.graph:
-            raise ValueError("IcpRefiner: trace=True needs graph=False (a replayed graph cannot hand out its iterations)")
+            raise ValueError("%s: trace=True needs graph=False (a replayed graph cannot hand out its iterations)" % self._name)
         if not self.per_stream and (active is not None or restart is not None):
-            raise ValueError("IcpRefiner: active / restart masks need per_stream=True")
+            raise ValueError("%s: active / restart masks need per_stream=True" % self._name)
         if self._words is not None:
-            raise RuntimeError("IcpRefiner: the words are the caller's (adopt_words): call register_adopted")
+            raise RuntimeError("%s: the words are the caller's (adopt_words): call register_adopted" % self._name)
         act = None if active is None else self._mask(active, "active")
         rst = None if restart is None else self._mask(restart, "restart")
         return self._register(cloud, init, act, rst, trace, every=act is None)
@@ -565,7 +567,7 @@ class IcpRefiner:
         first, own, plain = self.bufs is None, self._words is None, act is None and rst is None
         if first:                                           # every row of the cloud starts defined; the per-stream view
             seen = None if not self.per_stream else act if own else self._words[0]        # reads the mask once, here
-            _, cloud = stream_masks.seed_idle_rows(seen, self.streams, "IcpRefiner", cloud)
+            _, cloud = stream_masks.seed_idle_rows(seen, self.streams, self._name, cloud)
         if init.dim() == 2:
             init = evaluation.rows_to_transforms(init)
         if first:
