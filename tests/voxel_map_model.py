@@ -227,6 +227,54 @@ def register(grid, cloud, init, normals32=None, iters=10, sigma=0.5, max_dist=1.
     return T, status, steps
 
 
+# ---- the stand-alone ops with their masks --------------------------------------------------------------------------------------------
+
+def frame_voxels_share_no_cell(slot, want):
+    """The invariant voxel_claim_kernel rests on: among the rows of one frame that are inserted, every cell is asked for by
+    one voxel only.  slot, want: what ``Grid.slots`` returns."""
+    slot, want = np.asarray(slot), np.asarray(want)
+    kept = slot >= 0
+    pairs = np.unique(np.stack([slot[kept] >> 3, want[kept]], axis=1), axis=0)
+    return len(np.unique(pairs[:, 0])) == len(pairs)
+
+
+def insert_pose(grid, T=None, use_nonempty=True):
+    """vm_insert_pose: I for an empty map (where the nonempty word is passed), else P T, or P where no T is given."""
+    if use_nonempty and not grid.nonempty:
+        return np.eye(4)
+    return grid.P.copy() if T is None else pose_mul(grid.P, np.asarray(T, dtype=np.float64))
+
+
+def masked_begin(grid, active=1, restart=0, armed=0):
+    """``voxel_map.begin`` for one stream: cleared where ``active and (restart or armed)``; armed is only read.
+    -> whether the stream was cleared."""
+    clear = bool(active) and (bool(restart) or bool(armed))
+    if clear:
+        grid.begin()
+    return clear
+
+
+def masked_insert(grid, cloud, normals32, T=None, use_nonempty=True, active=1, insert=1):
+    """``voxel_map.insert`` for one stream -> slot (n,), or None where the stream does not insert (its slot rows are not
+    written).  P, nonempty and seq stay: they are ``masked_pose``'s."""
+    if not (bool(active) and bool(insert)):
+        return None
+    W = insert_pose(grid, T, use_nonempty)
+    assert frame_voxels_share_no_cell(*grid.slots(cloud, W)[1:])
+    return grid.insert(cloud, normals32, W)
+
+
+def masked_pose(grid, T=None, armed=0, active=1, insert=1):
+    """``voxel_map.pose`` for one stream -> the armed word afterwards."""
+    if not bool(active):
+        return armed
+    grid.P = insert_pose(grid, T)
+    if bool(insert):
+        grid.seq += 1
+        grid.nonempty = 1
+    return 0
+
+
 # ---- scenes --------------------------------------------------------------------------------------------------------------------------
 
 def walk_clouds(seed, frames, n, step, spread):
