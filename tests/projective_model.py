@@ -2,7 +2,12 @@
 22): projection, z-buffer, normal map, model build, association and the registration loop, with the sums and the solve
 taken from tests/icp_model.py.  A point's pixel is computed in fp32 in the device's (the reference's) order of operations;
 ``margin`` says in fp64 how far the coordinates are from a rounding boundary or a validity limit, so that a test can keep
-its inputs away from where the last bit of an fp32 atan2 / asin decides.  Everything else is fp64."""
+its inputs away from where the last bit of an fp32 atan2 / asin decides.  Everything else is fp64.
+
+``planted(name)`` makes the model wrong in one named way (FAULTS) for as long as the block lasts: tests/test_projective_cases_cpu.py
+uses it to prove that a case of tests/projective_cases.py tells the right answer from the wrong one."""
+import contextlib
+
 import numpy as np
 
 import icp_model as icp
@@ -10,6 +15,33 @@ import icp_model as icp
 EMPTY = -1
 DET_EPS = np.float32(1e-6)
 F = np.float32
+TILE_H, TILE_W = 8, 32                           # csrc/projective.hip: PROJ_TILE_H, PROJ_TILE_W
+
+FAULTS = {
+    "seam_wrap": "a column that rounds to W wraps to column 0 instead of being refused",
+    "half_up": "rows and columns round half up, not half to even",
+    "tie_highest": "a z-buffer keeps the highest index among equal ranges",
+    "ignore_range": "a z-buffer keeps the lowest index, whatever the ranges",
+    "halo_low": "a tile of the normal map stages one pixel less of border above and to the left",
+    "halo_high": "a tile of the normal map stages one pixel less of border below and to the right",
+    "edge_next_row": "the normal map's bounds check lets column W through, which is the next row's column 0",
+    "slot_tie_le": "association takes a later slot at an equal distance (<= for <)",
+    "max_dist_lt": "association refuses a pair at exactly max_dist (< for <=)",
+    "zero_normal_skip": "association skips a slot without a normal instead of refusing the pair",
+    "no_cursor_clamp": "the handover uses the cursor as it is: a slot of a neighbouring stream, or nothing",
+}
+FAULT = None
+
+
+@contextlib.contextmanager
+def planted(name):
+    global FAULT
+    assert name in FAULTS and FAULT is None
+    FAULT = name
+    try:
+        yield
+    finally:
+        FAULT = None
 
 
 def image(H, W, up_fov, down_fov):
@@ -32,6 +64,10 @@ def pixels(pts, im):
         col = (F(0.5) * (theta / F(np.pi) + F(1.0))) * F(W)
         row = (F(1.0) - (phi + im["down"]) / im["fov"]) * F(H)
         rr, rc = np.rint(row), np.rint(col)
+        if FAULT == "half_up":
+            rr, rc = np.floor(row + F(0.5)), np.floor(col + F(0.5))
+        if FAULT == "seam_wrap":
+            rc = np.where(rc == W, F(0.0), rc)
         valid = (r > 0) & np.isfinite(r) & (rr >= 0) & (rr <= H - 1) & (rc >= 0) & (rc <= W - 1)
         p64 = p.astype(np.float64)
         r64 = np.sqrt((p64[:, :3] ** 2).sum(axis=1))
@@ -45,13 +81,32 @@ def pixels(pts, im):
     return ri, ci, r, valid, margin
 
 
+def coords(pts, im):
+    """pts (n, >=3) fp32 -> dict(row32, col32: the fp32 coordinates before rounding, as ``pixels`` computes them; row64, col64:
+    the same in fp64; r: the fp32 range).  For tests that have to know where a point lies, not only which pixel it gets."""
+    p = np.asarray(pts, dtype=np.float32)
+    x, y, z = p[:, 0], p[:, 1], p[:, 2]
+    H, W = im["H"], im["W"]
+    with np.errstate(all="ignore"):
+        r = np.sqrt((x * x + y * y) + z * z, dtype=np.float32)
+        col = (F(0.5) * (-np.arctan2(y, x, dtype=np.float32) / F(np.pi) + F(1.0))) * F(W)
+        row = (F(1.0) - (np.arcsin(z / r, dtype=np.float32) + im["down"]) / im["fov"]) * F(H)
+        p64 = p.astype(np.float64)
+        r64 = np.sqrt((p64[:, :3] ** 2).sum(axis=1))
+        col64 = 0.5 * (-np.arctan2(p64[:, 1], p64[:, 0]) / np.pi + 1.0) * W
+        row64 = (1.0 - (np.arcsin(p64[:, 2] / r64) + im["down64"]) / im["fov64"]) * H
+    return dict(row32=row, col32=col, row64=row64, col64=col64, r=r)
+
+
 def zbuffer(pix, r, valid, HW):
     """pix (n,) pixel indices, r (n,) fp32 ranges -> winner (HW,) int64: per pixel the index of the smallest r, the lowest
     index among equal r; -1 for an empty pixel."""
     win = np.full((HW,), EMPTY, dtype=np.int64)
     idx = np.flatnonzero(valid)
     if idx.size:
-        order = idx[np.lexsort((idx, r[idx], pix[idx]))]          # by pixel, then range, then index
+        tie = -idx if FAULT == "tie_highest" else idx
+        rng = np.zeros_like(r[idx]) if FAULT == "ignore_range" else r[idx]
+        order = idx[np.lexsort((tie, rng, pix[idx]))]             # by pixel, then range, then index
         first = np.ones(order.size, dtype=bool)
         first[1:] = pix[order][1:] != pix[order][:-1]
         win[pix[order][first]] = order[first]
@@ -80,10 +135,20 @@ def moments(vmap, k):
     h = k // 2
     v = np.zeros((H + 2 * h, W + 2 * h, 3))
     v[h:h + H, h:h + W] = vmap.astype(np.float64)
+    if FAULT == "edge_next_row":
+        v[h:h + H - 1, h + W] = vmap[1:, 0].astype(np.float64)
+    lo, hi = h - (FAULT == "halo_low"), h - (FAULT == "halo_high")
+    ys, xs = np.arange(H), np.arange(W)
+    y0, x0 = ys // TILE_H * TILE_H, xs // TILE_W * TILE_W
     m, C = np.zeros((H, W, 3)), np.zeros((H, W, 3, 3))
     for dy in range(k):
         for dx in range(k):
             w = v[dy:dy + H, dx:dx + W]
+            if lo < h or hi < h:                                   # what the pixel's own tile did not stage reads as zero
+                sy, sx = ys + dy - h, xs + dx - h
+                w = w.copy()
+                w[(sy < y0 - lo) | (sy >= y0 + TILE_H + hi)] = 0.0
+                w[:, (sx < x0 - lo) | (sx >= x0 + TILE_W + hi)] = 0.0
             m += w
             C += w[..., :, None] * w[..., None, :]
     return m, C
@@ -156,13 +221,16 @@ def associate(vmap, model_v, model_n, T, im, max_dist, pixel=None):
         d = q32 - y
         dist = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2], dtype=np.float32)
         cand = (pix >= 0) & (y != 0).any(axis=1)
-        take = cand & ((best < 0) | (dist < bd))
+        if FAULT == "zero_normal_skip":
+            cand &= (mn[m, at] != 0).any(axis=1)
+        with np.errstate(invalid="ignore"):
+            take = cand & ((best < 0) | ((dist <= bd) if FAULT == "slot_tie_le" else (dist < bd)))
         second = np.where(take & (best >= 0), bd, np.where(cand & ~take, np.minimum(second, dist), second))
         best = np.where(take, m, best)
         bd = np.where(take, dist, bd)
     with np.errstate(invalid="ignore", divide="ignore"):
         gap = np.where(np.isfinite(second), (second - bd) / np.maximum(second, 1e-30), np.inf)
-        ok = (best >= 0) & (bd <= np.float32(max_dist))
+        ok = (best >= 0) & ((bd < np.float32(max_dist)) if FAULT == "max_dist_lt" else (bd <= np.float32(max_dist)))
     ok &= (mn[np.clip(best, 0, M - 1), at] != 0).any(axis=1)
     return dict(q32=q32, pixel=pix, own_pixel=own, slot=np.where(ok, best, EMPTY), margin=np.where(occupied, margin, np.inf),
                 gap=gap, dist=bd)
@@ -220,6 +288,25 @@ class Map:
         self.A[slot], self.live[slot] = np.eye(4), 1
         self.v[slot], self.n[slot] = vmap, nmap
         self.cursor = (slot + 1) % self.M
+
+
+def map_push(T, vmap, nmap, map_v, map_n, A, live, cursor):
+    """The handover of every stream, in place, as projective.map_push: T (S, 4, 4), vmap / nmap (S, H, W, 3), map_v / map_n
+    (S, M, H, W, 3), A (S, M, 4, 4), live (S, M), cursor (S,).  A cursor outside [0, M) is clamped first."""
+    S, M = live.shape
+    fv, fn = map_v.reshape((S * M,) + map_v.shape[2:]), map_n.reshape((S * M,) + map_n.shape[2:])
+    for s in range(S):
+        slot = min(max(int(cursor[s]), 0), M - 1)
+        if FAULT == "no_cursor_clamp":
+            slot = int(cursor[s])
+        if 0 <= s * M + slot < S * M:
+            fv[s * M + slot], fn[s * M + slot] = vmap[s], nmap[s]
+        for m in range(M):
+            if m == slot:
+                A[s, m], live[s, m] = np.eye(4), 1
+            elif live[s, m]:
+                A[s, m] = A[s, m] @ T[s]
+        cursor[s] = 0 if slot + 1 == M else slot + 1
 
 
 def register(mp, vmap, nmap, init, im, iters=10, sigma=0.5, max_dist=1.0, damping=1e-6, threshold=1e-4, min_pairs=64,
