@@ -1205,6 +1205,63 @@ void voxel_accumulate_kernel_wrapper(int S, int n, int nx, int ny, int nz, doubl
                                      const double *T, const void *grid, double sigma, float max_dist, double *partial,
                                      int *cell, int *octant, float *dist, const int *active);
 
+/* ---- 10. pose-graph backend: SE(3) graph optimisation per stream --------------------------------
+ * The reference's GraphSLAM (slam/backend.py) without g2o: per stream a graph of at most N = max_poses vertices X (N,S,4,4)
+ * fp64 row-major (count[s] in use, vertex 0 the identity), the odometry edge k-1 -> k with measurement Zc[k] (N,S,4,4) and
+ * information diag(2,2,2,5,5,5) for every vertex k >= 1, nloops[s] <= ML loop edges loop_ij (S,ML,2) ints (i < j), loop_Z
+ * (S,ML,4,4) the pose of j in i's frame, loop_Om (S,ML,6,6), and nabs[s] <= MA absolute edges abs_i (S,MA) ints, abs_G
+ * (S,MA,4,4), abs_Om (S,MA,6,6).  Edge ids of a stream: chain edge k at k, loop l at N + l, absolute edge a at N + ML + a; E =
+ * N + ML + MA.  Error of an edge: Delta = Z^-1 X_i^-1 X_j (absolute: G^-1 X_i), e = (t_Delta, q_x, q_y, q_z) with q the unit
+ * quaternion of R_Delta by Shepperd's branch selection, w >= 0; chi2 = sum e^T Omega e.  Retraction X <- X . [R(q), rho], q =
+ * (sqrt(1 - |nu|^2), nu), the rotation of the product rebuilt from its normalised quaternion.  Slots (S,E,136) doubles per
+ * edge: e 0..5, Omega e 6..11, Ji^T Omega Ji 12..47, Ji^T Omega Jj 48..83, Jj^T Omega Jj 84..119, Ji^T Omega e 120..125, Jj^T
+ * Omega e 126..131, chi2 132.  inc_ptr (S,N+1), inc_ent (S,2 ML + MA) ints: per vertex the loop and absolute edges that touch
+ * it, entries edge id * 2 + side (1: the vertex is the edge's j; absolute edges have side 1), written by the host.  Status
+ * words (S) ints: 1 converged, 2 a chain without loop or absolute edge, 4 a non-finite chi2 (an idle stream keeps its word, so there is no idle bit); active (S) ints or NULL in
+ * every call: a stream with active[s] == 0, or with a non-zero status word, is skipped and keeps every bit.  S <= 1024; all
+ * capacities >= 1.  All pointers DEVICE memory; every sum has a fixed order and there is no atomic. */
+
+/* First launch of an optimisation of `iters` <= diag_stride iterations: status = 0, or 3 for a graph with a single vertex or
+ * without loop and absolute edges (then chi2 = 0); rows [0, iters) of pcg_used, relres, accepted (S,diag_stride) are cleared. */
+void pose_graph_begin_kernel_wrapper(int S, int iters, int diag_stride, const int *active, const int *count, const int *nloops,
+                                     const int *nabs, int *status, int *pcg_used, double *relres, int *accepted, double *chi2);
+/* One thread per stream, with stream_record_refined's words: pair (active and valid; valid NULL: every active stream): k =
+ * count, X[k] = X[k-1] . Z, Zc[k] = Z, count = k + 1, with Z = rel[s] (S,4,4) fp64 or quat2mat of rows[s] (S,7) fp32 (exactly
+ * one of the two is given); stream_count (S ints or NULL): the stream engine's count after its own append, then k =
+ * stream_count - 1, which must equal the graph's count; k >= N or a k that is not the next vertex sets *overflow and writes
+ * nothing.  Prime (active and not valid): the empty graph: X[0] =
+ * I, count = 1, nloops = nabs = 0, epoch[s] += 1. */
+void pose_graph_append_kernel_wrapper(int S, int N, const int *active, const int *valid, const int *stream_count,
+                                      const double *rel, const float *rows, double *X, double *Zc, int *count, int *nloops, int *nabs, int *epoch, int *overflow);
+/* One thread per edge at the poses X.  slots given: the whole slot of every edge; chi_only (S,E) given instead: the chi2
+ * term alone (the evaluation at trial poses). */
+void pose_graph_linearise_kernel_wrapper(int S, int N, int ML, int MA, const int *active, const int *status, const int *count,
+                                         const int *nloops, const int *nabs, const double *X, const double *Zc,
+                                         const int *loop_ij, const double *loop_Z, const double *loop_Om, const int *abs_i,
+                                         const double *abs_G, const double *abs_Om, double *slots, double *chi_only);
+/* One workgroup per stream, iteration `it` of the call.  chi2[s] = the sum of the slots' chi2 terms (not finite: status 4);
+ * b and the 6 x 6 block diagonal of H gathered per vertex (chain edge v, chain edge v + 1, then the incidence list); it == 0:
+ * lam[s] = 1e-5 max diag H, nu[s] = 2; max |b| <= 1e-12: status 1.  Then block-Jacobi preconditioned conjugate gradients on
+ * (H + lam I) delta = -b from delta = 0 over the free vertices (vertex 0 is fixed where fix_first != 0) until |r| <= pcg_tol
+ * |b| or pcg_iters iterations; delta (S,N,6), the trial poses Xt (N,S,4,4) = X . D(delta), pcg_used[s,it], relres[s,it] = |r| /
+ * |b|.  work: S N 66 doubles. */
+void pose_graph_solve_kernel_wrapper(int S, int N, int ML, int MA, int fix_first, int it, int pcg_iters, double pcg_tol,
+                                     const int *active, int *status, const int *count, const int *nloops, const int *nabs,
+                                     const int *loop_ij, const int *abs_i, const int *inc_ptr, const int *inc_ent,
+                                     const double *slots, const double *X, double *work, double *delta, double *Xt, double *lam,
+                                     double *nu, double *chi2, int *pcg_used, double *relres, int diag_stride);
+/* The retraction alone: Xt[v] = X[v] . D(delta[v]) for the vertices in use (a fixed vertex is copied). */
+void pose_graph_retract_kernel_wrapper(int S, int N, int fix_first, const int *active, const int *status, const int *count,
+                                       const double *X, const double *delta, double *Xt);
+/* One workgroup per stream.  chi_new (S,E): the chi2 terms at Xt.  rho = (chi2 - chi2_new) / (delta^T (lam delta - b)); accepted
+ * where rho > 0 and chi2_new is finite: X <- Xt, lam <- lam max(1/3, 1 - (2 rho - 1)^3), nu = 2, chi2 = chi2_new, status 1 where
+ * chi2 - chi2_new <= 1e-9 chi2; otherwise lam <- lam nu, nu <- 2 nu.  accepted[s,it] = the decision. */
+void pose_graph_judge_kernel_wrapper(int S, int N, int ML, int MA, int fix_first, int it, const int *active, int *status,
+                                     const int *count, const int *nloops, const int *nabs, const int *loop_ij, const int *abs_i,
+                                     const int *inc_ptr, const int *inc_ent, const double *slots, const double *chi_new,
+                                     const double *delta, const double *Xt, double *X, double *lam, double *nu, double *chi2,
+                                     int *accepted, int diag_stride);
+
 #ifdef __cplusplus
 }
 #endif

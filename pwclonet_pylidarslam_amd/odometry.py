@@ -110,7 +110,7 @@ class StreamingOdometry:
     start as copies of the first active stream's, so that no step ever reads an uninitialised buffer."""
 
     def __init__(self, net, streams=1, num_points=None, max_frames=4096, graph=True, warmup=1, sweeps=None,
-                 per_stream=False, refine=None):
+                 per_stream=False, refine=None, backend=None):
         if not 1 <= int(streams) <= MAX_STREAMS:
             raise ValueError("StreamingOdometry: streams=%d outside [1, %d]" % (int(streams), MAX_STREAMS))
         if int(max_frames) < 1:
@@ -158,6 +158,21 @@ class StreamingOdometry:
                 raise ValueError("StreamingOdometry: refine=dict(kind=\"projective\") registers the rows before the grid, "
                                  "which the front end does not keep when voxel_size is set: leave voxel_size out")
         self._refiner = self._ref_rel = self._ref_abs = self._ref_restart = None
+        self._backend = None        # backend=: pose_graph.PoseGraph, one vertex per recorded frame
+        self._backend_cfg = None if backend is None else dict(backend)
+        self._backend_source = None
+        if backend is not None:
+            self._backend_source = self._backend_cfg.pop("source", "refined" if refine is not None else "network")
+            if self._backend_source not in ("refined", "network"):
+                raise ValueError("StreamingOdometry: backend=dict(source=%r): \"refined\" or \"network\""
+                                 % (self._backend_source,))
+            if self._backend_source == "refined" and refine is None:
+                raise ValueError("StreamingOdometry: backend=dict(source=\"refined\") takes the refiner's poses and needs "
+                                 "refine=dict(...)")
+            for key in ("streams", "max_poses", "graph", "device"):
+                if key in self._backend_cfg:
+                    raise ValueError("StreamingOdometry: backend=dict(%s=...) is the stream's own (streams, max_frames, "
+                                     "graph)" % key)
         self._tapped = None         # refine: the frame batch the last step's graph (or eager step) sampled from
         if refine is not None and self.per_stream != bool(self._refine_cfg.get("per_stream", False)):
             if self.per_stream:
@@ -240,6 +255,8 @@ class StreamingOdometry:
             self._overflow.zero_()
         if self._refiner is not None:
             self._refiner.reset()                           # the maps too
+        if self._backend is not None:
+            self._backend.reset()                           # the graphs too
         self._reset_motion(None)
 
     def _reset_motion(self, mask):
@@ -377,6 +394,37 @@ class StreamingOdometry:
             raise RuntimeError("StreamingOdometry: refined poses need refine=dict(...)")
         return buf
 
+    def backend(self):
+        """With ``backend=``: the ``pose_graph.PoseGraph`` that holds one vertex per recorded frame and stream (``add_loop``,
+        ``add_absolute``, ``optimize``); None before the first frame or without ``backend``."""
+        return self._backend
+
+    def _need_backend(self):
+        if self._backend_cfg is None:
+            raise RuntimeError("StreamingOdometry: optimized poses need backend=dict(...)")
+        return None if self._backend is None else self._backend.bufs["X"]
+
+    def optimized_trajectory(self, stream=None):
+        """With ``backend=``: (frames_seen, S, 4, 4) fp64 device view of the graph's vertices: the source trajectory until
+        ``backend().optimize()`` corrects it; ``stream=i`` as ``trajectory``."""
+        return self._view(self._need_backend(), stream)
+
+    def optimized_relative_poses(self, stream=None):
+        """With ``backend=``: the relative poses of ``optimized_trajectory()``, row 0 the identity, row k = X[k-1]^-1 X[k]
+        (device tensor, not a view)."""
+        X = self.optimized_trajectory(stream)
+        out = torch.eye(4, dtype=torch.float64, device=X.device).expand(X.shape).clone()
+        if X.shape[0] > 1:
+            Rt = X[:-1, ..., :3, :3].transpose(-1, -2)
+            out[1:, ..., :3, :3] = Rt @ X[1:, ..., :3, :3]
+            out[1:, ..., :3, 3] = (Rt @ (X[1:, ..., :3, 3] - X[:-1, ..., :3, 3]).unsqueeze(-1)).squeeze(-1)
+        return out
+
+    def _backend_append(self, rel):
+        """One launch: the graph's vertex of this call's frame, with the step's words (a stream that primed gets an empty
+        graph; idle streams keep theirs).  rel: (S, 4, 4) fp64 or (S, 7) fp32 rows."""
+        self._backend.append(rel, active=self._active, valid=self._valid, count=self._counts)
+
     def refiner(self):
         """The ``registration.IcpRefiner`` behind ``refine=`` (``status()``, ``diagnostics()``); None before the first
         frame or without ``refine``."""
@@ -407,6 +455,10 @@ class StreamingOdometry:
             self._fused_id = id(fused)
         if self._rel is None:
             self._alloc(device)
+        if self._backend_cfg is not None and self._backend is None:
+            from . import pose_graph
+            self._backend = pose_graph.PoseGraph(self.streams, max_poses=self.max_frames, graph=self.graph, device=device,
+                                                 **self._backend_cfg)
         return fused
 
     def _tap(self, source):
@@ -444,6 +496,8 @@ class StreamingOdometry:
         self._feed_motion(T)
         _lib.call("stream_record_refined_kernel_wrapper", cloud.device, self.streams, self.max_frames, _p(self._active),
                   _p(self._valid), _p(self._counts), _p(T), _p(self._ref_rel), _p(self._ref_abs))
+        if self._backend_source == "refined":
+            self._backend_append(T)
 
     def _refine_projective(self, pose):
         """``kind="projective"`` (lock step): the rows the front end kept -- after the filter and the
@@ -460,6 +514,8 @@ class StreamingOdometry:
         self._feed_motion(T)
         _lib.call("stream_record_refined_kernel_wrapper", pose.device, self.streams, self.max_frames, _p(self._active),
                   _p(self._valid), _p(self._counts), _p(T), _p(self._ref_rel), _p(self._ref_abs))
+        if self._backend_source == "refined":
+            self._backend_append(T)
 
     def _feed_motion(self, T):
         """``refine=dict(..., feedback=True)``, one launch after the registration: the streams that registered a pair in
@@ -554,6 +610,8 @@ class StreamingOdometry:
         frame: the pair stage has joined its side streams by the time it returns)."""
         pose, new = fused.stream_step(self._slot, source(), self.num_points)
         self._append(pose)
+        if self._backend_source == "network":          # the level-1 rows: identity for a stream that is no pair
+            self._backend_append(pose[:, 0, :].contiguous())
         self._hand_motion(pose)                        # primed streams' rows are the identity by now
         self._slot.copy_frame1_masked_(new, self._active)
         return pose
