@@ -40,6 +40,8 @@ unsigned *device_error_word();
   } while (0)
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+// Is p a multiple of a (a power of two)?  nullptr is: the launchers ask it of optional pointers too.
+static inline bool aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 // Host-side decision of a scatter-add gradient launcher (group_points.hip: gp_grad_plan, interpolate.hip: ti_grad_plan), in
 // the order the *_grad_plan_query entry points report it (include/pwclo_ops.h).

@@ -68,18 +68,17 @@ __global__ __launch_bounds__(256) void icp_queries_kernel(int M, int n, const do
   const int sm = blockIdx.y, s = sm / M, i = blockIdx.x * 256 + threadIdx.x;
   if (active != nullptr && active[s] == 0) return;        // idle: the stream's q rows stay as they are
   if (i >= n) return;
-  double a[12];
-  const double *am = A + (size_t)sm * 16;
-  if (T != nullptr) {
-    icp_pose_mul(am, T + (size_t)s * 16, a);
+  Se3 a;
+  if (T != nullptr) {                                     // T first: the branches then share no load, and A and T arrive together
+    const Se3 t = se3_load(T + (size_t)s * 16);
+    a = se3_mul(se3_load(A + (size_t)sm * 16), t);
   } else {
-#pragma unroll
-    for (int e = 0; e < 12; ++e) a[e] = am[e];
+    a = se3_load(A + (size_t)sm * 16);
   }
   const float *pi = p + ((size_t)s * n + i) * 3;
   const float pt[3] = {pi[0], pi[1], pi[2]};
   double o[3];
-  icp_pose_apply(a, pt, o);
+  se3_apply(a, pt, o);
   float *qi = q + ((size_t)sm * n + i) * 3;
   qi[0] = (float)o[0]; qi[1] = (float)o[1]; qi[2] = (float)o[2];
 }
@@ -92,13 +91,11 @@ __global__ __launch_bounds__(ICP_ACC_THREADS) void icp_accumulate_kernel(
     const float *__restrict__ dist, const float *__restrict__ map_xyz, const float *__restrict__ map_normals,
     const int *__restrict__ live, const double *__restrict__ Rm, const double *__restrict__ T, double sigma, float max_dist,
     double *__restrict__ partial, const int *__restrict__ active) {
-  __shared__ double wave_row[ICP_ACC_THREADS / 64][ICP_ROW];
   const int s = blockIdx.y, i = blockIdx.x * ICP_ACC_THREADS + threadIdx.x;
   if (active != nullptr && active[s] == 0) {              // idle: a zero row, no gather (the whole workgroup leaves)
-    if (threadIdx.x < ICP_ROW) partial[((size_t)s * gridDim.x + blockIdx.x) * ICP_ROW + threadIdx.x] = 0.0;
+    icp_store_zero_row(partial, s);
     return;
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   double acc[ICP_TERMS];
 #pragma unroll
   for (int e = 0; e < ICP_TERMS; ++e) acc[e] = 0.0;
@@ -122,33 +119,15 @@ __global__ __launch_bounds__(ICP_ACC_THREADS) void icp_accumulate_kernel(
         const float y[3] = {yr[0], yr[1], yr[2]}, nn[3] = {nr[0], nr[1], nr[2]}, qq[3] = {qr[0], qr[1], qr[2]},
                     pp[3] = {pr[0], pr[1], pr[2]};
         if (nn[0] != 0.0f || nn[1] != 0.0f || nn[2] != 0.0f) {
-          double t[12], r9[9];
-#pragma unroll
-          for (int e = 0; e < 12; ++e) t[e] = T[(size_t)s * 16 + e];
+          double r9[9];
 #pragma unroll
           for (int e = 0; e < 9; ++e) r9[e] = Rm[sm * 9 + e];
-          icp_add_pair(pp, qq, y, nn, t, r9, sigma, acc);
+          icp_add_pair(pp, qq, y, nn, se3_load(T + (size_t)s * 16), r9, sigma, acc);
         }
       }
     }
   }
-#pragma unroll
-  for (int e = 0; e < ICP_TERMS; ++e) {
-    double v = acc[e];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    if (lane == 0) wave_row[wave][e] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < ICP_ROW) {
-    double v = 0.0;
-    if (threadIdx.x < ICP_TERMS) {
-      v = wave_row[0][threadIdx.x];
-#pragma unroll
-      for (int w = 1; w < ICP_ACC_THREADS / 64; ++w) v += wave_row[w][threadIdx.x];
-    }
-    partial[((size_t)s * gridDim.x + blockIdx.x) * ICP_ROW + threadIdx.x] = v;
-  }
+  icp_reduce_store_row(acc, partial, s);
 }
 
 // One workgroup.  32 lanes add the columns of a stream's rows in group order, then one thread per stream solves.
@@ -194,12 +173,9 @@ __global__ __launch_bounds__(ICP_SOLVE_THREADS) void icp_solve_kernel(
 #pragma unroll
           for (int e = 0; e < 6; ++e) delta[e] = 0.0;
         } else {
-          double t[12];
-#pragma unroll
-          for (int e = 0; e < 12; ++e) t[e] = T[(size_t)s * 16 + e];
+          Se3 t = se3_load(T + (size_t)s * 16);
           icp_update_pose(delta, t);
-#pragma unroll
-          for (int e = 0; e < 12; ++e) T[(size_t)s * 16 + e] = t[e];
+          se3_store_rows(T + (size_t)s * 16, t);                 // row 3 of the caller's matrix stays
           double nd = 0.0;
 #pragma unroll
           for (int e = 0; e < 6; ++e) nd += delta[e] * delta[e];
@@ -245,32 +221,9 @@ __global__ __launch_bounds__(1024) void icp_map_push_kernel(int M, int n, int S,
     for (size_t j = threadIdx.x; j < nbox; j += 1024) dbox[j] = sbox[j];
   }
   const int m = threadIdx.x;
-  if (m < M) {
-    double *am = A + ((size_t)s * M + m) * 16, *rm = Rm + ((size_t)s * M + m) * 9;
-    if (ins && m == slot) {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) am[e] = (e % 5 == 0) ? 1.0 : 0.0;
-#pragma unroll
-      for (int e = 0; e < 9; ++e) rm[e] = (e % 4 == 0) ? 1.0 : 0.0;
-      live[s * M + m] = 1;
-    } else if (live[s * M + m] != 0) {
-      double a[12], t[12], c[12], r[9];
-#pragma unroll
-      for (int e = 0; e < 12; ++e) {
-        a[e] = am[e];
-        t[e] = T[(size_t)s * 16 + e];
-      }
-      icp_pose_mul(a, t, c);
-#pragma unroll
-      for (int e = 0; e < 12; ++e) am[e] = c[e];
-#pragma unroll
-      for (int e = 0; e < 9; ++e) r[e] = rm[e];
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) rm[3 * i + j] = (t[i] * r[j] + t[4 + i] * r[3 + j]) + t[8 + i] * r[6 + j];   // R_new^T R
-    }
-  }
+  if (m < M)
+    icp_slot_after_push(ins && m == slot, live + s * M + m, A + ((size_t)s * M + m) * 16, T + (size_t)s * 16,
+                        Rm + ((size_t)s * M + m) * 9);
   __syncthreads();                                         // everyone has read the cursor
   if (ins && threadIdx.x == 0) cursor[s] = slot + 1 == M ? 0 : slot + 1;
 }
@@ -291,11 +244,7 @@ __global__ __launch_bounds__(ICP_MAX_SLOTS) void icp_begin_kernel(int M, const i
   if (!clear) return;
   const int m = threadIdx.x;
   if (m < M) {
-    double *am = A + ((size_t)s * M + m) * 16, *rm = Rm + ((size_t)s * M + m) * 9;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) am[e] = (e % 5 == 0) ? 1.0 : 0.0;
-#pragma unroll
-    for (int e = 0; e < 9; ++e) rm[e] = (e % 4 == 0) ? 1.0 : 0.0;
+    icp_slot_identity(A + ((size_t)s * M + m) * 16, Rm + ((size_t)s * M + m) * 9);
     live[s * M + m] = 0;
   }
   if (m == 0) {
@@ -308,15 +257,13 @@ __global__ __launch_bounds__(ICP_MAX_SLOTS) void icp_begin_kernel(int M, const i
 
 using namespace pwclo;
 
-static bool icp_aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 extern "C" void icp_normals_kernel_wrapper(int b, int n, int k, const float *xyz, const int *idx, float *normals,
                                            double *eig) {
   if (b <= 0) return;
   PWCLO_REQUIRE(n >= 2 && (long long)n * 3 < (1ll << 31) && b <= 65535, "icp_normals: b=%d n=%d out of range", b, n);
   PWCLO_REQUIRE(k >= 1 && k <= 63 && k < n, "icp_normals: k=%d outside [1, min(63, n - 1)] for n=%d", k, n);
   PWCLO_REQUIRE((long long)n * (k + 1) < (1ll << 31), "icp_normals: n=%d k=%d neighbour lists too long", n, k);
-  PWCLO_REQUIRE(xyz != nullptr && idx != nullptr && normals != nullptr && eig != nullptr && icp_aligned(eig, 8),
+  PWCLO_REQUIRE(xyz != nullptr && idx != nullptr && normals != nullptr && eig != nullptr && aligned(eig, 8),
                 "icp_normals: xyz, idx, normals and eig (8-byte aligned) are required%s", "");
   hipLaunchKernelGGL(icp_normals_kernel, dim3(ceil_div(n, 256), b), dim3(256), 0, current_stream(), n, k, xyz, idx, normals,
                      eig);
@@ -329,7 +276,7 @@ static void icp_queries_launch(const char *what, int S, int M, int n, const doub
   if (S <= 0) return;
   PWCLO_REQUIRE(M >= 1 && M <= ICP_MAX_SLOTS && n >= 1 && (long long)n * 3 < (1ll << 31) && (long long)S * M <= 65535,
                 "%s: S=%d M=%d n=%d out of range (M <= %d, S * M <= 65535)", what, S, M, n, ICP_MAX_SLOTS);
-  PWCLO_REQUIRE(A != nullptr && p != nullptr && q != nullptr && icp_aligned(A, 8) && icp_aligned(T, 8),
+  PWCLO_REQUIRE(A != nullptr && p != nullptr && q != nullptr && aligned(A, 8) && aligned(T, 8),
                 "%s: A (8-byte aligned), p and q are required", what);
   hipLaunchKernelGGL(icp_queries_kernel, dim3(ceil_div(n, 256), S * M), dim3(256), 0, current_stream(), M, n, A, T, p, q,
                      active);
@@ -342,7 +289,7 @@ extern "C" void icp_queries_kernel_wrapper(int S, int M, int n, const double *A,
 
 extern "C" void icp_queries_masked_kernel_wrapper(int S, int M, int n, const double *A, const double *T, const float *p,
                                                   float *q, const int *active) {
-  PWCLO_REQUIRE(S <= 0 || (active != nullptr && icp_aligned(active, 4)), "icp_queries_masked: active is required%s", "");
+  PWCLO_REQUIRE(S <= 0 || (active != nullptr && aligned(active, 4)), "icp_queries_masked: active is required%s", "");
   icp_queries_launch("icp_queries_masked", S, M, n, A, T, p, q, active);
 }
 
@@ -361,7 +308,7 @@ static void icp_accumulate_launch(const char *what, int S, int M, int n, const f
   PWCLO_REQUIRE(p != nullptr && q != nullptr && idx != nullptr && dist != nullptr && map_xyz != nullptr &&
                 map_normals != nullptr && live != nullptr && R != nullptr && T != nullptr && partial != nullptr,
                 "%s: every pointer is required", what);
-  PWCLO_REQUIRE(icp_aligned(R, 8) && icp_aligned(T, 8) && icp_aligned(partial, 8),
+  PWCLO_REQUIRE(aligned(R, 8) && aligned(T, 8) && aligned(partial, 8),
                 "%s: R, T and partial must be 8-byte aligned", what);
   hipLaunchKernelGGL(icp_accumulate_kernel, dim3(icp_accumulate_groups(n), S), dim3(ICP_ACC_THREADS), 0, current_stream(), M,
                      n, p, q, idx, dist, map_xyz, map_normals, live, R, T, sigma, max_dist, partial, active);
@@ -380,7 +327,7 @@ extern "C" void icp_accumulate_masked_kernel_wrapper(int S, int M, int n, const 
                                                      const float *dist, const float *map_xyz, const float *map_normals,
                                                      const int *live, const double *R, const double *T, double sigma,
                                                      float max_dist, double *partial, const int *active) {
-  PWCLO_REQUIRE(S <= 0 || (active != nullptr && icp_aligned(active, 4)), "icp_accumulate_masked: active is required%s", "");
+  PWCLO_REQUIRE(S <= 0 || (active != nullptr && aligned(active, 4)), "icp_accumulate_masked: active is required%s", "");
   icp_accumulate_launch("icp_accumulate_masked", S, M, n, p, q, idx, dist, map_xyz, map_normals, live, R, T, sigma,
                         max_dist, partial, active);
 }
@@ -394,8 +341,8 @@ static void icp_solve_launch(const char *what, int S, int groups, int it, const 
                 "%s: damping=%g and threshold=%g must be >= 0, min_pairs=%d >= 1", what, damping, threshold, min_pairs);
   PWCLO_REQUIRE(partial != nullptr && T != nullptr && status != nullptr && iters != nullptr && pairs != nullptr &&
                 cost != nullptr && sum != nullptr && delta != nullptr, "%s: every pointer is required", what);
-  PWCLO_REQUIRE(icp_aligned(partial, 8) && icp_aligned(T, 8) && icp_aligned(cost, 8) && icp_aligned(sum, 8) &&
-                icp_aligned(delta, 8), "%s: fp64 arrays must be 8-byte aligned", what);
+  PWCLO_REQUIRE(aligned(partial, 8) && aligned(T, 8) && aligned(cost, 8) && aligned(sum, 8) &&
+                aligned(delta, 8), "%s: fp64 arrays must be 8-byte aligned", what);
   hipLaunchKernelGGL(icp_solve_kernel, dim3(1), dim3(ICP_SOLVE_THREADS), 0, current_stream(), S, groups, it, partial, damping,
                      threshold, min_pairs, T, status, iters, pairs, cost, sum, delta, active);
   check_launch(what);
@@ -411,7 +358,7 @@ extern "C" void icp_solve_kernel_wrapper(int S, int groups, int it, const double
 extern "C" void icp_solve_masked_kernel_wrapper(int S, int groups, int it, const double *partial, double damping,
                                                 double threshold, int min_pairs, double *T, int *status, int *iters,
                                                 int *pairs, double *cost, double *sum, double *delta, const int *active) {
-  PWCLO_REQUIRE(S <= 0 || (active != nullptr && icp_aligned(active, 4)), "icp_solve_masked: active is required%s", "");
+  PWCLO_REQUIRE(S <= 0 || (active != nullptr && aligned(active, 4)), "icp_solve_masked: active is required%s", "");
   icp_solve_launch("icp_solve_masked", S, groups, it, partial, damping, threshold, min_pairs, T, status, iters, pairs, cost,
                    sum, delta, active);
 }
@@ -428,8 +375,8 @@ static void icp_map_push_launch(const char *what, int S, int M, int n, const dou
   PWCLO_REQUIRE(T != nullptr && cloud != nullptr && normals != nullptr && stage_ws != nullptr && map_xyz != nullptr &&
                 map_normals != nullptr && map_ws != nullptr && A != nullptr && R != nullptr && live != nullptr &&
                 cursor != nullptr, "%s: every pointer is required", what);
-  PWCLO_REQUIRE(icp_aligned(stage_ws, 16) && icp_aligned(map_ws, 16) && icp_aligned(T, 8) && icp_aligned(A, 8) &&
-                icp_aligned(R, 8), "%s: structures must be 16-byte, fp64 arrays 8-byte aligned", what);
+  PWCLO_REQUIRE(aligned(stage_ws, 16) && aligned(map_ws, 16) && aligned(T, 8) && aligned(A, 8) &&
+                aligned(R, 8), "%s: structures must be 16-byte, fp64 arrays 8-byte aligned", what);
   const int nblk = (int)(per / (64 * 16 + 32));
   hipLaunchKernelGGL(icp_map_push_kernel, dim3(S), dim3(1024), 0, current_stream(), M, n, S, nblk, T, cloud, normals,
                      static_cast<const float4 *>(stage_ws), map_xyz, map_normals, static_cast<float4 *>(map_ws), A, R, live,
@@ -448,7 +395,7 @@ extern "C" void icp_map_push_masked_kernel_wrapper(int S, int M, int n, const do
                                                    const float *normals, const void *stage_ws, float *map_xyz,
                                                    float *map_normals, void *map_ws, double *A, double *R, int *live,
                                                    int *cursor, const int *active) {
-  PWCLO_REQUIRE(S <= 0 || (active != nullptr && icp_aligned(active, 4)), "icp_map_push_masked: active is required%s", "");
+  PWCLO_REQUIRE(S <= 0 || (active != nullptr && aligned(active, 4)), "icp_map_push_masked: active is required%s", "");
   icp_map_push_launch("icp_map_push_masked", S, M, n, T, cloud, normals, stage_ws, map_xyz, map_normals, map_ws, A, R, live,
                       cursor, active);
 }
@@ -459,7 +406,7 @@ extern "C" void keyframe_icp_push_kernel_wrapper(int S, int M, int n, const doub
                                                  const float *normals, const void *stage_ws, float *map_xyz,
                                                  float *map_normals, void *map_ws, double *A, double *R, int *live,
                                                  int *cursor, const int *active, const int *insert) {
-  PWCLO_REQUIRE(S <= 0 || (insert != nullptr && icp_aligned(insert, 4) && icp_aligned(active, 4)),
+  PWCLO_REQUIRE(S <= 0 || (insert != nullptr && aligned(insert, 4) && aligned(active, 4)),
                 "keyframe_icp_push: insert is required, and insert and active must be 4-byte aligned%s", "");
   icp_map_push_launch("keyframe_icp_push", S, M, n, T, cloud, normals, stage_ws, map_xyz, map_normals, map_ws, A, R, live,
                       cursor, active, insert);
@@ -472,8 +419,8 @@ extern "C" void icp_begin_kernel_wrapper(int S, int M, const int *active, const 
                 "icp_begin: S=%d M=%d out of range (M <= %d, S * M <= 65535)", S, M, ICP_MAX_SLOTS);
   PWCLO_REQUIRE(active != nullptr && restart != nullptr && A != nullptr && R != nullptr && live != nullptr &&
                 cursor != nullptr, "icp_begin: every pointer but armed is required%s", "");
-  PWCLO_REQUIRE(icp_aligned(A, 8) && icp_aligned(R, 8) && icp_aligned(active, 4) && icp_aligned(restart, 4) &&
-                icp_aligned(armed, 4), "icp_begin: fp64 arrays must be 8-byte, mask words 4-byte aligned%s", "");
+  PWCLO_REQUIRE(aligned(A, 8) && aligned(R, 8) && aligned(active, 4) && aligned(restart, 4) &&
+                aligned(armed, 4), "icp_begin: fp64 arrays must be 8-byte, mask words 4-byte aligned%s", "");
   hipLaunchKernelGGL(icp_begin_kernel, dim3(S), dim3(ICP_MAX_SLOTS), 0, current_stream(), M, active, restart, armed, A, R,
                      live, cursor);
   check_launch("icp_begin");

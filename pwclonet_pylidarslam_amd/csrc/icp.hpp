@@ -1,15 +1,18 @@
 // Arithmetic of the point-to-plane registration against a sliding local map, shared by the kernels of
-// icp.hip and by host code that wants the same numbers: one definition of a normal, of a row of the normal equations, of
-// the 6x6 solve and of the pose update (the pattern of grid.hpp, deskew.hpp and rows.hpp).  Everything here is fp64 on fp32
-// inputs; no function has a data-dependent loop bound.
+// icp.hip, projective.hip and voxel_map.hip and by host code that wants the same numbers: one definition of a normal, of a
+// row of the normal equations, of the 6x6 solve and of the pose update (the pattern of grid.hpp, deskew.hpp and rows.hpp),
+// and the two pieces the three refiners' kernels have in common: the end of an accumulate kernel (icp_reduce_store_row,
+// icp_store_zero_row) and what a map slot does after a push (icp_slot_after_push).  Everything here is fp64 on fp32 inputs;
+// no function has a data-dependent loop bound.
 //
-// Conventions.  A pose is rows 0..2 of a 4x4 row-major transform (12 doubles, m[4 * i + j], j = 3 the translation).  The
-// registered pose T of a frame maps that frame's points into the previous frame.  A twist is [w, v], rotation first, and
-// updates from the left: T <- [Rodrigues(w) | v] T.
+// Conventions.  A pose is an Se3 (se3.hpp, which holds all rigid-transform arithmetic).  The registered pose T of a frame
+// maps that frame's points into the previous frame.  A twist is [w, v], rotation first, and updates from the left:
+// T <- [Rodrigues(w) | v] T.
 #pragma once
 #include <math.h>
 
 #include "common.hpp"
+#include "se3.hpp"
 
 namespace pwclo {
 
@@ -89,30 +92,6 @@ ICP_HD void icp_normal(const double c[6], const float y[3], float out[3], double
   out[0] = (float)(sg * vec[0]); out[1] = (float)(sg * vec[1]); out[2] = (float)(sg * vec[2]);
 }
 
-// ---- poses -------------------------------------------------------------------------------------------------------------------
-
-ICP_HD void icp_pose_identity(double m[12]) {
-#pragma unroll
-  for (int i = 0; i < 12; ++i) m[i] = (i % 5 == 0) ? 1.0 : 0.0;
-}
-// c = a . b (c may not alias a or b)
-ICP_HD void icp_pose_mul(const double a[12], const double b[12], double c[12]) {
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      double s = (a[4 * i] * b[j] + a[4 * i + 1] * b[4 + j]) + a[4 * i + 2] * b[8 + j];
-      if (j == 3) s += a[4 * i + 3];
-      c[4 * i + j] = s;
-    }
-}
-// o = a p in fp64
-ICP_HD void icp_pose_apply(const double a[12], const float p[3], double o[3]) {
-  const double x = p[0], y = p[1], z = p[2];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) o[i] = ((a[4 * i] * x + a[4 * i + 1] * y) + a[4 * i + 2] * z) + a[4 * i + 3];
-}
-
 // ---- one row of the normal equations -------------------------------------------------------------------------------------------
 
 // The reference's _HuberScheme through _WLSScheme.weights, squared: cost / max(|r|, eps)^2 with cost = r^2 below sigma.
@@ -125,14 +104,14 @@ ICP_HD double icp_huber_w2(double r, double sigma) {
 
 // Adds the pair (query q matched to map point y with normal n, both in slot coordinates, all fp32 values) to acc.  p: the
 // frame's point, T: its pose estimate, Rm: the 3x3 rotation from the slot into the previous frame.
-ICP_HD void icp_add_pair(const float p[3], const float q[3], const float y[3], const float n[3], const double T[12],
+ICP_HD void icp_add_pair(const float p[3], const float q[3], const float y[3], const float n[3], const Se3 &T,
                          const double Rm[9], double sigma, double acc[ICP_TERMS]) {
   const double r = (((double)n[0] * ((double)q[0] - (double)y[0])) + ((double)n[1] * ((double)q[1] - (double)y[1]))) +
                    ((double)n[2] * ((double)q[2] - (double)y[2]));
   double np[3], pp[3], J[6];
 #pragma unroll
   for (int i = 0; i < 3; ++i) np[i] = (Rm[3 * i] * (double)n[0] + Rm[3 * i + 1] * (double)n[1]) + Rm[3 * i + 2] * (double)n[2];
-  icp_pose_apply(T, p, pp);
+  se3_apply(T, p, pp);
   J[0] = pp[1] * np[2] - pp[2] * np[1];
   J[1] = pp[2] * np[0] - pp[0] * np[2];
   J[2] = pp[0] * np[1] - pp[1] * np[0];
@@ -207,7 +186,7 @@ ICP_HD bool icp_solve6(const double sum[ICP_ROW], double damping, double delta[6
 
 // T <- [Rodrigues(w) | v] T, then the rotation re-orthonormalised by Gram-Schmidt on its columns (first column kept in
 // direction, third = first x second).  Rodrigues: I + a K + b K^2, a = sin(th) / th, b = (sin(th / 2) / (th / 2))^2 / 2.
-ICP_HD void icp_update_pose(const double delta[6], double T[12]) {
+ICP_HD void icp_update_pose(const double delta[6], Se3 &T) {
   const double wx = delta[0], wy = delta[1], wz = delta[2];
   const double th2 = (wx * wx + wy * wy) + wz * wz, th = sqrt(th2);
   double a = 1.0, b = 0.5;
@@ -216,14 +195,13 @@ ICP_HD void icp_update_pose(const double delta[6], double T[12]) {
     a = sin(th) / th;
     b = 0.5 * (h * h);
   }
-  double E[12];
-  E[0] = 1.0 - b * (wy * wy + wz * wz); E[1] = b * (wx * wy) - a * wz;        E[2] = b * (wx * wz) + a * wy;
-  E[4] = b * (wx * wy) + a * wz;        E[5] = 1.0 - b * (wx * wx + wz * wz); E[6] = b * (wy * wz) - a * wx;
-  E[8] = b * (wx * wz) - a * wy;        E[9] = b * (wy * wz) + a * wx;        E[10] = 1.0 - b * (wx * wx + wy * wy);
-  E[3] = delta[3]; E[7] = delta[4]; E[11] = delta[5];
-  double N[12];
-  icp_pose_mul(E, T, N);
-  double c0[3] = {N[0], N[4], N[8]}, c1[3] = {N[1], N[5], N[9]};
+  Se3 E;
+  E.m[0] = 1.0 - b * (wy * wy + wz * wz); E.m[1] = b * (wx * wy) - a * wz;        E.m[2] = b * (wx * wz) + a * wy;
+  E.m[4] = b * (wx * wy) + a * wz;        E.m[5] = 1.0 - b * (wx * wx + wz * wz); E.m[6] = b * (wy * wz) - a * wx;
+  E.m[8] = b * (wx * wz) - a * wy;        E.m[9] = b * (wy * wz) + a * wx;        E.m[10] = 1.0 - b * (wx * wx + wy * wy);
+  E.m[3] = delta[3]; E.m[7] = delta[4]; E.m[11] = delta[5];
+  const Se3 N = se3_mul(E, T);
+  double c0[3] = {N.m[0], N.m[4], N.m[8]}, c1[3] = {N.m[1], N.m[5], N.m[9]};
   const double i0 = 1.0 / sqrt((c0[0] * c0[0] + c0[1] * c0[1]) + c0[2] * c0[2]);
 #pragma unroll
   for (int i = 0; i < 3; ++i) c0[i] *= i0;
@@ -236,7 +214,71 @@ ICP_HD void icp_update_pose(const double delta[6], double T[12]) {
   const double c2[3] = {c0[1] * c1[2] - c0[2] * c1[1], c0[2] * c1[0] - c0[0] * c1[2], c0[0] * c1[1] - c0[1] * c1[0]};
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
-    T[4 * i] = c0[i]; T[4 * i + 1] = c1[i]; T[4 * i + 2] = c2[i]; T[4 * i + 3] = N[4 * i + 3];
+    T.m[4 * i] = c0[i]; T.m[4 * i + 1] = c1[i]; T.m[4 * i + 2] = c2[i]; T.m[4 * i + 3] = N.m[4 * i + 3];
+  }
+}
+
+// ---- what the refiners' kernels share ------------------------------------------------------------------------------------------
+
+// The end of an accumulate kernel (a workgroup of ICP_ACC_THREADS, every thread arrives): the threads' acc -> the
+// workgroup's row of partial (S, gridDim.x, ICP_ROW), s = the workgroup's stream.  Every term goes through the xor butterfly
+// of its wave (32, 16, .., 1), then the four waves' results are added in the order 0, 1, 2, 3; the two padding words are
+// zero.  The order is fixed so that two runs, and the three refiners on the same pairs, give the same bits; it is the
+// parity contract with tests/icp_model.py, whose accumulate() adds the same terms and allows for this order of adding
+// them by the rounding of the sum of their magnitudes.  Change it here, for all three kernels at once, or not at all.
+__device__ __forceinline__ void icp_reduce_store_row(const double acc[ICP_TERMS], double *__restrict__ partial, int s) {
+  __shared__ double wave_row[ICP_ACC_THREADS / 64][ICP_ROW];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int e = 0; e < ICP_TERMS; ++e) {
+    double v = acc[e];
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    if (lane == 0) wave_row[wave][e] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < ICP_ROW) {
+    double v = 0.0;
+    if (threadIdx.x < ICP_TERMS) {
+      v = wave_row[0][threadIdx.x];
+#pragma unroll
+      for (int w = 1; w < ICP_ACC_THREADS / 64; ++w) v += wave_row[w][threadIdx.x];
+    }
+    partial[((size_t)s * gridDim.x + blockIdx.x) * ICP_ROW + threadIdx.x] = v;
+  }
+}
+// The row of an idle stream's workgroup: zeros, nothing gathered.  The whole workgroup leaves after it.
+__device__ __forceinline__ void icp_store_zero_row(double *__restrict__ partial, int s) {
+  if (threadIdx.x < ICP_ROW) partial[((size_t)s * gridDim.x + blockIdx.x) * ICP_ROW + threadIdx.x] = 0.0;
+}
+
+// A map slot emptied or just filled: A = I (all 16 words) and, where the refiner keeps one (Rm != nullptr), Rm = I.
+__device__ __forceinline__ void icp_slot_identity(double *A, double *Rm) {
+  se3_store(A, se3_identity());
+  if (Rm != nullptr) {
+#pragma unroll
+    for (int e = 0; e < 9; ++e) Rm[e] = (e % 4 == 0) ? 1.0 : 0.0;
+  }
+}
+// What one slot does after a push of the frame with pose T (4x4): the slot the frame went to (fresh) becomes the identity
+// and live; any other live slot is re-based on the new frame, A <- A T in rows 0..2 (row 3 stays) and Rm <- R_T^T Rm.  The
+// caller moves the cursor, after a barrier.
+__device__ __forceinline__ void icp_slot_after_push(bool fresh, int *live, double *A, const double *T, double *Rm) {
+  if (fresh) {
+    icp_slot_identity(A, Rm);
+    *live = 1;
+  } else if (*live != 0) {
+    const Se3 t = se3_load(T);
+    se3_store_rows(A, se3_mul(se3_load(A), t));
+    if (Rm != nullptr) {
+      double r[9];
+#pragma unroll
+      for (int e = 0; e < 9; ++e) r[e] = Rm[e];
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) Rm[3 * i + j] = (t.m[i] * r[j] + t.m[4 + i] * r[3 + j]) + t.m[8 + i] * r[6 + j];
+    }
   }
 }
 

@@ -63,7 +63,7 @@ extern "C" void keyframe_gate_kernel_wrapper(int S, int M, const double *T, cons
                 "keyframe_gate: trans=%g and rot=%g must be finite and >= 0", trans, rot);
   PWCLO_REQUIRE(T != nullptr && live != nullptr && kf_delta != nullptr && kf_insert != nullptr && kf_count != nullptr,
                 "keyframe_gate: every pointer but active is required%s", "");
-  PWCLO_REQUIRE(((reinterpret_cast<uintptr_t>(T) | reinterpret_cast<uintptr_t>(kf_delta)) & 7) == 0,
+  PWCLO_REQUIRE(aligned(T, 8) && aligned(kf_delta, 8),
                 "keyframe_gate: fp64 arrays must be 8-byte aligned%s", "");
   hipLaunchKernelGGL(keyframe_gate_kernel, dim3(1), dim3(ceil_div(S, 64) * 64), 0, current_stream(), S, M, T, live, active,
                      trans, rot, kf_delta, kf_insert, kf_count);

@@ -168,9 +168,9 @@ __global__ __launch_bounds__(PG_EDGE_THREADS) void pg_linearise_kernel(PgGraph g
   const Se3 Z = se3_load(Zp);
   const Se3 Xj = se3_load(X + pg_pose_at(g, s, vj));
   Se3 A = Xj;                                    // absolute: the fixed vertex is G itself and Z = I
-  if (!absolute) A = se3_mul(pg_rigid_inv(se3_load(X + pg_pose_at(g, s, vi))), Xj);
-  const Se3 D = se3_mul(pg_rigid_inv(Z), A);
-  const PgQuat q = pg_quat(D);
+  if (!absolute) A = se3_mul(se3_rigid_inv(se3_load(X + pg_pose_at(g, s, vi))), Xj);
+  const Se3 D = se3_mul(se3_rigid_inv(Z), A);
+  const Quat q = se3_quat(D);
   const double sg = q.w < 0.0 ? -1.0 : 1.0;
   double e[6] = {D.m[3], D.m[7], D.m[11], sg * q.x, sg * q.y, sg * q.z};
   double Oe[6];

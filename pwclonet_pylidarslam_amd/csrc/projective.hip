@@ -101,11 +101,8 @@ __global__ __launch_bounds__(PROJ_TILE_W *PROJ_TILE_H) void proj_normal_map_kern
 }
 
 // The pose that moves slot (s, m)'s points into the newest frame: the rigid inverse of A[s, m] (newest frame -> slot).
-__device__ static inline void proj_slot_pose(const double *__restrict__ A, size_t sm, double inv[12]) {
-  double a[12];
-#pragma unroll
-  for (int e = 0; e < 12; ++e) a[e] = A[sm * 16 + e];
-  proj_pose_inverse(a, inv);
+__device__ static inline Se3 proj_slot_pose(const double *__restrict__ A, size_t sm) {
+  return se3_rigid_inv(se3_load(A + sm * 16));
 }
 
 // map_v (S, M, HW, 3), A (S, M, 4, 4), live (S, M) -> keys (S, M, HW), preset to all ones.  A dead slot adds nothing.
@@ -117,9 +114,8 @@ __global__ __launch_bounds__(256) void proj_model_key_kernel(ProjImage im, const
   const float *pr = map_v + ((size_t)sm * HW + i) * 3;
   const float p[3] = {pr[0], pr[1], pr[2]};
   if (p[0] == 0.0f && p[1] == 0.0f && p[2] == 0.0f) return;
-  double inv[12], o[3];
-  proj_slot_pose(A, (size_t)sm, inv);
-  icp_pose_apply(inv, p, o);
+  double o[3];
+  se3_apply(proj_slot_pose(A, (size_t)sm), p, o);
   float r;
   int row, col;
   if (!proj_pixel(im, (float)o[0], (float)o[1], (float)o[2], &r, &row, &col)) return;
@@ -142,14 +138,15 @@ __global__ __launch_bounds__(256) void proj_model_resolve_kernel(int HW, const f
     from = min((int)(key & 0xffffffffull), HW - 1);
     const float *pr = map_v + ((size_t)sm * HW + from) * 3, *nr = map_n + ((size_t)sm * HW + from) * 3;
     const float p[3] = {pr[0], pr[1], pr[2]};
-    const double nx = nr[0], ny = nr[1], nz = nr[2];
-    double inv[12], o[3];
-    proj_slot_pose(A, (size_t)sm, inv);
-    icp_pose_apply(inv, p, o);
+    const double nd[3] = {nr[0], nr[1], nr[2]};
+    const Se3 inv = proj_slot_pose(A, (size_t)sm);
+    double o[3], on[3];
+    se3_apply(inv, p, o);
+    se3_rotate(inv, nd, on);
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
       v[a] = (float)o[a];
-      n[a] = (float)((inv[4 * a] * nx + inv[4 * a + 1] * ny) + inv[4 * a + 2] * nz);
+      n[a] = (float)on[a];
     }
   }
   float *vo = model_v + ((size_t)sm * HW + i) * 3, *no = model_n + ((size_t)sm * HW + i) * 3;
@@ -164,9 +161,7 @@ __global__ __launch_bounds__(ICP_ACC_THREADS) void proj_accumulate_kernel(
     ProjImage im, int M, const float *__restrict__ vmap, const float *__restrict__ model_v,
     const float *__restrict__ model_n, const double *__restrict__ T, double sigma, float max_dist,
     double *__restrict__ partial, int *__restrict__ slot_out, int *__restrict__ pixel_out) {
-  __shared__ double wave_row[ICP_ACC_THREADS / 64][ICP_ROW];
   const int HW = im.H * im.W, s = blockIdx.y, i = blockIdx.x * ICP_ACC_THREADS + threadIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   double acc[ICP_TERMS];
 #pragma unroll
   for (int e = 0; e < ICP_TERMS; ++e) acc[e] = 0.0;
@@ -175,10 +170,9 @@ __global__ __launch_bounds__(ICP_ACC_THREADS) void proj_accumulate_kernel(
     const float *pr = vmap + ((size_t)s * HW + i) * 3;
     const float p[3] = {pr[0], pr[1], pr[2]};
     if (p[0] != 0.0f || p[1] != 0.0f || p[2] != 0.0f) {
-      double t[12], o[3];
-#pragma unroll
-      for (int e = 0; e < 12; ++e) t[e] = T[(size_t)s * 16 + e];
-      icp_pose_apply(t, p, o);
+      const Se3 t = se3_load(T + (size_t)s * 16);
+      double o[3];
+      se3_apply(t, p, o);
       const float q[3] = {(float)o[0], (float)o[1], (float)o[2]};
       float r;
       int row, col;
@@ -213,23 +207,7 @@ __global__ __launch_bounds__(ICP_ACC_THREADS) void proj_accumulate_kernel(
     if (slot_out != nullptr) slot_out[(size_t)s * HW + i] = best;
     if (pixel_out != nullptr) pixel_out[(size_t)s * HW + i] = pixel;
   }
-#pragma unroll
-  for (int e = 0; e < ICP_TERMS; ++e) {
-    double v = acc[e];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    if (lane == 0) wave_row[wave][e] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < ICP_ROW) {
-    double v = 0.0;
-    if (threadIdx.x < ICP_TERMS) {
-      v = wave_row[0][threadIdx.x];
-#pragma unroll
-      for (int w = 1; w < ICP_ACC_THREADS / 64; ++w) v += wave_row[w][threadIdx.x];
-    }
-    partial[((size_t)s * gridDim.x + blockIdx.x) * ICP_ROW + threadIdx.x] = v;
-  }
+  icp_reduce_store_row(acc, partial, s);
 }
 
 // The new frame's images (S, HW3) into slot cursor[s] of map_v / map_n (S, M, HW3).  Reads the cursor, never writes it.
@@ -244,31 +222,14 @@ __global__ __launch_bounds__(256) void proj_map_copy_kernel(int M, int HW3, cons
   map_n[dst] = nmap[from];
 }
 
-// icp_map_push_kernel's bookkeeping without the search structures: A <- A T for the live slots, A = I and live = 1 for
-// the slot the frame went to, the cursor moves on.  One workgroup per stream, one thread per slot.
+// icp_map_push_kernel's bookkeeping without the search structures and without Rm (icp.hpp: icp_slot_after_push), then the
+// cursor moves on.  One workgroup per stream, one thread per slot.
 __global__ __launch_bounds__(PROJ_MAX_SLOTS) void proj_map_book_kernel(int M, const double *__restrict__ T,
                                                                        double *__restrict__ A, int *__restrict__ live,
                                                                        int *__restrict__ cursor) {
   const int s = blockIdx.x, m = threadIdx.x;
   const int slot = min(max(cursor[s], 0), M - 1);
-  if (m < M) {
-    double *am = A + ((size_t)s * M + m) * 16;
-    if (m == slot) {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) am[e] = (e % 5 == 0) ? 1.0 : 0.0;
-      live[s * M + m] = 1;
-    } else if (live[s * M + m] != 0) {
-      double a[12], t[12], c[12];
-#pragma unroll
-      for (int e = 0; e < 12; ++e) {
-        a[e] = am[e];
-        t[e] = T[(size_t)s * 16 + e];
-      }
-      icp_pose_mul(a, t, c);
-#pragma unroll
-      for (int e = 0; e < 12; ++e) am[e] = c[e];
-    }
-  }
+  if (m < M) icp_slot_after_push(m == slot, live + s * M + m, A + ((size_t)s * M + m) * 16, T + (size_t)s * 16, nullptr);
   __syncthreads();                                         // everyone has read the cursor
   if (threadIdx.x == 0) cursor[s] = slot + 1 == M ? 0 : slot + 1;
 }
@@ -276,8 +237,6 @@ __global__ __launch_bounds__(PROJ_MAX_SLOTS) void proj_map_book_kernel(int M, co
 }  // namespace pwclo
 
 using namespace pwclo;
-
-static bool proj_aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 static bool proj_image_ok(int H, int W, double up_fov, double down_fov) {
   return H >= 1 && W >= 1 && (long long)H * W * 3 < (1ll << 31) && isfinite(up_fov) && isfinite(down_fov) &&
@@ -307,7 +266,7 @@ extern "C" void proj_vertex_map_kernel_wrapper(int S, int R, int C, int H, int W
   PWCLO_REQUIRE(R >= 1 && (C == 3 || C == 4) && (long long)R * C < (1ll << 31) && S <= 65535,
                 "proj_vertex_map: S=%d R=%d C=%d out of range (C = 3 or 4)", S, R, C);
   PWCLO_REQUIRE(points != nullptr && workspace != nullptr && vmap != nullptr && rows != nullptr &&
-                proj_aligned(workspace, 8), "proj_vertex_map: points, workspace (8-byte aligned), vmap and rows are required%s",
+                aligned(workspace, 8), "proj_vertex_map: points, workspace (8-byte aligned), vmap and rows are required%s",
                 "");
   const ProjImage im = proj_image(H, W, up_fov, down_fov);
   unsigned long long *keys = static_cast<unsigned long long *>(workspace);
@@ -352,7 +311,7 @@ extern "C" void proj_model_build_kernel_wrapper(int S, int M, int H, int W, doub
   PWCLO_REQUIRE(map_v != nullptr && map_n != nullptr && A != nullptr && live != nullptr && workspace != nullptr &&
                 model_v != nullptr && model_n != nullptr && src != nullptr, "proj_model_build: every pointer is required%s",
                 "");
-  PWCLO_REQUIRE(proj_aligned(A, 8) && proj_aligned(workspace, 8), "proj_model_build: A and workspace must be 8-byte aligned%s",
+  PWCLO_REQUIRE(aligned(A, 8) && aligned(workspace, 8), "proj_model_build: A and workspace must be 8-byte aligned%s",
                 "");
   const ProjImage im = proj_image(H, W, up_fov, down_fov);
   unsigned long long *keys = static_cast<unsigned long long *>(workspace);
@@ -377,7 +336,7 @@ extern "C" void proj_accumulate_kernel_wrapper(int S, int M, int H, int W, doubl
                 sigma, (double)max_dist);
   PWCLO_REQUIRE(vmap != nullptr && model_v != nullptr && model_n != nullptr && T != nullptr && partial != nullptr,
                 "proj_accumulate: every pointer but slot and pixel is required%s", "");
-  PWCLO_REQUIRE(proj_aligned(T, 8) && proj_aligned(partial, 8), "proj_accumulate: T and partial must be 8-byte aligned%s", "");
+  PWCLO_REQUIRE(aligned(T, 8) && aligned(partial, 8), "proj_accumulate: T and partial must be 8-byte aligned%s", "");
   const ProjImage im = proj_image(H, W, up_fov, down_fov);
   hipLaunchKernelGGL(proj_accumulate_kernel, dim3(icp_accumulate_groups(H * W), S), dim3(ICP_ACC_THREADS), 0,
                      current_stream(), im, M, vmap, model_v, model_n, T, sigma, max_dist, partial, slot, pixel);
@@ -392,7 +351,7 @@ extern "C" void proj_map_push_kernel_wrapper(int S, int M, int H, int W, const d
                 "proj_map_push: S=%d M=%d H=%d W=%d out of range (M <= %d)", S, M, H, W, PROJ_MAX_SLOTS);
   PWCLO_REQUIRE(T != nullptr && vmap != nullptr && nmap != nullptr && map_v != nullptr && map_n != nullptr && A != nullptr &&
                 live != nullptr && cursor != nullptr, "proj_map_push: every pointer is required%s", "");
-  PWCLO_REQUIRE(proj_aligned(T, 8) && proj_aligned(A, 8), "proj_map_push: T and A must be 8-byte aligned%s", "");
+  PWCLO_REQUIRE(aligned(T, 8) && aligned(A, 8), "proj_map_push: T and A must be 8-byte aligned%s", "");
   const int HW3 = H * W * 3;
   hipLaunchKernelGGL(proj_map_copy_kernel, dim3(ceil_div(HW3, 256), S), dim3(256), 0, current_stream(), M, HW3, vmap, nmap,
                      map_v, map_n, cursor);

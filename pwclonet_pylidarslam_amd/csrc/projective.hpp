@@ -1,6 +1,6 @@
 // Arithmetic of the projective frame-to-model registration on spherical vertex maps, shared by the
 // kernels of projective.hip and by host code that wants the same numbers (the pattern of icp.hpp): one definition of a
-// point's pixel, of a z-buffer key and of a pixel's normal.
+// point's pixel, of a z-buffer key and of a pixel's normal.  Poses and their inverses are se3.hpp's.
 //
 // The reference's ICPFrameToModel over a ProjectiveLocalMap (slam/odometry/local_map.py:84-240) projects every sweep to a
 // spherical image (slam/common/projection.py:20-82, 340-436), takes normals from box-filtered moments of that image
@@ -61,16 +61,6 @@ ICP_HD unsigned long long proj_key(float r, unsigned int index) {
   memcpy(&bits, &r, 4);
 #endif
   return ((unsigned long long)bits << 32) | (unsigned long long)index;
-}
-
-// The rigid inverse of the pose a (12 doubles): [R^T | -R^T t].
-ICP_HD void proj_pose_inverse(const double a[12], double o[12]) {
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-#pragma unroll
-    for (int j = 0; j < 3; ++j) o[4 * i + j] = a[4 * j + i];
-    o[4 * i + 3] = -((a[i] * a[3] + a[4 + i] * a[7]) + a[8 + i] * a[11]);
-  }
 }
 
 // The normal of a pixel from the moments of its window about the sensor: m = sum p (3), c = sum p p^T ([xx xy xz yy yz zz]).

@@ -60,7 +60,7 @@ __global__ __launch_bounds__(256) void voxel_begin_kernel(VmGrid g, const int *_
     if (j < cells) vm_store(c + j, VM_EMPTY);
   }
   if (blockIdx.x == 0) {
-    if (threadIdx.x < 16) P[(size_t)s * 16 + threadIdx.x] = (threadIdx.x % 5 == 0) ? 1.0 : 0.0;
+    if (threadIdx.x == 0) se3_store(P + (size_t)s * 16, se3_identity());
     if (threadIdx.x == 16) nonempty[s] = 0;
     if (threadIdx.x == 17) seq[s] = 0;
   }
@@ -68,38 +68,25 @@ __global__ __launch_bounds__(256) void voxel_begin_kernel(VmGrid g, const int *_
 
 // The pose a frame is inserted with: I for a stream whose map is empty (nonempty given and zero), else P[s] T[s] (T given)
 // or P[s].
-__device__ __forceinline__ void vm_insert_pose(int s, const double *__restrict__ P, const double *__restrict__ T,
-                                               const int *__restrict__ nonempty, double w[12]) {
-  if (nonempty != nullptr && nonempty[s] == 0) {
-    icp_pose_identity(w);
-    return;
-  }
-  double a[12];
-#pragma unroll
-  for (int e = 0; e < 12; ++e) a[e] = P[(size_t)s * 16 + e];
-  if (T != nullptr) {
-    double t[12];
-#pragma unroll
-    for (int e = 0; e < 12; ++e) t[e] = T[(size_t)s * 16 + e];
-    icp_pose_mul(a, t, w);
-  } else {
-#pragma unroll
-    for (int e = 0; e < 12; ++e) w[e] = a[e];
-  }
+__device__ __forceinline__ Se3 vm_insert_pose(int s, const double *__restrict__ P, const double *__restrict__ T,
+                                              const int *__restrict__ nonempty) {
+  if (nonempty != nullptr && nonempty[s] == 0) return se3_identity();
+  const Se3 a = se3_load(P + (size_t)s * 16);
+  return T != nullptr ? se3_mul(a, se3_load(T + (size_t)s * 16)) : a;
 }
 
 // w = fp32(W p); -> the slot (cell * 8 + octant) the point asks for, -1 when it is not inserted; want: its voxel's word.
-__device__ __forceinline__ int vm_insert_slot(const VmGrid &g, const double W[12], const float p[3], float w[3],
+__device__ __forceinline__ int vm_insert_slot(const VmGrid &g, const Se3 &W, const float p[3], float w[3],
                                               unsigned long long *want) {
   double o[3];
-  icp_pose_apply(W, p, o);
+  se3_apply(W, p, o);
   w[0] = (float)o[0]; w[1] = (float)o[1]; w[2] = (float)o[2];
   if (!(vm_finite(w[0]) && vm_finite(w[1]) && vm_finite(w[2]))) return -1;
   const int N[3] = {g.nx, g.ny, g.nz};
   int h[3];
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    if (!(fabs((double)w[a] - W[4 * a + 3]) < (double)(N[a] / 2 - 1) * g.voxel)) return -1;
+    if (!(fabs((double)w[a] - W.m[4 * a + 3]) < (double)(N[a] / 2 - 1) * g.voxel)) return -1;
     if (!vm_half_index(w[a], g.half, &h[a])) return -1;
   }
   const int cx = h[0] >> 1, cy = h[1] >> 1, cz = h[2] >> 1;
@@ -123,8 +110,7 @@ __global__ __launch_bounds__(256) void voxel_claim_kernel(VmGrid g, int n, const
   const int s = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
   if (!vm_inserts(s, active, insert)) return;
   if (i >= n) return;
-  double W[12];
-  vm_insert_pose(s, P, T, nonempty, W);
+  const Se3 W = vm_insert_pose(s, P, T, nonempty);
   const float *pr = cloud + ((size_t)s * n + i) * 3;
   const float p[3] = {pr[0], pr[1], pr[2]};
   float w[3];
@@ -167,17 +153,17 @@ __global__ __launch_bounds__(256) void voxel_resolve_kernel(VmGrid g, int n, con
   const size_t e = (size_t)s * g.cells() * VM_OCTANTS + (size_t)sl;
   const unsigned long long key = ((unsigned long long)(unsigned)seq[s] << 32) | (unsigned)i;
   if (g.keys[e] != key) return;
-  double W[12];
-  vm_insert_pose(s, P, T, nonempty, W);
+  const Se3 W = vm_insert_pose(s, P, T, nonempty);
   const float *pr = cloud + ((size_t)s * n + i) * 3, *nr = normals + ((size_t)s * n + i) * 3;
   const float p[3] = {pr[0], pr[1], pr[2]};
-  double o[3];
-  icp_pose_apply(W, p, o);
-  const double nx = nr[0], ny = nr[1], nz = nr[2];
+  const double nd[3] = {nr[0], nr[1], nr[2]};
+  double o[3], on[3];
+  se3_apply(W, p, o);
+  se3_rotate(W, nd, on);
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
     g.pts[e * 3 + a] = (float)o[a];
-    g.nrm[e * 3 + a] = (float)((W[4 * a] * nx + W[4 * a + 1] * ny) + W[4 * a + 2] * nz);
+    g.nrm[e * 3 + a] = (float)on[a];
   }
 }
 
@@ -192,10 +178,7 @@ __global__ __launch_bounds__(VM_MAX_STREAMS) void voxel_pose_kernel(int S, const
   const int s = threadIdx.x;
   if (s >= S) return;
   if (active != nullptr && active[s] == 0) return;
-  double w[12];
-  vm_insert_pose(s, P, T, nonempty, w);
-#pragma unroll
-  for (int e = 0; e < 12; ++e) P[(size_t)s * 16 + e] = w[e];
+  se3_store_rows(P + (size_t)s * 16, vm_insert_pose(s, P, T, nonempty));
   if (insert == nullptr || insert[s] != 0) {
     seq[s] += 1;
     nonempty[s] = 1;
@@ -210,31 +193,21 @@ __global__ __launch_bounds__(ICP_ACC_THREADS) void voxel_accumulate_kernel(
     VmGrid g, int n, const float *__restrict__ p, const double *__restrict__ P, const double *__restrict__ T, double sigma,
     float max_dist, double *__restrict__ partial, int *__restrict__ cell_out, int *__restrict__ octant_out,
     float *__restrict__ dist_out, const int *__restrict__ active) {
-  __shared__ double wave_row[ICP_ACC_THREADS / 64][ICP_ROW];
   const int s = blockIdx.y, i = blockIdx.x * ICP_ACC_THREADS + threadIdx.x;
   if (active != nullptr && active[s] == 0) {              // idle: a zero row, no gather (the whole workgroup leaves)
-    if (threadIdx.x < ICP_ROW) partial[((size_t)s * gridDim.x + blockIdx.x) * ICP_ROW + threadIdx.x] = 0.0;
+    icp_store_zero_row(partial, s);
     return;
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   double acc[ICP_TERMS];
 #pragma unroll
   for (int e = 0; e < ICP_TERMS; ++e) acc[e] = 0.0;
   if (i < n) {
-    double a[12], t[12], W[12];
-#pragma unroll
-    for (int e = 0; e < 12; ++e) a[e] = P[(size_t)s * 16 + e];
-    if (T != nullptr) {
-#pragma unroll
-      for (int e = 0; e < 12; ++e) t[e] = T[(size_t)s * 16 + e];
-    } else {
-      icp_pose_identity(t);
-    }
-    icp_pose_mul(a, t, W);
+    const Se3 a = se3_load(P + (size_t)s * 16), t = T != nullptr ? se3_load(T + (size_t)s * 16) : se3_identity();
+    const Se3 W = se3_mul(a, t);
     const float *pr = p + ((size_t)s * n + i) * 3;
     const float pp[3] = {pr[0], pr[1], pr[2]};
     double o[3];
-    icp_pose_apply(W, pp, o);
+    se3_apply(W, pp, o);
     const float q[3] = {(float)o[0], (float)o[1], (float)o[2]};
     int best = -1;
     float bd = INFINITY;
@@ -278,7 +251,7 @@ __global__ __launch_bounds__(ICP_ACC_THREADS) void voxel_accumulate_kernel(
 #pragma unroll
           for (int r = 0; r < 3; ++r)
 #pragma unroll
-            for (int cc = 0; cc < 3; ++cc) r9[3 * r + cc] = a[4 * cc + r];       // R_P^T: the map frame -> the previous frame
+            for (int cc = 0; cc < 3; ++cc) r9[3 * r + cc] = a.m[4 * cc + r];       // R_P^T: the map frame -> the previous frame
           icp_add_pair(pp, q, y, nn, t, r9, sigma, acc);
         }
       }
@@ -289,30 +262,12 @@ __global__ __launch_bounds__(ICP_ACC_THREADS) void voxel_accumulate_kernel(
       dist_out[(size_t)s * n + i] = bd;
     }
   }
-#pragma unroll
-  for (int e = 0; e < ICP_TERMS; ++e) {
-    double v = acc[e];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    if (lane == 0) wave_row[wave][e] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < ICP_ROW) {
-    double v = 0.0;
-    if (threadIdx.x < ICP_TERMS) {
-      v = wave_row[0][threadIdx.x];
-#pragma unroll
-      for (int w = 1; w < ICP_ACC_THREADS / 64; ++w) v += wave_row[w][threadIdx.x];
-    }
-    partial[((size_t)s * gridDim.x + blockIdx.x) * ICP_ROW + threadIdx.x] = v;
-  }
+  icp_reduce_store_row(acc, partial, s);
 }
 
 }  // namespace pwclo
 
 using namespace pwclo;
-
-static bool vm_aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 static bool vm_extent_ok(int S, int nx, int ny, int nz) {
   const int N[3] = {nx, ny, nz};
@@ -342,16 +297,16 @@ static VmGrid vm_grid(int S, int nx, int ny, int nz, double voxel, void *grid) {
   PWCLO_REQUIRE(vm_extent_ok(S, nx, ny, nz), "%s: S=%d extent=(%d, %d, %d) out of range (S <= %d; even, 4 <= N <= %d, "  \
                 "Nx Ny Nz < 2^28)", what, S, nx, ny, nz, VM_MAX_STREAMS, VM_MAX_AXIS);                                  \
   PWCLO_REQUIRE(voxel > 0.0 && isfinite(voxel), "%s: voxel_size=%g must be finite and > 0", what, voxel);              \
-  PWCLO_REQUIRE(grid != nullptr && vm_aligned(grid, 8), "%s: the grid (8-byte aligned) is required", what)
+  PWCLO_REQUIRE(grid != nullptr && aligned(grid, 8), "%s: the grid (8-byte aligned) is required", what)
 
 extern "C" void voxel_begin_kernel_wrapper(int S, int nx, int ny, int nz, const int *active, const int *restart,
                                            const int *armed, void *grid, double *P, int *nonempty, int *seq) {
   if (S <= 0) return;
   const double voxel = 1.0;
   VM_REQUIRE_GRID("voxel_begin");
-  PWCLO_REQUIRE(P != nullptr && nonempty != nullptr && seq != nullptr && vm_aligned(P, 8),
+  PWCLO_REQUIRE(P != nullptr && nonempty != nullptr && seq != nullptr && aligned(P, 8),
                 "voxel_begin: P (8-byte aligned), nonempty and seq are required%s", "");
-  PWCLO_REQUIRE(vm_aligned(active, 4) && vm_aligned(restart, 4) && vm_aligned(armed, 4),
+  PWCLO_REQUIRE(aligned(active, 4) && aligned(restart, 4) && aligned(armed, 4),
                 "voxel_begin: mask words must be 4-byte aligned%s", "");
   const VmGrid g = vm_grid(S, nx, ny, nz, voxel, grid);
   const long long cells = (long long)nx * ny * nz;
@@ -368,7 +323,7 @@ extern "C" void voxel_insert_kernel_wrapper(int S, int n, int nx, int ny, int nz
   PWCLO_REQUIRE(n >= 1 && (long long)n * 3 < (1ll << 31), "voxel_insert: n=%d out of range", n);
   PWCLO_REQUIRE(cloud != nullptr && normals != nullptr && P != nullptr && seq != nullptr && slot != nullptr,
                 "voxel_insert: cloud, normals, P, seq and slot are required%s", "");
-  PWCLO_REQUIRE(vm_aligned(P, 8) && vm_aligned(T, 8) && vm_aligned(active, 4) && vm_aligned(insert, 4),
+  PWCLO_REQUIRE(aligned(P, 8) && aligned(T, 8) && aligned(active, 4) && aligned(insert, 4),
                 "voxel_insert: fp64 arrays must be 8-byte, mask words 4-byte aligned%s", "");
   const VmGrid g = vm_grid(S, nx, ny, nz, voxel, grid);
   const dim3 blocks(ceil_div(n, 256), S);
@@ -384,7 +339,7 @@ extern "C" void voxel_pose_kernel_wrapper(int S, const double *T, double *P, int
                                           const int *active, const int *insert) {
   if (S <= 0) return;
   PWCLO_REQUIRE(S <= VM_MAX_STREAMS, "voxel_pose: S=%d out of range (S <= %d)", S, VM_MAX_STREAMS);
-  PWCLO_REQUIRE(P != nullptr && nonempty != nullptr && seq != nullptr && vm_aligned(P, 8) && vm_aligned(T, 8),
+  PWCLO_REQUIRE(P != nullptr && nonempty != nullptr && seq != nullptr && aligned(P, 8) && aligned(T, 8),
                 "voxel_pose: P (8-byte aligned), nonempty and seq are required%s", "");
   hipLaunchKernelGGL(voxel_pose_kernel, dim3(1), dim3(ceil_div(S, 64) * 64), 0, current_stream(), S, T, P, nonempty, seq,
                      armed, active, insert);
@@ -401,8 +356,8 @@ extern "C" void voxel_accumulate_kernel_wrapper(int S, int n, int nx, int ny, in
   PWCLO_REQUIRE(sigma > 0.0 && isfinite(sigma) && max_dist >= 0.0f && (double)max_dist <= voxel,
                 "voxel_accumulate: sigma=%g must be > 0 and 0 <= max_dist=%g <= voxel_size=%g", sigma, (double)max_dist,
                 voxel);
-  PWCLO_REQUIRE(p != nullptr && P != nullptr && partial != nullptr && vm_aligned(P, 8) && vm_aligned(T, 8) &&
-                vm_aligned(partial, 8), "voxel_accumulate: p, P and partial (fp64 arrays 8-byte aligned) are required%s", "");
+  PWCLO_REQUIRE(p != nullptr && P != nullptr && partial != nullptr && aligned(P, 8) && aligned(T, 8) &&
+                aligned(partial, 8), "voxel_accumulate: p, P and partial (fp64 arrays 8-byte aligned) are required%s", "");
   PWCLO_REQUIRE((cell == nullptr) == (octant == nullptr) && (cell == nullptr) == (dist == nullptr),
                 "voxel_accumulate: cell, octant and dist come together%s", "");
   const VmGrid g = vm_grid(S, nx, ny, nz, voxel, const_cast<void *>(grid));

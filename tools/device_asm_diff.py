@@ -12,8 +12,10 @@ dropped as well.  Exit status 0 and one ``identical`` line per source when nothi
 
 ``--rename REGEX=REPL`` (repeatable) pairs kernels whose signature changed: symbols are demangled (llvm-cxxfilt or c++filt) and the
 substitution is applied to the BASE tree's names before matching, e.g. ``--rename ', int, float const\*\)$=)'`` for a
-dropped trailing argument.  A kernel paired that way can never be "identical" by name alone, so every kernel that
-differs is listed with base -> working VGPRs, SGPRs, LDS bytes, scratch bytes and body lines.
+dropped trailing argument.
+
+Every kernel that differs, renamed or not, is listed with base -> working VGPRs, SGPRs, LDS bytes, scratch bytes and
+body lines: whether a change of device code costs registers, scratch or occupancy is read off that row.
 """
 import argparse
 import concurrent.futures
@@ -116,7 +118,7 @@ def compare(name, base_tree, tmp, renames=()):
             problems.append("%s: descriptor differs" % sym)
         if old[sym][0] != new[sym][0]:
             problems.append("%s: instructions differ (%d / %d lines)" % (sym, len(old[sym][0]), len(new[sym][0])))
-        if renames and old[sym] != new[sym]:
+        if old[sym] != new[sym]:
             problems.append("        " + ", ".join("%s %s -> %s" % (k, a, b) for (k, a), (_, b) in
                                                    zip(resources(old[sym]), resources(new[sym]))))
     ninstr = sum(len(b) for b, _ in new.values())
