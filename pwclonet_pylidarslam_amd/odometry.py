@@ -426,8 +426,8 @@ class StreamingOdometry:
         self._backend.append(rel, active=self._active, valid=self._valid, count=self._counts)
 
     def refiner(self):
-        """The ``registration.IcpRefiner`` behind ``refine=`` (``status()``, ``diagnostics()``); None before the first
-        frame or without ``refine``."""
+        """The refiner behind ``refine=``, of the class its ``kind`` names (``status()``, ``diagnostics()``); None before the
+        first frame or without ``refine``."""
         return self._refiner
 
     def valid(self):
@@ -477,45 +477,40 @@ class StreamingOdometry:
         (the identity for a frame that primes), and record the refined relative pose at the stream's own frame counter.
         The refiner reads the step's words: ``active``, and ``restart = active * (1 - valid)`` (a stream that primed in
         this call starts a new map), written as one launch: valid is set for active streams only, so the product is the
-        difference."""
+        difference.
+        ``kind="projective"`` (lock step) registers the rows the front end kept instead -- after the
+        filter and the de-skew, packed, before the sampler -- as spherical vertex maps, with the same guess and record."""
         if self._refine_cfg is None:
             return
+        if self._refiner is None:
+            self._make_refiner(pose.device)
         if self._refine_kind == "projective":
-            return self._refine_projective(pose)
-        from . import registration, voxel_map
-        cloud = self._tapped[:, :self.num_points, :3].contiguous()
-        if self._refiner is None:
-            make = voxel_map.VoxelMapRefiner if self._refine_kind == "voxel_map" else registration.IcpRefiner
-            self._refiner = make(self.streams, self.num_points, graph=self.graph, **self._refine_cfg)
-            self._ref_rel = torch.zeros((self.max_frames, self.streams, 4, 4), dtype=torch.float64, device=cloud.device)
-            self._ref_abs = torch.zeros_like(self._ref_rel)
-            self._ref_restart = torch.zeros_like(self._active)
-            self._refiner.adopt_words(self._active, self._ref_restart)
-        torch.sub(self._active, self._valid, out=self._ref_restart)
-        T = self._refiner.register_adopted(cloud, pose[:, 0, :], all_active=not self.per_stream)
-        self._feed_motion(T)
-        _lib.call("stream_record_refined_kernel_wrapper", cloud.device, self.streams, self.max_frames, _p(self._active),
-                  _p(self._valid), _p(self._counts), _p(T), _p(self._ref_rel), _p(self._ref_abs))
-        if self._backend_source == "refined":
-            self._backend_append(T)
-
-    def _refine_projective(self, pose):
-        """``kind="projective"`` (lock step): the rows the front end kept -- after the filter and the
-        de-skew, packed, before the sampler -- are registered as spherical vertex maps, the level-1 row's transform the
-        guess; the refined pose is recorded by the launch that serves ``kind="knn"``."""
-        from . import projective
-        front = self._front.bufs
-        if self._refiner is None:
-            self._refiner = projective.ProjectiveIcpRefiner(self.streams, self._front.width, graph=self.graph,
-                                                            **self._refine_cfg)
-            self._ref_rel = torch.zeros((self.max_frames, self.streams, 4, 4), dtype=torch.float64, device=pose.device)
-            self._ref_abs = torch.zeros_like(self._ref_rel)
-        T = self._refiner.register(front["packed"], front["counts"], pose[:, 0, :])
+            front = self._front.bufs
+            T = self._refiner.register(front["packed"], front["counts"], pose[:, 0, :])
+        else:
+            cloud = self._tapped[:, :self.num_points, :3].contiguous()
+            torch.sub(self._active, self._valid, out=self._ref_restart)
+            T = self._refiner.register_adopted(cloud, pose[:, 0, :], all_active=not self.per_stream)
         self._feed_motion(T)
         _lib.call("stream_record_refined_kernel_wrapper", pose.device, self.streams, self.max_frames, _p(self._active),
                   _p(self._valid), _p(self._counts), _p(T), _p(self._ref_rel), _p(self._ref_abs))
         if self._backend_source == "refined":
             self._backend_append(T)
+
+    def _make_refiner(self, device):
+        """The refiner of ``refine=dict(kind=...)`` and the refined trajectories.  The two that register the sampled cloud
+        read the step's words in place (``adopt_words``)."""
+        from . import projective, registration, voxel_map
+        if self._refine_kind == "projective":
+            self._refiner = projective.ProjectiveIcpRefiner(self.streams, self._front.width, graph=self.graph,
+                                                            **self._refine_cfg)
+        else:
+            make = voxel_map.VoxelMapRefiner if self._refine_kind == "voxel_map" else registration.IcpRefiner
+            self._refiner = make(self.streams, self.num_points, graph=self.graph, **self._refine_cfg)
+            self._ref_restart = torch.zeros_like(self._active)
+            self._refiner.adopt_words(self._active, self._ref_restart)
+        self._ref_rel = torch.zeros((self.max_frames, self.streams, 4, 4), dtype=torch.float64, device=device)
+        self._ref_abs = torch.zeros_like(self._ref_rel)
 
     def _feed_motion(self, T):
         """``refine=dict(..., feedback=True)``, one launch after the registration: the streams that registered a pair in

@@ -114,8 +114,7 @@ def accumulate(vmap, model_v, model_n, T, up_fov=3.0, down_fov=-24.8, sigma=0.5,
         raise ValueError("accumulate: model_v must be (S, M, H, W, 3)")
     S, M, H, W, _ = model_v.shape
     H, W, up, down = _image_args("accumulate", H, W, up_fov, down_fov)
-    if not float(sigma) > 0.0 or not float(max_dist) >= 0.0:
-        raise ValueError("accumulate: sigma=%r must be > 0 and max_dist=%r >= 0" % (sigma, max_dist))
+    registration._need_pairing(sigma, max_dist)
     if not 1 <= M <= MAX_SLOTS or S < 1 or S > 65535:
         raise ValueError("accumulate: S=%d M=%d out of range (M <= %d)" % (S, M, MAX_SLOTS))
     _need(vmap, "accumulate: vmap", torch.float32, (S, H, W, 3))

@@ -47,6 +47,12 @@ def _need(t, name, dtype, shape=None):
         raise ValueError("%s must be contiguous" % name)
 
 
+def _need_pairing(sigma, max_dist):
+    """The check of the ``accumulate`` ops of this module and of ``projective``."""
+    if not float(sigma) > 0.0 or not float(max_dist) >= 0.0:
+        raise ValueError("accumulate: sigma=%r must be > 0 and max_dist=%r >= 0" % (sigma, max_dist))
+
+
 def groups(n):
     """Rows of partial sums per stream that ``accumulate`` writes for clouds of n points."""
     return (int(n) + 255) // 256
@@ -124,8 +130,7 @@ def accumulate(p, q, idx, dist, map_xyz, map_normals, live, R, T, sigma=0.5, max
     if not isinstance(q, torch.Tensor) or q.dim() != 4:
         raise ValueError("accumulate: q must be (S, M, n, 3)")
     S, M, n, _ = q.shape
-    if not float(sigma) > 0.0 or not float(max_dist) >= 0.0:
-        raise ValueError("accumulate: sigma=%r must be > 0 and max_dist=%r >= 0" % (sigma, max_dist))
+    _need_pairing(sigma, max_dist)
     _need(p, "accumulate: p", torch.float32, (S, n, 3))
     _need(q, "accumulate: q", torch.float32, (S, M, n, 3))
     _need(idx, "accumulate: idx", torch.int32, (S, M, n))
@@ -193,26 +198,30 @@ def begin(active, restart, A, R, live, cursor, armed=None):
               _p(cursor))
 
 
+def _need_push(what, T, cloud, normals_, stage_ws, map_xyz, map_normals, map_ws, A, R, live, cursor):
+    """The argument check of ``map_push`` and ``map_push_keyframe`` -> (S, M, n)."""
+    if not isinstance(map_xyz, torch.Tensor) or map_xyz.dim() != 4:
+        raise ValueError("%s: map_xyz must be (S, M, n, 3)" % what)
+    S, M, n, _ = map_xyz.shape
+    lib = _lib.load()
+    for t, name, dtype, shape in (
+            (T, "T", torch.float64, (S, 4, 4)), (cloud, "cloud", torch.float32, (S, n, 3)),
+            (normals_, "normals", torch.float32, (S, n, 3)),
+            (stage_ws, "stage_ws", torch.uint8, (lib.knn_point_build_bytes(S, n),)),
+            (map_xyz, "map_xyz", torch.float32, (S, M, n, 3)), (map_normals, "map_normals", torch.float32, (S, M, n, 3)),
+            (map_ws, "map_ws", torch.uint8, (lib.knn_point_build_bytes(S * M, n),)),
+            (A, "A", torch.float64, (S, M, 4, 4)), (R, "R", torch.float64, (S, M, 3, 3)),
+            (live, "live", torch.int32, (S, M)), (cursor, "cursor", torch.int32, (S,))):
+        _need(t, "%s: %s" % (what, name), dtype, shape)
+    return S, M, n
+
+
 def map_push(T, cloud, normals_, stage_ws, map_xyz, map_normals, map_ws, A, R, live, cursor, active=None):
     """The handover after a registration, in place: the staged frame (cloud, normals (S, n, 3), stage_ws: its structure,
     built for S clouds) goes into slot cursor[s] of map_xyz / map_normals (S, M, n, 3) and map_ws (built for S * M clouds),
     the live slots' A / R are re-based with T (S, 4, 4), the cursor moves on.  ``active`` (S,) int32: the masked launch,
     which leaves idle streams alone."""
-    if not isinstance(map_xyz, torch.Tensor) or map_xyz.dim() != 4:
-        raise ValueError("map_push: map_xyz must be (S, M, n, 3)")
-    S, M, n, _ = map_xyz.shape
-    lib = _lib.load()
-    _need(T, "map_push: T", torch.float64, (S, 4, 4))
-    _need(cloud, "map_push: cloud", torch.float32, (S, n, 3))
-    _need(normals_, "map_push: normals", torch.float32, (S, n, 3))
-    _need(stage_ws, "map_push: stage_ws", torch.uint8, (lib.knn_point_build_bytes(S, n),))
-    _need(map_xyz, "map_push: map_xyz", torch.float32, (S, M, n, 3))
-    _need(map_normals, "map_push: map_normals", torch.float32, (S, M, n, 3))
-    _need(map_ws, "map_push: map_ws", torch.uint8, (lib.knn_point_build_bytes(S * M, n),))
-    _need(A, "map_push: A", torch.float64, (S, M, 4, 4))
-    _need(R, "map_push: R", torch.float64, (S, M, 3, 3))
-    _need(live, "map_push: live", torch.int32, (S, M))
-    _need(cursor, "map_push: cursor", torch.int32, (S,))
+    S, M, n = _need_push("map_push", T, cloud, normals_, stage_ws, map_xyz, map_normals, map_ws, A, R, live, cursor)
     args = (S, M, n, _p(T), _p(cloud), _p(normals_), _p(stage_ws), _p(map_xyz), _p(map_normals), _p(map_ws), _p(A), _p(R),
             _p(live), _p(cursor))
     if active is None:
@@ -226,22 +235,8 @@ def map_push_keyframe(T, cloud, normals_, stage_ws, map_xyz, map_normals, map_ws
     """``map_push`` behind the keyframe gate: ``insert`` (S,) int32, the gate's decision.  A stream
     with insert != 0 gets the bits of ``map_push``; one with insert == 0 keeps its slots, ``live`` and ``cursor``, and every
     live slot's A / R is re-based with T.  ``active`` (S,) int32 or None, as there."""
-    if not isinstance(map_xyz, torch.Tensor) or map_xyz.dim() != 4:
-        raise ValueError("map_push_keyframe: map_xyz must be (S, M, n, 3)")
-    S, M, n, _ = map_xyz.shape
-    lib = _lib.load()
     what = "map_push_keyframe"
-    _need(T, "%s: T" % what, torch.float64, (S, 4, 4))
-    _need(cloud, "%s: cloud" % what, torch.float32, (S, n, 3))
-    _need(normals_, "%s: normals" % what, torch.float32, (S, n, 3))
-    _need(stage_ws, "%s: stage_ws" % what, torch.uint8, (lib.knn_point_build_bytes(S, n),))
-    _need(map_xyz, "%s: map_xyz" % what, torch.float32, (S, M, n, 3))
-    _need(map_normals, "%s: map_normals" % what, torch.float32, (S, M, n, 3))
-    _need(map_ws, "%s: map_ws" % what, torch.uint8, (lib.knn_point_build_bytes(S * M, n),))
-    _need(A, "%s: A" % what, torch.float64, (S, M, 4, 4))
-    _need(R, "%s: R" % what, torch.float64, (S, M, 3, 3))
-    _need(live, "%s: live" % what, torch.int32, (S, M))
-    _need(cursor, "%s: cursor" % what, torch.int32, (S,))
+    S, M, n = _need_push(what, T, cloud, normals_, stage_ws, map_xyz, map_normals, map_ws, A, R, live, cursor)
     _need(insert, "%s: insert" % what, torch.int32, (S,))
     if active is not None:
         _need_mask(active, what, S)
