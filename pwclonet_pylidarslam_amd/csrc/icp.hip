@@ -86,6 +86,10 @@ __global__ __launch_bounds__(256) void icp_queries_kernel(int M, int n, const do
 // p (S, n, 3), q / idx / dist (S, M, n[, 3]) from the search with nsample = 1, map_xyz / map_normals (S, M, n, 3), live
 // (S, M), Rm (S, M, 3, 3), T (S, 4, 4) -> partial (S, gridDim.x, ICP_ROW).  A dead slot's idx, dist and map rows are never
 // read.  active: (S) or nullptr.
+// The slot of a point is the live slot of the smallest dist, the lower slot on a tie.  A NaN dist is never smaller, so one
+// in a later slot is passed over; one in the FIRST live slot is taken as the running best, which nothing then beats, and the
+// point is rejected (NaN <= max_dist fails) even when a later slot is finite.  The search writes no NaN for finite clouds;
+// tests/test_gpu_icp_edges.py pins this rule.  dist = +inf pairs only under max_dist = +inf; an idx outside [0, n) rejects.
 __global__ __launch_bounds__(ICP_ACC_THREADS) void icp_accumulate_kernel(
     int M, int n, const float *__restrict__ p, const float *__restrict__ q, const int *__restrict__ idx,
     const float *__restrict__ dist, const float *__restrict__ map_xyz, const float *__restrict__ map_normals,
@@ -194,7 +198,9 @@ __global__ __launch_bounds__(ICP_SOLVE_THREADS) void icp_solve_kernel(
 // re-based on the new frame; the cursor moves on.  insert (S) or nullptr: the keyframe gate's decision (keyframe.hip,
 // DESIGN.md section 23).  nullptr is the ungated push.  A stream with insert[s] == 0 keeps its slots, live flags and cursor:
 // nothing is copied and every live slot, the cursor's included, is only re-based.  The word is the same for the whole
-// workgroup, so the exit is uniform.
+// workgroup, so the exit is uniform.  A cursor word outside [0, M) is read as the nearest slot (-1 as 0, M as M - 1), so no
+// word can send the copy outside the stream's map; an inserting push then leaves the cursor in range, a push that does not
+// insert leaves the word as it found it.
 __global__ __launch_bounds__(1024) void icp_map_push_kernel(int M, int n, int S, int nblk, const double *__restrict__ T,
                                                             const float *__restrict__ cloud,
                                                             const float *__restrict__ normals,

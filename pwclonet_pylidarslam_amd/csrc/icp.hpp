@@ -37,6 +37,9 @@ constexpr int ICP_ACC_THREADS = 256;        // points per workgroup of the accum
 // ---- normals -----------------------------------------------------------------------------------------------------------------
 
 // Eigen-decomposition of the symmetric 3x3 matrix c = [xx xy xz yy yz zz]: val ascending, vec the unit eigenvector of val[0].
+// A NaN off the diagonal is skipped like a zero (no rotation can remove it), so the diagonal then decides alone; the
+// covariance of a neighbourhood with a NaN or Inf point has a diagonal that is not finite either, and icp_normal's rank test
+// turns that into the zero normal.
 ICP_HD void icp_eig3(const double c[6], double val[3], double vec[3]) {
   double a[3][3] = {{c[0], c[1], c[2]}, {c[1], c[3], c[4]}, {c[2], c[4], c[5]}};
   double v[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
@@ -133,7 +136,7 @@ ICP_HD void icp_add_pair(const float p[3], const float q[3], const float y[3], c
 // ---- solve and update ------------------------------------------------------------------------------------------------------------
 
 // delta = -(H / sw + damping I)^-1 (g / sw) from a row of sums, by Cholesky.  false (delta untouched) when a pivot is not
-// positive (NaN included).
+// positive (NaN included) or the step is not finite: a NaN in g alone passes every pivot, and would otherwise reach the pose.
 ICP_HD bool icp_solve6(const double sum[ICP_ROW], double damping, double delta[6]) {
   double L[6][6], b[6];
   const double sw = sum[ICP_SW];
@@ -179,6 +182,9 @@ ICP_HD bool icp_solve6(const double sum[ICP_ROW], double damping, double delta[6
     for (int k = i + 1; k < 6; ++k) s -= L[k][i] * b[k];
     b[i] = s / L[i][i];
   }
+#pragma unroll
+  for (int i = 0; i < 6; ++i)
+    if (!(fabs(b[i]) <= 1.7976931348623157e308)) return false;   // NaN or inf
 #pragma unroll
   for (int i = 0; i < 6; ++i) delta[i] = -b[i];
   return true;

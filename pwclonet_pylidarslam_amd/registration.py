@@ -302,6 +302,11 @@ class IcpRefiner:
     points found a partner within ``max_dist`` (bit 2) or when the damped 6x6 system has a pivot that is not positive (bit
     4); a stream frozen by bit 2 or 4 in iteration 0 returns ``init`` bit for bit.  ``damping`` is added to the diagonal of
     the system normalised by the sum of weights: a direction the scene does not constrain keeps the initial guess.
+    Edges the kernels pin (tests/test_gpu_icp_edges.py): a point pairs with the live slot of the smallest distance, the
+    lower slot on a tie; a NaN distance in a stream's first live slot rejects the point even when a later slot is finite
+    (a NaN in a later slot is passed over); a neighbour index outside [0, n) rejects the point; a row of sums with a NaN in
+    its gradient is refused like a bad pivot (bit 4, the pose untouched); a map cursor outside [0, map_size) is read as
+    the nearest slot.
     ``graph=True``: the first call runs eagerly (it loads every kernel), the second captures one graph that every later
     call replays.  ``register(..., trace=True)`` (``graph=False`` only) also returns, per iteration, clones of the queries,
     ``idx``, ``dist``, the summed row, ``delta`` and ``T``.

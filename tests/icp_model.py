@@ -53,6 +53,40 @@ def normals(xyz, k):
     return nrm, val, gap
 
 
+def eig3(c):
+    """icp_eig3 restated operation for operation (8 sweeps of cyclic Jacobi over (0,1), (0,2), (1,2)): c = [xx xy xz yy yz zz]
+    -> (val (3,) ascending, vec (3,) the unit eigenvector of val[0]).  Where np.linalg.eigh leaves a sign or a basis of a
+    repeated eigenvalue open, this is the device's choice."""
+    a = np.array([[c[0], c[1], c[2]], [c[1], c[3], c[4]], [c[2], c[4], c[5]]], dtype=np.float64)
+    v = np.eye(3)
+    with np.errstate(all="ignore"):
+        for _ in range(8):
+            for p, q in ((0, 1), (0, 2), (1, 2)):
+                apq = a[p, q]
+                if apq == 0.0 or apq != apq:
+                    continue
+                theta = (a[q, q] - a[p, p]) / (2.0 * apq)
+                t = (-1.0 if theta < 0.0 else 1.0) / (np.abs(theta) + np.sqrt(theta * theta + 1.0))
+                cs = 1.0 / np.sqrt(t * t + 1.0)
+                sn = t * cs
+                o = 3 - p - q
+                app, aqq, aop, aoq = a[p, p], a[q, q], a[o, p], a[o, q]
+                a[p, p], a[q, q] = app - t * apq, aqq + t * apq
+                a[p, q] = a[q, p] = 0.0
+                a[o, p] = a[p, o] = cs * aop - sn * aoq
+                a[o, q] = a[q, o] = sn * aop + cs * aoq
+                for i in range(3):
+                    vip, viq = v[i, p], v[i, q]
+                    v[i, p], v[i, q] = cs * vip - sn * viq, sn * vip + cs * viq
+        d0, d1, d2 = a[0, 0], a[1, 1], a[2, 2]
+        lo = 0 if (d0 <= d1 and d0 <= d2) else (1 if d1 <= d2 else 2)
+        e1, e2 = (d1 if lo == 0 else d0), (d1 if lo == 2 else d2)
+        val = np.array([(d0, d1, d2)[lo], e1 if e1 <= e2 else e2, e2 if e1 <= e2 else e1])
+        x, y, z = v[0, lo], v[1, lo], v[2, lo]
+        inv = 1.0 / np.sqrt((x * x + y * y) + z * z)
+        return val, np.array([x * inv, y * inv, z * inv])
+
+
 # ---- queries, accumulate, solve, push --------------------------------------------------------------------------------------
 
 def queries(A, p, T=None):
@@ -98,10 +132,15 @@ def choose(dist, live, max_dist):
     return best, ok
 
 
-def accumulate(p, q32, idx, dist, map_xyz, map_normals, live, R, T, sigma, max_dist):
-    """One stream.  -> (sum (32,), sum of |term| (32,)) over the pairs; the inputs as the device kernel takes them."""
+def accumulate(p, q32, idx, dist, map_xyz, map_normals, live, R, T, sigma, max_dist, points=None):
+    """One stream.  -> (sum (32,), sum of |term| (32,)) over the pairs; the inputs as the device kernel takes them.
+    ``points``: a slice of point indices; only their pairs are added (one workgroup's row: tests/icp_cases.py)."""
     n = p.shape[0]
     slot, ok = choose(dist, live, max_dist)
+    if points is not None:
+        inside = np.zeros((n,), dtype=bool)
+        inside[points] = True
+        ok = ok & inside
     sel = np.flatnonzero(ok)
     out, mag = np.zeros((ROW,)), np.zeros((ROW,))
     if sel.size == 0:
@@ -181,6 +220,8 @@ def solve(row, T, status, it, damping, threshold, min_pairs):
         return dict(delta=delta, T=T.copy(), status=BAD_PIVOT, moved=True)
     z = np.linalg.solve(L, g)
     delta = -np.linalg.solve(L.T, z)
+    if not np.isfinite(delta).all():                            # a NaN in g alone passes every pivot: icp_solve6 refuses the step
+        return dict(delta=np.zeros((6,)), T=T.copy(), status=BAD_PIVOT, moved=True)
     new = exp_update(delta, T)
     return dict(delta=delta, T=new, status=CONVERGED if np.linalg.norm(delta) < threshold else 0, moved=True)
 

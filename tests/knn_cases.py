@@ -17,6 +17,11 @@ the rest is exhaustive); "prebuilt" = knn_build_kernel_wrapper + knn_point_prebu
 N is a number, or ``NBlk(t, side)``: the first / last n whose structure has t blocks, found by scanning the plan query (the
 register-count boundaries of the rows kernels are stated in blocks; the table cannot go stale when the slab rule moves).
 
+There are two tables.  ``CASES`` is the one every sweep runs over (reachability, every instantiation, both sides of every
+boundary).  ``REFINER_CASES`` holds the three search shapes of the knn refiner (registration.IcpRefiner) with their own
+inputs (``refiner_inputs``) and their own truth (tests/icp_model.py's knn, and the oracle); the sweeps over ``CASES`` do not
+see them, and they add no instantiation that ``CASES`` does not reach.
+
 Everything here is CPU torch / numpy.  ``python tests/knn_cases.py --rows0`` is the child process of the PWCLO_KNN_ROWS=0
 test: it checks K <= 32 on the pruned kernel against the oracle and exits non-zero on any difference.
 """
@@ -168,6 +173,27 @@ CASES = (
 # the child process under PWCLO_KNN_ROWS=0: K <= 32 on knn_pruned_kernel, two cloud kinds
 ROWS0_CASES = [Case("rows0-%s-k%d" % (cloud, k), "point", 2, k, 2500, 301, cloud, query, _pruned(4))
                for cloud, query in (("lattice", "own"), ("kitti_outlier", "box")) for k in (1, 6, 16, 32)]
+
+
+# The search forms of the knn refiner (registration.IcpRefiner) at its smallest clouds: one iteration's search, K = 1 over
+# S * M = 12 clouds of the frame's moved points, and the staging's own-neighbour lists, K = k_normals + 1 = 11 with every
+# point of a cloud as a query.  No (b, n, s, k) of these was in CASES (its prebuilt rows have b = 2 and s = 1, 5, 67).  A table
+# of its own: CASES keeps b <= 2, and these are compared with tests/icp_model.py's knn, the registration model's search.
+REFINER_CASES = [Case("refiner-search-b12-n64-k1", "prebuilt", 12, 1, 64, 64, "uniform", "moved", _rows(1, 16, 2)),
+                 Case("refiner-self-b3-n64-k11", "prebuilt", 3, 11, 64, 64, "lattice", "self", _rows(1, 16, 2)),
+                 Case("refiner-self-b3-n65-k11", "prebuilt", 3, 11, 65, 65, "uniform", "self", _rows(1, 16, 2))]
+
+
+def refiner_inputs(case):
+    """-> xyz (b, n, 3), queries (b, n, 3): the clouds themselves ("self") or the clouds turned by 0.05 rad about z and
+    shifted by a few centimetres ("moved"), rounded to fp32 once, as icp_queries_kernel hands them to the search."""
+    xyz = torch.stack([make_cloud(case.cloud, 1 + i, case.n) for i in range(case.b)]).contiguous()
+    if case.query == "self":
+        return xyz, xyz.clone()
+    c, s = np.cos(0.05), np.sin(0.05)
+    rot = torch.tensor([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]], dtype=torch.float64)
+    moved = xyz.double() @ rot.T + torch.tensor([0.07, -0.03, 0.02], dtype=torch.float64)
+    return xyz, moved.float().contiguous()
 
 
 def case_id(c):

@@ -50,6 +50,24 @@ def test_knn_every_instantiation_equals_the_oracle(cuda, case):
         assert torch.equal(got[1], ex[1]) and torch.equal(got[0], ex[0])
 
 
+@pytest.mark.parametrize("case", T.REFINER_CASES, ids=T.case_id)
+def test_refiner_search_forms_equal_the_registration_model(cuda, case):
+    """The two searches of the knn refiner at its smallest clouds, bit for bit against tests/icp_model.py's knn (fp32 keys in
+    the header's order, equal keys by ascending index) and against the oracle."""
+    import numpy as np
+
+    import icp_model
+    assert T.instantiations(T.plan_of(case, use_rows=True)) == case.want
+    xyz, queries = T.refiner_inputs(case)
+    dist, idx = T.run(case, xyz, queries, cuda)
+    want = T.oracle(case, xyz, queries)
+    assert torch.equal(idx.cpu(), want[1]) and torch.equal(dist.cpu(), want[0])
+    for c in range(case.b):
+        wi, wd = icp_model.knn(queries[c].numpy(), xyz[c].numpy(), case.k)
+        assert np.array_equal(idx[c].cpu().numpy(), wi), c
+        assert np.array_equal(dist[c].cpu().numpy().view(np.int32), wd.view(np.int32)), c
+
+
 def test_pruned_kernel_serves_k_up_to_32_with_rows_off(cuda):
     """PWCLO_KNN_ROWS is read once per process, so K <= 32 on knn_pruned_kernel needs a process of its own: the child asserts
     through the plan query that its cases select the pruned kernel, compares K = 1, 6, 16, 32 on two cloud kinds with the

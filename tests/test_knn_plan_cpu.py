@@ -122,6 +122,27 @@ def test_every_dispatched_instantiation_is_selectable_and_in_the_table(E):
         print("%-26s %d cases: %s" % (inst, len(reached[inst]), " ".join(reached[inst][:6]) + (" ..." if len(reached[inst]) > 6 else "")))
 
 
+def test_refiner_cases_select_their_kernels_and_were_missing(E):
+    """The knn refiner's search forms at its smallest clouds: (b, n, s, k) = (12, 64, 64, 1), (3, 64, 64, 11), (3, 65, 65, 11),
+    none of them a shape of the main table, each on the kernels it names; the model's knn agrees with the oracle on them."""
+    import numpy as np
+
+    import icp_model
+    assert [(c.b, c.n, c.s, c.k) for c in T.REFINER_CASES] == [(12, 64, 64, 1), (3, 64, 64, 11), (3, 65, 65, 11)]
+    have = {(c.b, c.n, c.s, c.k) for c in T.CASES if not isinstance(c.n, T.NBlk)}
+    for case in T.REFINER_CASES:
+        assert (case.b, case.n, case.s, case.k) not in have
+        assert T.instantiations(T.plan_of(case, use_rows=True)) == case.want
+        xyz, queries = T.refiner_inputs(case)
+        assert xyz.shape == (case.b, case.n, 3) and queries.shape == (case.b, case.s, 3) and queries.dtype == torch.float32
+        want = T.oracle(case, xyz, queries)
+        for c in range(case.b):
+            wi, wd = icp_model.knn(queries[c].numpy(), xyz[c].numpy(), case.k)
+            assert np.array_equal(want[1][c].numpy(), wi) and np.array_equal(want[0][c].numpy().view(np.int32), wd.view(np.int32))
+        if case.cloud == "lattice":                                  # ties at every rank: the index decides
+            assert len(torch.unique(xyz[0], dim=0)) < case.n
+
+
 def test_rows_bound_table_holds_every_block_of_every_n(E):
     """For every 64 <= n <= 16384, ceil(nblk / L) <= the largest R built for that L (17 for L = 16, 9 for L = 32): with the
     rows switch on, K <= 32 never falls through to the pruned kernel, and the R selected is the smallest that holds nblk."""
