@@ -1262,6 +1262,62 @@ void pose_graph_judge_kernel_wrapper(int S, int N, int ML, int MA, int fix_first
                                      const double *delta, const double *Xt, double *X, double *lam, double *nu, double *chi2,
                                      int *accepted, int diag_stride);
 
+/* ---- 11. loop detection: Scan Context search that feeds the pose graph ---------------------------
+ * Per stream a database of at most MK = max_keyframes places.  A place is the column-normalised polar height image Dn of one
+ * frame (NR rings x NS sectors, 1 <= NR <= 64, 8 <= NS <= 64), the 64-bit mask of its non-empty columns, its frame id and,
+ * where closures are verified, its (n,3) cloud: db_desc (S,MK,NS,NR) floats (an entry's columns, each contiguous), db_mask
+ * (S,MK) 64-bit words, db_frame (S,MK) ints, db_cloud (S,MK,n,3) floats, count (S) ints.  One detection is build, score,
+ * select, fetch, two registrations of section 6's refiner, accept, insert.  active (S) ints or NULL (every stream): a stream
+ * with active[s] == 0 keeps its database, count and log.  S <= 1024.  All pointers DEVICE memory; every sum has a fixed
+ * order, and the only atomic is build's LDS max, whose result does not depend on the order of the points. */
+
+/* One workgroup per stream.  cloud (S,n,3); lengths (S) ints or NULL: rows [0, lengths[s]) count (clamped to [0, n]).  With
+ * up_neg_y the descriptor's (x, y, z) are (c2, -c0, -c1) of a row (c0, c1, c2).  A row is dropped where a coordinate is not
+ * finite, r2 = x x + y y is 0 or >= ring_b[NR-1], or h = z + z_offset <= 0.  ring_b (NR) floats: the squared ring boundaries
+ * b_1..b_NR; ring = #{k < NR : b_k <= r2}.  sector_d (NS,2) floats: the sector directions; sector = the s with dot_s > 0,
+ * cross_s >= 0 and cross_{s+1} < 0.  D (S,NR,NS) = max h of the cell (0: empty); Dn = D / column norm (0 for an empty column,
+ * the sum of squares taken ring-ascending); mask (S) 64-bit words, bit j = column j is not empty.  count, nlog, epoch (S) ints,
+ * all three or all NULL, with restart (S) ints: a stream with active and restart gets count = nlog = 0 and epoch + 1 before
+ * anything is searched. */
+void scan_context_build_kernel_wrapper(int S, int n, int NR, int NS, int up_neg_y, float z_offset, const float *cloud,
+                                       const int *lengths, const float *ring_b, const float *sector_d, float *D, float *Dn,
+                                       void *mask, const int *active, const int *restart, int *count, int *nlog, int *epoch);
+/* Grid (MK / 4, S), one wave per entry e, lane = shift.  Entry e of stream s counts where e < count[s], db_frame[e] +
+ * min_id_distance <= frame_id[s] and, with traj (traj_frames,S,4,4) doubles given, both frame ids lie inside it and the
+ * squared distance of their translations is < max_distance^2; every other entry scores +Inf with shift 0.  Otherwise c(s) =
+ * sum_j sum_r Qn[r][(j+s) mod NS] En[r][j] (j outer, r inner, fp32, unfused), v(s) = popcount(rot(qmask, s) & mask_e), d(s) =
+ * 1 - c(s) / v(s) (+Inf where v(s) = 0); scores (S,MK) = min_s d(s), shifts (S,MK) = the smallest s that reaches it. */
+void loop_score_kernel_wrapper(int S, int NR, int NS, int MK, const float *Qn, const void *qmask, const float *db_desc,
+                               const void *db_mask, const int *db_frame, const int *count, const int *active,
+                               const int *frame_id, int min_id_distance, const double *traj, int traj_frames,
+                               double max_distance, float *scores, int *shifts);
+/* One workgroup per stream: the entry of the lowest score, the lowest entry on a tie.  match (S,4) ints: found (its score <
+ * threshold), entry (-1: no finite score), the entry's frame id, its shift; match_score (S) floats; found (S) ints; T0
+ * (S,4,4) doubles = T0_table[shift] (NS,4,4) where found, else the identity.  slot[s] = count[s] where the stream is active,
+ * frame_id[s] >= 0 is a multiple of stride and the database has room; a full database sets *overflow; otherwise -1.  An idle
+ * stream gets found = 0 and slot = -1. */
+void loop_select_kernel_wrapper(int S, int NS, int MK, int stride, float threshold, const float *scores, const int *shifts,
+                                const int *db_frame, const int *count, const int *active, const int *frame_id,
+                                const double *T0_table, int *match, float *match_score, int *found, double *T0, int *slot,
+                                int *overflow);
+/* staging (S,n,3) = the matched entry's cloud, chosen by the device-side index, for the streams with found != 0. */
+void loop_fetch_kernel_wrapper(int S, int n, int MK, const int *found, const int *match, const float *db_cloud,
+                               float *staging);
+/* One thread per stream.  A found stream is accepted where the refiner's status word has bits 2 and 4 clear, pairs >=
+ * min_fitness n and cost / pairs <= max_mean_cost (status, pairs, cost all NULL: every match is accepted, pairs = cost = 0).
+ * An accepted closure is record nlog[s] of the stream's log: log_i (S,ML,4) ints i = the entry's frame, j = frame_id[s],
+ * shift, pairs; log_T (S,ML,4,4) doubles = T[s], the pose of j in i; log_c (S,ML,2) doubles score, cost.  A full log sets
+ * *log_overflow and writes nothing.  accepted (S) ints: this call's decision. */
+void loop_accept_kernel_wrapper(int S, int n, int ML, const int *found, const int *match, const float *match_score,
+                                const int *frame_id, const double *T, const int *status, const int *pairs, const double *cost,
+                                double min_fitness, double max_mean_cost, int *log_i, double *log_T, double *log_c, int *nlog,
+                                int *log_overflow, int *accepted);
+/* The frame of this call becomes entry slot[s] (select's decision; < 0: nothing is written): its Dn transposed, qmask,
+ * frame_id[s] and, with cloud and db_cloud given (both or neither), its rows; count[s] = slot[s] + 1. */
+void loop_insert_kernel_wrapper(int S, int n, int NR, int NS, int MK, const int *slot, const int *frame_id, const float *Qn,
+                                const void *qmask, const float *cloud, float *db_desc, void *db_mask, int *db_frame,
+                                float *db_cloud, int *count);
+
 #ifdef __cplusplus
 }
 #endif

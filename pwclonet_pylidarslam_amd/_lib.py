@@ -211,6 +211,12 @@ SIGNATURES = {
     "pose_graph_solve_kernel_wrapper": ([_i] * 7 + [ctypes.c_double] + [_F] * 19 + [_i], None),
     "pose_graph_retract_kernel_wrapper": ([_i] * 3 + [_F] * 6, None),
     "pose_graph_judge_kernel_wrapper": ([_i] * 6 + [_F] * 18 + [_i], None),
+    "scan_context_build_kernel_wrapper": ([_i] * 5 + [ctypes.c_float] + [_F] * 12, None),
+    "loop_score_kernel_wrapper": ([_i] * 4 + [_F] * 8 + [_i, _F, _i, ctypes.c_double, _F, _F], None),
+    "loop_select_kernel_wrapper": ([_i] * 4 + [ctypes.c_float] + [_F] * 13, None),
+    "loop_fetch_kernel_wrapper": ([_i] * 3 + [_F] * 4, None),
+    "loop_accept_kernel_wrapper": ([_i] * 3 + [_F] * 8 + [ctypes.c_double] * 2 + [_F] * 6, None),
+    "loop_insert_kernel_wrapper": ([_i] * 5 + [_F] * 10, None),
 }
 
 _lib = None

@@ -110,7 +110,7 @@ class StreamingOdometry:
     start as copies of the first active stream's, so that no step ever reads an uninitialised buffer."""
 
     def __init__(self, net, streams=1, num_points=None, max_frames=4096, graph=True, warmup=1, sweeps=None,
-                 per_stream=False, refine=None, backend=None):
+                 per_stream=False, refine=None, backend=None, loop=None):
         if not 1 <= int(streams) <= MAX_STREAMS:
             raise ValueError("StreamingOdometry: streams=%d outside [1, %d]" % (int(streams), MAX_STREAMS))
         if int(max_frames) < 1:
@@ -173,7 +173,18 @@ class StreamingOdometry:
                 if key in self._backend_cfg:
                     raise ValueError("StreamingOdometry: backend=dict(%s=...) is the stream's own (streams, max_frames, "
                                      "graph)" % key)
-        self._tapped = None         # refine: the frame batch the last step's graph (or eager step) sampled from
+        self._loop = None           # loop=: loop_closure.ScanContextLoopDetector over the step's clouds
+        self._loop_cfg = None if loop is None else dict(loop)
+        self._loop_restart = self._loop_ids = None
+        if loop is not None:
+            if backend is None:
+                raise ValueError("StreamingOdometry: loop=dict(...) hands its closures to the pose graph and needs "
+                                 "backend=dict(...)")
+            for key in ("streams", "num_points", "graph", "device"):
+                if key in self._loop_cfg:
+                    raise ValueError("StreamingOdometry: loop=dict(%s=...) is the stream's own (streams, num_points, graph)"
+                                     % key)
+        self._tapped = None         # refine / loop: the frame batch the last step's graph (or eager step) sampled from
         if refine is not None and self.per_stream != bool(self._refine_cfg.get("per_stream", False)):
             if self.per_stream:
                 raise ValueError("StreamingOdometry: per_stream=True registers with the masked refiner, which the refine "
@@ -257,6 +268,8 @@ class StreamingOdometry:
             self._refiner.reset()                           # the maps too
         if self._backend is not None:
             self._backend.reset()                           # the graphs too
+        if self._loop is not None:
+            self._loop.reset()                              # the places and the closure logs too
         self._reset_motion(None)
 
     def _reset_motion(self, mask):
@@ -425,6 +438,44 @@ class StreamingOdometry:
         graph; idle streams keep theirs).  rel: (S, 4, 4) fp64 or (S, 7) fp32 rows."""
         self._backend.append(rel, active=self._active, valid=self._valid, count=self._counts)
 
+    def loop_detector(self):
+        """With ``loop=``: the ``loop_closure.ScanContextLoopDetector`` (``match()``, ``loops()``, ``counts()``); None before
+        the first frame or without ``loop``."""
+        return self._loop
+
+    def _detect(self, pose):
+        """After the step, the refinement and the backend's append (outside the step's graph): the detector searches and
+        stores the cloud the step sampled from, with the step's own words -- ``active``, ``restart = active * (1 - valid)``
+        (a stream that primed starts an empty database, as its graph did), frame ids ``frame_counts() - 1`` -- and the
+        backend's vertices as the positions of the distance gate.  No sync."""
+        if self._loop_cfg is None:
+            return
+        if self._loop is None:
+            from . import loop_closure
+            cfg = dict(self._loop_cfg)
+            if "up" not in cfg:     # raw KITTI sweeps come out of the front end in the camera frame
+                cfg["up"] = "-y" if self._front is not None and self._front.dataset == "kitti" else "z"
+            self._loop = loop_closure.ScanContextLoopDetector(self.streams, self.num_points, graph=self.graph,
+                                                              device=pose.device, **cfg)
+            self._loop_restart, self._loop_ids = torch.zeros_like(self._active), torch.zeros_like(self._active)
+        cloud = self._tapped[:, :self.num_points, :3].contiguous()
+        torch.sub(self._active, self._valid, out=self._loop_restart)
+        torch.sub(self._counts, 1, out=self._loop_ids)
+        self._loop.process(cloud, self._loop_ids, active=self._active, restart=self._loop_restart,
+                           trajectory=self._backend.bufs["X"], lengths=self.survivor_counts())      # raw mode: the kept rows
+
+    def poll_loops(self, optimize=False):
+        """With ``loop=``: reads the closures the detector accepted since the last poll (a host read) and hands each to
+        ``backend().add_loop(stream, i, j, T)``; ``optimize=True`` then runs ``backend().optimize()`` where there was one.
+        A stream that primed meanwhile emptied its database and log with its graph, so none of its old records is left;
+        a record the graph refuses all the same is kept, with the reason, in ``loop_detector().dropped``.  -> the records
+        handed over (``ScanContextLoopDetector.hand_over``)."""
+        if self._loop_cfg is None:
+            raise RuntimeError("StreamingOdometry: poll_loops needs loop=dict(...)")
+        if self._loop is None:
+            return []
+        return self._loop.hand_over(self._backend, optimize)
+
     def refiner(self):
         """The refiner behind ``refine=``, of the class its ``kind`` names (``status()``, ``diagnostics()``); None before the
         first frame or without ``refine``."""
@@ -464,7 +515,7 @@ class StreamingOdometry:
     def _tap(self, source):
         """``source`` itself, or with ``refine=`` a wrapper that remembers the frame batch it returned: the refiner
         registers the cloud the step sampled from.  The step's launches are the same either way."""
-        if self._refine_cfg is None:
+        if self._refine_cfg is None and self._loop_cfg is None:
             return source
 
         def tapped():
@@ -638,6 +689,7 @@ class StreamingOdometry:
         counter; lock step knows on the host that this call primed every stream (the first since ``reset()``) and
         returns None for it."""
         self._refine(pose)
+        self._detect(pose)
         self.frames_seen += 1
         return None if not self.per_stream and self.frames_seen == 1 else pose
 
