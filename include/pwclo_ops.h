@@ -1318,6 +1318,34 @@ void loop_insert_kernel_wrapper(int S, int n, int NR, int NS, int MK, const int 
                                 const void *qmask, const float *cloud, float *db_desc, void *db_mask, int *db_frame,
                                 float *db_cloud, int *count);
 
+/* Translation search on elevation grids, between select and the verifying registration (optional: image, score, choose).
+ * G = cells, even in [8, 128]; Y = 2 Yh + 1 yaw candidates, odd in [1, 17]; W = window in [0, 16]; L = tolerance in
+ * [1, 255].  The grid of a cloud under a planar rotation (cs, sn), fp32 and unfused in this order, on the descriptor's (x, y,
+ * z) of build: xr = cs x - sn y, yr = sn x + cs y, fx = floorf(xr / cell_size), fy = floorf(yr / cell_size), h = z + z_offset;
+ * a row is dropped where a coordinate is not finite, fx or fy lies outside [-G/2, G/2) (compared as floats) or h <= 0; its
+ * level is q = 255 where l = floorf(h / z_step) >= 254, else (int)l + 1; cell (fx + G/2, fy + G/2) holds the largest q, 0
+ * where empty.  Every kernel skips the streams with found[s] == 0. */
+
+/* Grid (1 + Y, S).  Image 0 is E: staging (S,n,3), every row, at the identity.  Image 1 + k is Q_k: cloud (S,n,3), rows
+ * [0, lengths[s]) (lengths NULL: all), under rot[shift Y + k] (NS Y,2) floats cos / sin, shift = match[s][3].  img
+ * (S,1+Y,G,G) bytes; occ (S,1+Y) ints, the non-empty cells; list (S,Y,G G) ints, i | j << 8 | q << 16 of the non-empty cells
+ * of Q_k in any order. */
+void elevation_image_kernel_wrapper(int S, int n, int NS, int G, int Y, int up_neg_y, float z_offset, float cell_size,
+                                    float z_step, const float *cloud, const float *staging, const int *lengths,
+                                    const int *found, const int *match, const float *rot, void *img, int *occ, int *list);
+/* One wave per 64 consecutive candidates of one (stream, k), lane = candidate.  A (S,Y,2W+1,2W+1) ints: A[k][a+W][b+W] = the
+ * sum of max(0, L - |Q_k[i][j] - E[i+a][j+b]|) over the cells where both are non-empty and (i+a, j+b) lies inside the grid. */
+void elevation_score_kernel_wrapper(int S, int G, int Y, int W, int L, const int *found, const void *img, const int *occ,
+                                    const int *list, int *A);
+/* One workgroup per stream: the largest A, the lowest index ((k (2W+1)) + a + W)(2W+1) + b + W on a tie; found where A > 0
+ * and, in fp32, (float)A >= min_agreement * (float)(L min(occ_Qk, occ_E)).  record (S,8) ints: found, k, a, b, A, occ_Qk,
+ * occ_E, 0.  T1 (S,4,4) doubles: where found, the rotation of pose[shift Y + k] (NS Y,4,4) with the translation (a c, b c, 0)
+ * (up_neg_y: (-b c, 0, a c)), c = (double)cell_size; else T0[s] (S,4,4), as is.  A stream with found[s] == 0 gets a record
+ * of zeros and T1 = T0. */
+void elevation_choose_kernel_wrapper(int S, int NS, int Y, int W, int L, int up_neg_y, float min_agreement, float cell_size,
+                                     const int *found, const int *match, const int *A, const int *occ, const double *pose,
+                                     const double *T0, int *record, double *T1);
+
 #ifdef __cplusplus
 }
 #endif

@@ -217,6 +217,9 @@ SIGNATURES = {
     "loop_fetch_kernel_wrapper": ([_i] * 3 + [_F] * 4, None),
     "loop_accept_kernel_wrapper": ([_i] * 3 + [_F] * 8 + [ctypes.c_double] * 2 + [_F] * 6, None),
     "loop_insert_kernel_wrapper": ([_i] * 5 + [_F] * 10, None),
+    "elevation_image_kernel_wrapper": ([_i] * 6 + [ctypes.c_float] * 3 + [_F] * 9, None),
+    "elevation_score_kernel_wrapper": ([_i] * 5 + [_F] * 5, None),
+    "elevation_choose_kernel_wrapper": ([_i] * 6 + [ctypes.c_float] * 2 + [_F] * 8, None),
 }
 
 _lib = None

@@ -29,6 +29,10 @@ VERIFY_DEFAULTS = dict(iters=20, sigma=0.5, max_dist=2.0, min_fitness=0.3, max_m
 # accepted closure lies inside the band the caller declared as inlier noise.  threshold=0.2 is Scan Context's customary one.
 # No real LiDAR data was at hand when they were chosen, so neither default is measured.
 
+TRANSLATION_DEFAULTS = dict(cells=128, cell_size=1.0, window=16, yaw_div=2, yaw_half=4, z_step=0.25, tolerance=4,
+                            min_agreement=0.5)
+EL_RECORD = 8                                        # csrc/elevation.hpp: found, k, a, b, A, occ_Q, occ_E, 0
+
 LoopRecord = collections.namedtuple("LoopRecord", "stream i j T score shift pairs cost")
 
 
@@ -62,6 +66,47 @@ def tables(rings, sectors, max_range, up="z"):
         c, sn = np.cos(-ang[s]), np.sin(-ang[s])
         T0[s, :3, :3] = P.T @ np.array([[c, -sn, 0.0], [sn, c, 0.0], [0.0, 0.0, 1.0]]) @ P
     return ring_b, sector_d, T0
+
+
+def _translation(what, translation):
+    """The checked ``translation=dict(...)`` with its defaults filled in; ValueError for anything else."""
+    unknown = set(translation) - set(TRANSLATION_DEFAULTS)
+    if unknown:
+        raise ValueError("%s: translation=dict(%s=...): the keys are %s" % (what, sorted(unknown)[0], sorted(TRANSLATION_DEFAULTS)))
+    t = dict(TRANSLATION_DEFAULTS, **translation)
+    whole = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+    for key, lo, hi in (("cells", 8, 128), ("window", 0, 16), ("yaw_div", 1, 8), ("yaw_half", 0, 8), ("tolerance", 1, 255)):
+        if not whole(t[key]) or not lo <= t[key] <= hi:
+            raise ValueError("%s: translation=dict(%s=%r): an integer in [%d, %d]" % (what, key, t[key], lo, hi))
+        t[key] = int(t[key])
+    if t["cells"] % 2:
+        raise ValueError("%s: translation=dict(cells=%d) must be even" % (what, t["cells"]))
+    for key in ("cell_size", "z_step"):
+        v = float(np.float32(t[key]))                   # the kernels' fp32 value must itself be finite and > 0
+        if not (v > 0.0 and math.isfinite(v)):
+            raise ValueError("%s: translation=dict(%s=%r) must be finite and > 0" % (what, key, t[key]))
+        t[key] = float(t[key])
+    if not 0.0 <= float(t["min_agreement"]) <= 1.0:
+        raise ValueError("%s: translation=dict(min_agreement=%r) outside [0, 1]" % (what, t["min_agreement"]))
+    t["min_agreement"] = float(t["min_agreement"])
+    return t
+
+
+def elevation_tables(sectors, yaw_div, yaw_half, up="z"):
+    """The host tables of the translation search, computed in fp64, row ``shift * Y + k`` with Y = 2 yaw_half + 1: rot (NS Y, 2)
+    fp32 = fp32(cos, sin)(theta) and pose (NS Y, 4, 4) fp64 = [Rz(theta), 0] (for ``up="-y"`` conjugated as ``tables`` does),
+    theta = -(shift + (k - yaw_half) / yaw_div) 2 pi / NS: the sign of ``T0``."""
+    NS, Y = int(sectors), 2 * int(yaw_half) + 1
+    rot = np.zeros((NS * Y, 2), dtype=np.float32)
+    pose = np.tile(np.eye(4), (NS * Y, 1, 1))
+    P = np.array([[0.0, 0.0, 1.0], [-1.0, 0.0, 0.0], [0.0, -1.0, 0.0]]) if up == "-y" else np.eye(3)
+    for s in range(NS):
+        for k in range(Y):
+            theta = -(float(s) + float(k - int(yaw_half)) / float(yaw_div)) * (2.0 * np.pi) / float(NS)
+            c, sn = np.cos(theta), np.sin(theta)
+            rot[s * Y + k] = c, sn
+            pose[s * Y + k, :3, :3] = P.T @ np.array([[c, -sn, 0.0], [sn, c, 0.0], [0.0, 0.0, 1.0]]) @ P
+    return rot, pose
 
 
 def _kind(t, name, dtype, shape):
@@ -132,7 +177,7 @@ class ScanContextLoopDetector:
 
     def __init__(self, streams, num_points, rings=20, sectors=60, max_range=80.0, z_offset=2.0, up="z", max_keyframes=1024,
                  max_loops=256, stride=1, min_id_distance=200, max_distance=None, threshold=0.2, verify=VERIFY_DEFAULTS,
-                 graph=True, device="cuda"):
+                 graph=True, device="cuda", translation=None):
         what = "ScanContextLoopDetector"
         S, n, MK, ML = int(streams), int(num_points), int(max_keyframes), int(max_loops)
         if not 1 <= S <= MAX_STREAMS:
@@ -162,6 +207,11 @@ class ScanContextLoopDetector:
                 raise ValueError("%s: verify needs iters >= 1, sigma > 0 and max_dist >= 0" % what)
             if not 0.0 <= float(verify["min_fitness"]) <= 1.0 or not float(verify["max_mean_cost"] or 0.0) >= 0.0:
                 raise ValueError("%s: verify needs min_fitness in [0, 1] and max_mean_cost >= 0" % what)
+        if translation is not None:
+            if verify is None:
+                raise ValueError("%s: translation= images the stored clouds, which only verify= keeps" % what)
+            translation = _translation(what, translation)
+        self.translation = translation
         self.streams, self.num_points, self.rings, self.sectors = S, n, NR, NS
         self.max_range, self.z_offset, self.up = float(max_range), float(z_offset), up
         self.max_keyframes, self.max_loops, self.stride, self.min_id_distance = MK, ML, int(stride), int(min_id_distance)
@@ -199,12 +249,26 @@ class ScanContextLoopDetector:
             accepted=i32(S), eye=torch.eye(4, dtype=torch.float64, device=dev).expand(S, 4, 4).contiguous())
         if self.verify is not None:
             self.bufs.update(db_cloud=f32(S, MK, n, 3), staging=f32(S, n, 3))
+        if self.translation is not None:
+            t = self.translation
+            G, Y, side = t["cells"], 2 * t["yaw_half"] + 1, 2 * t["window"] + 1
+            rot, pose = elevation_tables(NS, t["yaw_div"], t["yaw_half"], self.up)
+            self.bufs.update(ei_rot=torch.from_numpy(rot).to(dev), ei_pose=torch.from_numpy(pose).to(dev),
+                             ei_img=torch.zeros((S, 1 + Y, G, G), dtype=torch.uint8, device=dev), ei_occ=i32(S, 1 + Y),
+                             ei_list=i32(S, Y, G * G), ei_A=i32(S, Y, side, side), ei_record=i32(S, EL_RECORD),
+                             T1=torch.eye(4, dtype=torch.float64, device=dev).expand(S, 4, 4).contiguous())
 
     def map_bytes(self):
-        """Bytes of the databases and logs of all streams (96 KiB of cloud per place at n = 8192 with verification)."""
+        """Bytes of the databases and logs of all streams (96 KiB of cloud per place at n = 8192 with verification) and,
+        with ``translation``, of the images, lists and scores of one call (per stream, not per place)."""
         S, n, MK, ML = self.streams, self.num_points, self.max_keyframes, self.max_loops
         per_place = self.rings * self.sectors * 4 + 8 + 4 + (n * 12 if self.verify is not None else 0)
-        return S * (MK * per_place + ML * (16 + 128 + 16))
+        per_call = 0
+        if self.translation is not None:
+            t = self.translation
+            G, Y, side = t["cells"], 2 * t["yaw_half"] + 1, 2 * t["window"] + 1
+            per_call = (1 + Y) * (G * G + 4) + Y * G * G * 4 + Y * side * side * 4 + EL_RECORD * 4 + 128
+        return S * (MK * per_place + ML * (16 + 128 + 16) + per_call)
 
     def counts(self):
         """(S,) int32 device view: the places stored per stream.  None before the first call."""
@@ -245,6 +309,16 @@ class ScanContextLoopDetector:
         m = b["match"]
         return dict(found=m[:, 0], entry=m[:, 1], frame_i=m[:, 2], shift=m[:, 3], score=b["match_score"], T0=b["T0"],
                     accepted=b["accepted"])
+
+    def seed(self):
+        """With ``translation``: device views of the last call's translation search per stream: found, k (the yaw
+        candidate), a, b (the offset in cells), A (its agreement), occ_q, occ_e (the non-empty cells of the two images) and T1
+        (S, 4, 4), the pose the verification started from (``T0`` where nothing was found).  None before the first call or
+        without ``translation``."""
+        if self.bufs is None or self.translation is None:
+            return None
+        r = self.bufs["ei_record"]
+        return dict(found=r[:, 0], k=r[:, 1], a=r[:, 2], b=r[:, 3], A=r[:, 4], occ_q=r[:, 5], occ_e=r[:, 6], T1=self.bufs["T1"])
 
     def database(self, stream):
         """Device tensors of one stream's places: Dn (count, NR, NS), mask (count,), frame_id (count,) and, with
@@ -336,6 +410,31 @@ class ScanContextLoopDetector:
         _lib.call("loop_fetch_kernel_wrapper", self.device, self.streams, self.num_points, self.max_keyframes, _p(b["found"]),
                   _p(b["match"]), _p(b["db_cloud"]), _p(b["staging"]))
 
+    def image(self):
+        b, t = self.bufs, self.translation
+        _lib.call("elevation_image_kernel_wrapper", self.device, self.streams, self.num_points, self.sectors, t["cells"],
+                  2 * t["yaw_half"] + 1, int(self.up == "-y"), self.z_offset, t["cell_size"], t["z_step"], _p(b["cloud"]),
+                  _p(b["staging"]), _p(b["lengths"]), _p(b["found"]), _p(b["match"]), _p(b["ei_rot"]), _p(b["ei_img"]),
+                  _p(b["ei_occ"]), _p(b["ei_list"]))
+
+    def agreement(self):
+        b, t = self.bufs, self.translation
+        _lib.call("elevation_score_kernel_wrapper", self.device, self.streams, t["cells"], 2 * t["yaw_half"] + 1, t["window"],
+                  t["tolerance"], _p(b["found"]), _p(b["ei_img"]), _p(b["ei_occ"]), _p(b["ei_list"]), _p(b["ei_A"]))
+
+    def choose(self):
+        b, t = self.bufs, self.translation
+        _lib.call("elevation_choose_kernel_wrapper", self.device, self.streams, self.sectors, 2 * t["yaw_half"] + 1,
+                  t["window"], t["tolerance"], int(self.up == "-y"), t["min_agreement"], t["cell_size"], _p(b["found"]),
+                  _p(b["match"]), _p(b["ei_A"]), _p(b["ei_occ"]), _p(b["ei_pose"]), _p(b["T0"]), _p(b["ei_record"]),
+                  _p(b["T1"]))
+
+    def translate(self):
+        """Image, score and choose alone: the three launches of the translation search, after ``fetch``."""
+        self.image()
+        self.agreement()
+        self.choose()
+
     def accept(self, T):
         b, v = self.bufs, self.verify
         r = None if v is None else self._refiner.bufs
@@ -365,8 +464,12 @@ class ScanContextLoopDetector:
         T = b["T0"]
         if self.verify is not None:
             self.fetch()
+            start = b["T0"]
+            if self.translation is not None:
+                self.translate()
+                start = b["T1"]
             self._refiner.register(b["staging"], b["eye"], active=b["found"], restart=b["found"])
-            T = self._refiner.register(b["cloud"], b["T0"], active=b["found"])
+            T = self._refiner.register(b["cloud"], start, active=b["found"])
         self.accept(T)
         self.insert()
 

@@ -6,6 +6,11 @@ Per (streams, stored places) at n = 8192: one captured replay of descriptor + sc
 verification (fetch, two registrations, accept, insert), medians and spread over ``--repeats`` timed batches of replays
 between two events on the stream; beside it the same search in NumPy on 16 host threads.  Then one ``StreamingOdometry``
 step with and without ``loop=``, alternated in one process.  Prints one JSON line per size and one for the step.
+
+    python tools/loop_closure_bench.py --translation [--out profiles/loop_closure/translation_bench.jsonl]
+
+times instead the whole chain with and without ``translation=`` (its defaults), alternated in one process, for S = 1 and 8:
+the yardstick of the translation search is the same chain without it at the same commit.
 """
 import argparse
 import concurrent.futures
@@ -121,16 +126,75 @@ def step_with_and_without(dev, repeats, points, frames=21):
     return out
 
 
+def replays(graph, inner=10):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(inner):
+        graph.replay()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / inner * 1e3
+
+
+def chain_with_and_without(dev, repeats, points, places=1024):
+    """The whole chain (every replay finds, fetches, registers and accepts place 0, the query itself) with and without
+    ``translation=``, one captured graph each, timed in alternation: -> one line per stream count."""
+    lines = []
+    for S in (1, 8):
+        frames = torch.from_numpy(cloud(7, S, points)).to(dev)
+        dets, graphs = {}, {}
+        for name, tr in (("plain", None), ("translation", dict())):
+            det = ScanContextLoopDetector(S, points, max_keyframes=places + 8, min_id_distance=0, device=dev, translation=tr)
+            det.process(frames, [places] * S)
+            fill(det, places, 11)
+
+            def chain(det=det):
+                det.bufs["count"].fill_(places)
+                det._body(None)
+            chain()
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with _lib.capture(g):
+                chain()
+            for _ in range(3):
+                g.replay()
+            torch.cuda.synchronize()
+            dets[name], graphs[name] = det, g
+        times = dict(plain=[], translation=[])
+        for _ in range(repeats):
+            for name in times:
+                times[name].append(replays(graphs[name]))
+        seed = dets["translation"].seed()
+        line = dict(streams=S, places=places, points=points, parameters=dets["translation"].translation,
+                    seed_found=seed["found"].tolist(), seed_cells=seed["occ_q"].tolist(),
+                    accepted=dets["translation"].match()["accepted"].tolist())
+        line.update({name: dict(median_us=statistics.median(t), min_us=min(t), max_us=max(t)) for name, t in times.items()})
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+        del dets, graphs
+        torch.cuda.empty_cache()
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=9)
     ap.add_argument("--points", type=int, default=8192)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--translation", action="store_true", help="the whole chain with and without translation=, alternated")
     args = ap.parse_args()
     if args.repeats < 7:
         raise SystemExit("--repeats must be >= 7")
     dev = torch.device("cuda:0")
     torch.set_grad_enabled(False)
+    if args.translation:
+        lines = chain_with_and_without(dev, args.repeats, args.points)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                for line in lines:
+                    f.write(json.dumps(line) + "\n")
+        return
     pool = concurrent.futures.ThreadPoolExecutor(THREADS)
     lines = []
     for S in (1, 8):
