@@ -54,10 +54,10 @@ def descriptor(cloud, rings=20, sectors=60, max_range=80.0, z_offset=2.0, up="z"
 def normalise(D):
     rings, sectors = D.shape
     total = np.zeros(sectors, dtype=F)
-    for r in range(rings):
-        total = total + D[r] * D[r]
-    norm = np.sqrt(total)
-    with np.errstate(all="ignore"):
+    with np.errstate(all="ignore"):                      # a square may overflow: the norm is inf then, the column 0
+        for r in range(rings):
+            total = total + D[r] * D[r]
+        norm = np.sqrt(total)
         Dn = np.where(norm > 0, D / norm[None, :], F(0)).astype(F)
     mask = 0
     for j in range(sectors):
@@ -155,3 +155,93 @@ def start_pose(shift, sectors, up="z"):
     T = np.eye(4)
     T[:3, :3] = P.T @ Rz @ P
     return T
+
+
+# ---- the bookkeeping stages: select, accept, insert, fetch and the words of build ---------------------------------------------
+
+FEW_PAIRS, BAD_PIVOT = 2, 4                             # the refiner's status bits that refuse a closure
+NO_MATCH = (0, -1, -1, 0)
+
+
+def build_words(active, restart, count, nlog, epoch):
+    """The detector's words after build: an idle stream keeps all three; ``restart`` empties an active one."""
+    if active != 0 and restart != 0:
+        return 0, 0, epoch + 1
+    return count, nlog, epoch
+
+
+def build(cloud, length, active, restart, count, nlog, epoch, **params):
+    """-> None for an idle stream (nothing is written), else dict(D, Dn, mask, count, nlog, epoch)."""
+    if active == 0:
+        return None
+    D, Dn, mask = descriptor(cloud, length=length, **params)
+    count, nlog, epoch = build_words(active, restart, count, nlog, epoch)
+    return dict(D=D, Dn=Dn, mask=mask, count=count, nlog=nlog, epoch=epoch)
+
+
+def select(scores, shifts, frame_ids, count, active, f, stride, threshold, MK):
+    """-> dict(match (found, entry, frame_i, shift), score fp32, found, slot, overflow, row): the lowest score below +inf
+    wins (a NaN never does), the lowest entry on a tie (-0.0 == 0.0 is one); ``row``: the row of the T0 table, None for the
+    identity.  The slot: ``count`` where the stream is active, f >= 0, f % stride == 0 and count < MK; a full database
+    raises overflow; an idle stream gets the no-match record and slot -1."""
+    out = dict(match=NO_MATCH, score=F(np.inf), found=0, slot=-1, overflow=False, row=None)
+    if not active:
+        return out
+    v = np.asarray(scores, dtype=F)[:MK]
+    wins = v < F(np.inf)                                 # false for NaN and for +inf
+    if wins.any():
+        e = int(np.nonzero(wins & (v == v[wins].min()))[0][0])
+        d = v[e]                                         # the winner's own bits: -0.0 and 0.0 compare equal
+        found = int(d < F(threshold))
+        out.update(match=(found, e, int(frame_ids[e]), int(shifts[e])), score=d, found=found,
+                   row=int(shifts[e]) if found else None)
+    if f >= 0 and f % stride == 0:
+        if count < MK:
+            out["slot"] = int(count)
+        else:
+            out["overflow"] = True
+    return out
+
+
+def accept(found, match, score, f, T, status, pairs, cost, n, min_fitness, max_mean_cost, nlog, ML):
+    """-> dict(accepted, nlog, overflow, record): refused where a status bit 2 or 4 is set, not ``pairs >= min_fitness n``
+    or not ``cost / pairs <= max_mean_cost`` (fp64, so a NaN on either side refuses); ``status=None``: every match, with
+    pairs 0 and cost 0.  record: None or (log_i (4,) int32, log_T (4, 4) fp64, log_c (2,) fp64); a full log raises overflow."""
+    out = dict(accepted=0, nlog=int(nlog), overflow=False, record=None)
+    if not found:
+        return out
+    if status is None:
+        pairs, cost = 0, np.float64(0.0)
+    else:
+        pairs, cost = int(pairs), np.float64(cost)
+        if status & (FEW_PAIRS | BAD_PIVOT):
+            return out
+        with np.errstate(all="ignore"):
+            if not (np.float64(pairs) >= np.float64(min_fitness) * np.float64(n)):
+                return out
+            if not (cost / np.float64(pairs) <= np.float64(max_mean_cost)):
+                return out
+    if nlog >= ML:
+        out["overflow"] = True
+        return out
+    rec = (np.array([match[2], f, match[3], pairs], dtype=np.int32), np.array(T, dtype=np.float64).reshape(4, 4),
+           np.array([np.float64(F(score)), cost], dtype=np.float64))
+    out.update(accepted=1, nlog=int(nlog) + 1, record=rec)
+    return out
+
+
+def insert(slot, f, Qn, qmask, cloud, MK):
+    """-> None (nothing is written) or dict(entry, desc (NS, NR): the columns of Qn, each contiguous, mask, frame, cloud,
+    count = slot + 1 whatever the count held)."""
+    if slot < 0 or slot >= MK:
+        return None
+    return dict(entry=int(slot), desc=np.ascontiguousarray(np.asarray(Qn, dtype=F).T), mask=int(qmask), frame=int(f),
+                cloud=None if cloud is None else np.asarray(cloud, dtype=F), count=int(slot) + 1)
+
+
+def fetch(found, match, db_cloud, MK):
+    """-> None (staging keeps its words) or the matched entry's (n, 3) cloud."""
+    e = match[1]
+    if not found or e < 0 or e >= MK:
+        return None
+    return np.asarray(db_cloud, dtype=F)[e]
