@@ -1239,6 +1239,27 @@ void pose_graph_linearise_kernel_wrapper(int S, int N, int ML, int MA, const int
                                          const int *nloops, const int *nabs, const double *X, const double *Zc,
                                          const int *loop_ij, const double *loop_Z, const double *loop_Om, const int *abs_i,
                                          const double *abs_G, const double *abs_Om, double *slots, double *chi_only);
+/* The same launch with a robust kernel on the edge classes of edge_mask (1 chain | 2 loop | 4
+ * absolute, in [1, 7]).  With c = e^T Omega e the raw term of such an edge, kind 1 Huber: c <= delta^2: rho = c, w = 1,
+ * otherwise s = sqrt(c), rho = (2 s) delta - delta delta, w = delta / s; kind 2 Geman-McClure: a = delta / (delta + c), rho = c
+ * a, w = a a; kind 3 DCS (delta is Phi): s = (2 delta) / (delta + c), s >= 1: rho = c, w = 1, otherwise w = s s, rho = w c.  An
+ * edge outside the mask has rho = c, w = 1.  The chi2 term (slot double 132, or chi_only) is rho; the three blocks and the two
+ * gradients are the finished plain ones times w (first order: no rho'' term); e and Omega e stay raw; the full form also
+ * writes c into slot double 133 and w into 134, which the plain launch never touches.  A non-finite c gives a non-finite
+ * rho.  delta finite and > 0, kind in [1, 3]: anything else is refused before the launch.  Solve, retract and judge read the
+ * slots and chi terms as before. */
+void pose_graph_linearise_robust_kernel_wrapper(int S, int N, int ML, int MA, int kind, int edge_mask, double delta,
+                                                const int *active, const int *status, const int *count, const int *nloops,
+                                                const int *nabs, const double *X, const double *Zc, const int *loop_ij,
+                                                const double *loop_Z, const double *loop_Om, const int *abs_i,
+                                                const double *abs_G, const double *abs_Om, double *slots, double *chi_only);
+/* The read-out of the weights: one thread per loop and absolute edge id, for every stream, idle and frozen ones included.
+ * out (S, ML + MA, 2) doubles: c and w of loop l at row l and of absolute edge a at row ML + a, at the poses X as they stand;
+ * zeros past nloops[s] / nabs[s].  kind 0: no kernel, w = 1 (edge_mask and delta are not read); otherwise as above. */
+void pose_graph_edge_weights_kernel_wrapper(int S, int N, int ML, int MA, int kind, int edge_mask, double delta,
+                                            const int *nloops, const int *nabs, const double *X, const int *loop_ij,
+                                            const double *loop_Z, const double *loop_Om, const int *abs_i, const double *abs_G,
+                                            const double *abs_Om, double *out);
 /* One workgroup per stream, iteration `it` of the call.  chi2[s] = the sum of the slots' chi2 terms (not finite: status 4);
  * b and the 6 x 6 block diagonal of H gathered per vertex (chain edge v, chain edge v + 1, then the incidence list); it == 0:
  * lam[s] = 1e-5 max diag H, nu[s] = 2; max |b| <= 1e-12: status 1.  Then block-Jacobi preconditioned conjugate gradients on

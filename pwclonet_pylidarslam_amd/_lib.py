@@ -208,6 +208,8 @@ SIGNATURES = {
     "pose_graph_begin_kernel_wrapper": ([_i] * 3 + [_F] * 9, None),
     "pose_graph_append_kernel_wrapper": ([_i, _i] + [_F] * 12, None),
     "pose_graph_linearise_kernel_wrapper": ([_i] * 4 + [_F] * 15, None),
+    "pose_graph_linearise_robust_kernel_wrapper": ([_i] * 6 + [ctypes.c_double] + [_F] * 15, None),
+    "pose_graph_edge_weights_kernel_wrapper": ([_i] * 6 + [ctypes.c_double] + [_F] * 10, None),
     "pose_graph_solve_kernel_wrapper": ([_i] * 7 + [ctypes.c_double] + [_F] * 19 + [_i], None),
     "pose_graph_retract_kernel_wrapper": ([_i] * 3 + [_F] * 6, None),
     "pose_graph_judge_kernel_wrapper": ([_i] * 6 + [_F] * 18 + [_i], None),

@@ -10,7 +10,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from .pose_graph import PoseGraph, default_information
+from .pose_graph import EDGE_CLASSES, PoseGraph, default_information, robust_settings
 
 
 def _mul(a, b):
@@ -22,6 +22,18 @@ def _mul(a, b):
             s = (a[i, 0] * b[0, j] + a[i, 1] * b[1, j]) + a[i, 2] * b[2, j]
             c[i, j] = s + a[i, 3] if j == 3 else s
     return c
+
+
+@dataclass(frozen=True)
+class RobustKernel:
+    """What ``GraphSLAM.robust_kernel`` takes in place of a g2o kernel object: ``name`` "huber", "geman_mcclure" or "dcs"
+    and its ``delta`` (g2o's ``setDelta``; Phi for "dcs")."""
+    name: str
+    delta: float = 1.0
+
+    def settings(self):
+        """As ``PoseGraph(robust=...)`` takes it, on all three edge classes: the reference sets the kernel on every edge."""
+        return dict(kernel=self.name, delta=self.delta, edges=tuple(EDGE_CLASSES))
 
 
 @dataclass
@@ -48,6 +60,27 @@ class GraphSLAM:
         self._constraints = None
         self.need_to_update_pose = False
         self._graph = None
+        self._robust_kernel = None
+
+    @property
+    def robust_kernel(self):
+        """None or a ``RobustKernel``.  *Departure:* the reference hands the kernel to the edges ``next_frame`` adds after
+        the assignment; here it acts on every chain, loop and absolute edge of the graph from the next ``optimize`` on."""
+        return self._robust_kernel
+
+    @robust_kernel.setter
+    def robust_kernel(self, robust_kernel):
+        if robust_kernel is not None:
+            if not isinstance(robust_kernel, RobustKernel):
+                raise ValueError("GraphSLAM: robust_kernel must be None or a RobustKernel(name, delta), not %r"
+                                 % (robust_kernel,))
+            robust_settings(robust_kernel.settings(), "GraphSLAM.robust_kernel")
+        self._robust_kernel = robust_kernel
+        if self._graph is not None:
+            self._graph.set_robust(self._robust_settings())
+
+    def _robust_settings(self):
+        return None if self._robust_kernel is None else self._robust_kernel.settings()
 
     @staticmethod
     def _regexes():
@@ -80,7 +113,7 @@ class GraphSLAM:
         c = self.config
         if self._graph is None:
             self._graph = PoseGraph(1, c.max_poses, c.max_loops, c.max_absolute, iters=c.max_optim_iterations,
-                                    fix_first=c.fix_first_frame, device=c.device)
+                                    fix_first=c.fix_first_frame, device=c.device, robust=self._robust_settings())
         else:
             self._graph.reset()
         self._constraints = None

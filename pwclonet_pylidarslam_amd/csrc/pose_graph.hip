@@ -12,7 +12,8 @@
 //   judge      one workgroup per stream: chi2_new, the gain ratio, accept / reject, lambda, the status word; an accepted
 //              step copies the trial poses over the vertices
 // Every sum is taken in a fixed order (block_sum below), there is no atomic, and no workgroup waits on another.  A stream
-// with active[s] == 0, or whose status word is set, is skipped by every kernel.
+// with active[s] == 0, or whose status word is set, is skipped by every kernel but the read-out of the edge weights.  With a
+// robust kernel (section 25.1) linearise writes rho(c) as an edge's chi2 term and its blocks and gradients times the weight w.
 #include "pose_graph.hpp"
 
 namespace pwclo {
@@ -125,79 +126,134 @@ __device__ __forceinline__ void mat6_tvec_add(const double *a, const double *x, 
   }
 }
 
-// grid (ceil(E / 64), S).  FULL: the whole slot from the poses X; otherwise only the chi2 term, into chi_out (S, E).
-template <bool FULL>
+// One edge id of a stream resolved: its ends, measurement, information (nullptr: an odometry edge) and class bit.
+struct PgEdge {
+  int vi, vj, cls;
+  const double *Zp, *Omp;
+  bool absolute;
+};
+// false where the id is no edge of the stream
+__device__ __forceinline__ bool pg_edge_at(const PgGraph &g, int s, int id, PgEdge &ed) {
+  ed.Omp = nullptr;
+  ed.absolute = false;
+  if (id < g.N) {
+    if (id < 1 || id >= g.count[s]) return false;
+    ed.vi = id - 1; ed.vj = id;
+    ed.Zp = g.Zc + pg_pose_at(g, s, id);
+    ed.cls = PG_CLASS_CHAIN;
+  } else if (id < g.N + g.ML) {
+    const int l = id - g.N;
+    if (l >= g.nloops[s]) return false;
+    ed.vi = g.loop_ij[((size_t)s * g.ML + l) * 2];
+    ed.vj = g.loop_ij[((size_t)s * g.ML + l) * 2 + 1];
+    ed.Zp = g.loop_Z + ((size_t)s * g.ML + l) * 16;
+    ed.Omp = g.loop_Om + ((size_t)s * g.ML + l) * 36;
+    ed.cls = PG_CLASS_LOOP;
+  } else {
+    const int a = id - g.N - g.ML;
+    if (a >= g.nabs[s]) return false;
+    ed.vi = ed.vj = g.abs_i[(size_t)s * g.MA + a];
+    ed.Zp = g.abs_G + ((size_t)s * g.MA + a) * 16;
+    ed.Omp = g.abs_Om + ((size_t)s * g.MA + a) * 36;
+    ed.absolute = true;
+    ed.cls = PG_CLASS_ABSOLUTE;
+  }
+  return true;
+}
+
+// The error of an edge at the poses X: Delta = Z^-1 X_i^-1 X_j, e = (t_Delta, sg q_xyz), Omega e and chi = e^T Omega e.
+struct PgError {
+  double Om[36], e[6], Oe[6], chi, sg;
+  Se3 Z, A, D;
+  Quat q;
+};
+__device__ __forceinline__ void pg_edge_error(const PgGraph &g, const double *__restrict__ X, int s, const PgEdge &ed,
+                                              PgError &r) {
+  if (ed.Omp != nullptr) {
+#pragma unroll
+    for (int k = 0; k < 36; ++k) r.Om[k] = ed.Omp[k];
+  } else {                                       // an odometry edge: diag(2, 2, 2, 5, 5, 5)
+#pragma unroll
+    for (int k = 0; k < 36; ++k) r.Om[k] = (k % 7 == 0) ? (k < 21 ? 2.0 : 5.0) : 0.0;
+  }
+  r.Z = se3_load(ed.Zp);
+  const Se3 Xj = se3_load(X + pg_pose_at(g, s, ed.vj));
+  r.A = Xj;                                      // absolute: the fixed vertex is G itself and Z = I
+  if (!ed.absolute) r.A = se3_mul(se3_rigid_inv(se3_load(X + pg_pose_at(g, s, ed.vi))), Xj);
+  r.D = se3_mul(se3_rigid_inv(r.Z), r.A);
+  r.q = se3_quat(r.D);
+  r.sg = r.q.w < 0.0 ? -1.0 : 1.0;
+  r.e[0] = r.D.m[3]; r.e[1] = r.D.m[7]; r.e[2] = r.D.m[11];
+  r.e[3] = r.sg * r.q.x; r.e[4] = r.sg * r.q.y; r.e[5] = r.sg * r.q.z;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    double t = r.Om[k * 6] * r.e[0];
+#pragma unroll
+    for (int m = 1; m < 6; ++m) t += r.Om[k * 6 + m] * r.e[m];
+    r.Oe[k] = t;
+  }
+  double chi = r.e[0] * r.Oe[0];
+#pragma unroll
+  for (int m = 1; m < 6; ++m) chi += r.e[m] * r.Oe[m];
+  r.chi = chi;
+}
+
+// The kernel of a launch: kind PG_HUBER .. PG_DCS (PG_ROBUST_NONE: none), its delta, and the mask of edge classes it acts on.
+struct PgRobust {
+  int kind, mask;
+  double delta;
+};
+// rho and w of an edge of class cls with raw term c: an edge outside the mask keeps rho = c, w = 1
+__device__ __forceinline__ void pg_edge_robustify(const PgRobust &rb, int cls, double c, double *rho, double *w) {
+  pg_robustify((rb.mask & cls) != 0 ? rb.kind : PG_ROBUST_NONE, rb.delta, c, rho, w);
+}
+// dst (n doubles) = w times the finished block or gradient src (the one order the model repeats); without a kernel: src
+template <bool ROBUST, int n>
+__device__ __forceinline__ void pg_put(double *__restrict__ dst, const double *src, double w) {
+#pragma unroll
+  for (int k = 0; k < n; ++k) dst[k] = ROBUST ? w * src[k] : src[k];
+}
+
+// grid (ceil(E / 64), S).  FULL: the whole slot from the poses X; otherwise only the chi2 term, into chi_out (S, E).  ROBUST:
+// the chi2 term is rho(c), the blocks and gradients carry the weight w = rho'(c) (first order: no rho'' term), and the full
+// form leaves the raw c and w in the slot's spare doubles; the plain form never reads rb and never touches those doubles.
+template <bool FULL, bool ROBUST>
 __global__ __launch_bounds__(PG_EDGE_THREADS) void pg_linearise_kernel(PgGraph g, const double *__restrict__ X,
                                                                        double *__restrict__ slots,
-                                                                       double *__restrict__ chi_out) {
+                                                                       double *__restrict__ chi_out, PgRobust rb) {
   const int s = blockIdx.y;
   if (!pg_runs(g, s)) return;
   const int id = blockIdx.x * PG_EDGE_THREADS + threadIdx.x;
   const int E = g.N + g.ML + g.MA;
   if (id >= E) return;
-  int vi, vj;
-  const double *Zp, *Omp = nullptr;
-  bool absolute = false;
-  if (id < g.N) {
-    if (id < 1 || id >= g.count[s]) return;
-    vi = id - 1; vj = id;
-    Zp = g.Zc + pg_pose_at(g, s, id);
-  } else if (id < g.N + g.ML) {
-    const int l = id - g.N;
-    if (l >= g.nloops[s]) return;
-    vi = g.loop_ij[((size_t)s * g.ML + l) * 2];
-    vj = g.loop_ij[((size_t)s * g.ML + l) * 2 + 1];
-    Zp = g.loop_Z + ((size_t)s * g.ML + l) * 16;
-    Omp = g.loop_Om + ((size_t)s * g.ML + l) * 36;
-  } else {
-    const int a = id - g.N - g.ML;
-    if (a >= g.nabs[s]) return;
-    vi = vj = g.abs_i[(size_t)s * g.MA + a];
-    Zp = g.abs_G + ((size_t)s * g.MA + a) * 16;
-    Omp = g.abs_Om + ((size_t)s * g.MA + a) * 36;
-    absolute = true;
-  }
-  double Om[36];
-  if (Omp != nullptr) {
-#pragma unroll
-    for (int k = 0; k < 36; ++k) Om[k] = Omp[k];
-  } else {                                       // an odometry edge: diag(2, 2, 2, 5, 5, 5)
-#pragma unroll
-    for (int k = 0; k < 36; ++k) Om[k] = (k % 7 == 0) ? (k < 21 ? 2.0 : 5.0) : 0.0;
-  }
-  const Se3 Z = se3_load(Zp);
-  const Se3 Xj = se3_load(X + pg_pose_at(g, s, vj));
-  Se3 A = Xj;                                    // absolute: the fixed vertex is G itself and Z = I
-  if (!absolute) A = se3_mul(se3_rigid_inv(se3_load(X + pg_pose_at(g, s, vi))), Xj);
-  const Se3 D = se3_mul(se3_rigid_inv(Z), A);
-  const Quat q = se3_quat(D);
-  const double sg = q.w < 0.0 ? -1.0 : 1.0;
-  double e[6] = {D.m[3], D.m[7], D.m[11], sg * q.x, sg * q.y, sg * q.z};
-  double Oe[6];
-#pragma unroll
-  for (int r = 0; r < 6; ++r) {
-    double t = Om[r * 6] * e[0];
-#pragma unroll
-    for (int m = 1; m < 6; ++m) t += Om[r * 6 + m] * e[m];
-    Oe[r] = t;
-  }
-  double chi = e[0] * Oe[0];
-#pragma unroll
-  for (int m = 1; m < 6; ++m) chi += e[m] * Oe[m];
+  PgEdge ed;
+  if (!pg_edge_at(g, s, id, ed)) return;
+  PgError er;
+  pg_edge_error(g, X, s, ed, er);
+  double rho = er.chi, w = 1.0;
+  if (ROBUST) pg_edge_robustify(rb, ed.cls, er.chi, &rho, &w);
   if (!FULL) {
-    chi_out[(size_t)s * E + id] = chi;
+    chi_out[(size_t)s * E + id] = rho;
     return;
   }
   double *slot = slots + ((size_t)s * E + id) * PG_SLOT;
 #pragma unroll
   for (int m = 0; m < 6; ++m) {
-    slot[PG_E + m] = e[m];
-    slot[PG_OE + m] = Oe[m];
+    slot[PG_E + m] = er.e[m];
+    slot[PG_OE + m] = er.Oe[m];
   }
-  slot[PG_CHI] = chi;
+  slot[PG_CHI] = rho;
+  if (ROBUST) {
+    slot[PG_RAW] = er.chi;
+    slot[PG_W] = w;
+  }
+  const Se3 &Z = er.Z, &A = er.A, &D = er.D;
+  const Quat &q = er.q;
+  const double sg = er.sg;
+  const double *Om = er.Om, *Oe = er.Oe;
   // d e_q / d nu_j = sg (w I + [v]x), d e_t / d rho_j = R_Delta
   const double v[3] = {q.x, q.y, q.z};
-  double Jj[36], Ji[36], T[36];
+  double Jj[36], Ji[36], T[36], B[36], gr[6];
 #pragma unroll
   for (int k = 0; k < 36; ++k) Jj[k] = Ji[k] = 0.0;
 #pragma unroll
@@ -209,9 +265,11 @@ __global__ __launch_bounds__(PG_EDGE_THREADS) void pg_linearise_kernel(PgGraph g
   Jj[4 * 6 + 3] = sg * v[2]; Jj[4 * 6 + 4] = sg * q.w; Jj[4 * 6 + 5] = sg * -v[0];
   Jj[5 * 6 + 3] = sg * -v[1]; Jj[5 * 6 + 4] = sg * v[0]; Jj[5 * 6 + 5] = sg * q.w;
   mat6_mul(Om, Jj, T);
-  mat6_tmul(Jj, T, slot + PG_HJJ);
-  mat6_tvec(Jj, Oe, slot + PG_BJ);
-  if (absolute) return;                          // the i side of an absolute edge is the fixed vertex: never read
+  mat6_tmul(Jj, T, B);
+  pg_put<ROBUST, 36>(slot + PG_HJJ, B, w);
+  mat6_tvec(Jj, Oe, gr);
+  pg_put<ROBUST, 6>(slot + PG_BJ, gr, w);
+  if (ed.absolute) return;                       // the i side of an absolute edge is the fixed vertex: never read
   // d e_t / d rho_i = -R_Z^T, d e_t / d nu_i = 2 R_Z^T [t_A]x, d e_q / d nu_i = sg (-w I + [v]x) R_Z^T
   const double ta[3] = {A.m[3], A.m[7], A.m[11]};
   const double tx[9] = {0.0, -ta[2], ta[1], ta[2], 0.0, -ta[0], -ta[1], ta[0], 0.0};
@@ -225,10 +283,35 @@ __global__ __launch_bounds__(PG_EDGE_THREADS) void pg_linearise_kernel(PgGraph g
       Ji[(3 + r) * 6 + 3 + c] = sg * ((qm[r * 3] * Z.m[4 * c] + qm[r * 3 + 1] * Z.m[4 * c + 1]) + qm[r * 3 + 2] * Z.m[4 * c + 2]);
     }
   }
-  mat6_tmul(Ji, T, slot + PG_HIJ);               // Ji^T (Omega Jj)
-  mat6_tvec(Ji, Oe, slot + PG_BI);
+  mat6_tmul(Ji, T, B);                           // Ji^T (Omega Jj)
+  pg_put<ROBUST, 36>(slot + PG_HIJ, B, w);
+  mat6_tvec(Ji, Oe, gr);
+  pg_put<ROBUST, 6>(slot + PG_BI, gr, w);
   mat6_mul(Om, Ji, T);
-  mat6_tmul(Ji, T, slot + PG_HII);
+  mat6_tmul(Ji, T, B);
+  pg_put<ROBUST, 36>(slot + PG_HII, B, w);
+}
+
+// The read-out of the weights: grid (ceil((ML + MA) / 64), S), one thread per loop and absolute edge id.  out (S, ML + MA, 2):
+// the raw term c and the weight w of the edge at the vertices X as they stand, zeros past nloops / nabs.  It runs for idle
+// and frozen streams too; without a kernel (or for a class outside the mask) w = 1.
+__global__ __launch_bounds__(PG_EDGE_THREADS) void pg_edge_weights_kernel(PgGraph g, const double *__restrict__ X,
+                                                                          double *__restrict__ out, PgRobust rb) {
+  const int s = blockIdx.y;
+  const int k = blockIdx.x * PG_EDGE_THREADS + threadIdx.x;
+  if (k >= g.ML + g.MA) return;
+  double c = 0.0, w = 0.0;
+  PgEdge ed;
+  if (pg_edge_at(g, s, g.N + k, ed)) {
+    PgError er;
+    pg_edge_error(g, X, s, ed, er);
+    double rho;
+    pg_edge_robustify(rb, ed.cls, er.chi, &rho, &w);
+    c = er.chi;
+  }
+  double *o = out + ((size_t)s * (g.ML + g.MA) + k) * 2;
+  o[0] = c;
+  o[1] = w;
 }
 
 // ---- per-vertex gathers, in one order everywhere: chain edge v (its j side), chain edge v + 1 (its i side), then the vertex's
@@ -699,11 +782,76 @@ extern "C" void pose_graph_linearise_kernel_wrapper(int S, int N, int ML, int MA
   PWCLO_REQUIRE(X && (slots != nullptr) != (chi_only != nullptr),
                 "pose_graph_linearise: X and exactly one of slots and chi_only are needed");
   const dim3 grid(ceil_div(N + ML + MA, PG_EDGE_THREADS), S);
+  const PgRobust none{PG_ROBUST_NONE, 0, 0.0};
   if (slots != nullptr)
-    hipLaunchKernelGGL(pg_linearise_kernel<true>, grid, dim3(PG_EDGE_THREADS), 0, current_stream(), g, X, slots, chi_only);
+    hipLaunchKernelGGL((pg_linearise_kernel<true, false>), grid, dim3(PG_EDGE_THREADS), 0, current_stream(), g, X, slots,
+                       chi_only, none);
   else
-    hipLaunchKernelGGL(pg_linearise_kernel<false>, grid, dim3(PG_EDGE_THREADS), 0, current_stream(), g, X, slots, chi_only);
+    hipLaunchKernelGGL((pg_linearise_kernel<false, false>), grid, dim3(PG_EDGE_THREADS), 0, current_stream(), g, X, slots,
+                       chi_only, none);
   check_launch("pose_graph_linearise");
+}
+
+// kind 0 (no kernel) is accepted only where `optional`; a kernel needs a finite delta > 0 and a mask of at least one class
+static bool pg_robust(PgRobust &rb, const char *what, bool optional, int kind, int edge_mask, double delta) {
+  if (!(kind >= (optional ? PG_ROBUST_NONE : PG_HUBER) && kind <= PG_DCS)) {
+    set_error(PWCLO_EINVAL, "%s: kernel kind %d outside [%d, %d]", what, kind, optional ? PG_ROBUST_NONE : PG_HUBER, PG_DCS);
+    return false;
+  }
+  const int all = PG_CLASS_CHAIN | PG_CLASS_LOOP | PG_CLASS_ABSOLUTE;
+  if (kind != PG_ROBUST_NONE && !(edge_mask >= 1 && edge_mask <= all)) {
+    set_error(PWCLO_EINVAL, "%s: edge_mask=%d outside [1, %d]", what, edge_mask, all);
+    return false;
+  }
+  if (kind != PG_ROBUST_NONE && !(delta > 0.0 && delta <= 1.79769313486231570815e308)) {
+    set_error(PWCLO_EINVAL, "%s: delta=%g must be finite and > 0", what, delta);
+    return false;
+  }
+  rb = kind == PG_ROBUST_NONE ? PgRobust{PG_ROBUST_NONE, 0, 0.0} : PgRobust{kind, edge_mask, delta};
+  return true;
+}
+
+extern "C" void pose_graph_linearise_robust_kernel_wrapper(int S, int N, int ML, int MA, int kind, int edge_mask, double delta,
+                                                           const int *active, const int *status, const int *count,
+                                                           const int *nloops, const int *nabs, const double *X,
+                                                           const double *Zc, const int *loop_ij, const double *loop_Z,
+                                                           const double *loop_Om, const int *abs_i, const double *abs_G,
+                                                           const double *abs_Om, double *slots, double *chi_only) {
+  PgGraph g;
+  PgRobust rb;
+  if (!pg_graph(g, "pose_graph_linearise_robust", true, S, N, ML, MA, 1, active, status, count, nloops, nabs, Zc, loop_ij,
+                loop_Z, loop_Om, abs_i, abs_G, abs_Om, nullptr, nullptr) ||
+      !pg_robust(rb, "pose_graph_linearise_robust", false, kind, edge_mask, delta))
+    return;
+  PWCLO_REQUIRE(X && (slots != nullptr) != (chi_only != nullptr),
+                "pose_graph_linearise_robust: X and exactly one of slots and chi_only are needed");
+  const dim3 grid(ceil_div(N + ML + MA, PG_EDGE_THREADS), S);
+  if (slots != nullptr)
+    hipLaunchKernelGGL((pg_linearise_kernel<true, true>), grid, dim3(PG_EDGE_THREADS), 0, current_stream(), g, X, slots,
+                       chi_only, rb);
+  else
+    hipLaunchKernelGGL((pg_linearise_kernel<false, true>), grid, dim3(PG_EDGE_THREADS), 0, current_stream(), g, X, slots,
+                       chi_only, rb);
+  check_launch("pose_graph_linearise_robust");
+}
+
+extern "C" void pose_graph_edge_weights_kernel_wrapper(int S, int N, int ML, int MA, int kind, int edge_mask, double delta,
+                                                       const int *nloops, const int *nabs, const double *X,
+                                                       const int *loop_ij, const double *loop_Z, const double *loop_Om,
+                                                       const int *abs_i, const double *abs_G, const double *abs_Om,
+                                                       double *out) {
+  PgGraph g;
+  PgRobust rb;
+  const int *unread = nloops;                    // status and count: a read-out runs whatever they say, and reads no chain edge
+  const double *none = nullptr;
+  if (!pg_graph(g, "pose_graph_edge_weights", false, S, N, ML, MA, 1, nullptr, unread, unread, nloops, nabs, none, loop_ij,
+                loop_Z, loop_Om, abs_i, abs_G, abs_Om, nullptr, nullptr) ||
+      !pg_robust(rb, "pose_graph_edge_weights", true, kind, edge_mask, delta))
+    return;
+  PWCLO_REQUIRE(X && out && loop_Z && loop_Om && abs_G && abs_Om, "pose_graph_edge_weights: a null argument");
+  hipLaunchKernelGGL(pg_edge_weights_kernel, dim3(ceil_div(ML + MA, PG_EDGE_THREADS), S), dim3(PG_EDGE_THREADS), 0,
+                     current_stream(), g, X, out, rb);
+  check_launch("pose_graph_edge_weights");
 }
 
 extern "C" void pose_graph_solve_kernel_wrapper(int S, int N, int ML, int MA, int fix_first, int it, int pcg_iters,

@@ -15,11 +15,44 @@ constexpr int PG_EDGE_THREADS = 64;    // linearise: one thread per edge
 // one edge's slot of doubles: e, Omega e, Ji^T Omega Ji, Ji^T Omega Jj, Jj^T Omega Jj, Ji^T Omega e, Jj^T Omega e, chi2
 constexpr int PG_E = 0, PG_OE = 6, PG_HII = 12, PG_HIJ = 48, PG_HJJ = 84, PG_BI = 120, PG_BJ = 126, PG_CHI = 132;
 constexpr int PG_SLOT = 136;
+// the slot's spare doubles, written by the robust linearise alone: the raw e^T Omega e and the weight rho'(c) (PG_CHI is rho)
+constexpr int PG_RAW = 133, PG_W = 134;
+// robust kernels (section 25.1): one kind and one delta per graph, applied to the edge classes of a mask
+constexpr int PG_ROBUST_NONE = 0, PG_HUBER = 1, PG_GEMAN_MCCLURE = 2, PG_DCS = 3;
+constexpr int PG_CLASS_CHAIN = 1, PG_CLASS_LOOP = 2, PG_CLASS_ABSOLUTE = 4;
 // sections of the solver's workspace, each (S, N, 6) doubles but the last, (S, N, 36)
 constexpr int PG_W_R = 0, PG_W_Z = 1, PG_W_P = 2, PG_W_AP = 3, PG_W_G = 4, PG_W_MINV = 5;
 constexpr int PG_WORK_PER_VERTEX = 5 * 6 + 36;
 // status bits (an active stream with a non-zero word is frozen for the rest of the call)
 constexpr int PG_CONVERGED = 1, PG_TRIVIAL = 2, PG_NONFINITE = 4;   // (an idle stream keeps its word: there is no idle bit)
+
+// rho(c) and w = rho'(c) of a robust kernel at the raw term c = e^T Omega e, each expression in the order of
+// tests/pose_graph_robust_model.py.  A non-finite c gives a non-finite rho with every kind, so the solve still reports it.
+__host__ __device__ __forceinline__ void pg_robustify(int kind, double delta, double c, double *rho, double *w) {
+  if (kind == PG_HUBER) {
+    if (c <= delta * delta) {
+      *rho = c; *w = 1.0;
+    } else {
+      const double s = sqrt(c);
+      *rho = (2.0 * s) * delta - delta * delta;
+      *w = delta / s;
+    }
+  } else if (kind == PG_GEMAN_MCCLURE) {
+    const double a = delta / (delta + c);
+    *rho = c * a;
+    *w = a * a;
+  } else if (kind == PG_DCS) {
+    const double s = (2.0 * delta) / (delta + c);
+    if (s >= 1.0) {
+      *rho = c; *w = 1.0;
+    } else {
+      *w = s * s;
+      *rho = *w * c;
+    }
+  } else {
+    *rho = c; *w = 1.0;
+  }
+}
 
 // The rotation of a unit quaternion into rows 0..2 of a (its translation stays).
 __device__ __forceinline__ void pg_set_rotation(Se3 &a, const Quat &q) {

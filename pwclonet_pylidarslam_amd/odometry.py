@@ -173,6 +173,8 @@ class StreamingOdometry:
                 if key in self._backend_cfg:
                     raise ValueError("StreamingOdometry: backend=dict(%s=...) is the stream's own (streams, max_frames, "
                                      "graph)" % key)
+            from .pose_graph import robust_settings             # backend=dict(robust=dict(...)): refused here, not at the first frame
+            robust_settings(self._backend_cfg.get("robust"), "StreamingOdometry: backend")
         self._loop = None           # loop=: loop_closure.ScanContextLoopDetector over the step's clouds
         self._loop_cfg = None if loop is None else dict(loop)
         self._loop_restart = self._loop_ids = None

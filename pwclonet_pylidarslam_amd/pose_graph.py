@@ -26,6 +26,9 @@ OM_ODOMETRY = (2.0, 2.0, 2.0, 5.0, 5.0, 5.0)     # slam/backend.py:348-358, as d
 OM_LOOP_FAR = (0.1, 0.1, 0.1, 0.5, 0.5, 0.5)
 OM_ABSOLUTE = (1.0, 1.0, 1.0, 0.001, 0.001, 0.001)
 NEAR = 4                                         # loops with |i - j| <= 4 get the odometry information
+SLOT_RAW, SLOT_W = 133, 134                      # the robust linearise's raw e^T Omega e and weight (csrc/pose_graph.hpp)
+ROBUST_KERNELS = {"huber": 1, "geman_mcclure": 2, "dcs": 3}
+EDGE_CLASSES = {"chain": 1, "loop": 2, "absolute": 4}
 
 
 def default_information(kind, i=0, j=0):
@@ -33,6 +36,29 @@ def default_information(kind, i=0, j=0):
     if kind == "absolute":
         return np.diag(OM_ABSOLUTE)
     return np.diag(OM_ODOMETRY if kind == "odometry" or abs(int(i) - int(j)) <= NEAR else OM_LOOP_FAR)
+
+
+def robust_settings(robust, what="PoseGraph"):
+    """``robust=`` checked and as the launches take it: None, or (kind, delta, edge mask) from ``dict(kernel="huber" |
+    "geman_mcclure" | "dcs", delta=1.0, edges=("loop",))``.  Anything else is refused with ValueError."""
+    if robust is None:
+        return None
+    if not isinstance(robust, dict):
+        raise ValueError("%s: robust=%r must be None or a dict(kernel=, delta=, edges=)" % (what, robust))
+    unknown = set(robust) - {"kernel", "delta", "edges"}
+    if unknown or "kernel" not in robust:
+        raise ValueError("%s: robust=dict(...) takes kernel (required), delta and edges, not %s" % (what, sorted(unknown)))
+    name = robust["kernel"]
+    if not isinstance(name, str) or name not in ROBUST_KERNELS:
+        raise ValueError("%s: robust=dict(kernel=%r): one of %s" % (what, name, sorted(ROBUST_KERNELS)))
+    delta = robust.get("delta", 1.0)
+    if isinstance(delta, bool) or not isinstance(delta, (int, float)) or not (0.0 < float(delta) < float("inf")):
+        raise ValueError("%s: robust=dict(delta=%r) must be a finite number > 0" % (what, delta))
+    edges = robust.get("edges", ("loop",))
+    edges = (edges,) if isinstance(edges, str) else tuple(edges)
+    if not edges or any(not isinstance(e, str) or e not in EDGE_CLASSES for e in edges) or len(set(edges)) != len(edges):
+        raise ValueError("%s: robust=dict(edges=%r): a non-empty choice of %s, each once" % (what, edges, sorted(EDGE_CLASSES)))
+    return ROBUST_KERNELS[name], float(delta), sum(EDGE_CLASSES[e] for e in edges)
 
 
 def _information(what, kind, i, j, information):
@@ -72,11 +98,17 @@ class PoseGraph:
     absolute edge: chi2 = 0, nothing moves), NONFINITE (chi2 is not finite).  ``active`` there: (S,) int32 device mask or
     None; idle streams keep vertices, edges, lambda and status.
 
+    ``robust=dict(kernel="huber" | "geman_mcclure" | "dcs", delta=1.0, edges=("loop",))`` (section 25.1; also
+    ``set_robust``): every edge of the classes in ``edges`` ("chain", "loop", "absolute") contributes rho(c) of its raw term
+    ``c = e^T Omega e`` to chi2 and carries the weight ``w = rho'(c)`` on its blocks and gradients; one kind and one delta
+    per object (for "dcs" delta is Phi).  ``None`` (the default): no kernel, the launches and bits of a graph without one.
+    ``edge_weights()`` reads out ``(c, w)`` of every loop and absolute edge at the vertices as they stand.
+
     Views (device tensors): ``poses()`` / ``relative_poses()`` (max count, S, 4, 4), or ``stream=i``: (count_i, 4, 4);
     ``chi2()``, ``status()`` (S,); ``diagnostics()``: dict of lam, nu, count, pcg_used, relres, accepted."""
 
     def __init__(self, streams, max_poses=4096, max_loops=256, max_absolute=256, iters=20, pcg_iters=None, pcg_tol=1e-8,
-                 fix_first=True, graph=True, device="cuda"):
+                 fix_first=True, graph=True, device="cuda", robust=None):
         S, N, ML, MA = int(streams), int(max_poses), int(max_loops), int(max_absolute)
         if not 1 <= S <= MAX_STREAMS:
             raise ValueError("PoseGraph: streams=%d outside [1, %d]" % (S, MAX_STREAMS))
@@ -90,6 +122,7 @@ class PoseGraph:
         self.streams, self.max_poses, self.max_loops, self.max_absolute = S, N, ML, MA
         self.iters, self.pcg_iters, self.pcg_tol = int(iters), pcg_iters, float(pcg_tol)
         self.fix_first, self.graph = bool(fix_first), bool(graph)
+        self._robust = robust_settings(robust)
         self.device = torch.device(device)
         self.captures = 0
         self.calls = 0
@@ -111,7 +144,8 @@ class PoseGraph:
             abs_i=i32(S, MA), abs_G=eye(S, MA), abs_Om=f64(S, MA, 6, 6), inc_ptr=i32(S, N + 1), inc_ent=i32(S, 2 * ML + MA),
             slots=f64(S, E, SLOT), chi_new=f64(S, E), work=f64(S * N * WORK_PER_VERTEX), delta=f64(S, N, 6), lam=f64(S),
             nu=f64(S), chi2=f64(S), status=i32(S), active=torch.ones(S, dtype=torch.int32, device=dev),
-            pcg_used=i32(S, self.iters), relres=f64(S, self.iters), accepted=i32(S, self.iters))
+            pcg_used=i32(S, self.iters), relres=f64(S, self.iters), accepted=i32(S, self.iters),
+            weights=f64(S, ML + MA, 2))
         self._loops = [[] for _ in range(S)]          # host: (i, j) per stream, in edge order
         self._abs = [[] for _ in range(S)]
         self._epoch = [0] * S
@@ -189,6 +223,19 @@ class PoseGraph:
         self._write_incidence(s)
         b["nabs"][s:s + 1].fill_(a + 1)
 
+    def set_robust(self, robust):
+        """Another kernel, delta or choice of classes (or None: none) from the next ``optimize`` on, for every edge of
+        those classes.  A captured ``optimize`` holds the old settings in its launches, so it is dropped and the next
+        call captures again."""
+        new = robust_settings(robust, "set_robust")
+        if new != self._robust:
+            self._robust = new
+            self._graph = None
+
+    def robust(self):
+        """The settings in force: None or (kind, delta, edge mask)."""
+        return self._robust
+
     def reset(self, streams=None):
         """Empties the graphs of ``streams`` (host indices; None: all): vertex 0 alone, no edges, status 0."""
         which = range(self.streams) if streams is None else [self._stream_arg("reset", s) for s in streams]
@@ -233,10 +280,16 @@ class PoseGraph:
     def linearise(self, trial=False):
         """One launch: the slots at the vertices, or (``trial=True``) the chi2 terms at the trial poses."""
         b = self.bufs
-        _lib.call("pose_graph_linearise_kernel_wrapper", self.device, *self._graph_args(), _p(b["active"]), _p(b["status"]),
-                  _p(b["count"]), _p(b["nloops"]), _p(b["nabs"]), _p(b["Xt"] if trial else b["X"]), _p(b["Zc"]),
-                  _p(b["loop_ij"]), _p(b["loop_Z"]), _p(b["loop_Om"]), _p(b["abs_i"]), _p(b["abs_G"]), _p(b["abs_Om"]),
-                  0 if trial else _p(b["slots"]), _p(b["chi_new"]) if trial else 0)
+        graph = (_p(b["active"]), _p(b["status"]), _p(b["count"]), _p(b["nloops"]), _p(b["nabs"]),
+                 _p(b["Xt"] if trial else b["X"]), _p(b["Zc"]), _p(b["loop_ij"]), _p(b["loop_Z"]), _p(b["loop_Om"]),
+                 _p(b["abs_i"]), _p(b["abs_G"]), _p(b["abs_Om"]), 0 if trial else _p(b["slots"]),
+                 _p(b["chi_new"]) if trial else 0)
+        if self._robust is None:
+            _lib.call("pose_graph_linearise_kernel_wrapper", self.device, *self._graph_args(), *graph)
+        else:
+            kind, delta, mask = self._robust
+            _lib.call("pose_graph_linearise_robust_kernel_wrapper", self.device, *self._graph_args(), kind, mask, delta,
+                      *graph)
 
     def solve(self, it=0):
         b = self.bufs
@@ -320,6 +373,27 @@ class PoseGraph:
 
     def status(self):
         return self.bufs["status"]
+
+    def edge_weights(self, stream=None):
+        """One launch at the vertices as they stand, idle and frozen streams included -> (loops (S, max_loops, 2),
+        absolutes (S, max_absolute, 2)) fp64 device views, or with ``stream=i`` that stream's (max_loops, 2) and
+        (max_absolute, 2): per edge the raw ``c = e^T Omega e`` and the weight ``w`` its class's kernel gives it (1 without
+        one); zeros past the edges in use."""
+        b = self.bufs
+        kind, delta, mask = (0, 0.0, 0) if self._robust is None else self._robust
+        _lib.call("pose_graph_edge_weights_kernel_wrapper", self.device, *self._graph_args(), kind, mask, delta,
+                  _p(b["nloops"]), _p(b["nabs"]), _p(b["X"]), _p(b["loop_ij"]), _p(b["loop_Z"]), _p(b["loop_Om"]),
+                  _p(b["abs_i"]), _p(b["abs_G"]), _p(b["abs_Om"]), _p(b["weights"]))
+        loops, absolutes = b["weights"][:, :self.max_loops], b["weights"][:, self.max_loops:]
+        if stream is None:
+            return loops, absolutes
+        s = self._stream_arg("edge_weights", stream)
+        return loops[s], absolutes[s]
+
+    def loop_weights(self, stream):
+        """(nloops, 2): ``(c, w)`` of the stream's loops in use, in the order they were added."""
+        s = self._stream_arg("loop_weights", stream)
+        return self.edge_weights(s)[0][:int(self.bufs["nloops"][s])]
 
     def overflowed(self):
         return bool(self.bufs["overflow"].item())

@@ -2,7 +2,7 @@
 pose_graph_bench.json.  Nothing is asserted.
 
     python tools/pose_graph_bench.py [--poses 4541] [--loops 20] [--streams 1 8] [--repeats 7] [--iters 20]
-                                     [--pcg-iters N] [--skip-host]
+                                     [--pcg-iters N] [--skip-host] [--robust]
 
 The problem: a noisy chain of ``--poses`` vertices per stream with ``--loops`` exact long-range measurements spread over it
 (tests/pose_graph_cases.noisy_chain).  Per stream count, alternated over ``--repeats`` rounds, the graph is put back to its
@@ -10,6 +10,10 @@ odometry and one captured ``optimize`` of ``--iters`` LM iterations is replayed 
 Beside it: CG iterations used and the final relative residual per LM step, whether CG hit ``pcg_iters``, and the same problem
 through the model's ``scipy.sparse.linalg.spsolve`` path on the host (the only baseline there is: g2o is not installed, so no
 time against the reference exists).  ``--pcg-iters`` bounds one solve; the default is the constructor's 12 max_poses.
+
+``--robust`` measures instead what a robust kernel costs: per stream count two graphs of the same
+problem, one without a kernel and one with Geman-McClure, delta = 1, on the loops, replayed in turn in one process; the
+yardstick is the plain replay of the same run.  It writes profiles/pose_graph_robust/ and skips the host baseline.
 """
 import argparse
 import json
@@ -77,12 +81,15 @@ def host_baseline(g, iters):
     return dict(seconds=time.perf_counter() - t0, lm_steps=steps, chi2=float(out["chi"]), threads=os.cpu_count())
 
 
-def device_run(graphs, args):
+ROBUST = dict(kernel="geman_mcclure", delta=1.0, edges=("loop",))
+
+
+def device_run(graphs, args, robust=None):
     from pwclonet_pylidarslam_amd.pose_graph import PoseGraph
     import pose_graph_device as pgd
     g0 = graphs[0]
     pg = PoseGraph(len(graphs), max_poses=g0.N, max_loops=g0.ML, max_absolute=g0.MA, iters=args.iters,
-                   pcg_iters=args.pcg_iters)
+                   pcg_iters=args.pcg_iters, robust=robust)
     pgd.load(pg, graphs)
     start = {k: pg.bufs[k].clone() for k in ("X", "lam", "nu", "chi2", "status")}
 
@@ -97,6 +104,48 @@ def device_run(graphs, args):
     return pg, once
 
 
+def robust_main(args):
+    """Plain and robust replays of the same problems, alternated; the ratio is taken of the medians of one process."""
+    out = args.out or os.path.join(ROOT, "profiles", "pose_graph_robust")
+    runs = {}
+    for S in args.streams:
+        for name, robust in (("plain", None), ("robust", ROBUST)):
+            runs[S, name] = device_run([problem(args.poses, args.loops, 100 + s) for s in range(S)], args, robust)
+    times = {k: [] for k in runs}
+    for _ in range(args.repeats):
+        for k in runs:
+            times[k].append(runs[k][1]())
+    result = dict(poses=args.poses, loops=args.loops, iters=args.iters, repeats=args.repeats, robust=ROBUST, device={})
+    lines = ["# Pose-graph backend: one `optimize` replay with and without a robust kernel", "",
+             "`python tools/pose_graph_bench.py --robust` on one MI355X; the data is `pose_graph_robust_bench.json`.  N = %d poses, "
+             "%d exact loops, %d LM iterations, %d repeats alternated between the two graphs in one process, median (min - "
+             "max).  The kernel: Geman-McClure, delta = 1, on the loops.  The two graphs need not take the same LM path, so the "
+             "CG iterations of each are listed; the kernel itself adds a few flops per edge to two of the four launches of an "
+             "iteration." % (args.poses, args.loops, args.iters, args.repeats), "",
+             "| streams | no kernel | with the kernel | ratio of medians | CG iterations, no kernel / kernel (stream 0, summed) |",
+             "|---|---|---|---|---|"]
+    for S in args.streams:
+        row = {}
+        for name in ("plain", "robust"):
+            pg, t = runs[S, name][0], times[S, name]
+            row[name] = dict(ms_median=float(np.median(t)), ms_min=float(np.min(t)), ms_max=float(np.max(t)), ms_all=t,
+                             pcg_used=pg.bufs["pcg_used"].cpu().numpy().tolist(), status=pg.status().tolist(),
+                             chi2=pg.chi2().tolist())
+        row["min_loop_weight"] = float(torch.stack([runs[S, "robust"][0].loop_weights(s)[:, 1].min() for s in range(S)]).min())
+        result["device"][str(S)] = row
+        a, b = row["plain"], row["robust"]
+        lines.append("| %d | %.1f ms (%.1f - %.1f) | %.1f ms (%.1f - %.1f) | %.3f | %d / %d |" % (
+            S, a["ms_median"], a["ms_min"], a["ms_max"], b["ms_median"], b["ms_min"], b["ms_max"],
+            b["ms_median"] / a["ms_median"], sum(a["pcg_used"][0]), sum(b["pcg_used"][0])))
+    os.makedirs(out, exist_ok=True)
+    with open(os.path.join(out, "pose_graph_robust_bench.json"), "w") as f:
+        json.dump(result, f, indent=1)
+    with open(os.path.join(out, "README.md"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print(json.dumps({"device_ms": {str(S): [result["device"][str(S)][n]["ms_median"] for n in ("plain", "robust")]
+                                    for S in args.streams}}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--poses", type=int, default=4541)
@@ -106,8 +155,12 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--pcg-iters", type=int, default=None)
     ap.add_argument("--skip-host", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pose_graph"))
+    ap.add_argument("--robust", action="store_true")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.robust:
+        return robust_main(args)
+    args.out = args.out or os.path.join(ROOT, "profiles", "pose_graph")
     runs = {}
     for S in args.streams:
         runs[S] = device_run([problem(args.poses, args.loops, 100 + s) for s in range(S)], args)
