@@ -1367,6 +1367,50 @@ void elevation_choose_kernel_wrapper(int S, int NS, int Y, int W, int L, int up_
                                      const int *found, const int *match, const int *A, const int *occ, const double *pose,
                                      const double *T0, int *record, double *T1);
 
+/* ---- 12. global map: keyframe bank and voxel-hashed world map per stream ---------------------------
+ * Per stream a bank of at most MK = max_keyframes clouds of n rows: bank_cloud (S,MK,n,3) floats, bank_frame (S,MK) ints,
+ * bank_len (S,MK) ints.  Row i < bank_len[k] of keyframe k has the global row id g = k n + i, the world point w =
+ * float32(X[bank_frame[k]] p) (X (frames,S,4,4) doubles; fp64, ((m0 x + m1 y) + m2 z) + m3, one rounding) and the key of
+ * grid_sample_keep's rule applied to w; it is no candidate where that rule says so or where bank_frame[k] lies outside
+ * [0, frames).  The map is the w of the rows with the lowest g of their key, in ascending g.  The table of a stream has T =
+ * 2^ceil(log2(2 MK n)) slots, at least 64: keys (S,T) 64-bit words, rows (S,T+2) 32-bit words, slots (S,MK,n) ints, blocks
+ * (S,MK,ceil(n/256)) ints.  state (S,8) ints: count, built, total, dirty, todo, slot, run, 0.  One call is begin, push, clear,
+ * insert, count, scan, write, end, each a launch of its own; E = max_new bounds the keyframes a call enters.  S <= 1024,
+ * MK <= 65535, MK n <= 2^29.  All pointers DEVICE memory; every launcher refuses a bad argument before it launches. */
+
+/* Bytes of all device buffers of S streams (table, bank, block counts, state, outputs of `capacity` rows); 0: out of range. */
+long long global_map_bytes(int S, int MK, int n, int capacity);
+/* One thread per stream.  mode 0, a streaming call: a stream with active[s] == 0 (active NULL: none) keeps every word; one
+ * with restart[s] != 0 (NULL: none) gets count = built = total = 0 and dirty = 1 first; then frame_id[s] >= 0 with frame_id[s]
+ * % stride == 0 is banked at slot = count (bank_frame = frame_id[s], bank_len = lengths[s] clamped to [0, n], NULL: n; count +
+ * 1), or sets *overflow where count == MK.  mode 1, a rebuild: every stream gets built = total = 0 and dirty = 1.  todo =
+ * min(count - built, E). */
+void global_map_begin_kernel_wrapper(int S, int MK, int n, int stride, int E, int mode, const int *active,
+                                     const int *restart, const int *frame_id, const int *lengths, int *state,
+                                     int *bank_frame, int *bank_len, int *overflow);
+/* bank_cloud[s][slot] = cloud[s] (S,n,3), all n rows, for the streams with slot >= 0. */
+void global_map_push_kernel_wrapper(int S, int MK, int n, const float *cloud, const int *state, float *bank_cloud);
+/* keys and rows all ones for the streams with run and dirty. */
+void global_map_clear_kernel_wrapper(int S, int MK, int n, const int *state, void *keys, void *rows);
+/* Grid (ceil(n/256), E, S): rows of keyframe built + blockIdx.y < built + todo enter the table; slots = the slot, -1 for a
+ * row that is no candidate. */
+void global_map_insert_kernel_wrapper(int S, int MK, int n, int E, double voxel, const double *X, int frames,
+                                      const float *bank_cloud, const int *bank_frame, const int *bank_len,
+                                      const int *state, void *keys, void *rows, int *slots);
+/* blocks[s][blockIdx.y][blockIdx.x] = the winners among the workgroup's rows. */
+void global_map_count_kernel_wrapper(int S, int MK, int n, int E, const int *bank_len, const int *state, void *keys,
+                                     void *rows, const int *slots, int *blocks);
+/* One workgroup per stream: blocks = total + the exclusive scan of the first ceil(n/256) todo counts; total += their sum. */
+void global_map_scan_kernel_wrapper(int S, int MK, int n, int *state, int *blocks);
+/* Winner number r of the stream (in ascending g) goes to points[s][r] (S,capacity,3) floats and source[s][r] (S,capacity,2)
+ * ints (frame id, row) where r < capacity. */
+void global_map_write_kernel_wrapper(int S, int MK, int n, int E, int capacity, const double *X, int frames,
+                                     const float *bank_cloud, const int *bank_frame, const int *bank_len,
+                                     const int *state, void *keys, void *rows, const int *slots, const int *blocks,
+                                     float *points, int *source);
+/* built += todo and dirty = 0 for the streams with run. */
+void global_map_end_kernel_wrapper(int S, int *state);
+
 #ifdef __cplusplus
 }
 #endif

@@ -222,6 +222,15 @@ SIGNATURES = {
     "elevation_image_kernel_wrapper": ([_i] * 6 + [ctypes.c_float] * 3 + [_F] * 9, None),
     "elevation_score_kernel_wrapper": ([_i] * 5 + [_F] * 5, None),
     "elevation_choose_kernel_wrapper": ([_i] * 6 + [ctypes.c_float] * 2 + [_F] * 8, None),
+    "global_map_bytes": ([_i] * 4, ctypes.c_longlong),
+    "global_map_begin_kernel_wrapper": ([_i] * 6 + [_F] * 8, None),
+    "global_map_push_kernel_wrapper": ([_i] * 3 + [_F] * 3, None),
+    "global_map_clear_kernel_wrapper": ([_i] * 3 + [_F] * 3, None),
+    "global_map_insert_kernel_wrapper": ([_i] * 4 + [ctypes.c_double, _F, _i] + [_F] * 7, None),
+    "global_map_count_kernel_wrapper": ([_i] * 4 + [_F] * 6, None),
+    "global_map_scan_kernel_wrapper": ([_i] * 3 + [_F] * 2, None),
+    "global_map_write_kernel_wrapper": ([_i] * 5 + [_F, _i] + [_F] * 10, None),
+    "global_map_end_kernel_wrapper": ([_i, _F], None),
 }
 
 _lib = None

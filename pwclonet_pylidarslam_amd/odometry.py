@@ -91,6 +91,16 @@ class StreamingOdometry:
     their rows.  Pose rows, ``relative_poses()`` and ``trajectory()`` stay the network's in both settings, and without the
     key ``motion()`` holds the bits it always held.
 
+    Global map (``map=dict(voxel_size=0.3, max_keyframes=1024, capacity=None, stride=1, max_new=1, source=...,
+    rebuild_on_optimize=True)``, ``global_map.GlobalMap``'s keywords): after the step, the refinement,
+    the backend's append and the detector, one more captured graph banks the cloud the step sampled from (every
+    ``stride``-th frame of a stream) and extends the stream's map, one point per occupied voxel, at the poses of ``source``:
+    ``"optimized"`` (the pose graph's vertices; needs ``backend=``; the default with it), ``"refined"`` (needs ``refine=``)
+    or ``"network"``.  It reads the step's words (``active``, ``restart = active * (1 - valid)``, frame ids
+    ``frame_counts() - 1``), so dropouts and restarts need no new capture.  ``poll_loops`` rebuilds the map at the corrected
+    vertices where the graph was optimised since the map last saw it.  ``global_map()``, ``map_points(stream)``; without
+    ``map=`` every path launches what it launched before.
+
     Per-stream mode (``per_stream=True``): ``step(frames, active=None, restart=None)`` and ``step_sweeps(sweeps, lengths,
     active=None, restart=None)`` take two (S,) masks, bool or integer, host sequences or device tensors (device tensors
     are read on the device, without a sync); ``None`` = all active, none restarting.  ``active[s]``: stream s delivered a
@@ -110,7 +120,7 @@ class StreamingOdometry:
     start as copies of the first active stream's, so that no step ever reads an uninitialised buffer."""
 
     def __init__(self, net, streams=1, num_points=None, max_frames=4096, graph=True, warmup=1, sweeps=None,
-                 per_stream=False, refine=None, backend=None, loop=None):
+                 per_stream=False, refine=None, backend=None, loop=None, map=None):
         if not 1 <= int(streams) <= MAX_STREAMS:
             raise ValueError("StreamingOdometry: streams=%d outside [1, %d]" % (int(streams), MAX_STREAMS))
         if int(max_frames) < 1:
@@ -186,7 +196,35 @@ class StreamingOdometry:
                 if key in self._loop_cfg:
                     raise ValueError("StreamingOdometry: loop=dict(%s=...) is the stream's own (streams, num_points, graph)"
                                      % key)
-        self._tapped = None         # refine / loop: the frame batch the last step's graph (or eager step) sampled from
+        self._map = None            # map=: global_map.GlobalMap over the step's clouds
+        self._map_cfg = None if map is None else dict(map)
+        self._map_source, self._map_rebuild = None, True
+        self._map_restart = self._map_ids = None
+        self._map_optimized = 0     # backend().calls when the map was last rebuilt: the optimisations it has seen
+        if map is not None:
+            default = "optimized" if backend is not None else "refined" if refine is not None else "network"
+            self._map_source = self._map_cfg.pop("source", default)
+            self._map_rebuild = self._map_cfg.pop("rebuild_on_optimize", True)
+            if self._map_source not in ("optimized", "refined", "network"):
+                raise ValueError("StreamingOdometry: map=dict(source=%r): \"optimized\", \"refined\" or \"network\""
+                                 % (self._map_source,))
+            if self._map_source == "optimized" and backend is None:
+                raise ValueError("StreamingOdometry: map=dict(source=\"optimized\") places the keyframes at the pose graph's "
+                                 "vertices and needs backend=dict(...)")
+            if self._map_source == "refined" and refine is None:
+                raise ValueError("StreamingOdometry: map=dict(source=\"refined\") places the keyframes at the refiner's "
+                                 "poses and needs refine=dict(...)")
+            if not isinstance(self._map_rebuild, (bool, np.bool_)):
+                raise ValueError("StreamingOdometry: map=dict(rebuild_on_optimize=%r) must be a bool" % (self._map_rebuild,))
+            for key in ("streams", "num_points", "graph", "device"):
+                if key in self._map_cfg:
+                    raise ValueError("StreamingOdometry: map=dict(%s=...) is the stream's own (streams, num_points, graph)"
+                                     % key)
+            unknown = set(self._map_cfg) - {"voxel_size", "max_keyframes", "capacity", "stride", "max_new"}
+            if unknown:
+                raise ValueError("StreamingOdometry: map=dict(%s=...): the keys are voxel_size, max_keyframes, capacity, "
+                                 "stride, max_new, source, rebuild_on_optimize" % sorted(unknown)[0])
+        self._tapped = None         # refine / loop / map: the frame batch the last step's graph (or eager step) sampled from
         if refine is not None and self.per_stream != bool(self._refine_cfg.get("per_stream", False)):
             if self.per_stream:
                 raise ValueError("StreamingOdometry: per_stream=True registers with the masked refiner, which the refine "
@@ -272,6 +310,8 @@ class StreamingOdometry:
             self._backend.reset()                           # the graphs too
         if self._loop is not None:
             self._loop.reset()                              # the places and the closure logs too
+        if self._map is not None:
+            self._map.reset()                               # the banks and the maps too
         self._reset_motion(None)
 
     def _reset_motion(self, mask):
@@ -476,7 +516,46 @@ class StreamingOdometry:
             raise RuntimeError("StreamingOdometry: poll_loops needs loop=dict(...)")
         if self._loop is None:
             return []
-        return self._loop.hand_over(self._backend, optimize)
+        added = self._loop.hand_over(self._backend, optimize)
+        if self._map is not None and self._map_rebuild and self._map_source == "optimized" \
+                and self._backend.calls != self._map_optimized:     # by this poll or by backend().optimize() before it
+            self._map.rebuild(self._backend.bufs["X"])      # the keyframes at the corrected vertices
+            self._map_optimized = self._backend.calls
+        return added
+
+    def global_map(self):
+        """With ``map=``: the ``global_map.GlobalMap`` over the step's clouds (``points``, ``sources``, ``totals``,
+        ``rebuild``); None before the first frame or without ``map``."""
+        return self._map
+
+    def map_points(self, stream):
+        """With ``map=``: (m, 3) fp32 device view of one stream's global map (reads its size: a sync); None before the
+        first frame."""
+        if self._map_cfg is None:
+            raise RuntimeError("StreamingOdometry: map_points needs map=dict(...)")
+        return None if self._map is None else self._map.points(stream)
+
+    def _map_poses(self):
+        return {"optimized": lambda: self._backend.bufs["X"], "refined": lambda: self._ref_abs,
+                "network": lambda: self._abs}[self._map_source]()
+
+    def _extend_map(self, pose):
+        """After the step, the refinement, the backend's append and the detector (outside the step's graph): the global map
+        banks the cloud the step sampled from and extends itself at the poses of ``map=dict(source=...)``, with the words
+        the detector gets: ``active``, ``restart = active - valid``, frame ids ``frame_counts() - 1``, the front end's
+        lengths.  No sync."""
+        if self._map_cfg is None:
+            return
+        if self._map is None:
+            from . import global_map
+            self._map = global_map.GlobalMap(self.streams, self.num_points, graph=self.graph, device=pose.device,
+                                             **self._map_cfg)
+            self._map_restart, self._map_ids = torch.zeros_like(self._active), torch.zeros_like(self._active)
+        cloud = self._tapped[:, :self.num_points, :3].contiguous()
+        torch.sub(self._active, self._valid, out=self._map_restart)
+        torch.sub(self._counts, 1, out=self._map_ids)
+        self._map.advance(cloud, self._map_ids, self._map_poses(), active=self._active, restart=self._map_restart,
+                          lengths=self.survivor_counts())
 
     def refiner(self):
         """The refiner behind ``refine=``, of the class its ``kind`` names (``status()``, ``diagnostics()``); None before the
@@ -517,7 +596,7 @@ class StreamingOdometry:
     def _tap(self, source):
         """``source`` itself, or with ``refine=`` a wrapper that remembers the frame batch it returned: the refiner
         registers the cloud the step sampled from.  The step's launches are the same either way."""
-        if self._refine_cfg is None and self._loop_cfg is None:
+        if self._refine_cfg is None and self._loop_cfg is None and self._map_cfg is None:
             return source
 
         def tapped():
@@ -692,6 +771,7 @@ class StreamingOdometry:
         returns None for it."""
         self._refine(pose)
         self._detect(pose)
+        self._extend_map(pose)
         self.frames_seen += 1
         return None if not self.per_stream and self.frames_seen == 1 else pose
 
