@@ -18,6 +18,9 @@ import numpy as np
 import torch
 
 from . import _lib, stream_masks
+from .stream_engine import need as _need, ptr as _p
+from .stream_engine import (Replay, Replayed, frame_ids as _frame_ids, need_cuda, pose_stack, stream_count, stream_index,
+                            stream_indices)
 
 MAX_STREAMS = 1024                               # csrc/global_map.hpp: GM_MAX_STREAMS, GM_MAX_KEYFRAMES, GM_MAX_ROWS
 MAX_KEYFRAMES = 65535
@@ -25,10 +28,6 @@ MAX_ROWS = 1 << 29
 BLOCK = 256
 WORDS = 8
 DEFAULT_CAPACITY = 1 << 22                       # capacity=None of the class: min(MK n, 2^22) rows per stream
-
-
-def _p(t):
-    return t.data_ptr() if t is not None else 0
 
 
 def table_slots(max_keyframes, num_points):
@@ -50,9 +49,7 @@ def map_bytes(S, max_keyframes, num_points, capacity):
 
 def _sizes(what, S, MK, n, voxel_size, capacity, stride=1, max_new=1):
     """-> (S, MK, n, voxel_size, capacity); ValueError naming the argument otherwise."""
-    S, MK, n = int(S), int(MK), int(n)
-    if not 1 <= S <= MAX_STREAMS:
-        raise ValueError("%s: streams=%d outside [1, %d]" % (what, S, MAX_STREAMS))
+    S, MK, n = stream_count(what, S, MAX_STREAMS), int(MK), int(n)
     if n < 1:
         raise ValueError("%s: num_points=%d must be >= 1" % (what, n))
     if not 1 <= MK <= MAX_KEYFRAMES:
@@ -71,20 +68,6 @@ def _sizes(what, S, MK, n, voxel_size, capacity, stride=1, max_new=1):
     if not 1 <= int(max_new) <= MK:
         raise ValueError("%s: max_new=%d outside [1, max_keyframes = %d]" % (what, int(max_new), MK))
     return S, MK, n, float(voxel_size), int(capacity)
-
-
-def _kind(t, name, dtype, shape):
-    if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape):
-        raise ValueError("%s must be a %s tensor of shape %s, got %s %s" % (
-            name, str(dtype).replace("torch.", ""), tuple(shape), getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ()))))
-    if not t.is_contiguous():
-        raise ValueError("%s must be contiguous" % name)
-
-
-def _poses(what, poses, S):
-    if not isinstance(poses, torch.Tensor) or poses.dim() != 4 or poses.shape[0] < 1:
-        raise ValueError("%s: poses must be float64 (frames >= 1, %d, 4, 4)" % (what, S))
-    _kind(poses, "%s: poses" % what, torch.float64, (poses.shape[0], S, 4, 4))
 
 
 def _buffers(S, MK, n, capacity, device, bank_cloud=None):
@@ -132,14 +115,12 @@ def build(clouds, poses, voxel_size, lengths=None, capacity=None):
     if not isinstance(clouds, torch.Tensor) or clouds.dim() != 3 or clouds.shape[2] != 3 or clouds.shape[0] < 1:
         raise ValueError("%s: clouds must be float32 (K >= 1, n, 3), got %s" % (what, tuple(getattr(clouds, "shape", ()))))
     K, n = int(clouds.shape[0]), int(clouds.shape[1])
-    _kind(clouds, "%s: clouds" % what, torch.float32, (K, n, 3))
-    _kind(poses, "%s: poses" % what, torch.float64, (K, 4, 4))
+    _need(clouds, "%s: clouds" % what, torch.float32, (K, n, 3), cuda=False)
+    _need(poses, "%s: poses" % what, torch.float64, (K, 4, 4), cuda=False)
     if lengths is not None:
-        _kind(lengths, "%s: lengths" % what, torch.int32, (K,))
+        _need(lengths, "%s: lengths" % what, torch.int32, (K,), cuda=False)
     _, K, n, voxel_size, capacity = _sizes(what, 1, K, n, voxel_size, K * n if capacity is None else capacity)
-    for t in (clouds, poses, lengths):
-        if t is not None and not t.is_cuda:
-            raise RuntimeError("CPU not supported")
+    need_cuda(clouds, poses, lengths)
     dev = clouds.device
     b = _buffers(1, K, n, capacity, dev, bank_cloud=clouds.view(1, K, n, 3))
     b["bank_frame"].copy_(torch.arange(K, dtype=torch.int32, device=dev).view(1, K))
@@ -158,7 +139,7 @@ def build(clouds, poses, voxel_size, lengths=None, capacity=None):
 
 # ---- the map of S streams ----------------------------------------------------------------------------------------------
 
-class GlobalMap:
+class GlobalMap(Replayed):
     """S global maps on the device, one per stream, each over a bank of at most ``max_keyframes`` clouds of ``num_points``
     rows.
 
@@ -168,8 +149,8 @@ class GlobalMap:
     ``restart`` empties bank and map first; the frame is banked where ``frame_id % stride == 0`` (a full bank sets the
     overflow word and stores nothing); then at most ``max_new`` of the banked keyframes that are not yet in the map enter
     it, the others wait for the next call.  ``active`` / ``restart``: masks as ``registration.IcpRefiner`` takes them; an
-    idle stream keeps every word.  ``lengths`` (S,) int32: only rows [0, lengths[s]) are candidates.  No sync: the first
-    call runs eagerly, later calls replay one graph per poses buffer.
+    idle stream keeps every word.  ``lengths`` (S,) int32: only rows [0, lengths[s]) are candidates.  No sync;
+    replayed as one graph per poses buffer.
 
     ``rebuild(poses)``: the map of every banked keyframe at these poses (same launches with ``max_new = max_keyframes``, a
     graph of its own).  ``points(stream)`` / ``sources(stream)``: the first ``min(total, capacity)`` rows, (m, 3) fp32 and
@@ -184,10 +165,8 @@ class GlobalMap:
             what, streams, max_keyframes, num_points, voxel_size, capacity, stride, max_new)
         self.stride, self.max_new, self.graph = int(stride), int(max_new), bool(graph)
         self.device = torch.device(device)
-        self.calls = 0
-        self.captures = 0
+        self.replay = Replay(graph)
         self.bufs = None
-        self._graphs = {}
 
     # ---- state -------------------------------------------------------------------------------------------------------
 
@@ -221,16 +200,10 @@ class GlobalMap:
         """Whether a full bank ever refused a keyframe (a host read)."""
         return self.bufs is not None and bool(self.bufs["overflow"].item())
 
-    def _stream_arg(self, what, stream):
-        s = int(stream)
-        if not 0 <= s < self.streams:
-            raise ValueError("GlobalMap: %s: stream=%d outside [0, %d)" % (what, s, self.streams))
-        return s
-
     def reset(self, streams=None):
         """Empties the banks and maps of ``streams`` (host indices; None: all, and the overflow word) on the device,
         without a sync."""
-        which = range(self.streams) if streams is None else [self._stream_arg("reset", s) for s in streams]
+        which = stream_indices("GlobalMap", "reset", streams, self.streams)
         if self.bufs is None:
             return
         st = self.bufs["state"]
@@ -244,7 +217,7 @@ class GlobalMap:
         """Marks the maps of ``streams`` (host indices; None: all) for re-entry and keeps their banks: the table is cleared
         in the next call, and the banked keyframes enter the map again, ``max_new`` per ``advance``, at the poses those
         calls are given: a rebuild spread over the calls that follow.  On the device, without a sync."""
-        which = range(self.streams) if streams is None else [self._stream_arg("invalidate", s) for s in streams]
+        which = stream_indices("GlobalMap", "invalidate", streams, self.streams)
         if self.bufs is None:
             return
         st = self.bufs["state"]
@@ -253,7 +226,7 @@ class GlobalMap:
             st[s, 3:4].fill_(1)
 
     def _rows(self, what, stream, name):
-        s = self._stream_arg(what, stream)
+        s = stream_index("GlobalMap", what, stream, self.streams)
         if self.bufs is None:
             return None
         m = min(int(self.bufs["state"][s, 2].item()), self.capacity)
@@ -269,7 +242,7 @@ class GlobalMap:
 
     def bank(self, stream):
         """Device views of one stream's bank: cloud (count, n, 3), frame_id (count,), length (count,) (reads the count)."""
-        s = self._stream_arg("bank", stream)
+        s = stream_index("GlobalMap", "bank", stream, self.streams)
         b = self.bufs
         c = int(b["state"][s, 0].item())
         return dict(cloud=b["bank_cloud"][s, :c], frame_id=b["bank_frame"][s, :c], length=b["bank_len"][s, :c])
@@ -288,41 +261,19 @@ class GlobalMap:
         _map_launches(b, S, MK, n, E, self.capacity, self.voxel_size, poses)
 
     def _run(self, mode, poses):
-        if not self.graph or self.calls == 0:
-            self._body(mode, poses)
-        else:
-            key = (mode, poses.data_ptr(), int(poses.shape[0]))
-            g = self._graphs.get(key)
-            if g is None:
-                torch.cuda.synchronize(self.device)
-                g = torch.cuda.CUDAGraph()
-                with _lib.capture(g):
-                    self._body(mode, poses)
-                self._graphs[key] = g
-                self.captures += 1
-            g.replay()
-        self.calls += 1
+        self.replay.run(lambda: self._body(mode, poses), self.device, (mode, poses.data_ptr(), int(poses.shape[0])))
 
     def advance(self, cloud, frame_ids, poses, active=None, restart=None, lengths=None):
         what = "GlobalMap"
         S, n = self.streams, self.num_points
-        _kind(cloud, "%s: cloud" % what, torch.float32, (S, n, 3))          # every argument's kind and shape first
-        given = frame_ids if isinstance(frame_ids, torch.Tensor) else None
-        if given is not None:
-            _kind(frame_ids, "%s: frame_ids" % what, torch.int32, (S,))
-        else:
-            ids = np.asarray(frame_ids)
-            if ids.shape != (S,) or ids.dtype.kind not in "iu" or ids.min() < 0:
-                raise ValueError("%s: frame_ids must be (%d,) non-negative integers" % (what, S))
-            frame_ids = torch.from_numpy(ids.astype(np.int32))
-        _poses(what, poses, S)
+        _need(cloud, "%s: cloud" % what, torch.float32, (S, n, 3), cuda=False)      # every argument's kind and shape first
+        given, frame_ids = _frame_ids(what, frame_ids, S)
+        pose_stack(what, "poses", poses, S)
         if lengths is not None:
-            _kind(lengths, "%s: lengths" % what, torch.int32, (S,))
+            _need(lengths, "%s: lengths" % what, torch.int32, (S,), cuda=False)
         act = None if active is None else stream_masks.stream_mask(active, S, "active", what)
         rst = None if restart is None else stream_masks.stream_mask(restart, S, "restart", what)
-        for t in (cloud, given, poses, lengths):
-            if t is not None and not t.is_cuda:
-                raise RuntimeError("CPU not supported")
+        need_cuda(cloud, given, poses, lengths)
         if self.bufs is None:
             self.device = cloud.device
             self._alloc()
@@ -330,17 +281,13 @@ class GlobalMap:
         stream_masks.load_words(b["active"], b["restart"], act, rst)
         b["cloud"].copy_(cloud)
         b["frame_id"].copy_(frame_ids)
-        if lengths is None:
-            b["lengths"].fill_(n)
-        else:
-            b["lengths"].copy_(lengths)
+        stream_masks.load_lengths(b["lengths"], lengths, n)
         self._run(0, poses)
 
     def rebuild(self, poses):
         what = "GlobalMap: rebuild"
-        _poses(what, poses, self.streams)
-        if not poses.is_cuda:
-            raise RuntimeError("CPU not supported")
+        pose_stack(what, "poses", poses, self.streams)
+        need_cuda(poses)
         if self.bufs is None:
             self.device = poses.device
             self._alloc()

@@ -20,7 +20,9 @@ import numpy as np
 import torch
 
 from . import _lib, stream_masks
-from .registration import _need, _p
+from .stream_engine import need as _need, ptr as _p
+from .stream_engine import (Replay, Replayed, frame_ids as _frame_ids, need_cuda, pose_stack, stream_count, stream_index,
+                            stream_indices)
 
 MAX_STREAMS = 1024                                   # csrc/loop_closure.hpp
 MAX_RINGS, MIN_SECTORS, MAX_SECTORS = 64, 8, 64
@@ -109,23 +111,14 @@ def elevation_tables(sectors, yaw_div, yaw_half, up="z"):
     return rot, pose
 
 
-def _kind(t, name, dtype, shape):
-    """``registration._need`` without the question where the tensor lives: ValueError for the wrong kind, shape or layout."""
-    if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape):
-        raise ValueError("%s must be a %s tensor of shape %s, got %s %s" % (
-            name, str(dtype).replace("torch.", ""), tuple(shape), getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ()))))
-    if not t.is_contiguous():
-        raise ValueError("%s must be contiguous" % name)
-
-
 def _check_cloud(what, cloud, S=None, n=None, cuda=True):
     if not isinstance(cloud, torch.Tensor) or cloud.dim() != 3 or cloud.shape[2] != 3 or cloud.dtype != torch.float32 \
             or (S is not None and tuple(cloud.shape) != (S, n, 3)):
         raise ValueError("%s: cloud must be float32 (%s, %s, 3), got %s %s"
                          % (what, "S" if S is None else S, "n" if n is None else n, getattr(cloud, "dtype", type(cloud)),
                             tuple(getattr(cloud, "shape", ()))))
-    if cuda and not cloud.is_cuda:
-        raise RuntimeError("CPU not supported")
+    if cuda:
+        need_cuda(cloud)
     if not cloud.is_contiguous():
         raise ValueError("%s: cloud must be contiguous" % what)
     if cloud.shape[0] < 1 or cloud.shape[0] > MAX_STREAMS or cloud.shape[1] < 1:
@@ -153,7 +146,7 @@ def scan_context(cloud, rings=20, sectors=60, max_range=80.0, z_offset=2.0, up="
     return D, Dn, mask
 
 
-class ScanContextLoopDetector:
+class ScanContextLoopDetector(Replayed):
     """S loop detectors on the device, one per stream, each with a database of at most ``max_keyframes`` places.
 
     ``process(cloud, frame_ids, active=None, restart=None, trajectory=None, lengths=None)``: cloud (S, n, 3) fp32, frame_ids
@@ -163,7 +156,8 @@ class ScanContextLoopDetector:
     where its distance is below ``threshold``; the match is verified (below) and an accepted closure appended to the
     stream's log; then the frame is stored where ``f % stride == 0``.  ``active`` / ``restart``: masks as
     ``registration.IcpRefiner`` takes them; a stream with ``restart`` loses its places and its log before the search, an
-    idle one keeps every word of its database and log.  No sync: the first call runs eagerly, later calls replay one graph.
+    idle one keeps every word of its database and log.  No sync; replayed as one graph per trajectory buffer (DESIGN.md
+    section 21.2).
 
     ``verify=dict(iters=20, sigma=0.5, max_dist=2.0, min_fitness=0.3, max_mean_cost=None)`` (None: ``sigma ** 2``): a private
     ``IcpRefiner(map_size=1, per_stream=True)`` registers the matched place's stored cloud (fetched by the device-side
@@ -179,9 +173,7 @@ class ScanContextLoopDetector:
                  max_loops=256, stride=1, min_id_distance=200, max_distance=None, threshold=0.2, verify=VERIFY_DEFAULTS,
                  graph=True, device="cuda", translation=None):
         what = "ScanContextLoopDetector"
-        S, n, MK, ML = int(streams), int(num_points), int(max_keyframes), int(max_loops)
-        if not 1 <= S <= MAX_STREAMS:
-            raise ValueError("%s: streams=%d outside [1, %d]" % (what, S, MAX_STREAMS))
+        S, n, MK, ML = stream_count(what, streams, MAX_STREAMS), int(num_points), int(max_keyframes), int(max_loops)
         if n < 1:
             raise ValueError("%s: num_points=%d must be >= 1" % (what, n))
         NR, NS = _params(what, rings, sectors, max_range, z_offset, up)
@@ -218,10 +210,8 @@ class ScanContextLoopDetector:
         self.max_distance = None if max_distance is None else float(max_distance)
         self.threshold, self.verify, self.graph = float(threshold), verify, bool(graph)
         self.device = torch.device(device)
-        self.calls = 0
-        self.captures = 0
+        self.replay = Replay(graph)
         self.bufs = None
-        self._graphs = {}
         self._refiner = None
         self._cursor = [0] * S                      # loops(): nothing; poll(): the records already handed out
         self._epoch = [0] * S
@@ -280,15 +270,9 @@ class ScanContextLoopDetector:
             return False
         return bool(self.bufs["overflow"].item()) or bool(self.bufs["log_overflow"].item())
 
-    def _stream_arg(self, what, stream):
-        s = int(stream)
-        if not 0 <= s < self.streams:
-            raise ValueError("ScanContextLoopDetector: %s: stream=%d outside [0, %d)" % (what, s, self.streams))
-        return s
-
     def reset(self, streams=None):
         """Empties the databases and logs of ``streams`` (host indices; None: all) on the device, without a sync."""
-        which = range(self.streams) if streams is None else [self._stream_arg("reset", s) for s in streams]
+        which = stream_indices("ScanContextLoopDetector", "reset", streams, self.streams)
         if self.bufs is None:
             return
         b = self.bufs
@@ -323,7 +307,7 @@ class ScanContextLoopDetector:
     def database(self, stream):
         """Device tensors of one stream's places: Dn (count, NR, NS), mask (count,), frame_id (count,) and, with
         verification, cloud (count, n, 3) (reads the count: a sync)."""
-        s = self._stream_arg("database", stream)
+        s = stream_index("ScanContextLoopDetector", "database", stream, self.streams)
         b = self.bufs
         c = int(b["count"][s])
         out = dict(Dn=b["db_desc"][s, :c].transpose(1, 2), mask=b["db_mask"][s, :c], frame_id=b["db_frame"][s, :c])
@@ -344,7 +328,7 @@ class ScanContextLoopDetector:
     def loops(self, stream=None):
         """The accepted closures of one stream or of all, as a list of ``LoopRecord(stream, i, j, T, score, shift, pairs,
         cost)``: frame j is frame i again and ``T`` (4, 4) fp64 is the pose of j in i.  The one host read."""
-        which = range(self.streams) if stream is None else [self._stream_arg("loops", stream)]
+        which = stream_indices("ScanContextLoopDetector", "loops", None if stream is None else [stream], self.streams)
         if self.bufs is None:
             return []
         return [r for s in which for r in self._records(s, 0)]
@@ -491,25 +475,14 @@ class ScanContextLoopDetector:
         what = "ScanContextLoopDetector"
         S, n = self.streams, self.num_points
         _check_cloud(what, cloud, S, n, cuda=False)         # every argument's kind and shape first, then where it lives
-        given = frame_ids if isinstance(frame_ids, torch.Tensor) else None      # a host sequence may stay on the host
-        if given is not None:
-            _kind(frame_ids, "%s: frame_ids" % what, torch.int32, (S,))
-        else:
-            ids = np.asarray(frame_ids)
-            if ids.shape != (S,) or ids.dtype.kind not in "iu" or ids.min() < 0:
-                raise ValueError("%s: frame_ids must be (%d,) non-negative integers" % (what, S))
-            frame_ids = torch.from_numpy(ids.astype(np.int32))
+        given, frame_ids = _frame_ids(what, frame_ids, S)
         if lengths is not None:
-            _kind(lengths, "%s: lengths" % what, torch.int32, (S,))
+            _need(lengths, "%s: lengths" % what, torch.int32, (S,), cuda=False)
         if trajectory is not None:
-            if not isinstance(trajectory, torch.Tensor) or trajectory.dim() != 4 or trajectory.shape[0] < 1:
-                raise ValueError("%s: trajectory must be float64 (frames >= 1, %d, 4, 4)" % (what, S))
-            _kind(trajectory, "%s: trajectory" % what, torch.float64, (trajectory.shape[0], S, 4, 4))
+            pose_stack(what, "trajectory", trajectory, S)
         act = None if active is None else stream_masks.stream_mask(active, S, "active", what)
         rst = None if restart is None else stream_masks.stream_mask(restart, S, "restart", what)
-        for t in (cloud, given, lengths, trajectory):
-            if t is not None and not t.is_cuda:
-                raise RuntimeError("CPU not supported")
+        need_cuda(cloud, given, lengths, trajectory)
         if self.bufs is None:
             self.device = cloud.device
             self._alloc()
@@ -517,27 +490,12 @@ class ScanContextLoopDetector:
         stream_masks.load_words(b["active"], b["restart"], act, rst)
         b["cloud"].copy_(cloud)
         b["frame_id"].copy_(frame_ids)
-        if lengths is None:
-            b["lengths"].fill_(n)
-        else:
-            b["lengths"].copy_(lengths)
+        stream_masks.load_lengths(b["lengths"], lengths, n)
         if self.verify is not None and self._refiner is None:
             self._make_refiner()
         gate = trajectory is not None and self.max_distance is not None
-        if not self.graph or self.calls == 0:
-            self._body(trajectory)
-        else:
-            key = (trajectory.data_ptr(), int(trajectory.shape[0])) if gate else None
-            g = self._graphs.get(key)
-            if g is None:
-                torch.cuda.synchronize(self.device)
-                g = torch.cuda.CUDAGraph()
-                with _lib.capture(g):
-                    self._body(trajectory)
-                self._graphs[key] = g
-                self.captures += 1
-            g.replay()
-        self.calls += 1
+        key = (trajectory.data_ptr(), int(trajectory.shape[0])) if gate else None
+        self.replay.run(lambda: self._body(trajectory), self.device, key)
 
 
 class ScanContextLoopClosure:

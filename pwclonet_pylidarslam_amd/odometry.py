@@ -24,13 +24,10 @@ import numpy as np
 import torch
 
 from . import _lib, preprocess, stream_masks
+from .stream_engine import ptr as _p
 
 MAX_STREAMS = 1024          # stream_append_masked_kernel: one workgroup, one thread per stream
 RAW_NUM_POINTS = 8192       # raw mode: points sampled from every sweep's survivors (BASELINE configs[4])
-
-
-def _p(t):
-    return t.data_ptr() if t is not None else 0
 
 
 class StreamingOdometry:

@@ -16,7 +16,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .registration import _need, _p
+from .stream_engine import need as _need, ptr as _p
+from .stream_engine import Replay, Replayed, need_iters, stream_count, stream_index, stream_indices
 
 MAX_STREAMS = 1024                               # csrc/pose_graph.hpp
 SLOT = 136
@@ -78,7 +79,7 @@ def _transform(what, T):
     return t
 
 
-class PoseGraph:
+class PoseGraph(Replayed):
     """S pose graphs on the device, one per stream.
 
     ``append(rel, active=None, valid=None)``: one vertex per stream and call: ``X_k = X_{k-1} . rel`` with the current,
@@ -92,8 +93,8 @@ class PoseGraph:
     buffers, so a captured ``optimize`` honours them without a new capture.  Refused with ValueError, before anything is
     written: ``i >= j``, an index beyond the stream's count, a full edge list, a non-symmetric or non-finite information.
 
-    ``optimize(iters=None)``: ``iters`` Levenberg-Marquardt iterations (4 launches each, one more to begin); the first call
-    runs eagerly, the second captures one graph that later calls replay.  A stream freezes with a status bit: CONVERGED (an
+    ``optimize(iters=None)``: ``iters`` Levenberg-Marquardt iterations (4 launches each, one more to begin), replayed as
+    one graph (another ``iters`` captures again).  A stream freezes with a status bit: CONVERGED (an
     accepted step that lowered chi2 by at most 1e-9 of it, or a gradient below 1e-12), TRIVIAL (a chain without loop or
     absolute edge: chi2 = 0, nothing moves), NONFINITE (chi2 is not finite).  ``active`` there: (S,) int32 device mask or
     None; idle streams keep vertices, edges, lambda and status.
@@ -109,13 +110,10 @@ class PoseGraph:
 
     def __init__(self, streams, max_poses=4096, max_loops=256, max_absolute=256, iters=20, pcg_iters=None, pcg_tol=1e-8,
                  fix_first=True, graph=True, device="cuda", robust=None):
-        S, N, ML, MA = int(streams), int(max_poses), int(max_loops), int(max_absolute)
-        if not 1 <= S <= MAX_STREAMS:
-            raise ValueError("PoseGraph: streams=%d outside [1, %d]" % (S, MAX_STREAMS))
+        S, N, ML, MA = stream_count("PoseGraph", streams, MAX_STREAMS), int(max_poses), int(max_loops), int(max_absolute)
         if N < 1 or ML < 1 or MA < 1:
             raise ValueError("PoseGraph: max_poses=%d, max_loops=%d and max_absolute=%d must be >= 1" % (N, ML, MA))
-        if int(iters) < 1:
-            raise ValueError("PoseGraph: iters=%d must be >= 1" % int(iters))
+        need_iters("PoseGraph", iters)
         pcg_iters = 12 * N if pcg_iters is None else int(pcg_iters)
         if pcg_iters < 1 or not 0.0 <= float(pcg_tol) < 1.0:
             raise ValueError("PoseGraph: pcg_iters=%d must be >= 1 and pcg_tol=%r in [0, 1)" % (pcg_iters, pcg_tol))
@@ -124,9 +122,7 @@ class PoseGraph:
         self.fix_first, self.graph = bool(fix_first), bool(graph)
         self._robust = robust_settings(robust)
         self.device = torch.device(device)
-        self.captures = 0
-        self.calls = 0
-        self._graph = None
+        self.replay = Replay(graph)
         self._alloc()
 
     # ---- state -------------------------------------------------------------------------------------------------------
@@ -177,14 +173,8 @@ class PoseGraph:
         self.bufs["inc_ptr"][s].copy_(torch.from_numpy(ptr))
         self.bufs["inc_ent"][s].copy_(torch.from_numpy(ent))
 
-    def _stream_arg(self, what, stream):
-        s = int(stream)
-        if not 0 <= s < self.streams:
-            raise ValueError("%s: stream=%d outside [0, %d)" % (what, s, self.streams))
-        return s
-
     def add_loop(self, stream, i, j, T, information=None):
-        s = self._stream_arg("add_loop", stream)
+        s = stream_index(None, "add_loop", stream, self.streams)
         i, j = int(i), int(j)
         Z = _transform("add_loop", T)
         om = _information("add_loop", "loop", i, j, information)
@@ -205,7 +195,7 @@ class PoseGraph:
         b["nloops"][s:s + 1].fill_(l + 1)
 
     def add_absolute(self, stream, i, T, information=None):
-        s = self._stream_arg("add_absolute", stream)
+        s = stream_index(None, "add_absolute", stream, self.streams)
         i = int(i)
         G = _transform("add_absolute", T)
         om = _information("add_absolute", "absolute", i, i, information)
@@ -230,7 +220,7 @@ class PoseGraph:
         new = robust_settings(robust, "set_robust")
         if new != self._robust:
             self._robust = new
-            self._graph = None
+            self.replay.drop()
 
     def robust(self):
         """The settings in force: None or (kind, delta, edge mask)."""
@@ -238,9 +228,8 @@ class PoseGraph:
 
     def reset(self, streams=None):
         """Empties the graphs of ``streams`` (host indices; None: all): vertex 0 alone, no edges, status 0."""
-        which = range(self.streams) if streams is None else [self._stream_arg("reset", s) for s in streams]
         b = self.bufs
-        for s in which:
+        for s in stream_indices(None, "reset", streams, self.streams):
             self._loops[s], self._abs[s] = [], []
             for name in ("nloops", "nabs", "status"):
                 b[name][s:s + 1].zero_()
@@ -337,18 +326,9 @@ class PoseGraph:
             b["active"].fill_(1)
         else:
             b["active"].copy_(self._mask("optimize", active))
-        if not self.graph or self.calls == 0:
-            self._body(iters)
-        else:
-            if self._graph is None or self._graph[0] != iters:
-                torch.cuda.synchronize(self.device)
-                g = torch.cuda.CUDAGraph()
-                with _lib.capture(g):
-                    self._body(iters)
-                self._graph = (iters, g)
-                self.captures += 1
-            self._graph[1].replay()
-        self.calls += 1
+        if self.replay.graph(iters) is None:                # one graph at a time: another iters replaces the one held
+            self.replay.drop()
+        self.replay.run(lambda: self._body(iters), self.device, iters)
 
     # ---- views -------------------------------------------------------------------------------------------------------
 
@@ -356,7 +336,7 @@ class PoseGraph:
         counts = self.bufs["count"]
         if stream is None:
             return buf[:int(counts.max())]
-        s = self._stream_arg("poses", stream)
+        s = stream_index(None, "poses", stream, self.streams)
         return buf[:int(counts[s]), s]
 
     def poses(self, stream=None):
@@ -387,12 +367,12 @@ class PoseGraph:
         loops, absolutes = b["weights"][:, :self.max_loops], b["weights"][:, self.max_loops:]
         if stream is None:
             return loops, absolutes
-        s = self._stream_arg("edge_weights", stream)
+        s = stream_index(None, "edge_weights", stream, self.streams)
         return loops[s], absolutes[s]
 
     def loop_weights(self, stream):
         """(nloops, 2): ``(c, w)`` of the stream's loops in use, in the order they were added."""
-        s = self._stream_arg("loop_weights", stream)
+        s = stream_index(None, "loop_weights", stream, self.streams)
         return self.edge_weights(s)[0][:int(self.bufs["nloops"][s])]
 
     def overflowed(self):

@@ -17,6 +17,8 @@ import torch
 
 from . import _lib, evaluation, registration
 from .registration import _need, _p, BAD_PIVOT, CONVERGED, FEW_PAIRS, ROW    # noqa: F401  (the status bits are section 21's)
+from .stream_engine import (Replay, Replayed, init_poses, need_cuda, need_iters, need_max_dist, need_sigma, need_solver,
+                            stream_count)
 
 MAX_STREAMS = registration.MAX_STREAMS
 MAX_SLOTS = registration.MAX_SLOTS
@@ -152,15 +154,15 @@ def map_push(T, vmap, nmap, map_v, map_n, A, live, cursor):
 
 # ---- the refiner -------------------------------------------------------------------------------------------------------
 
-class ProjectiveIcpRefiner:
+class ProjectiveIcpRefiner(Replayed):
     """Registers one sweep per call and stream against each stream's map of the last ``map_size`` frames' vertex maps.
 
     ``register(points, lengths, init)``: points (S, R <= capacity, 3|4) fp32 (the channel count is fixed by the first
     call), lengths (S,) device integers or a host sequence, init (S, 4, 4) fp64 or (S, 7) fp32 pose rows -> the refined
     pose (S, 4, 4) fp64, a static buffer that the next call overwrites.  The launch sequence is fixed: the frame's vertex
     map (a memset, 2 launches), its normal map, the model images (a memset, 2 launches), ``iters`` x (``accumulate``,
-    ``registration.solve``'s kernel), the push (2 launches); with ``graph=True`` the first call runs eagerly and the second
-    captures one graph that every later call replays.  Status words and freezing are ``registration.IcpRefiner``'s: the
+    ``registration.solve``'s kernel), the push (2 launches); with ``graph=True`` it replays as one graph (DESIGN.md
+    section 21.2).  Status words and freezing are ``registration.IcpRefiner``'s: the
     first frame after a reset finds no live slot, freezes in iteration 0 with the few-pairs bit, returns ``init`` bit for
     bit and fills slot 0.  ``register(..., trace=True)`` (``graph=False`` only) also returns the frame's images, the model
     images and, per iteration, clones of the pairs, the summed row, ``delta`` and ``T``.
@@ -175,28 +177,18 @@ class ProjectiveIcpRefiner:
         if per_stream:
             raise ValueError("%s: lock step only: per-stream masks, idle streams and restarts inside the graph are out of "
                              "scope of the projective refiner (per_stream=True is registration.IcpRefiner's)" % what)
-        S, cap, M = int(streams), int(capacity), int(map_size)
-        if not 1 <= S <= MAX_STREAMS:
-            raise ValueError("%s: streams=%d outside [1, %d]" % (what, S, MAX_STREAMS))
+        S, cap, M = stream_count(what, streams, MAX_STREAMS), int(capacity), int(map_size)
         if not 1 <= cap or cap * 4 >= 1 << 31:
             raise ValueError("%s: capacity=%d out of range" % (what, cap))
         H, W, up, down = _image_args(what, height, width, up_fov, down_fov)
         if not 1 <= M <= MAX_SLOTS or S * M > 65535:
             raise ValueError("%s: map_size=%d outside [1, %d] (and streams * map_size <= 65535)" % (what, M, MAX_SLOTS))
-        if int(iters) < 1:
-            raise ValueError("%s: iters=%d must be >= 1" % (what, int(iters)))
-        if not float(sigma) > 0.0 or not np.isfinite(float(sigma)):
-            raise ValueError("%s: sigma=%r must be finite and > 0" % (what, sigma))
-        if not float(max_dist) >= 0.0:
-            raise ValueError("%s: max_dist=%r must be >= 0" % (what, max_dist))
+        need_iters(what, iters)
+        need_sigma(what, sigma)
+        need_max_dist(what, max_dist)
         if int(kernel_size) not in KERNEL_SIZES:
             raise ValueError("%s: kernel_size=%r is not instantiated (3 or 5)" % (what, kernel_size))
-        if not float(damping) >= 0.0 or not np.isfinite(float(damping)):
-            raise ValueError("%s: damping=%r must be finite and >= 0" % (what, damping))
-        if not float(threshold_delta_pose) >= 0.0:
-            raise ValueError("%s: threshold_delta_pose=%r must be >= 0" % (what, threshold_delta_pose))
-        if int(min_pairs) < 1:
-            raise ValueError("%s: min_pairs=%d must be >= 1 (an empty map freezes a stream through it)" % (what, int(min_pairs)))
+        need_solver(what, damping, threshold_delta_pose, min_pairs)
         self.streams, self.capacity, self.height, self.width, self.up_fov, self.down_fov = S, cap, H, W, up, down
         self.map_size, self.iters, self.kernel_size = M, int(iters), int(kernel_size)
         self.sigma, self.max_dist, self.damping = float(sigma), float(max_dist), float(damping)
@@ -204,9 +196,7 @@ class ProjectiveIcpRefiner:
         self.per_stream = False
         self.bufs = None
         self.channels = None
-        self.calls = 0              # register() calls so far: call 0 is eager, call 1 captures
-        self.captures = 0
-        self._graph = None
+        self.replay = Replay(graph)
 
     # ---- state -------------------------------------------------------------------------------------------------------
 
@@ -230,17 +220,8 @@ class ProjectiveIcpRefiner:
             partial=f64(S, G, ROW), status=i32(S), iterations=i32(S), pairs=i32(S), cost=f64(S), sum=f64(S, ROW),
             delta=f64(S, 6), slot=i32(S, H, W), pixel=i32(S, H, W))
 
-    def status(self):
-        """(S,) int32 device view: 0 = the stream moved in every iteration of the last registration, else the bits of why
-        it froze (1 converged, 2 too few pairs, 4 pivot not positive).  None before the first call."""
-        return None if self.bufs is None else self.bufs["status"]
-
-    def diagnostics(self):
-        """Device views of the last registration: iterations used, pairs and the weighted cost sum w^2 r^2 of the last
-        iteration a stream took part in.  None before the first call."""
-        if self.bufs is None:
-            return None
-        return dict(iterations=self.bufs["iterations"], pairs=self.bufs["pairs"], cost=self.bufs["cost"])
+    status = registration.IcpRefiner.status                 # section 21's words (no stream is ever idle here)
+    diagnostics = registration.IcpRefiner.diagnostics
 
     def map_state(self):
         """Device views of the maps' bookkeeping: A (S, M, 4, 4) the newest frame -> slot, live (S, M), cursor (S,)."""
@@ -295,14 +276,8 @@ class ProjectiveIcpRefiner:
                                 tuple(getattr(points, "shape", ()))))
         if self.channels is not None and points.shape[2] != self.channels:
             raise ValueError("%s: points have %d channels, the first call fixed %d" % (what, points.shape[2], self.channels))
-        ok = isinstance(init, torch.Tensor) and (
-            (init.dtype == torch.float64 and tuple(init.shape) == (S, 4, 4)) or
-            (init.dtype == torch.float32 and tuple(init.shape) == (S, 7)))
-        if not ok:
-            raise ValueError("%s: init must be float64 (%d, 4, 4) or float32 (%d, 7) pose rows, got %s %s"
-                             % (what, S, S, getattr(init, "dtype", type(init)), tuple(getattr(init, "shape", ()))))
-        if not points.is_cuda or not init.is_cuda:
-            raise RuntimeError("CPU not supported")
+        init_poses(what, init, S)
+        need_cuda(points, init)
         R = points.shape[1]
         if isinstance(lengths, torch.Tensor) and lengths.is_cuda:
             if tuple(lengths.shape) != (S,) or lengths.dtype.is_floating_point or lengths.dtype == torch.bool:
@@ -333,16 +308,5 @@ class ProjectiveIcpRefiner:
             b["lengths"].clamp_(max=R)
         b["T"].copy_(init)
         out = dict(steps=[]) if trace else None
-        if not self.graph or self.calls == 0:
-            self._body(out)
-        else:
-            if self._graph is None:
-                torch.cuda.synchronize(points.device)
-                g = torch.cuda.CUDAGraph()
-                with _lib.capture(g):
-                    self._body()
-                self._graph = g
-                self.captures += 1
-            self._graph.replay()
-        self.calls += 1
+        self.replay.run(lambda: self._body(out), points.device)
         return (b["T"], out) if trace else b["T"]

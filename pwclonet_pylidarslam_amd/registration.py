@@ -23,6 +23,9 @@ import numpy as np
 import torch
 
 from . import _lib, evaluation, stream_masks
+from .stream_engine import need as _need, ptr as _p
+from .stream_engine import (Replay, Replayed, init_poses, need_cuda, need_iters, need_max_dist, need_sigma, need_solver,
+                            stream_count)
 
 MAX_STREAMS = 1024
 MAX_SLOTS = 64                                   # csrc/icp.hip: ICP_MAX_SLOTS
@@ -30,21 +33,6 @@ ROW = 32                                         # csrc/icp.hpp: ICP_ROW and the
 H0, G0, SW, COST, PAIRS = 0, 21, 27, 28, 29
 CONVERGED, FEW_PAIRS, BAD_PIVOT = 1, 2, 4        # status bits
 IDLE = 8                                         # masked registration: the stream delivered no frame in this call
-
-
-def _p(t):
-    return t.data_ptr() if t is not None else 0
-
-
-def _need(t, name, dtype, shape=None):
-    if not isinstance(t, torch.Tensor) or t.dtype != dtype or (shape is not None and tuple(t.shape) != tuple(shape)):
-        raise ValueError("%s must be a %s tensor%s, got %s %s" % (
-            name, str(dtype).replace("torch.", ""), "" if shape is None else " of shape %s" % (tuple(shape),),
-            getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ()))))
-    if not t.is_cuda:
-        raise RuntimeError("CPU not supported")
-    if not t.is_contiguous():
-        raise ValueError("%s must be contiguous" % name)
 
 
 def _need_pairing(sigma, max_dist):
@@ -291,7 +279,7 @@ def keyframe_gate(T, delta, live, trans, rot, active=None, count=None, insert=No
 
 # ---- the refiner -------------------------------------------------------------------------------------------------------
 
-class IcpRefiner:
+class IcpRefiner(Replayed):
     """Registers one frame per call and stream against each stream's map of the last ``map_size`` frames.
 
     ``register(cloud, init)``: cloud (S, n, 3) fp32, init (S, 4, 4) fp64 or (S, 7) fp32 pose rows [tx ty tz qw qx qy qz]
@@ -307,9 +295,9 @@ class IcpRefiner:
     (a NaN in a later slot is passed over); a neighbour index outside [0, n) rejects the point; a row of sums with a NaN in
     its gradient is refused like a bad pivot (bit 4, the pose untouched); a map cursor outside [0, map_size) is read as
     the nearest slot.
-    ``graph=True``: the first call runs eagerly (it loads every kernel), the second captures one graph that every later
-    call replays.  ``register(..., trace=True)`` (``graph=False`` only) also returns, per iteration, clones of the queries,
-    ``idx``, ``dist``, the summed row, ``delta`` and ``T``.
+    ``graph=True``: ``register`` replays as one graph (the protocol of DESIGN.md section 21.2; ``calls``, ``captures``).
+    ``register(..., trace=True)`` (``graph=False`` only) also returns, per iteration, clones of the queries, ``idx``,
+    ``dist``, the summed row, ``delta`` and ``T``.
 
     One engine runs both modes: the graph (begin, stage, ``iters`` x (queries, search, accumulate, solve), push: ``4 + 4
     iters + 1`` launches) reads two (S,) words from device memory.  ``active[s]``: stream s delivered a frame in this call;
@@ -342,41 +330,39 @@ class IcpRefiner:
     loads no mask at all."""
 
     _name = "IcpRefiner"        # in front of the messages of the methods a subclass shares
+    _graph = property(lambda self: self.replay.graph())     # read-only: the captured graph or None, as the tests read it
 
     def __init__(self, streams, num_points, map_size=4, iters=10, sigma=0.5, max_dist=1.0, k_normals=10, damping=1e-6,
                  threshold_delta_pose=1e-4, min_pairs=64, graph=True, per_stream=False, keyframe=None):
-        S, n, M, k = int(streams), int(num_points), int(map_size), int(k_normals)
-        self.keyframe = keyframe_args("IcpRefiner", keyframe)      # None or (trans, rot)
-        if not 1 <= S <= MAX_STREAMS:
-            raise ValueError("IcpRefiner: streams=%d outside [1, %d]" % (S, MAX_STREAMS))
+        what, n, k = self._name, int(num_points), int(k_normals)
+        self.keyframe = keyframe_args(what, keyframe)               # None or (trans, rot)
+        self.streams = stream_count(what, streams, MAX_STREAMS)
         if not 64 <= n <= 16384:
-            raise ValueError("IcpRefiner: num_points=%d outside [64, 16384] (the neighbour search's range)" % n)
-        if not 1 <= M <= MAX_SLOTS or S * M > 65535:
-            raise ValueError("IcpRefiner: map_size=%d outside [1, %d] (and streams * map_size <= 65535)" % (M, MAX_SLOTS))
-        if int(iters) < 1:
-            raise ValueError("IcpRefiner: iters=%d must be >= 1" % int(iters))
-        if not float(sigma) > 0.0 or not np.isfinite(float(sigma)):
-            raise ValueError("IcpRefiner: sigma=%r must be finite and > 0" % (sigma,))
-        if not float(max_dist) >= 0.0:
-            raise ValueError("IcpRefiner: max_dist=%r must be >= 0" % (max_dist,))
+            raise ValueError("%s: num_points=%d outside [64, 16384] (the neighbour search's range)" % (what, n))
+        self._need_map(map_size)
+        need_iters(what, iters)
+        need_sigma(what, sigma)
+        self._need_max_dist(max_dist)
         if not 1 <= k <= min(63, n - 1):
-            raise ValueError("IcpRefiner: k_normals=%d outside [1, %d]" % (k, min(63, n - 1)))
-        if not float(damping) >= 0.0 or not np.isfinite(float(damping)):
-            raise ValueError("IcpRefiner: damping=%r must be finite and >= 0" % (damping,))
-        if not float(threshold_delta_pose) >= 0.0:
-            raise ValueError("IcpRefiner: threshold_delta_pose=%r must be >= 0" % (threshold_delta_pose,))
-        if int(min_pairs) < 1:
-            raise ValueError("IcpRefiner: min_pairs=%d must be >= 1 (an empty map freezes a stream through it)"
-                             % int(min_pairs))
-        self.streams, self.num_points, self.map_size, self.iters, self.k_normals = S, n, M, int(iters), k
+            raise ValueError("%s: k_normals=%d outside [1, %d]" % (what, k, min(63, n - 1)))
+        need_solver(what, damping, threshold_delta_pose, min_pairs)
+        self.num_points, self.iters, self.k_normals = n, int(iters), k
         self.sigma, self.max_dist, self.damping = float(sigma), float(max_dist), float(damping)
         self.threshold_delta_pose, self.min_pairs, self.graph = float(threshold_delta_pose), int(min_pairs), bool(graph)
         self.per_stream = bool(per_stream)
         self.bufs = None
-        self.calls = 0              # register() calls so far: call 0 is eager, call 1 captures
-        self._graph = None
+        self.replay = Replay(graph)
         self._words = None          # adopt_words: the caller's (active, restart) words
         self._plain = False         # the refiner's own words are known to hold "all active, none restarting"
+
+    def _need_map(self, map_size):
+        """The map's own settings, checked where the constructor's order has them (a subclass has others)."""
+        M = self.map_size = int(map_size)
+        if not 1 <= M <= MAX_SLOTS or self.streams * M > 65535:
+            raise ValueError("IcpRefiner: map_size=%d outside [1, %d] (and streams * map_size <= 65535)" % (M, MAX_SLOTS))
+
+    def _need_max_dist(self, max_dist):
+        need_max_dist(self._name, max_dist)
 
     # ---- state -------------------------------------------------------------------------------------------------------
 
@@ -522,14 +508,8 @@ class IcpRefiner:
         if not isinstance(cloud, torch.Tensor) or cloud.dtype != torch.float32 or tuple(cloud.shape) != (S, n, 3):
             raise ValueError("%s: cloud must be float32 (%d, %d, 3), got %s %s"
                              % (self._name, S, n, getattr(cloud, "dtype", type(cloud)), tuple(getattr(cloud, "shape", ()))))
-        ok = isinstance(init, torch.Tensor) and (
-            (init.dtype == torch.float64 and tuple(init.shape) == (S, 4, 4)) or
-            (init.dtype == torch.float32 and tuple(init.shape) == (S, 7)))
-        if not ok:
-            raise ValueError("%s: init must be float64 (%d, 4, 4) or float32 (%d, 7) pose rows, got %s %s"
-                             % (self._name, S, S, getattr(init, "dtype", type(init)), tuple(getattr(init, "shape", ()))))
-        if not cloud.is_cuda or not init.is_cuda:
-            raise RuntimeError("CPU not supported")
+        init_poses(self._name, init, S)
+        need_cuda(cloud, init)
 
     def _mask(self, mask, what):
         return stream_masks.stream_mask(mask, self.streams, what, self._name)
@@ -586,17 +566,7 @@ class IcpRefiner:
             self._stage()
             self._seed_structures()
         steps = [] if trace else None
-        if not self.graph or self.calls == 0:
-            self._body(steps)
-        else:
-            if self._graph is None:
-                torch.cuda.synchronize(cloud.device)
-                g = torch.cuda.CUDAGraph()
-                with _lib.capture(g):
-                    self._body()
-                self._graph = g
-            self._graph.replay()
-        self.calls += 1
+        self.replay.run(lambda: self._body(steps), cloud.device)
         if trace and self.per_stream:
             return b["T"], steps, dict(active=b["active"].clone(), restart=b["restart"].clone())
         return (b["T"], steps) if trace else b["T"]

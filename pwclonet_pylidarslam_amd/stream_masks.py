@@ -44,6 +44,14 @@ def load_words(active, restart, act, rst):
         restart.copy_(rst)
 
 
+def load_lengths(word, lengths, n):
+    """The call's ``lengths`` ((S,) int32 anywhere; None: all n rows) into the (S,) device word a captured graph reads."""
+    if lengths is None:
+        word.fill_(n)
+    else:
+        word.copy_(lengths)
+
+
 def seed_idle_rows(act, S, owner, *tensors):
     """New static inputs need every row initialised: idle streams' rows start as copies of the first active stream's.
     ``act``: (S,) int32 mask anywhere (a device mask is read once, here) or None = all active; ``tensors``: (S, ...) or

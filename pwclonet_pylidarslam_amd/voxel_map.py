@@ -17,6 +17,7 @@ import torch
 
 from . import _lib, registration
 from .registration import ROW, _need, _need_mask, _p, groups
+from .stream_engine import need_sigma, stream_index
 
 MAX_STREAMS = 1024                               # csrc/voxel_map.hpp: VM_MAX_STREAMS, VM_MAX_AXIS, VM_CELL_BYTES
 MAX_AXIS = 1024
@@ -150,8 +151,7 @@ def accumulate(grid, extent, voxel_size, p, P, T=None, sigma=0.5, max_dist=1.0, 
     around fp32(P T p), (S, n) int32, int32 and fp32; -1, -1 and +Inf where there is none."""
     S, n = _streams("accumulate", p, "p")
     voxel_size, extent = extent_args("accumulate", voxel_size, extent)
-    if not float(sigma) > 0.0 or not np.isfinite(float(sigma)):
-        raise ValueError("accumulate: sigma=%r must be finite and > 0" % (sigma,))
+    need_sigma("accumulate", sigma)
     if not 0.0 <= float(max_dist) <= voxel_size:
         raise ValueError("accumulate: max_dist=%r outside [0, voxel_size=%r] (the 27 voxels hold every point that near)"
                          % (max_dist, voxel_size))
@@ -198,7 +198,7 @@ class VoxelMapRefiner(registration.IcpRefiner):
     freezes in iteration 0 with the few-pairs bit); idle streams keep every bit of their grid, ``pose()`` and counters and
     get status ``IDLE``; a restart empties the map on the device, inside the graph.  One registration is ``1 + 3 + 2 iters
     + 4`` launches (begin; stage; accumulate and solve per iteration; three launches of insertion and the pose), one more
-    with ``keyframe=``, and replays as one graph from the second call on.
+    with ``keyframe=``, and replays as one graph.
 
     The map: ``extent`` voxels (even, at least 4 per axis) of edge ``voxel_size`` around the sensor, 264 bytes each.  A
     frame is inserted with its absolute pose in the map frame; only points within ``(N / 2 - 1) voxel_size`` of the sensor
@@ -215,39 +215,17 @@ class VoxelMapRefiner(registration.IcpRefiner):
     def __init__(self, streams, num_points, voxel_size=1.0, extent=(128, 128, 32), iters=10, sigma=0.5, max_dist=1.0,
                  k_normals=10, damping=1e-6, threshold_delta_pose=1e-4, min_pairs=64, graph=True, per_stream=False,
                  keyframe=None):
-        what = self._name
-        self.keyframe = registration.keyframe_args(what, keyframe)
-        S, n, k = int(streams), int(num_points), int(k_normals)
-        if not 1 <= S <= MAX_STREAMS:
-            raise ValueError("%s: streams=%d outside [1, %d]" % (what, S, MAX_STREAMS))
-        if not 64 <= n <= 16384:
-            raise ValueError("%s: num_points=%d outside [64, 16384] (the neighbour search's range)" % (what, n))
-        self.voxel_size, self.extent = extent_args(what, voxel_size, extent)
-        if int(iters) < 1:
-            raise ValueError("%s: iters=%d must be >= 1" % (what, int(iters)))
-        if not float(sigma) > 0.0 or not np.isfinite(float(sigma)):
-            raise ValueError("%s: sigma=%r must be finite and > 0" % (what, sigma))
+        self.voxel_size, self.extent = voxel_size, extent            # checked by _need_map, where the parent's order has it
+        super().__init__(streams, num_points, None, iters, sigma, max_dist, k_normals, damping, threshold_delta_pose,
+                         min_pairs, graph, per_stream, keyframe)
+
+    def _need_map(self, map_size):
+        self.voxel_size, self.extent = extent_args(self._name, self.voxel_size, self.extent)
+
+    def _need_max_dist(self, max_dist):
         if not 0.0 <= float(max_dist) <= self.voxel_size:
             raise ValueError("%s: max_dist=%r outside [0, voxel_size=%r]: the lookup reads the 27 voxels around a query, "
-                             "which hold every stored point within one voxel edge" % (what, max_dist, self.voxel_size))
-        if not 1 <= k <= min(63, n - 1):
-            raise ValueError("%s: k_normals=%d outside [1, %d]" % (what, k, min(63, n - 1)))
-        if not float(damping) >= 0.0 or not np.isfinite(float(damping)):
-            raise ValueError("%s: damping=%r must be finite and >= 0" % (what, damping))
-        if not float(threshold_delta_pose) >= 0.0:
-            raise ValueError("%s: threshold_delta_pose=%r must be >= 0" % (what, threshold_delta_pose))
-        if int(min_pairs) < 1:
-            raise ValueError("%s: min_pairs=%d must be >= 1 (an empty map freezes a stream through it)"
-                             % (what, int(min_pairs)))
-        self.streams, self.num_points, self.iters, self.k_normals = S, n, int(iters), k
-        self.sigma, self.max_dist, self.damping = float(sigma), float(max_dist), float(damping)
-        self.threshold_delta_pose, self.min_pairs, self.graph = float(threshold_delta_pose), int(min_pairs), bool(graph)
-        self.per_stream = bool(per_stream)
-        self.bufs = None
-        self.calls = 0
-        self._graph = None
-        self._words = None
-        self._plain = False
+                             "which hold every stored point within one voxel edge" % (self._name, max_dist, self.voxel_size))
 
     # ---- state -------------------------------------------------------------------------------------------------------
 
@@ -291,9 +269,7 @@ class VoxelMapRefiner(registration.IcpRefiner):
         """The stored entries of one stream's map, compacted with torch ops (outside any graph; this syncs): dict(points
         (m, 3) fp32, normals (m, 3) fp32, voxels (m, 3) int64, octants (m,) int64, keys (m,) int64 = seq << 32 | row), in
         cell and octant order.  An entry counts where its cell has an owner and its key is not empty."""
-        i = int(stream)
-        if not 0 <= i < self.streams:
-            raise ValueError("%s: stream=%d outside [0, %d)" % (self._name, i, self.streams))
+        i = stream_index(self._name, None, stream, self.streams)
         if self.bufs is None:
             return None
         sec = sections(self.bufs["grid"], self.streams, self.extent)
