@@ -1411,6 +1411,40 @@ void global_map_write_kernel_wrapper(int S, int MK, int n, int E, int capacity, 
 /* built += todo and dirty = 0 for the streams with run. */
 void global_map_end_kernel_wrapper(int S, int *state);
 
+/* ---- 13. localisation in the global map: hashed lookup, plane fit, point-to-plane rows ---------------
+ * The map of section 12 is only read: keys (S,T) 64-bit words, points (S,capacity,3) floats, source (S,capacity,2) ints and
+ * the word total[s * total_stride] (M = min(max(total, 0), capacity) valid ranks); T a power of two in [2^6, 2^30].  index
+ * (S,T+1) ints, slot -> rank, is the caller's (slot T: the empty marker's voxel; -1: none).  An entry is never trusted: the
+ * slot found for a key h yields the candidate r = index[slot] only where 0 <= r < M, the key of points[r] (section 12's rule)
+ * is valid and equals h, and, with max_source_frame (S) given, source[r][0] <= max_source_frame[s].  S <= 1024.  All pointers
+ * DEVICE memory; every launcher refuses a bad argument before it launches. */
+
+/* Bytes of the index of S streams: 4 (T + 1) each; 0: out of range. */
+long long map_localize_index_bytes(int S, long long T);
+/* Two launches.  Ranks [lo, M) of every stream (lo = 0 where full != 0 or refill[s] != 0 (refill (S) ints, NULL: none), else
+ * max(indexed[s], 0)): the key of points[r], a
+ * read-only probe from its home slot until the slot's key equals it (index[slot] = r) or an empty slot or T steps (nothing);
+ * the empty marker's key goes to slot T.  Then indexed[s] = M. */
+void map_index_kernel_wrapper(int S, long long T, int capacity, double voxel, const void *keys, const float *points,
+                              const int *source, const int *total, int total_stride, int full, const int *refill, int *indexed,
+                              int *index);
+/* T[s] = init[s] (S,4,4 doubles, all 16 words) for the streams with active[s] != 0 (active NULL: all). */
+void map_localize_begin_kernel_wrapper(int S, const double *init, const int *active, double *T);
+/* One row of sums (section 6's layout) per 256 points of p (S,n,3): q = float32(pose[s] p) (pose (S,4,4) doubles; NULL: q = p
+ * and the sensor at the origin); c = rint((double)q / voxel), usable where |q / voxel| < 2^31 on every axis; the voxels c +
+ * (dx,dy,dz), dz outermost, dx innermost, each in [-radius, radius], radius 1 or 2, skipping coordinates of magnitude >=
+ * 2^31; the candidates in that order; the nearest by float32 sqrtf((dx dx + dy dy) + dz dz), strict <; the plane from the
+ * mean and then the covariance of all candidates in fp64; no pair where the query is unusable, count < min_neighbours,
+ * !(d <= max_dist), or the rank test fails.  0 <= max_dist <= radius * voxel.  rank, count, dist (S,n) and normal (S,n,3), or
+ * all NULL: the nearest candidate's rank (-1: none), the number of candidates, d (+Inf: none) and the plane's unit normal
+ * (0: no plane was fitted).  A stream with active[s] == 0 (NULL: none) gets zero rows and nothing else is written. */
+void map_localize_accumulate_kernel_wrapper(int S, int n, long long T, int capacity, double voxel, int radius,
+                                            const void *keys, const float *points, const int *source, const int *total,
+                                            int total_stride, const int *index, const float *p, const double *pose,
+                                            const int *max_source_frame, double sigma, float max_dist, int min_neighbours,
+                                            double *partial, int *rank, int *count, float *dist, float *normal,
+                                            const int *active);
+
 #ifdef __cplusplus
 }
 #endif

@@ -231,6 +231,11 @@ SIGNATURES = {
     "global_map_scan_kernel_wrapper": ([_i] * 3 + [_F] * 2, None),
     "global_map_write_kernel_wrapper": ([_i] * 5 + [_F, _i] + [_F] * 10, None),
     "global_map_end_kernel_wrapper": ([_i, _F], None),
+    "map_localize_index_bytes": ([_i, ctypes.c_longlong], ctypes.c_longlong),
+    "map_index_kernel_wrapper": ([_i, ctypes.c_longlong, _i, ctypes.c_double] + [_F] * 4 + [_i, _i, _F, _F, _F], None),
+    "map_localize_begin_kernel_wrapper": ([_i, _F, _F, _F], None),
+    "map_localize_accumulate_kernel_wrapper": ([_i, _i, ctypes.c_longlong, _i, ctypes.c_double, _i] + [_F] * 4 + [_i]
+                                               + [_F] * 4 + [ctypes.c_double, ctypes.c_float, _i] + [_F] * 6, None),
 }
 
 _lib = None

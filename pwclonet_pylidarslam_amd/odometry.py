@@ -98,6 +98,15 @@ class StreamingOdometry:
     vertices where the graph was optimised since the map last saw it.  ``global_map()``, ``map_points(stream)``; without
     ``map=`` every path launches what it launched before.
 
+    Localisation in that map (``localize=dict(min_id_distance=200, radius=1, iters=10, sigma=0.5, max_dist=None,
+    min_pairs=64, ...)``, ``map_localize.MapLocalizer``'s keywords; needs ``map=``): from the second
+    step on, before the map banks the step's frame, an index pass over what the map gained (in full after a rebuild or a
+    reset) and one ``localize`` of the step's cloud, the guess the frame's pose in the map's source trajectory and
+    ``max_source_frame = frame id - min_id_distance``, so that only old parts of the map attract and a stream that is not
+    revisiting freezes with the few-pairs bit.  ``localizer()``, ``localized_pose()``, ``localized_status()``;
+    ``poll_localization(optimize=False, information=None)`` (needs ``backend=``) hands the converged fixes to
+    ``backend().add_absolute``.  No existing output changes.
+
     Per-stream mode (``per_stream=True``): ``step(frames, active=None, restart=None)`` and ``step_sweeps(sweeps, lengths,
     active=None, restart=None)`` take two (S,) masks, bool or integer, host sequences or device tensors (device tensors
     are read on the device, without a sync); ``None`` = all active, none restarting.  ``active[s]``: stream s delivered a
@@ -117,7 +126,7 @@ class StreamingOdometry:
     start as copies of the first active stream's, so that no step ever reads an uninitialised buffer."""
 
     def __init__(self, net, streams=1, num_points=None, max_frames=4096, graph=True, warmup=1, sweeps=None,
-                 per_stream=False, refine=None, backend=None, loop=None, map=None):
+                 per_stream=False, refine=None, backend=None, loop=None, map=None, localize=None):
         if not 1 <= int(streams) <= MAX_STREAMS:
             raise ValueError("StreamingOdometry: streams=%d outside [1, %d]" % (int(streams), MAX_STREAMS))
         if int(max_frames) < 1:
@@ -221,6 +230,27 @@ class StreamingOdometry:
             if unknown:
                 raise ValueError("StreamingOdometry: map=dict(%s=...): the keys are voxel_size, max_keyframes, capacity, "
                                  "stride, max_new, source, rebuild_on_optimize" % sorted(unknown)[0])
+        self._loc = None            # localize=: map_localize.MapLocalizer in the global map
+        self._loc_cfg = None if localize is None else dict(localize)
+        self._loc_min_id = 200
+        self._loc_full = True       # the next step indexes in full (first pass, after a rebuild or a reset)
+        self._loc_refill = self._loc_ids = self._loc_newest = None
+        self._loc_fresh = False     # a localisation that no poll has looked at yet
+        self.localization_dropped = []      # (stream, frame, T, message): fixes the pose graph refused in poll_localization
+        if localize is not None:
+            if map is None:
+                raise ValueError("StreamingOdometry: localize=dict(...) localises in the global map and needs map=dict(...)")
+            self._loc_min_id = self._loc_cfg.pop("min_id_distance", 200)
+            if isinstance(self._loc_min_id, bool) or not isinstance(self._loc_min_id, (int, np.integer)) \
+                    or int(self._loc_min_id) < 1:
+                raise ValueError("StreamingOdometry: localize=dict(min_id_distance=%r) must be an integer >= 1"
+                                 % (self._loc_min_id,))
+            unknown = set(self._loc_cfg) - {"radius", "iters", "sigma", "max_dist", "min_pairs", "min_neighbours", "damping",
+                                            "threshold_delta_pose"}
+            if unknown:
+                raise ValueError("StreamingOdometry: localize=dict(%s=...): the keys are min_id_distance, radius, iters, "
+                                 "sigma, max_dist, min_pairs, min_neighbours, damping, threshold_delta_pose"
+                                 % sorted(unknown)[0])
         self._tapped = None         # refine / loop / map: the frame batch the last step's graph (or eager step) sampled from
         if refine is not None and self.per_stream != bool(self._refine_cfg.get("per_stream", False)):
             if self.per_stream:
@@ -309,6 +339,7 @@ class StreamingOdometry:
             self._loop.reset()                              # the places and the closure logs too
         if self._map is not None:
             self._map.reset()                               # the banks and the maps too
+            self._loc_full = True
         self._reset_motion(None)
 
     def _reset_motion(self, mask):
@@ -518,6 +549,79 @@ class StreamingOdometry:
                 and self._backend.calls != self._map_optimized:     # by this poll or by backend().optimize() before it
             self._map.rebuild(self._backend.bufs["X"])      # the keyframes at the corrected vertices
             self._map_optimized = self._backend.calls
+            self._loc_full = True                           # the ranks moved: the next step indexes in full
+        return added
+
+    def localizer(self):
+        """With ``localize=``: the ``map_localize.MapLocalizer`` (``status()``, ``diagnostics()``, ``indexed()``); None until
+        the map holds a frame (the second step) or without ``localize``."""
+        return self._loc
+
+    def localized_pose(self):
+        """With ``localize=``: (S, 4, 4) fp64 device view, the last step's frames localised in the global map; None until
+        the map holds a frame."""
+        return None if self._loc is None else self._loc.bufs["T"]
+
+    def localized_status(self):
+        """With ``localize=``: (S,) int32 device view of the last localisation's status words (``MapLocalizer.status``)."""
+        return None if self._loc is None else self._loc.status()
+
+    def _localize(self, pose):
+        """After the step, the refinement, the backend's append and the detector, before the map banks the frame: an index
+        pass over what the map gained (in full after a rebuild or a reset; from rank 0 for the streams whose map was
+        emptied by the last step), then the step's cloud localised in the map with the step's ``active`` word, the frame's
+        pose in the map's source trajectory as the guess and ``max_source_frame = frame id - min_id_distance``.  No sync."""
+        if self._loc_cfg is None or self._map is None or self._map.bufs is None:
+            return                                          # the first step: the map is still empty
+        if self._loc is None:
+            from . import map_localize
+            self._loc = map_localize.MapLocalizer(self._map, graph=self.graph, **self._loc_cfg)
+            self._loc_ids, self._loc_newest = torch.zeros_like(self._active), torch.zeros_like(self._active)
+        self._loc.index(full=self._loc_full, refill=None if self._loc_full else self._loc_refill)
+        self._loc_full = False
+        cloud = self._tapped[:, :self.num_points, :3].contiguous()
+        torch.sub(self._counts, 1, out=self._loc_ids)
+        torch.sub(self._loc_ids, int(self._loc_min_id), out=self._loc_newest)
+        X = self._map_poses()
+        at = self._loc_ids.clamp(0, X.shape[0] - 1).long()
+        init = X[at, torch.arange(self.streams, device=X.device)].contiguous()
+        self._loc.localize(cloud, init, active=self._active, max_source_frame=self._loc_newest)
+        self._loc_fresh = True
+
+    def poll_localization(self, optimize=False, information=None):
+        """With ``localize=`` and ``backend=``: reads the last localisation's words (a host read) and hands the pose of every
+        stream whose status is converged with at least ``min_pairs`` pairs to ``backend().add_absolute(stream, frame, T,
+        information)``, once per step; ``optimize=True`` then runs ``backend().optimize()`` where an edge was added (and
+        the map is rebuilt as ``poll_loops`` rebuilds it).  -> the list of ``(stream, frame, T (4, 4) ndarray)`` handed
+        over.  A fix the graph refuses (ValueError: the edge list is full, the pose is not finite) is kept, with the
+        reason, in ``localization_dropped`` as ``(stream, frame, T, message)``, as ``loop_detector().dropped`` keeps a
+        refused closure."""
+        if self._loc_cfg is None:
+            raise RuntimeError("StreamingOdometry: poll_localization needs localize=dict(...)")
+        if self._backend_cfg is None:
+            raise RuntimeError("StreamingOdometry: poll_localization hands absolute edges to the pose graph and needs "
+                               "backend=dict(...)")
+        if self._loc is None or not self._loc_fresh:
+            return []
+        self._loc_fresh = False
+        status = self._loc.status().cpu().numpy()
+        pairs = self._loc.diagnostics()["pairs"].cpu().numpy()
+        ids, T = self._loc_ids.cpu().numpy(), self._loc.bufs["T"].cpu().numpy()
+        added = []
+        for s in range(self.streams):
+            if status[s] == 1 and pairs[s] >= self._loc.min_pairs and ids[s] >= 0:
+                try:
+                    self._backend.add_absolute(s, int(ids[s]), T[s], information)
+                except ValueError as e:
+                    self.localization_dropped.append((s, int(ids[s]), T[s].copy(), str(e)))
+                    continue
+                added.append((s, int(ids[s]), T[s].copy()))
+        if optimize and added:
+            self._backend.optimize()
+            if self._map is not None and self._map_rebuild and self._map_source == "optimized":
+                self._map.rebuild(self._backend.bufs["X"])
+                self._map_optimized = self._backend.calls
+                self._loc_full = True
         return added
 
     def global_map(self):
@@ -553,6 +657,10 @@ class StreamingOdometry:
         torch.sub(self._counts, 1, out=self._map_ids)
         self._map.advance(cloud, self._map_ids, self._map_poses(), active=self._active, restart=self._map_restart,
                           lengths=self.survivor_counts())
+        if self._loc_cfg is not None:                       # the streams whose map this call emptied: indexed from rank 0 next
+            if self._loc_refill is None:
+                self._loc_refill = torch.zeros_like(self._active)
+            self._loc_refill.copy_(self._map_restart)
 
     def refiner(self):
         """The refiner behind ``refine=``, of the class its ``kind`` names (``status()``, ``diagnostics()``); None before the
@@ -768,6 +876,7 @@ class StreamingOdometry:
         returns None for it."""
         self._refine(pose)
         self._detect(pose)
+        self._localize(pose)
         self._extend_map(pose)
         self.frames_seen += 1
         return None if not self.per_stream and self.frames_seen == 1 else pose
